@@ -6,11 +6,21 @@ prefixes that is already resident in HBM, against IBF(s) resident in HBM.
 
 Headline workload (N = 1 and N > 1 alike) = BASELINE.json configs[2], the configuration the north star's target is stated
 on: 10 M reads x 360 bp against the GRCh38-scale depletion IBF (8192 bins, 8 GiB) -- ONE launch of 10 M reads per step and
-GPU.  The same line carries `other_configs`: configs[1] (c2, whose 0.41 GB table is partly Infinity-Cache resident),
+GPU.  With --full the same line carries `other_configs`: configs[1] (c2, whose 0.41 GB table is partly Infinity-Cache resident),
 configs[3] (c4: deplete + target, full check_unblock; full steps, CPU baseline, parity), configs[4] (c5: the 48-flowcell
 replay with its latency percentiles, plus a leg through the live step with concatenated undecided chunks), the shape of
 the reference's README benchmark (at 250 and at 360 bp) and two narrower shapes of the same filters (three targets alone; one
 deplete + one target) -- run in this process (and, for N > 1, by all ranks), after the headline measurement.
+
+A plain run (no --full) does only what the headline needs: set up, warm up, time the K steps, write the outputs of the last
+step if --dump-outputs is given, print the line.  The read-peak and request-bound probes, the CPU baseline, the parity check
+against the oracle, the latency legs, the multi-GPU pre-flight and `other_configs` run with --full only; a plain line carries
+"cpu_baseline" and "parity" as null.
+
+--dump-outputs DIR writes what the timed path returned in its last step -- the raw maxima, best bin, decision and status arrays a
+caller of rb_classify_batch_device receives -- as DIR/<name>.npy (float32; read_index.npy, float64, names the reads), for a fixed,
+seeded sample of at most DUMP_MAX_READS reads of rank 0's batch.  The inputs depend only on the arguments, so two builds can be
+compared output for output.
 
 With N > 1 every rank (one process per GPU) holds a replica of the IBF and its own shard of reads (weak scaling, no
 data-path collective); time = max over ranks, value = all reads / that time.  `python bench.py --gpus N` starts the N ranks
@@ -40,6 +50,32 @@ METRIC = "reads/sec (360bp prefixes classified vs IBF, unblock/keep decisions)"
 # test hook (tests/test_bench_ranks.py only; the line then carries "test_reads_divisor"): every leg's default batch divided by
 # this, so that the full default run -- headline + other_configs -- fits a unit test
 TEST_DIVISOR = max(1, int(os.environ.get("RB_BENCH_READS_DIVISOR", "1")))
+# --dump-outputs: reads per dump (config 3's 10 M reads would be 160 MB of float32) and the seed that picks them
+DUMP_MAX_READS = 1 << 20
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, torch, t_max, t_best, t_dec, t_st):
+    """the outputs of the last step as out_dir/<name>.npy: the same DUMP_SEED-drawn sample of reads (all of them up to
+    DUMP_MAX_READS) from every array, gathered on the device; u16 maxima, bin indices and u8 codes are exact in float32"""
+    n_reads = int(t_dec.shape[0])
+    if n_reads > DUMP_MAX_READS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_reads, size=DUMP_MAX_READS, replace=False))
+    else:
+        idx = np.arange(n_reads)
+    t_idx = torch.from_numpy(idx.astype(np.int64)).to(t_dec.device)
+    arrays = {"max_count": t_max.index_select(0, t_idx).cpu().numpy().view(np.uint16),  # (reads, filters): int16 storage of u16
+              "best_bin": t_best.index_select(0, t_idx).cpu().numpy(),
+              "decision": t_dec.index_select(0, t_idx).cpu().numpy(),
+              "status": t_st.index_select(0, t_idx).cpu().numpy()}
+    os.makedirs(out_dir, exist_ok=True)
+    files = []
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+        files.append(name + ".npy")
+    np.save(os.path.join(out_dir, "read_index.npy"), idx.astype(np.float64))
+    files.append("read_index.npy")
+    return {"dir": out_dir, "files": files, "reads": int(len(idx)), "of_reads": n_reads, "seed": DUMP_SEED}
 
 
 def host_cores():
@@ -444,7 +480,7 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="",
-                    help="default: c3 (BASELINE configs[2], 10 M reads per step) + other_configs; or one of c2, c3, c3np2, c1, c4, c5, "
+                    help="default: c3 (BASELINE configs[2], 10 M reads per step), with --full + other_configs; or one of c2, c3, c3np2, c1, c4, c5, "
                          "readme, grch38_f100k, zymo, zymo16 on its own")
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU per step (default: the config's batch)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -461,11 +497,22 @@ def parse():
     ap.add_argument("--phased", default="", help="tuning: 'off' or 'min_mib,max_mib,base_ticks,ticks_per_mib' for the clock-phased gathers of narrow filters")
     ap.add_argument("--serial-table-mib", type=int, default=-1,
                     help="tuning: filters up to this size take turns instead of overlapping (default: the engine's 64; 0 = round 1 behaviour)")
-    ap.add_argument("--no-extras", action="store_true", help="default run: leave `other_configs` out")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave `other_configs` out")
     ap.add_argument("--pool", action="store_true",
                     help="only the single-process multi-GPU legs: c3 and c4 through rb_pool_classify_batch from ONE host process "
                          "(rank 0 drives every GPU of the job; N = 1: the one GPU) from page-locked host memory")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: read-peak and request-bound probes, CPU baseline, oracle parity, latency legs, the "
+                         "multi-GPU pre-flight and (default workload) every other config as `other_configs`")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the outputs of the last step (a fixed, seeded sample of at most %d reads) as "
+                         "DIR/<name>.npy" % DUMP_MAX_READS)
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.pool or args.workload in ("c5", "c3_early")):
+        ap.error("--dump-outputs covers the throughput workloads (not --pool, c5 or c3_early)")
+    return args
 
 
 def load_json(name):
@@ -592,12 +639,14 @@ def workload_spec(ctx, name):
 
 
 def run_throughput(ctx, name, n_reads=0, read_len=0, steps=None, warmup=None, cpu_seconds=None, latency=False,
-                   bin_sharded=False):
+                   bin_sharded=False, dump_dir=""):
     """One throughput measurement as the contract describes it: W untimed steps, then K steps between barriers, time = max
-    over ranks.  Returns the result dict on rank 0 (None elsewhere): value, roofline (live hipEvent kernel time), parity
-    against the oracle, CPU baseline (N = 1)."""
+    over ranks.  Returns the result dict on rank 0 (None elsewhere): value, roofline (live hipEvent kernel time); with --full
+    also the read-peak / request-bound probes, parity against the oracle, CPU baseline (N = 1) and latency.  dump_dir: rank 0
+    writes the outputs of the last timed step there (dump_outputs)."""
     from readbouncer_amd import capi, synth
     args, torch, dist = ctx.args, ctx.torch, ctx.dist
+    full = args.full
     world, rank, dev, dev_index = ctx.world, ctx.rank, ctx.dev, ctx.dev_index
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
@@ -695,6 +744,7 @@ def run_throughput(ctx, name, n_reads=0, read_len=0, steps=None, warmup=None, cp
     per_rank_s = ctx.gather_floats(t_local)
     total_reads = n_reads * (1 if bin_sharded else world) * steps
     value = total_reads / elapsed
+    dumped = dump_outputs(dump_dir, torch, t_max, t_best, t_dec, t_st) if (dump_dir and rank == 0) else None
 
     result = None
     decisions = None
@@ -714,7 +764,7 @@ def run_throughput(ctx, name, n_reads=0, read_len=0, steps=None, warmup=None, cp
         # read peak of THIS device for the dominant filter's access pattern, measured now: random whole-block gathers from the
         # same table with no compute attached (rb_dibf_probe_read_peak, rb_probe.hip), 12 and 24 loads in flight per wave
         probe = None
-        if not bin_sharded and not os.environ.get("RB_BENCH_NO_PROBE"):
+        if full and not bin_sharded and not os.environ.get("RB_BENCH_NO_PROBE"):
             dom = max(filters, key=lambda f: f.info["bin_width"])
             bb = dom.device_stride() * 8
             row = 4096 if bb >= 3072 else 1024 if bb >= 1024 else 128 if bb >= 128 else 0
@@ -770,7 +820,7 @@ def run_throughput(ctx, name, n_reads=0, read_len=0, steps=None, warmup=None, cp
         tj_req = load_json("traffic.json").get("readme360" if (name == "readme" and read_len == 360) else name, {}) \
             if (read_len == default_len or (name == "readme" and read_len == 360)) else {}
         narrow = bool(plans) and all(pl.get("phased") or "merged" in pl.get("kernel", "") for pl in plans)
-        if narrow and tj_req.get("TCC_EA0_RDREQ") and tj_req.get("l2_hit_rate") is not None and not bin_sharded \
+        if full and narrow and tj_req.get("TCC_EA0_RDREQ") and tj_req.get("l2_hit_rate") is not None and not bin_sharded \
                 and not os.environ.get("RB_BENCH_NO_PROBE"):
             try:
                 ktab = max(int(pl.get("table_bytes", 0)) for pl in plans)
@@ -842,13 +892,15 @@ def run_throughput(ctx, name, n_reads=0, read_len=0, steps=None, warmup=None, cp
         if os.environ.get("RB_BENCH_DUMP_DECISIONS"):  # tests compare the N-rank decisions with the 1-rank run
             import hashlib
             result["config"]["decisions_sha1"] = hashlib.sha1(decisions.tobytes()).hexdigest()
+        if dumped:
+            result["dump_outputs"] = dumped
 
-    # ---------------------------------------------------------------- parity check + CPU baseline (rank 0)
+    # ---------------------------------------------------------------- parity check + CPU baseline (rank 0, --full)
     buf = None
-    if rank == 0:
+    if rank == 0 and full:
         cap = min(n_reads, 1 << 21)  # host copy of the head of the batch: CPU baseline, parity, latency legs
         buf = t_seq[: cap * read_len].cpu().numpy()
-    if rank == 0 and not args.no_cpu_baseline and cpu_seconds > 0:
+    if rank == 0 and full and not args.no_cpu_baseline and cpu_seconds > 0:
         from oracle import pyoracle as po
         views = [ctx.oracle_view(k) for k in dep_keys + tgt_keys]
         od, ot = views[:len(deplete)], views[len(deplete):]
@@ -899,7 +951,7 @@ def run_throughput(ctx, name, n_reads=0, read_len=0, steps=None, warmup=None, cp
         result["cpu_baseline"] = None
 
     # ---------------------------------------------------------------- per-read classify latency (small batches)
-    if rank == 0 and latency and not args.no_latency and not bin_sharded:
+    if rank == 0 and full and latency and not args.no_latency and not bin_sharded:
         lat = {}
         for mb in (64, 256, 1024):
             m = min(mb, len(buf) // read_len)
@@ -1578,7 +1630,7 @@ def null_engine_run(args, torch, dist, world, rank, backend):
         time.sleep(0.3)
         os.kill(os.getpid(), 11)  # SIGSEGV, like a GPU fault would end it
     others = {}
-    if not args.workload and not args.bin_sharded and not args.no_extras:
+    if args.full and not args.workload and not args.bin_sharded and not args.no_extras:
         for name in default_leg_names(world):
             others[name] = leg(name, 1, False)
     infos = [{"rank": rank, "device": None}]
@@ -1678,14 +1730,15 @@ def main():
         extras = False
     else:
         name = args.workload or "c3"
-        extras = not args.workload and not args.reads and not args.read_len and not args.no_extras and not bin_sharded
+        extras = args.full and not args.workload and not args.reads and not args.read_len and not args.no_extras and not bin_sharded
         if os.environ.get("RB_BENCH_NO_PREFLIGHT") == "1":
             pre = {"ran": False, "why": "RB_BENCH_NO_PREFLIGHT=1"}
         else:
-            pre = {"ran": False, "why": "default run on rank 0 only"}
+            pre = {"ran": False, "why": "default run with --full, on rank 0 only"}
             if rank == 0 and extras:
                 pre = {"ran": False, "why": "in the child process of the pool legs (filled in below)"} if pool_in_child(ctx) else xgmi_preflight(ctx)
-        result = run_throughput(ctx, name, n_reads=args.reads, read_len=args.read_len, latency=True, bin_sharded=bin_sharded)
+        result = run_throughput(ctx, name, n_reads=args.reads, read_len=args.read_len, latency=True, bin_sharded=bin_sharded,
+                                dump_dir=args.dump_outputs)
         infos = rank_diagnostics(ctx, time.time() - t_start)
         if rank == 0:
             result["ranks"] = {"backend": backend if dist is not None else None,

@@ -6,12 +6,12 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-python3 bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err
-python3 bench.py --workload c3 --reads 2000000 --steps 5 --warmup 1 --cpu-seconds 10 > $OUT/bench_c3.json 2> $OUT/bench_c3.err
-python3 bench.py --workload c3np2 --reads 2000000 --steps 3 --warmup 1 --no-cpu-baseline --no-latency > $OUT/bench_c3np2.json 2> /dev/null
-python3 bench.py --workload c4 --reads 2000000 --steps 5 --warmup 1 --cpu-seconds 10 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
-python3 bench.py --workload grch38_f100k --steps 3 --warmup 1 --cpu-seconds 8 > $OUT/bench_grch38_f100k.json 2> /dev/null
-python3 bench.py --workload c1 --steps 5 --warmup 1 --no-cpu-baseline --no-latency > $OUT/bench_c1.json 2> /dev/null
+python3 bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+python3 bench.py --full --workload c3 --reads 2000000 --steps 5 --warmup 1 --cpu-seconds 10 > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+python3 bench.py --full --workload c3np2 --reads 2000000 --steps 3 --warmup 1 --no-cpu-baseline --no-latency > $OUT/bench_c3np2.json 2> /dev/null
+python3 bench.py --full --workload c4 --reads 2000000 --steps 5 --warmup 1 --cpu-seconds 10 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+python3 bench.py --full --workload grch38_f100k --steps 3 --warmup 1 --cpu-seconds 8 > $OUT/bench_grch38_f100k.json 2> /dev/null
+python3 bench.py --full --workload c1 --steps 5 --warmup 1 --no-cpu-baseline --no-latency > $OUT/bench_c1.json 2> /dev/null
 python3 bench.py --workload c5 > $OUT/bench_c5_150k.json 2> /dev/null
 python3 bench.py --workload c5 --rate 18750 > $OUT/bench_c5_18750.json 2> /dev/null
 python3 profiles/latency_floor.py 2>/dev/null > $OUT/latency_floor.txt

@@ -90,9 +90,9 @@ def test_gpus2_self_launch_read_sharded_cpu():
 
 
 def test_gpus2_default_line_structure_cpu():
-    """the DEFAULT command (what the driver runs at N > 1): headline = config 3, the other BASELINE configs as sub-runs of all
+    """the default command with --full at N > 1: headline = config 3, the other BASELINE configs as sub-runs of all
     ranks, per-rank device records -- the structure a SCALE record will carry, checked on the null engine"""
-    p, d = _run(["--gpus", "2", "--steps", "2", "--warmup", "1"], CPU_HOOKS)
+    p, d = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], CPU_HOOKS)
     assert p.returncode == 0, p.stderr[-2000:]
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and "c3" in d["config"]["workload"]
     for key in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "higher_is_better", "vs_baseline", "dtype", "data",
@@ -184,9 +184,9 @@ def test_headline_survives_a_process_that_dies_later_cpu():
 
 @pytest.mark.parametrize("n", [1, 8])
 def test_default_line_is_bounded_cpu(n):
-    """the DEFAULT command at N = 1 and N = 8 on the null engine: one line, at most 4 KB, strict JSON, roofline / cpu_baseline /
+    """the default command with --full at N = 1 and N = 8 on the null engine: one line, at most 4 KB, strict JSON, roofline / cpu_baseline /
     parity keys present, every leg of the run summarised in a row; the sidecar holds the rest"""
-    p, d = _run(["--gpus", str(n), "--steps", "2", "--warmup", "1"], CPU_HOOKS, timeout=300)
+    p, d = _run(["--gpus", str(n), "--steps", "2", "--warmup", "1", "--full"], CPU_HOOKS, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     assert len([l for l in p.stdout.splitlines() if l.strip()]) == 1
     c = _check_line(d, n)
@@ -195,6 +195,52 @@ def test_default_line_is_bounded_cpu(n):
     assert "grch38_f100k" in bench.FULL_LEGS  # the reference-default human filter rides in the default N = 1 run
     if n > 1:
         assert len(c["ranks"]["per_rank_reads_per_s"]) == n and len(d["ranks"]["devices"]) == n
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_plain_run_carries_the_headline_only_cpu(n):
+    """the default command without --full: the headline and nothing else -- no other_configs, no CPU baseline, no parity --
+    with the contract fields and --steps timed steps; impossible step counts are refused"""
+    p, d = _run(["--gpus", str(n), "--steps", "3", "--warmup", "1"], CPU_HOOKS)
+    assert p.returncode == 0, p.stderr[-2000:]
+    c = _check_line(d, n)
+    assert "other_configs" not in d and "other_configs" not in c
+    assert c["cpu_baseline"] is None and c["parity"] is None
+    assert c["steps"] == 3 and c["warmup"] == 1 and c["ms_per_step"] > 0 and c["higher_is_better"] is True
+    assert c["unit"] == "reads/s" and c["dtype"] == "u64" and c["metric"].startswith("reads/sec")
+    p = subprocess.run([sys.executable, BENCH, "--steps", "0"], capture_output=True, text=True, timeout=60, cwd=ROOT)
+    assert p.returncode == 2 and "--steps" in p.stderr
+
+
+def test_dump_outputs_sample_is_fixed_and_exact_cpu(tmp_path, monkeypatch):
+    """dump_outputs on host tensors: the same seeded sample of reads from every array, sorted and without repeats, values
+    exact in float32 (u16 maxima stored as int16 included), all reads when the batch is small"""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_READS", 1000)
+    n, nf = 5000, 2
+    rng = np.random.default_rng(3)
+    t_max = torch.from_numpy(rng.integers(0, 65536, size=(n, nf), dtype=np.uint16).view(np.int16))
+    t_best = torch.from_numpy(rng.integers(-1, 31000, size=n, dtype=np.int32))
+    t_dec = torch.from_numpy(rng.integers(0, 3, size=n, dtype=np.uint8))
+    t_st = torch.from_numpy(rng.integers(0, 4, size=n, dtype=np.uint8))
+    rec = bench.dump_outputs(str(tmp_path / "a"), torch, t_max, t_best, t_dec, t_st)
+    bench.dump_outputs(str(tmp_path / "b"), torch, t_max, t_best, t_dec, t_st)
+    assert rec["reads"] == 1000 and rec["of_reads"] == n
+    got = {f: np.load(str(tmp_path / "a" / f)) for f in rec["files"]}
+    assert set(got) == {"max_count.npy", "best_bin.npy", "decision.npy", "status.npy", "read_index.npy"}
+    idx = got["read_index.npy"]
+    assert idx.dtype == np.float64 and len(np.unique(idx)) == 1000 and np.all(np.diff(idx) > 0) and idx[-1] < n
+    i = idx.astype(np.int64)
+    assert got["max_count.npy"].dtype == np.float32 and got["max_count.npy"].shape == (1000, nf)
+    assert np.array_equal(got["max_count.npy"], t_max.numpy().view(np.uint16)[i].astype(np.float32))
+    assert np.array_equal(got["best_bin.npy"], t_best.numpy()[i].astype(np.float32))
+    assert np.array_equal(got["decision.npy"], t_dec.numpy()[i]) and np.array_equal(got["status.npy"], t_st.numpy()[i])
+    for f in rec["files"]:
+        assert np.array_equal(got[f], np.load(str(tmp_path / "b" / f)))  # the same sample every time
+    rec = bench.dump_outputs(str(tmp_path / "c"), torch, t_max[:700], t_best[:700], t_dec[:700], t_st[:700])
+    assert rec["reads"] == 700 and np.array_equal(np.load(str(tmp_path / "c" / "read_index.npy")), np.arange(700))
 
 
 def test_compact_line_sheds_detail_but_keeps_the_contract():
@@ -282,12 +328,37 @@ def test_rccl_code_paths_with_a_group_of_one():
 
 
 @pytest.mark.gpu
+def test_dump_outputs_are_the_timed_outputs(tmp_path):
+    """--dump-outputs on a plain run: the four output arrays of the last timed step (all 20 000 reads: below the sample size),
+    float32, the decisions those the line reports; a second run with the same arguments dumps identical arrays"""
+    import numpy as np
+    runs = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        p, d = _run(["--gpus", "1", "--workload", "zymo", "--reads", "20000", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)],
+                    {"RB_BENCH_DUMP_DECISIONS": "1"}, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert d["_compact"]["parity"] is None and "other_configs" not in d and d["steps"] == 2
+        arrays = {f: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))}
+        assert sorted(arrays) == sorted(d["dump_outputs"]["files"]) and d["dump_outputs"]["reads"] == 20000
+        assert arrays["max_count.npy"].shape == (20000, 1) and arrays["max_count.npy"].dtype == np.float32
+        dec = arrays["decision.npy"]
+        assert dec.dtype == np.float32 and dec.shape == (20000,)
+        assert np.bincount(dec.astype(np.int64), minlength=3).tolist() == d["config"]["decisions"]
+        import hashlib
+        assert hashlib.sha1(dec.astype(np.uint8).tobytes()).hexdigest() == d["config"]["decisions_sha1"]
+        runs.append(arrays)
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
+
+
+@pytest.mark.gpu
 def test_gpus2_default_line_decisions_equal_one_rank_on_c3_and_c4():
-    """The default command at N = 2 (two ranks on the one GPU of the box, gloo) against N = 1: rank 0's decisions on the
+    """The default command with --full at N = 2 (two ranks on the one GPU of the box, gloo) against N = 1: rank 0's decisions on the
     headline (config 3, the 8 GiB filter) and on config 4 are the 1-rank decisions; the line has the SCALE structure.
     Batches divided by 50 (test hook) so that both runs fit a unit test."""
     small = {"RB_BENCH_READS_DIVISOR": "50", "RB_BENCH_DUMP_DECISIONS": "1"}
-    argv = ["--steps", "2", "--warmup", "1", "--cpu-seconds", "2"]
+    argv = ["--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--full"]
     p1, d1 = _run(["--gpus", "1"] + argv, small, timeout=900)
     assert p1.returncode == 0, p1.stderr[-2000:]
     p2, d2 = _run(["--gpus", "2"] + argv, dict(GPU_HOOKS, **small), timeout=900)
@@ -397,7 +468,8 @@ def test_narrow_leg_carries_a_request_bound():
     """a narrow-filter workload on its own: besides the byte roofline the result carries the request bound (a lower bound on the kernel
     time from two rates probed in the same run and the replayed hit / miss counts) -- under a name that cannot be read as an HBM
     fraction (`request_bound.request_bound_frac`); the structure is checked here, the numbers are bench output"""
-    p, d = _run(["--gpus", "1", "--workload", "targets3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-latency"], {}, timeout=600)
+    p, d = _run(["--gpus", "1", "--workload", "targets3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-latency", "--full"], {},
+                timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     assert "request_roofline" not in d["roofline"]
     q = d["roofline"]["request_bound"]
@@ -418,7 +490,8 @@ def test_request_bound_is_a_bound():
     """the request bound is meant as a true lower bound of the kernel time: no narrow leg may beat it (an earlier, additive form
     of the model was beaten by 18 % on a 64 MiB one-word table)"""
     for w in ("targets3", "w1_64mib", "readme"):
-        p, d = _run(["--gpus", "1", "--workload", w, "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-latency"], {}, timeout=600)
+        p, d = _run(["--gpus", "1", "--workload", w, "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-latency", "--full"], {},
+                    timeout=600)
         assert p.returncode == 0, p.stderr[-2000:]
         q = d["roofline"]["request_bound"]
         assert 0.3 < q["request_bound_frac"] <= 1.04, (w, q)
