@@ -191,7 +191,7 @@ RB_API int rb_engine_set_phase_slices(rb_engine *e, uint32_t slice_log2, uint32_
  * slice size.  Results are identical. */
 RB_API int rb_engine_set_phase_equal_slices(rb_engine *e, uint32_t n_slices);
 
-/* Two-word tables (65-128 bins, or two to three small targets merged) of up to 2^21 - 1 blocks (32 MiB), reads of up to 256 k-mers, phased
+/* Two-word tables (65-128 bins, or two to three small targets merged) of up to 2^21 - 2 blocks (32 MiB), reads of up to 256 k-mers, phased
  * form: `reads` = 2 or 3 takes the build that carries that many reads per wave through one pass of the windows -- AND accumulators in
  * registers, block numbers packed into LDS -- so that a pass, which reloads the table once per XCD whatever rides along, serves more
  * reads (40 instead of 28 per CU at two reads per wave); 1 = one read per wave with the offsets in LDS (eight waves per SIMD);

@@ -102,6 +102,18 @@ struct NarrowMerge {
     uint32_t out_offset[kMaxNarrow];  // member -> element offset in a row of the output
 };
 
+// Packed block numbers of the LDS-offset builds (ibf_count_max_phased_multi_kernel, rb_kernels.hip): three per k-mer in one 64-bit
+// word, kPackBits each for blocks of two to four words, kPackBits1 for one-word blocks (the third number's top two bits in a spill
+// register).  The all-ones number means "no lookup", so a table may hold at most 2^PB - 2 blocks: the ONE limit the planner, the
+// launchers and the merged copy's complemented twin (rb_engine.hip) all test against.
+constexpr uint32_t kPackBits = 21;
+constexpr uint32_t kPackMask = (1u << kPackBits) - 1u;
+constexpr uint32_t kPackBits1 = 22;
+constexpr uint32_t kPackMask1 = (1u << kPackBits1) - 1u;
+constexpr uint64_t pack_max_blocks(uint32_t pack_bits) { return (1ull << pack_bits) - 2u; }
+constexpr uint64_t kPackMaxBlocks = pack_max_blocks(kPackBits);    // 2 097 150: 32 MiB of two-word blocks
+constexpr uint64_t kPackMaxBlocks1 = pack_max_blocks(kPackBits1);  // 4 194 302: 32 MiB of one-word blocks
+
 struct CountLaunch {
     IbfDev f;
     ReadSrc src;

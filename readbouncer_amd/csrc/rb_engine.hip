@@ -231,7 +231,7 @@ struct MergedTable {
     std::vector<const rb_dibf *> key_filters;  // the members, in the order their bins sit in a merged block
     std::vector<uint32_t> key_bit_begin;
     uint64_t *d_words = nullptr;
-    uint64_t *d_inv = nullptr;  // two-word copies of fewer than 2^21 - 1 blocks: the COMPLEMENT of the copy, behind it in the same allocation (the
+    uint64_t *d_inv = nullptr;  // two-word copies of up to kPackMaxBlocks = 2^21 - 2 blocks: the COMPLEMENT of the copy, behind it in the same allocation (the
                                 // multi-read build of the phased kernel ORs complemented words instead of masking and ANDing: rb_kernels.hip)
     uint64_t stride = 0, width = 0, n_blocks = 0;
     IbfDev dev{};
@@ -326,7 +326,7 @@ struct rb_engine {
     uint32_t phase_xcd_skew = 2;      // rb_engine_set_phase_xcd_skew (RB_PHASE_XCD_SKEW): bit 0: slice = (window + XCD number) mod n_slices; bit 1: the
                                       // XCDs' windows start an eighth of a window apart (they refill their L2s one after the other).  Bit 1 is the
                                       // default since round 6: 1.2-4.4 % on every phased shape, never a loss (profiles/r06/multi/s13_skew_all_shapes.txt)
-    // rb_engine_set_reads_per_wave: two-word tables of up to 2^21 - 1 blocks, reads of up to 256 k-mers, phased: the build that carries
+    // rb_engine_set_reads_per_wave: two-word tables of up to 2^21 - 2 blocks (kPackMaxBlocks), reads of up to 256 k-mers, phased: the build that carries
     // that many reads per wave through a pass of the windows, offsets in LDS (rb_kernels.hip, ibf_count_max_phased_multi_kernel); 0: the
     // one-read build
     uint32_t multi_reads = 1;   // (default since round 6: 250 bp -10 ... -11 %, 360 bp -16 ... -19 % on two-word tables, profiles/r06/multi/)
@@ -1401,14 +1401,14 @@ static bool plan_geometry(const rb_engine *e, const rb_dibf *f, size_t n_reads, 
             while (slice_log2 >= 6 && (f->stride * 8) << (sh + 1) <= (1ull << slice_log2)) ++sh;  // (< 6: as small as max_slices allows)
             while (((f->geo.n_blocks + (1ull << sh) - 1) >> sh) > e->phase_max_slices) ++sh;
             uint32_t n_sl = (uint32_t)((f->geo.n_blocks + (1ull << sh) - 1) >> sh);
-            // the builds that keep the offsets in LDS (two-word blocks of up to 2^21 - 1 blocks, reads of up to 384 k-mers): planned here because the
+            // the builds that keep the offsets in LDS (two-word blocks of up to 2^21 - 2 blocks, reads of up to 384 k-mers): planned here because the
             // window belongs to the build (rb_phase_plan.h, phase_multi_window_ticks)
             // (lg 1: short_only 1 / 3 = at most 256 / 384 k-mers; lg 2, blocks of three and four words: short_only 5 = at most 256, 4 = at most 512 --
             // up to 384 of them fit one round of six tiles)
             const int multi_tiles = a.lg <= 1 ? (a.short_only == 1 ? 4 : a.short_only == 3 ? 6 : 0)
                                     : (a.lg == 2 && wide_short) ? (a.short_only == 5 ? 4 : (a.short_only == 4 && kmers <= 384 && e->multi_wide_six) ? 6 : 0) : 0;
             const bool multi_build = e->multi_reads && multi_tiles && a.planes <= 10 && a.col_begin == 0 &&
-                                     f->geo.n_blocks < (1ull << (a.lg == 0 ? 22 : 21)) - 1 &&  // (block numbers of 21 bits; one-word blocks: 22, rb_kernels.hip kPackBits1)
+                                     f->geo.n_blocks <= (a.lg == 0 ? kPackMaxBlocks1 : kPackMaxBlocks) &&  // (packed block numbers, rb_device.h)
                                      ((a.lg == 1 && a.col_end == 2 && f->stride == 2) || (a.lg == 2 && e->multi_wide && f->stride == 4) ||
                                       (a.lg == 0 && e->multi_one_word && a.col_end == 1 && f->stride == 1 && W == 1));
             // the four-word one-lane builds: slices of equal length, fewer than the 4 MiB ones (rb_phase_plan.h, phase_equal_slices)
@@ -1767,7 +1767,7 @@ static int ensure_merged_table(rb_engine *e, MergedGroup *g, hipStream_t st)
         if (!t->d_words) {
             t->stride = hbm_stride(g->width);
             t->n_blocks = g->n_blocks;
-            const bool twin = ((t->stride == 2 && g->width == 2) || (t->stride == 4 && g->width >= 3 && g->width <= 4)) && t->n_blocks < (1ull << 21) - 1;
+            const bool twin = ((t->stride == 2 && g->width == 2) || (t->stride == 4 && g->width >= 3 && g->width <= 4)) && t->n_blocks <= kPackMaxBlocks;
             if (hipMalloc((void **)&t->d_words, (t->n_blocks * t->stride + 8) * 8 * (twin ? 2 : 1)) != hipSuccess) {
                 (void)hipGetLastError();
                 t->d_words = nullptr;

@@ -1179,17 +1179,13 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
 // cost more VALU time than a window has.  R = 2 at five waves per SIMD: 40 reads per CU, 160 KiB of LDS -- all of it, which is why
 // a read's bases are staged inside its own last slot's region (the slot is hashed into registers before it is overwritten) and a
 // workgroup is ONE wave (LDS is granted per workgroup: 8 KiB units pack where 32 KiB units would not).
-// Packed block numbers: tables of at most 2^21 - 1 blocks (32 MiB of two-word blocks); 0x1FFFFF = no lookup, out of range of every
-// slice because a slice's descriptor ends with the table.  Same windows, same slices, same counting as the one-read build; results
-// are identical by construction (the same AND of the same words).
-constexpr uint32_t kPackBits = 21;
-constexpr uint32_t kPackMask = (1u << kPackBits) - 1u;
-// One-word blocks (8 bytes each: a table of 2^21 of them is only 16 MiB) pack 22-bit block numbers: the first two whole, the low 20 bits
-// of the third, and its top two bits in a per-lane SPILL word held in a register (two bits per slot, at most twelve slots) -- tables of
-// up to 2^22 - 2 blocks (32 MiB), which takes in the 64-bin filter of the reference's own test data (2.47 M blocks).  Two VALU operations
-// more per slot and window; 0x3FFFFF = no lookup.
-constexpr uint32_t kPackBits1 = 22;
-constexpr uint32_t kPackMask1 = (1u << kPackBits1) - 1u;
+// Packed block numbers (kPackBits, rb_device.h): tables of at most kPackMaxBlocks = 2^21 - 2 blocks (32 MiB of two-word blocks);
+// 0x1FFFFF = no lookup, out of range of every slice because a slice's descriptor ends with the table.  Same windows, same slices, same
+// counting as the one-read build; results are identical by construction (the same AND of the same words).
+// One-word blocks (8 bytes each: a table of 2^21 of them is only 16 MiB) pack 22-bit block numbers (kPackBits1): the first two whole, the
+// low 20 bits of the third, and its top two bits in a per-lane SPILL word held in a register (two bits per slot, at most twelve slots) --
+// tables of up to kPackMaxBlocks1 = 2^22 - 2 blocks (32 MiB), which takes in the 64-bin filter of the reference's own test data (2.47 M
+// blocks).  Two VALU operations more per slot and window; 0x3FFFFF = no lookup.
 #ifndef RB_MULTI_WAVES
 #define RB_MULTI_WAVES 5
 #endif
@@ -2195,7 +2191,7 @@ static hipError_t launch_phased(const CountLaunch &a, hipStream_t st)
     // two-word blocks, reads of up to 256 / 384 k-mers, tables whose block numbers fit 21 bits: offsets in LDS, one or two reads per wave
     if constexpr (LG == 1 && NP == 10) {
         if (a.multi_reads && a.multi_tiles && a.col_begin == 0 && a.col_end == 2 && a.f.stride == 2) {
-            if (a.f.n_blocks > kPackMask) return hipErrorInvalidValue;
+            if (a.f.n_blocks > kPackMaxBlocks) return hipErrorInvalidValue;
             const uint32_t R = a.multi_tiles == 6 ? 1u : (uint32_t)a.multi_reads;  // (six tiles: one read per wave)
             dim3 g2((a.n_reads + R - 1) / R);
 #define RB_LAUNCH_MULTI(RR, INV, TT)                                                                                                    \
@@ -2215,7 +2211,7 @@ static hipError_t launch_phased(const CountLaunch &a, hipStream_t st)
     // one-word blocks the same way (a filter of up to 64 bins on its own: the AND form)
     if constexpr (LG == 0 && NP == 10) {
         if (a.multi_reads && a.multi_tiles && a.col_begin == 0 && a.col_end == 1 && a.f.stride == 1) {
-            if (a.f.n_blocks >= kPackMask1) return hipErrorInvalidValue;  // (0x3FFFFF itself is "no lookup")
+            if (a.f.n_blocks > kPackMaxBlocks1) return hipErrorInvalidValue;
             dim3 g1(a.n_reads);
             if (a.multi_tiles == 6)
                 hipLaunchKernelGGL((ibf_count_max_phased_multi_kernel<1, false, 6, 1>), g1, dim3(64), 0, st, a.f, a.src, a.n_reads, a.phase, a.out, a.out_read_stride, a.narrow);
@@ -2260,7 +2256,7 @@ static hipError_t dispatch_phased(const CountLaunch &a, hipStream_t st)
         if constexpr (NP == 10) {
             // blocks of three and four words (stride 4), reads of up to 256 / 384 k-mers, block numbers of 21 bits: the builds with the offsets in LDS
             if (a.multi_reads && a.multi_tiles && a.col_begin == 0 && (a.col_end == 3 || a.col_end == 4) && a.f.stride == 4) {
-                if (a.f.n_blocks > kPackMask) return hipErrorInvalidValue;
+                if (a.f.n_blocks > kPackMaxBlocks) return hipErrorInvalidValue;
                 dim3 g1(a.n_reads);
 #define RB_LAUNCH_MULTI4(INV, TT)                                                                                                       \
     hipLaunchKernelGGL((ibf_count_max_phased_multi_kernel<1, INV, TT, 4>), g1, dim3(64), 0, st, a.f, a.src, a.n_reads, a.phase, a.out, \

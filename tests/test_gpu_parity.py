@@ -1845,7 +1845,8 @@ def test_several_reads_per_wave_match_oracle(widths, n_blocks):
     assert eng.plan(0, 4096, 500)["kernel"] != "ibf_count_max_phased_multi_kernel"
 
 
-def test_device_thresholds_match_the_reference_compiled_table():
+@pytest.mark.parametrize("k", [13, 15])
+def test_device_thresholds_match_the_reference_compiled_table(k):
     """SURVEY a.5 / a.6 on the device: the threshold table K2 reads is checked against tests/golden/thresholds_reference.json -- values the
     REFERENCE'S OWN calculateCI (src/IBF/IBF.hpp:268-338) computed when compiled under its own -Ofast, with the threshold expression of
     src/IBF/IBFClassify.cpp:154-159 (tests/golden/make_thresholds_reference.py) -- not against the oracle.  The table is observed through
@@ -1853,11 +1854,10 @@ def test_device_thresholds_match_the_reference_compiled_table():
     with m = t(L) - 1; a deplete-only check_unblock says "unblock" for the first and "keep" for the second iff the device's threshold for
     L is the reference's t(L) (Read::classify, IBFClassify.cpp:262-273: a match needs count >= threshold and count > 0).  Both error rates
     of adaptive_sampling.hpp:55 (r and r - 0.02), micro-batch and throughput forms, lengths from below the int16 wrap (negative
-    thresholds arrive as 65 5xx: never a match) up to 4 000."""
+    thresholds arrive as 65 5xx: never a match) up to 4 000.  For k = 13 and for k = 15, the fixture's two k-mer sizes."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
     import make_thresholds_reference as ref
     fx, full = ref.load_fixture()
-    k = 13
     rng = np.random.default_rng(2026)
     for rate in (0.1, 0.1 - 0.02):
         d = capi.DeviceIBF.create(0, 64, 3, k, 64 << 20)  # sparse: the planted k-mers are the only hits
