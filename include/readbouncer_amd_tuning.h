@@ -210,6 +210,12 @@ RB_API int rb_engine_set_reads_per_wave(rb_engine *e, uint32_t reads);
  * one strand. */
 RB_API int rb_engine_set_early_decision(rb_engine *e, int enabled);
 
+/* On by default.  The plain count kernel (wide filters, throughput form) stops gathering a lane's 16-byte column of the blocks once
+ * none of its bins can reach the read's maximum any more: every k-mer adds at most 1, so a bin whose count plus the k-mers still to
+ * come is at most the best count seen on either strand cannot change the maximum.  The maxima stay exact; 0 gathers everything (A/B
+ * runs, tests).  Results are identical. */
+RB_API int rb_engine_set_bound_pruning(rb_engine *e, int enabled);
+
 /* How the eight XCDs walk the slices of a phased table (each has an L2 of its own, so each reloads every slice): bit 0 of `mode` -- at
  * any time every XCD works on a different slice (slice = (window + XCD number) mod slices); bit 1 -- the XCDs' windows start an eighth
  * of a window apart, so that they refill their L2s one after the other instead of all in the same instant.  0 (default): one clock, one

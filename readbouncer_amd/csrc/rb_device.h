@@ -149,6 +149,8 @@ struct CountLaunch {
     // a wave can stop counting once a bin has reached the larger of the read's two thresholds for this filter (nullptr: count everything)
     const uint16_t *early_thr;
     uint32_t early_thr_len, early_nf, early_fi;
+    // plain throughput form: skip the gathers of bins that can no longer reach the read's maximum (rb_kernels.hip, count_strand; 0: off)
+    int bound_prune;
 };
 
 inline uint8_t geom_code(int lg, int wpl, int nt) { return (uint8_t)(lg | (wpl == 2 ? 8 : 0) | (nt ? 16 : 0)); }

@@ -334,6 +334,9 @@ struct rb_engine {
     // rb_engine_set_early_decision (opt-in, off by default): RB_MODE_CHECK_UNBLOCK calls of the throughput form that do not ask for the raw maxima
     // let a wave of the plain count kernel stop once a bin has reached the larger of the read's two thresholds (rb_kernels.hip, EarlyCfg)
     bool early_decision = false;
+    // rb_engine_set_bound_pruning (on by default): the plain count kernel stops gathering for bins that can no longer reach the read's
+    // maximum (rb_kernels.hip, count_strand); outputs are identical either way
+    bool bound_pruning = true;
     bool multi_one_word = true;  // ... for one-word blocks of up to 2^22 - 2 of them (32 MiB) (RB_MULTI_ONE_WORD=0: the register builds)
     bool multi_wide = true;      // ... and for blocks of three and four words (RB_MULTI_WIDE=0: those keep the register builds)
     bool multi_wide_six = true;  // ... six tiles in one round for their reads of 257-384 k-mers (RB_MULTI_WIDE_SIX=0: rounds of three tiles)
@@ -1183,6 +1186,14 @@ int rb_engine_set_early_decision(rb_engine *e, int enabled)
     return RB_OK;
 }
 
+int rb_engine_set_bound_pruning(rb_engine *e, int enabled)
+{
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->bound_pruning = enabled != 0;
+    return RB_OK;
+}
+
 int rb_engine_set_phase_xcd_skew(rb_engine *e, uint32_t mode)
 {
     if (!e || mode > 3) return rb::fail(RB_ERR_INVALID_ARG, "mode 0..3 (bit 0: slice skew, bit 1: time skew)");
@@ -2014,6 +2025,7 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
             continue;
         }
         if (a.n_slices != 1 || a.split_waves < 2) fold_ok = false;
+        a.bound_prune = e->bound_pruning ? 1 : 0;
         // (a target filter's count also picks best_target -- the strictly-greater argmax of IBFClassify.cpp:262-273 -- so target filters stop
         // early only when the caller does not ask for best_target; a deplete filter's count is seen through the two predicates alone)
         if (early_thr && a.split_waves < 2 && (fi < e->nd || !d_best_target)) {

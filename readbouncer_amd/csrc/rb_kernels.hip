@@ -472,18 +472,35 @@ __device__ __forceinline__ void phased_gather_x4(uint64_t (&x0)[N], uint64_t (&x
 // EARLY (the opt-in early-decision mode of the throughput form, rb_engine_set_early_decision): after every macro tile the running
 // maximum of this wave's counters is compared with `stop_at`; once it is reached the strand is left (the counters are a lower bound of
 // the read's, which is all the decision needs: see ibf_count_max_kernel) and true is returned.
+// BOUND PRUNING (`bound_best` != kNoBound; blocks of one wave's width, LG == 6, plain gathers): after every macro tile the wave takes
+// M = max(bound_best, max of its counters) -- bound_best is the exact maximum of the strand(s) counted before -- and rem = k-mers of
+// this strand still to come.  Every k-mer adds at most 1 to a bin, so a bin with c + rem <= M ends at or below M whatever it gathers
+// later.  A lane whose valid bins are all in that state is DEAD: its `ok` predicate goes false, so from the next tile on it loads
+// block 0 of its column (cache-resident, what past-the-end steps read anyway) and adds nothing; once the 8 lanes of a 128-byte line
+// are dead the line is no longer fetched from HBM, and once the whole wave is dead the strand is left.  Why the maximum stays exact:
+// every counter the wave keeps is at most the bin's true count (a dead bin's counter stops early), and every dead bin's true count is
+// at most the M it died against, which is itself a counter the wave still holds (counters never shrink) or the earlier strands' exact
+// maximum -- so max(counters, bound_best) is the true maximum.  M and rem are wave-uniform; the test "some valid bin has c > M - rem"
+// is a bit-sliced compare of the planes against that constant, MSB first, with a scalar branch per plane.  The caller passes
+// kNoBound where counters can wrap (n >= 2^NP: the 16-plane builds reproduce the reference's uint16_t wrap, and the bound is false
+// there) and where the engine switched pruning off (rb_engine_set_bound_pruning).
+constexpr uint32_t kNoBound = 0xFFFFFFFFu;
 template <int LG, int WPL, int NP, int H, bool NT, bool PH = false, bool EARLY = false>
 __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev &f, const LaneCols<WPL> &lc,
                                              const BaseSrc &seq, uint32_t len, uint32_t n, int strand,
                                              uint32_t mt_first, uint32_t mt_step, int blk_first, int blk_end,
-                                             uint8_t *stage, int lane, const PhaseCfg ph = PhaseCfg{0, 0, 0, 0, 0}, uint32_t stop_at = 0xFFFFFFFFu)
+                                             uint8_t *stage, int lane, const PhaseCfg ph = PhaseCfg{0, 0, 0, 0, 0}, uint32_t stop_at = 0xFFFFFFFFu,
+                                             uint32_t bound_best = kNoBound)
 {
     using T = TileShape<LG>;
     constexpr int NG = T::NG, SPT = T::SPT, J = T::J, ITEMS = T::ITEMS;
     constexpr int HR = H > 0 ? H : 1;
+    // the bound needs every lane to hold whole counts of its bins (one lane group per block) and a whole strand per wave
+    constexpr bool BOUND = (LG == 6) && !PH && (H > 0);
     const int g = lane >> LG;
     const uint32_t S = f.stride;  // words between consecutive blocks in HBM (>= bin_width, see rb_engine.hip)
     const uint32_t k = f.k;
+    bool lane_on = lc.colok;  // lane gathers (BOUND: and is not dead yet)
 
     for (uint32_t mt = mt_first; mt < n; mt += mt_step) {
         // ---- stage the bases of this macro tile as Dna5 ordinals ((Dna5String) conversion)
@@ -570,7 +587,7 @@ __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev
                         const int j = (SPT >= 8) ? 0 : (u / SPT);  // compile-time either way
                         const int it = (s % SPT) * NG + g;          // k-mer of this group within tile j
                         const uint32_t p = mt + (uint32_t)(j * 64 + it);
-                        const bool ok = (p < n) && lc.colok;
+                        const bool ok = (p < n) && lane_on;
                         okv[uu] = ok;
 #pragma unroll
                         for (int h = 0; h < H; ++h) {
@@ -630,10 +647,43 @@ __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev
 #pragma unroll
             for (int w = 0; w < WPL; ++w) pl[w].add8(x[w]);
         }
-        if constexpr (EARLY) {
+        if constexpr (EARLY && !BOUND) {
             // (with several lane groups per block every group holds the counts of ITS k-mers only: a lower bound of a lower bound, still
             // sufficient; the butterfly below is skipped when the wave leaves here)
             if (planes_max<NP, WPL>(pl, lc.valid) >= stop_at) return true;
+        }
+        if constexpr (BOUND) {
+            uint32_t m = 0;
+            if (EARLY || bound_best != kNoBound) m = planes_max<NP, WPL>(pl, lc.valid);  // wave-uniform
+            if (EARLY && m >= stop_at) return true;
+            const uint32_t done = mt + (uint32_t)ITEMS;
+            if (bound_best != kNoBound && done < n) {  // (after the last tile there is nothing left to skip)
+                const uint32_t M = __builtin_amdgcn_readfirstlane(max(m, bound_best));
+                const uint32_t rem = __builtin_amdgcn_readfirstlane(n - done);
+                if (M >= rem) {
+                    const uint32_t t = M - rem;  // a bin stays alive while its count exceeds t
+                    bool alive = false;
+                    if (t < (1u << NP) - 1u) {
+                        // bit-sliced c > t, MSB plane first: gt = bins already above t, eq = bins equal to t's leading bits so far
+#pragma unroll
+                        for (int w = 0; w < WPL; ++w) {
+                            uint64_t gt = 0, eq = lc.valid[w];
+#pragma unroll
+                            for (int i = NP - 1; i >= 0; --i) {
+                                if ((t >> i) & 1u) {  // scalar branch
+                                    eq &= pl[w].p[i];
+                                } else {
+                                    gt |= eq & pl[w].p[i];
+                                    eq &= ~pl[w].p[i];
+                                }
+                            }
+                            alive |= gt != 0ULL;
+                        }
+                    }
+                    lane_on = lane_on && alive;
+                    if (__ballot(lane_on) == 0ULL) break;  // wave-uniform: the rest of this strand cannot change the maximum
+                }
+            }
         }
     }
 
@@ -687,7 +737,7 @@ struct EarlyCfg {
 template <int LG, int WPL, int NP, int H, bool NT, bool EARLY = false>
 __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu((WPL == 1 && NP == 10 && H == 3) ? RB_WAVES_PLAIN : 3, 8))) void ibf_count_max_kernel(
     FilterSet set, ReadSrc src, uint32_t n_reads, uint32_t n_slices, uint16_t *__restrict__ out_base,
-    uint32_t out_read_stride, uint32_t out_slice_stride, EarlyCfg early)
+    uint32_t out_read_stride, uint32_t out_slice_stride, EarlyCfg early, uint32_t prune)
 {
     __shared__ uint8_t s_stage[kWavesPerBlock][kStageBytes];
     const IbfDev &f = set.f[blockIdx.y];  // filters of equal kernel geometry may share a launch (micro-batches)
@@ -715,13 +765,18 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
         const uint16_t *t = early.thr + ((size_t)tl * early.nf + early.fi[blockIdx.y]) * 2;
         stop_at = max(max((uint32_t)t[0], (uint32_t)t[1]), 1u);
     }
+    // bound pruning (see count_strand): on when asked for and no counter can wrap
+    const bool bound = prune && n < (1u << NP);
     uint32_t best = 0;
     for (int strand = 0; strand < 2; ++strand) {
+        // a strand counts at most n per bin: once the first strand's maximum has reached n the second cannot exceed it
+        if (bound && strand == 1 && best >= n) break;  // wave-uniform
         Planes<NP> pl[WPL];
 #pragma unroll
         for (int w = 0; w < WPL; ++w) pl[w].clear();
         const bool left = count_strand<LG, WPL, NP, H, NT, false, EARLY>(pl, f, lc, seq, len, n, strand, 0u, (uint32_t)TileShape<LG>::ITEMS, 0,
-                                                                         TileShape<LG>::STEPS / 8, s_stage[wave], lane, PhaseCfg{0, 0, 0, 0, 0}, stop_at);
+                                                                         TileShape<LG>::STEPS / 8, s_stage[wave], lane, PhaseCfg{0, 0, 0, 0, 0}, stop_at,
+                                                                         bound ? best : kNoBound);
         const uint32_t m = planes_max<NP, WPL>(pl, lc.valid);
         best = m > best ? m : best;
         if (EARLY && left) break;  // wave-uniform
@@ -1997,12 +2052,12 @@ static hipError_t launch_count_nt(const CountLaunch &a, hipStream_t st)
             early.nf = a.early_nf;
             early.fi[0] = a.early_fi;
             hipLaunchKernelGGL((ibf_count_max_kernel<LG, WPL, NP, H, NT, true>), grid, dim3(64 * kWavesPerBlock), 0, st, set, a.src,
-                               a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, early);
+                               a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, early, (uint32_t)a.bound_prune);
             return hipGetLastError();
         }
     }
     hipLaunchKernelGGL((ibf_count_max_kernel<LG, WPL, NP, H, NT>), grid, dim3(64 * kWavesPerBlock), 0, st, set, a.src,
-                       a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, early);
+                       a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, early, (uint32_t)a.bound_prune);
     return hipGetLastError();
 }
 
