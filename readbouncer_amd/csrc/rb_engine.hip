@@ -445,13 +445,21 @@ static uint64_t hbm_stride(uint64_t W)
     return (W + 15) / 16 * 16;
 }
 
-static int make_dev_desc(const rb_ibf_info &g, const uint64_t *d_words, uint64_t stride, IbfDev *d)
+// the geometries the kernels serve; dibf_alloc asks before it allocates anything, so a refused filter costs no HBM
+static int check_dev_geometry(const rb_ibf_info &g)
 {
     if (g.n_hash > rbspec::kMaxHash) return rb::fail(RB_ERR_UNSUPPORTED, "more than 8 hash functions");
     if (g.kmer_size > rbspec::kMaxKmer) return rb::fail(RB_ERR_UNSUPPORTED, "k-mer size above 32");
     if (g.n_blocks == 0) return rb::fail(RB_ERR_INVALID_ARG, "filter has no blocks (n_bits smaller than one block)");
     if (g.n_blocks >= (1ULL << 32)) return rb::fail(RB_ERR_UNSUPPORTED, "more than 2^32-1 blocks");
     if (g.n_bins >= (1ULL << 31)) return rb::fail(RB_ERR_UNSUPPORTED, "too many bins");
+    return RB_OK;
+}
+
+static int make_dev_desc(const rb_ibf_info &g, const uint64_t *d_words, uint64_t stride, IbfDev *d)
+{
+    const int st = check_dev_geometry(g);
+    if (st != RB_OK) return st;
     d->words = d_words;
     d->n_blocks = (uint32_t)g.n_blocks;
     const bool pow2 = (g.n_blocks & (g.n_blocks - 1)) == 0;
@@ -473,6 +481,7 @@ static uint64_t dibf_device_words(const rb_dibf *f) { return f->geo.n_blocks * f
 static int dibf_alloc(int device, const rb_ibf_info &g, bool zero, rb_dibf **out, bool defer_settle = false)
 {
     int st = check_device(device);
+    if (st == RB_OK) st = check_dev_geometry(g);
     if (st != RB_OK) return st;
     rb_dibf *f = new (std::nothrow) rb_dibf();
     if (!f) return rb::fail(RB_ERR_NOMEM, "alloc");
