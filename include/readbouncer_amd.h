@@ -256,6 +256,42 @@ RB_API int rb_pack_reads(const char *seqs, const uint64_t *offsets, const uint32
                          uint64_t *packed_offsets, uint8_t *nmask, uint64_t *nmask_offsets, uint64_t *packed_bytes,
                          uint64_t *nmask_bytes);
 
+/* ---- locate: WHICH bin and strand a read matched, and how many bins hit ---------------------------
+ * The reference has no such call.  It computes everything this reports and throws it away: count_matches counts both
+ * strands per bin (src/IBF/IBFClassify.cpp:149-150), max_matches keeps only the maximum over bins (:48-71) and
+ * select_matches leaves at the first bin with fwd >= t or rev >= t (:16-38).  A bin is a fragment_size stretch of a
+ * reference record (src/IBF/IBFBuild.cpp:165-204), so the bin number is a locus.  An opt-in second pass over the work
+ * items the caller selects; it always counts in full, whatever the engine's pruning / early-decision / merge / phased
+ * settings are, and changes nothing rb_classify_batch* returns.  Per (work item, filter), deplete filters first:
+ *   max_count   u16  M = max over bins b of max(fwd[b], rev[b]) -- the out_maxcount of rb_classify_batch for the same read
+ *                    (uint16_t counts: they wrap at 65 536 as seqan::count's vectors do)
+ *   best_bin    i32  the LOWEST bin b with max(fwd[b], rev[b]) == M; -1 when M == 0 or the item's status is not RB_OK
+ *   best_strand u8   0 when fwd[best_bin] == M, else 1 (forward wins a tie); 0 when best_bin == -1
+ *   hit_bins    u32  bins with fwd[b] >= t or rev[b] >= t, t = rb_threshold(length, k, error_rate, significance) as the
+ *                    decision stage reads it (t == 0 counts every bin, a wrapped t of 65 5xx none); 0 when status != RB_OK
+ * and per work item
+ *   status      u8   RB_OK, RB_ERR_BAD_CHUNK (chunk start beyond the read), RB_ERR_INVALID_ARG (longer than max_len),
+ *                    RB_ERR_SHORT_READ (shorter than the k of some filter of the engine)
+ * fwd / rev follow the engine's N rule (rb_engine_set_revcomp_of_n).  A column-sharded engine (rb_engine_set_column_shard,
+ * world > 1) refuses with RB_ERR_INVALID_ARG: a shard sees only its own bins. */
+typedef struct rb_locate_out { /* any member may be NULL, not all */
+    void *max_count;   /* u16 [n_items x n_filters] */
+    void *best_bin;    /* i32 [n_items x n_filters] */
+    void *best_strand; /* u8  [n_items x n_filters] */
+    void *hit_bins;    /* u32 [n_items x n_filters] */
+    void *status;      /* u8  [n_items] */
+} rb_locate_out;
+/* Device pointers, asynchronous on `stream` (NULL = the engine's own stream, synchronised before returning); rb_batch_desc
+ * in full: packed reads, chunk_start / chunk_length, d_read_ids = "only these reads".  Workspaces are the engine's: one
+ * stream per engine, as for rb_classify_batch_device. */
+RB_API int rb_locate_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance,
+                                  const rb_locate_out *d_out, void *stream);
+/* Host buffers.  read_ids (may be NULL) selects the reads to locate: work item j is read read_ids[j], outputs are indexed
+ * by work item; with read_ids == NULL the work items are the n_reads reads and n_items is not looked at. */
+RB_API int rb_locate_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads,
+                           const uint32_t *read_ids, size_t n_items, double error_rate, double significance,
+                           const rb_locate_out *out);
+
 /* bin-sharded operation: restrict the engine to word columns
  * [rank*ceil(W/world) , ...) of every block; out_maxcount then holds PARTIAL maxima that the
  * caller combines with an all-reduce(max) before rb_decide_device. world=1 restores the default. */

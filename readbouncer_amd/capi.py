@@ -24,6 +24,12 @@ class BatchDesc(C.Structure):
                 ("chunk_start", C.c_uint32), ("chunk_length", C.c_uint32), ("d_read_ids", C.c_void_p)]
 
 
+class LocateOut(C.Structure):
+    """rb_locate_out: any member may be NULL, not all"""
+    _fields_ = [("max_count", C.c_void_p), ("best_bin", C.c_void_p), ("best_strand", C.c_void_p), ("hit_bins", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("table_bytes", C.c_uint64), ("block_words", C.c_uint32), ("stride_words", C.c_uint32),
                 ("merged_members", C.c_uint32), ("lanes_per_block_log2", C.c_uint32), ("words_per_lane", C.c_uint32),
@@ -88,6 +94,8 @@ SIGNATURES = {
     "rb_classify_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _dbl, _dbl, _int, _vp, _vp, _vp, _vp]),
     "rb_classify_batch_ptrs": (_int, [_vp, _vp, _vp, _sz, _dbl, _dbl, _int, _vp, _vp, _vp, _vp]),
     "rb_classify_batch_device_ex": (_int, [_vp, C.POINTER(BatchDesc), _dbl, _dbl, _int, _vp, _vp, _vp, _vp, _vp]),
+    "rb_locate_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _dbl, _dbl, C.POINTER(LocateOut), _vp]),
+    "rb_locate_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _dbl, _dbl, C.POINTER(LocateOut)]),
     "rb_pack_reads": (_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "rb_host_alloc": (_int, [_sz, C.POINTER(_vp)]),
     "rb_host_free": (None, [_vp]),
@@ -439,6 +447,34 @@ class Engine:
                          d_read_ids)
         _check(lib().rb_classify_batch_device_ex(self.h, C.byref(desc), error_rate, significance, mode, d_maxcount, d_best,
                                                  d_decision, d_status, stream), "rb_classify_batch_device_ex")
+
+    def locate(self, seqs, offsets, lens, read_ids=None, error_rate=0.1, significance=0.95):
+        """which bin and strand each selected read matched and how many bins hit (rb_locate_batch): host buffers in, a dict of host
+        numpy arrays out -- max_count[n, nf] u16, best_bin[n, nf] i32, best_strand[n, nf] u8, hit_bins[n, nf] u32, status[n] u8, one
+        row per work item (read_ids[j], or every read when read_ids is None)"""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        ids = None if read_ids is None else np.ascontiguousarray(read_ids, dtype=np.uint32)
+        n = len(lens) if ids is None else len(ids)
+        nf = self.nd + self.nt
+        res = {"max_count": np.zeros((n, nf), dtype=np.uint16), "best_bin": np.full((n, nf), -1, dtype=np.int32),
+               "best_strand": np.zeros((n, nf), dtype=np.uint8), "hit_bins": np.zeros((n, nf), dtype=np.uint32),
+               "status": np.zeros(n, dtype=np.uint8)}
+        out = LocateOut(*[_ptr(res[k]) for k in ("max_count", "best_bin", "best_strand", "hit_bins", "status")])
+        _check(lib().rb_locate_batch(self.h, _ptr(seqs), _ptr(offsets), _ptr(lens), len(lens), None if ids is None else _ptr(ids), n,
+                                     error_rate, significance, C.byref(out)), "rb_locate_batch")
+        return res
+
+    def locate_device(self, d_seqs, d_offsets, d_lens, n_items, max_len, d_nmask=None, d_nmask_offsets=None, chunk_start=0,
+                      chunk_length=0, d_read_ids=None, error_rate=0.1, significance=0.95, d_max_count=None, d_best_bin=None,
+                      d_best_strand=None, d_hit_bins=None, d_status=None, stream=None):
+        """raw device pointers like classify_device_ex (rb_locate_batch_device); any output may be None, not all"""
+        desc = BatchDesc(d_seqs, d_offsets, d_lens, n_items, max_len, d_nmask, d_nmask_offsets, chunk_start, chunk_length,
+                         d_read_ids)
+        out = LocateOut(d_max_count, d_best_bin, d_best_strand, d_hit_bins, d_status)
+        _check(lib().rb_locate_batch_device(self.h, C.byref(desc), error_rate, significance, C.byref(out), stream),
+               "rb_locate_batch_device")
 
     def decide_device(self, d_maxcount, d_lens, n_reads, max_len, error_rate=0.1, significance=0.95,
                       mode=RB_MODE_CHECK_UNBLOCK, d_best=None, d_decision=None, d_status=None, stream=None):

@@ -191,6 +191,38 @@ struct FoldJob {
     DecideParams P;
 };
 
+// locate pass (rb_locate_batch_device; rb_kernels.hip, ibf_locate_kernel): what one column slice of a filter knows about a work item ...
+struct LocatePart {
+    uint32_t max_count;
+    uint32_t first_bin;  // lowest bin at max_count in this slice (undefined when max_count == 0)
+    uint32_t strand;
+    uint32_t hit_bins;   // bins of this slice with fwd >= t or rev >= t
+};
+// ... the caller's output arrays (any may be nullptr) ...
+struct LocateOut {
+    uint16_t *max_count;
+    int32_t *best_bin;
+    uint8_t *best_strand;
+    uint32_t *hit_bins;
+    uint8_t *status;
+};
+// ... and one filter's launch: always the plain form over the filter's own table, counted in full
+struct LocateLaunch {
+    IbfDev f;
+    ReadSrc src;
+    uint32_t n_items;
+    uint32_t col_begin, col_end;
+    uint32_t n_slices;
+    int lg, wpl, planes, nt;
+    const uint16_t *thr;  // the decision kernel's table [thr_len][nf][2]
+    uint32_t thr_len, nf, fi;
+    LocatePart *part;     // [n_slices][n_items]
+};
+hipError_t launch_ibf_locate(const LocateLaunch &a, hipStream_t st);
+hipError_t launch_reduce_locate_slices(const LocatePart *part, uint32_t n_slices, uint32_t n_items, const uint32_t *lens,
+                                       const uint8_t *pre_status, uint32_t max_len, uint32_t min_len, const LocateOut &out, uint32_t nf,
+                                       uint32_t fidx, hipStream_t st);
+
 hipError_t launch_ibf_count_max(const CountLaunch &a, hipStream_t st);
 hipError_t launch_ibf_count_max_merged(const CountLaunch &a, const MergeMap &map, hipStream_t st);
 // block b of a filter (width words at stride s_src, n_bins bins) -> bits [dst_bit, dst_bit + n_bins) of block b of dst (ORed in: dst starts zeroed)

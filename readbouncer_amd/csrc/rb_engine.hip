@@ -407,6 +407,8 @@ struct rb_engine {
     // staging for the host-pointer API
     DevBuf d_seqs, d_offsets, d_lens, d_best, d_decision, d_status;
     DevBuf d_efflens, d_prestatus;  // on-GPU chunking: effective lengths and the bad-chunk status per item
+    DevBuf d_locate_parts;          // locate pass: partial records of the column slices, all filters of a call
+    DevBuf d_locate_io;             // rb_locate_batch: read ids in, the five outputs back
     PinnedBuf h_in, h_out;
     // large host batches: slice i+1 is copied on this stream while slice i is counted on `stream`
     hipStream_t copy_stream = nullptr;
@@ -990,7 +992,7 @@ void rb_engine_destroy(rb_engine *e)
     }
     for (void *r : e->thr_retired_dev) (void)hipFree(r);
     for (PinnedBuf &h : e->thr_retired_host) h.release();
-    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
+    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_locate_parts, &e->d_locate_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
                       &e->d_decision, &e->d_status})
         b->release();
     e->h_in.release();
@@ -2532,6 +2534,194 @@ int rb_classify_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, c
         if (out_decision) RB_HIP(hipMemcpyAsync(out_decision, e->d_decision.p, n, hipMemcpyDeviceToHost, st));
         if (out_status) RB_HIP(hipMemcpyAsync(out_status, e->d_status.p, n, hipMemcpyDeviceToHost, st));
     }
+    RB_HIP(hipStreamSynchronize(st));
+    return RB_OK;
+}
+
+// ---- locate: which bin and strand a read matched, and how many bins hit (no counterpart in the reference; see the boundary header).
+// Always the plain form over each filter's OWN table, counted in full: the engine's pruning / early-decision / merge / phased settings
+// do not reach it.  One launch of ibf_locate_kernel per filter plus the merge of its column slices, in sequence on the call's stream.
+static int locate_device_impl(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, const rb_locate_out *d_out,
+                              void *stream)
+{
+    if (!desc || !d_out) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor or output struct");
+    if (!d_out->max_count && !d_out->best_bin && !d_out->best_strand && !d_out->hit_bins && !d_out->status)
+        return rb::fail(RB_ERR_INVALID_ARG, "rb_locate_out with no output");
+    int rc = check_device(e ? e->device : 0);  // (argument shape first, then the device, then the handle: without a GPU nothing here can work)
+    if (rc != RB_OK) return rc;
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    const size_t n_items = desc->n_items;
+    if (n_items >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    if (n_items == 0) return RB_OK;
+    if (!desc->d_seqs || !desc->d_offsets || !desc->d_lens) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
+    if ((desc->d_nmask == nullptr) != (desc->d_nmask_offsets == nullptr))
+        return rb::fail(RB_ERR_INVALID_ARG, "packed input needs both the N bitmap and its offsets");
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (e->shard_world != 1) return rb::fail(RB_ERR_INVALID_ARG, "locate on a column-sharded engine: a shard sees only its own bins");
+    const size_t nf = e->filters.size();
+    if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
+    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+    const bool chunked = desc->chunk_start != 0 || desc->chunk_length != 0 || desc->d_read_ids != nullptr;
+    const void *d_lens = desc->d_lens;
+    const uint8_t *d_pre_status = nullptr;
+    uint32_t max_len = desc->max_len;
+    if (chunked) {
+        rc = e->d_efflens.ensure(n_items * 4);
+        if (rc == RB_OK) rc = e->d_prestatus.ensure(n_items);
+        if (rc != RB_OK) return rc;
+        RB_HIP(launch_chunk_prep((const uint32_t *)desc->d_lens, (const uint32_t *)desc->d_read_ids, (uint32_t)n_items, desc->chunk_start,
+                                 desc->chunk_length, (uint32_t *)e->d_efflens.p, (uint8_t *)e->d_prestatus.p, st));
+        d_lens = e->d_efflens.p;
+        d_pre_status = (const uint8_t *)e->d_prestatus.p;
+        if (desc->chunk_length && desc->chunk_length < max_len) max_len = desc->chunk_length;
+    }
+    // t of hit_bins: the table the decision kernel reads, entry [len][filter][0]
+    const uint16_t *thr = nullptr;
+    uint32_t thr_len = 0;
+    if ((rc = ensure_thresholds(e, max_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
+    // geometry per filter as the plain kernel cuts it (whole filter: no shard), and one block of partial records for the call
+    std::vector<LocateLaunch> launches(nf);
+    size_t part_records = 0;
+    uint32_t min_len = 0;  // an item shorter than some filter's k is a short read: that filter has nothing to count
+    for (size_t fi = 0; fi < nf; ++fi) {
+        const rb_dibf *f = e->filters[fi];
+        LocateLaunch &a = launches[fi];
+        a = LocateLaunch{};
+        a.f = f->dev;
+        a.f.comp_n = e->revcomp_of_n;
+        a.src.seqs = (const uint8_t *)desc->d_seqs;
+        a.src.offsets = (const uint64_t *)desc->d_offsets;
+        a.src.lens = (const uint32_t *)d_lens;
+        a.src.nmask = (const uint8_t *)desc->d_nmask;
+        a.src.nmask_offsets = (const uint64_t *)desc->d_nmask_offsets;
+        a.src.ids = (const uint32_t *)desc->d_read_ids;
+        a.src.base_off = desc->chunk_start;
+        a.src.max_len = max_len;
+        a.n_items = (uint32_t)n_items;
+        const uint32_t W = (uint32_t)f->geo.bin_width;
+        a.col_begin = 0;
+        a.col_end = W;
+        if (W > 64) {
+            a.wpl = 2; a.lg = 6;
+        } else {
+            a.wpl = 1; a.lg = 0;
+            while ((1u << a.lg) < W) ++a.lg;
+        }
+        const uint32_t slice_words = (1u << a.lg) * a.wpl;
+        a.n_slices = (W + slice_words - 1) / slice_words;
+        const uint32_t kmers = max_len >= f->geo.kmer_size ? max_len - (uint32_t)f->geo.kmer_size + 1 : 0;
+        a.planes = kmers <= 1023 ? 10 : 16;
+        a.nt = f->geo.n_blocks * f->stride * 8 > e->nt_threshold_bytes;
+        a.thr = thr;
+        a.thr_len = thr_len;
+        a.nf = (uint32_t)nf;
+        a.fi = (uint32_t)fi;
+        part_records += (size_t)a.n_slices * n_items;
+        min_len = std::max<uint32_t>(min_len, (uint32_t)f->geo.kmer_size);
+    }
+    if ((rc = e->d_locate_parts.ensure(part_records * sizeof(LocatePart))) != RB_OK) return rc;
+    std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
+    if (e->timing && e->ev_used < ((size_t)1 << 16)) {
+        if (e->ev_used == e->ev_ring.size()) {
+            hipEvent_t a = nullptr, b = nullptr;
+            RB_HIP(hipEventCreate(&a));
+            RB_HIP(hipEventCreate(&b));
+            e->ev_ring.emplace_back(a, b);
+        }
+        evp = &e->ev_ring[e->ev_used++];
+        RB_HIP(hipEventRecord(evp->first, st));
+    }
+    LocateOut out;
+    out.max_count = (uint16_t *)d_out->max_count;
+    out.best_bin = (int32_t *)d_out->best_bin;
+    out.best_strand = (uint8_t *)d_out->best_strand;
+    out.hit_bins = (uint32_t *)d_out->hit_bins;
+    out.status = (uint8_t *)d_out->status;
+    LocatePart *part = (LocatePart *)e->d_locate_parts.p;
+    for (size_t fi = 0; fi < nf; ++fi) {
+        LocateLaunch &a = launches[fi];
+        a.part = part;
+        RB_HIP(launch_ibf_locate(a, st));
+        RB_HIP(launch_reduce_locate_slices(part, a.n_slices, (uint32_t)n_items, (const uint32_t *)d_lens, d_pre_status, max_len, min_len, out,
+                                           (uint32_t)nf, (uint32_t)fi, st));
+        part += (size_t)a.n_slices * n_items;
+    }
+    if (evp) RB_HIP(hipEventRecord(evp->second, st));
+    if (!stream) RB_HIP(hipStreamSynchronize(st));
+    return RB_OK;
+}
+
+int rb_locate_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, const rb_locate_out *d_out,
+                           void *stream)
+{
+    return locate_device_impl(e, desc, error_rate, significance, d_out, stream);
+}
+
+int rb_locate_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *read_ids,
+                    size_t n_items, double error_rate, double significance, const rb_locate_out *out)
+{
+    if (!out) return rb::fail(RB_ERR_INVALID_ARG, "null output struct");
+    if (!out->max_count && !out->best_bin && !out->best_strand && !out->hit_bins && !out->status)
+        return rb::fail(RB_ERR_INVALID_ARG, "rb_locate_out with no output");
+    int rc = check_device(e ? e->device : 0);
+    if (rc != RB_OK) return rc;
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    const size_t n = read_ids ? n_items : n_reads;  // without a selection the work items are the reads
+    if (n == 0) return RB_OK;
+    if (!seqs || !offsets || !lens || n_reads == 0) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
+    if (n >= (1ULL << 31) || n_reads >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    if (read_ids)
+        for (size_t i = 0; i < n; ++i)
+            if (read_ids[i] >= n_reads) return rb::fail(RB_ERR_INVALID_ARG, "read id beyond the batch");
+    uint64_t hi = 0, lo = ~0ULL;
+    uint32_t max_len = 0;
+    for (size_t i = 0; i < n_reads; ++i) {
+        hi = std::max<uint64_t>(hi, offsets[i] + lens[i]);
+        lo = std::min<uint64_t>(lo, offsets[i]);
+        max_len = std::max(max_len, lens[i]);
+    }
+    const size_t nf = e->filters.size();
+    const uint64_t span = hi - lo;
+    hipStream_t st = e->stream;
+    std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
+    // staging: u32 ids[n] | i32 best_bin[n*nf] | u32 hit_bins[n*nf] | u16 max_count[n*nf] | u8 best_strand[n*nf] | u8 status[n]
+    const size_t o_bin = 4 * n, o_hit = o_bin + 4 * n * nf, o_max = o_hit + 4 * n * nf, o_strand = o_max + 2 * n * nf, o_status = o_strand + n * nf;
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        if ((rc = e->d_seqs.ensure(span ? span : 1)) != RB_OK) return rc;
+        if ((rc = e->d_offsets.ensure(n_reads * 8)) != RB_OK) return rc;
+        if ((rc = e->d_lens.ensure(n_reads * 4)) != RB_OK) return rc;
+        if ((rc = e->d_locate_io.ensure(o_status + n)) != RB_OK) return rc;
+    }
+    char *io = (char *)e->d_locate_io.p;
+    if (span) RB_HIP(hipMemcpyAsync(e->d_seqs.p, seqs + lo, span, hipMemcpyHostToDevice, st));
+    RB_HIP(hipMemcpyAsync(e->d_offsets.p, offsets, n_reads * 8, hipMemcpyHostToDevice, st));
+    RB_HIP(hipMemcpyAsync(e->d_lens.p, lens, n_reads * 4, hipMemcpyHostToDevice, st));
+    if (read_ids) RB_HIP(hipMemcpyAsync(io, read_ids, 4 * n, hipMemcpyHostToDevice, st));
+    rb_batch_desc desc;
+    std::memset(&desc, 0, sizeof desc);
+    desc.d_seqs = (const char *)e->d_seqs.p - lo;  // device address of the caller's seqs[0]
+    desc.d_offsets = e->d_offsets.p;
+    desc.d_lens = e->d_lens.p;
+    desc.n_items = n;
+    desc.max_len = max_len;
+    desc.d_read_ids = read_ids ? io : nullptr;
+    rb_locate_out d_out;
+    d_out.max_count = out->max_count ? io + o_max : nullptr;
+    d_out.best_bin = out->best_bin ? io + o_bin : nullptr;
+    d_out.best_strand = out->best_strand ? io + o_strand : nullptr;
+    d_out.hit_bins = out->hit_bins ? io + o_hit : nullptr;
+    d_out.status = out->status ? io + o_status : nullptr;
+    rc = locate_device_impl(e, &desc, error_rate, significance, &d_out, (void *)st);
+    if (rc != RB_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if (out->max_count) RB_HIP(hipMemcpyAsync(out->max_count, io + o_max, 2 * n * nf, hipMemcpyDeviceToHost, st));
+    if (out->best_bin) RB_HIP(hipMemcpyAsync(out->best_bin, io + o_bin, 4 * n * nf, hipMemcpyDeviceToHost, st));
+    if (out->best_strand) RB_HIP(hipMemcpyAsync(out->best_strand, io + o_strand, n * nf, hipMemcpyDeviceToHost, st));
+    if (out->hit_bins) RB_HIP(hipMemcpyAsync(out->hit_bins, io + o_hit, 4 * n * nf, hipMemcpyDeviceToHost, st));
+    if (out->status) RB_HIP(hipMemcpyAsync(out->status, io + o_status, n, hipMemcpyDeviceToHost, st));
     RB_HIP(hipStreamSynchronize(st));
     return RB_OK;
 }

@@ -784,6 +784,160 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     if (lane == 0) out[(size_t)read * out_read_stride + (size_t)slice * out_slice_stride] = (uint16_t)best;
 }
 
+// LOCATE: the opt-in second pass (rb_locate_batch_device) that says WHERE a read matched.  One wave per (work item, column slice) as
+// in the plain kernel above and built from the same pieces -- make_lane_cols, make_base_src, count_strand with no bound, no early
+// exit, no phasing -- so the gather schedule is the measured one; it always counts in full (bound pruning leaves stale counters in
+// dead bins, and a dead bin may still TIE the maximum, so "the first bin at M" does not exist there).  What is new happens after a
+// strand's counters are complete (lanes < 2^LG hold whole counts of their columns: count_strand's closing butterfly):
+//   * M_s, MSB plane first as planes_max, but the candidate mask is kept: its lowest (word column, bit) over the wave is the lowest
+//     bin at M_s (one ballot for the lowest lane that has a candidate, ffs there);
+//   * a bit-sliced c >= t against the wave-uniform uint16_t threshold t of the decision kernel's table (the compare of the pruning
+//     code, one scalar branch per plane); the hit mask is ORed over the two strands -- the only per-lane state that lives across them.
+// The strands combine by the rule "lowest bin b with max(fwd[b], rev[b]) == M, forward wins a tie in that bin": M = max(M_0, M_1);
+// the strand that reaches M alone gives bin and strand; when both do, the lower first bin wins and strand 0 takes an equal bin.
+// A slice writes one partial record; reduce_locate_slices_kernel merges the slices of a filter and applies the per-item status.
+template <int LG, int WPL, int NP, int H, bool NT>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(3, 8))) void ibf_locate_kernel(
+    IbfDev f, uint32_t col_begin, uint32_t col_end, ReadSrc src, uint32_t n_items, uint32_t n_slices, const uint16_t *__restrict__ thr,
+    uint32_t thr_len, uint32_t nf, uint32_t fi, LocatePart *__restrict__ part)
+{
+    __shared__ uint8_t s_stage[kWavesPerBlock][kStageBytes];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const uint64_t witem = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
+    const uint32_t item = (uint32_t)(witem / n_slices);
+    const uint32_t slice = (uint32_t)(witem - (uint64_t)item * n_slices);
+    if (item >= n_items) return;  // wave-uniform; there are no block-level barriers below
+
+    const LaneCols<WPL> lc = make_lane_cols<LG, WPL>(f, lane, col_begin, col_end, slice);
+    uint32_t len;
+    const BaseSrc seq = make_base_src(src, item, &len);
+    const uint32_t n = len >= f.k ? len - f.k + 1 : 0;
+    // the threshold the decision kernel reads for this length and filter, at the caller's error rate
+    const uint32_t tl = len < thr_len ? len : thr_len - 1;
+    const uint32_t t = __builtin_amdgcn_readfirstlane((uint32_t)thr[((size_t)tl * nf + fi) * 2]);
+    const bool group0 = lane < (1 << LG);  // the lane group whose columns are reported (every group holds the same totals)
+    const uint32_t first_col = col_begin + slice * (uint32_t)((1 << LG) * WPL) + (uint32_t)((lane & ((1 << LG) - 1)) * WPL);
+
+    uint64_t hit[WPL];
+#pragma unroll
+    for (int w = 0; w < WPL; ++w) hit[w] = (t == 0) ? lc.valid[w] : 0ULL;
+    uint32_t best = 0, best_bin = 0, best_strand = 0;
+    for (int strand = 0; strand < 2; ++strand) {
+        Planes<NP> pl[WPL];
+#pragma unroll
+        for (int w = 0; w < WPL; ++w) pl[w].clear();
+        count_strand<LG, WPL, NP, H, NT>(pl, f, lc, seq, len, n, strand, 0u, (uint32_t)TileShape<LG>::ITEMS, 0, TileShape<LG>::STEPS / 8,
+                                         s_stage[wave], lane);
+        // ---- the strand's maximum, and the bins that hold it
+        uint64_t cand[WPL];
+#pragma unroll
+        for (int w = 0; w < WPL; ++w) cand[w] = lc.valid[w];
+        uint32_t m = 0;
+#pragma unroll
+        for (int i = NP - 1; i >= 0; --i) {
+            uint64_t c[WPL];
+            bool any = false;
+#pragma unroll
+            for (int w = 0; w < WPL; ++w) {
+                c[w] = cand[w] & pl[w].p[i];
+                any |= (c[w] != 0);
+            }
+            if (__ballot(any) != 0ULL) {  // wave-uniform
+                m |= 1u << i;
+#pragma unroll
+                for (int w = 0; w < WPL; ++w) cand[w] = c[w];
+            }
+        }
+        if (m > 0) {  // wave-uniform
+            bool has = false;
+            uint32_t mine = 0;  // lowest candidate bin of this lane
+#pragma unroll
+            for (int w = WPL - 1; w >= 0; --w) {
+                if (cand[w] != 0ULL) {
+                    has = true;
+                    mine = (first_col + (uint32_t)w) * 64u + (uint32_t)(__ffsll((unsigned long long)cand[w]) - 1);
+                }
+            }
+            // columns rise with the lane number inside a group: the lowest lane of group 0 with a candidate holds the lowest bin
+            const uint64_t who = __ballot(has && group0);
+            const uint32_t first = readlane32(mine, (int)__builtin_amdgcn_readfirstlane((uint32_t)(__ffsll((unsigned long long)who) - 1)));
+            if (m > best || (m == best && first < best_bin)) {  // (strand 0 enters through m > 0 == best; an equal bin stays with strand 0)
+                best_bin = first;
+                best_strand = (uint32_t)strand;
+            }
+            best = m > best ? m : best;
+        }
+        // ---- bins with c >= t, i.e. c > t - 1 (t == 0: every bin, set above; t beyond what NP planes can hold: none)
+        if (t > 0 && t <= (1u << NP) - 1u) {  // wave-uniform
+            const uint32_t tt = t - 1u;
+#pragma unroll
+            for (int w = 0; w < WPL; ++w) {
+                uint64_t gt = 0, eq = lc.valid[w];
+#pragma unroll
+                for (int i = NP - 1; i >= 0; --i) {
+                    if ((tt >> i) & 1u) {  // scalar branch
+                        eq &= pl[w].p[i];
+                    } else {
+                        gt |= eq & pl[w].p[i];
+                        eq &= ~pl[w].p[i];
+                    }
+                }
+                hit[w] |= gt;
+            }
+        }
+    }
+    uint32_t hits = 0;
+#pragma unroll
+    for (int w = 0; w < WPL; ++w) hits += (uint32_t)__popcll(hit[w]);
+    if (!group0) hits = 0;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) hits += shfl32(hits, lane ^ s);
+    if (lane == 0) {
+        rb_u32x4 rec;
+        rec.x = best;
+        rec.y = best_bin;
+        rec.z = best_strand;
+        rec.w = hits;
+        *reinterpret_cast<rb_u32x4 *>(part + ((size_t)slice * n_items + item)) = rec;
+    }
+}
+
+// Merge the column slices of one filter (slices hold rising bins: on equal maxima the earlier slice has the lower bin) and write the
+// outputs the caller asked for.  An item whose status is not RB_OK reports nothing: -1 / 0.  status[] itself is written by the call for
+// filter 0.  One thread per work item.
+__global__ void reduce_locate_slices_kernel(const LocatePart *__restrict__ part, uint32_t n_slices, uint32_t n_items,
+                                            const uint32_t *__restrict__ lens, const uint8_t *__restrict__ pre_status, uint32_t max_len,
+                                            uint32_t min_len, LocateOut out, uint32_t nf, uint32_t fidx)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    uint8_t status = RB_OK;
+    const uint32_t len = lens[i];
+    if (pre_status && pre_status[i] != RB_OK) status = pre_status[i];
+    else if (len > max_len) status = RB_ERR_INVALID_ARG;
+    else if (len < min_len) status = RB_ERR_SHORT_READ;
+    uint32_t m = 0, bin = 0, strand = 0, hits = 0;
+    if (status == RB_OK) {
+        for (uint32_t s = 0; s < n_slices; ++s) {
+            const LocatePart p = part[(size_t)s * n_items + i];
+            if (p.max_count > m || (p.max_count == m && m > 0 && p.first_bin < bin)) {
+                // (an equal bin cannot come from two slices: the second condition only guards the order of the slices)
+                m = p.max_count;
+                bin = p.first_bin;
+                strand = p.strand;
+            }
+            hits += p.hit_bins;
+        }
+    }
+    const size_t o = (size_t)i * nf + fidx;
+    if (out.max_count) out.max_count[o] = (uint16_t)m;
+    if (out.best_bin) out.best_bin[o] = m > 0 ? (int32_t)bin : -1;
+    if (out.best_strand) out.best_strand[o] = m > 0 ? (uint8_t)strand : (uint8_t)0;
+    if (out.hit_bins) out.hit_bins[o] = hits;
+    if (out.status && fidx == 0) out.status[i] = status;
+}
+
 // Throughput form over a MERGED table: several narrow filters of one hash geometry (same noOfBlocks, k and h -- every filter
 // the reference builds with one fragment_size has them: noOfBits = BinSizeBits x 64 x binWidth, so noOfBlocks = BinSizeBits
 // whatever the bin count, src/IBF/IBFBuild.cpp:404-413) hash a k-mer to the SAME block number, so their blocks can sit side
@@ -2417,6 +2571,62 @@ hipError_t launch_invert_words(const uint64_t *src, uint64_t *dst, uint64_t n_wo
     uint64_t blocks = (n_words + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;
     hipLaunchKernelGGL(invert_words_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, src, dst, n_words);
+    return hipGetLastError();
+}
+
+// locate: the (LG, WPL) cases of dispatch_geometry; non-temporal builds for blocks of a whole wave only (the tables beyond the Infinity
+// Cache are the wide ones; a narrow table of that size keeps the default cache policy, which costs speed, not results)
+template <int LG, int WPL, int NP, int H>
+static hipError_t launch_locate_nt(const LocateLaunch &a, hipStream_t st)
+{
+    const uint64_t items = (uint64_t)a.n_items * a.n_slices;
+    dim3 grid((uint32_t)((items + kWavesPerBlock - 1) / kWavesPerBlock));
+    if constexpr (LG == 6) {
+        if (a.nt) {
+            hipLaunchKernelGGL((ibf_locate_kernel<LG, WPL, NP, H, true>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.col_begin, a.col_end, a.src,
+                               a.n_items, a.n_slices, a.thr, a.thr_len, a.nf, a.fi, a.part);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((ibf_locate_kernel<LG, WPL, NP, H, false>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.col_begin, a.col_end, a.src,
+                       a.n_items, a.n_slices, a.thr, a.thr_len, a.nf, a.fi, a.part);
+    return hipGetLastError();
+}
+
+template <int NP, int H>
+static hipError_t dispatch_locate(const LocateLaunch &a, hipStream_t st)
+{
+    if (a.wpl == 2) return launch_locate_nt<6, 2, NP, H>(a, st);
+    switch (a.lg) {
+    case 0: return launch_locate_nt<0, 1, NP, H>(a, st);
+    case 1: return launch_locate_nt<1, 1, NP, H>(a, st);
+    case 2: return launch_locate_nt<2, 1, NP, H>(a, st);
+    case 3: return launch_locate_nt<3, 1, NP, H>(a, st);
+    case 4: return launch_locate_nt<4, 1, NP, H>(a, st);
+    case 5: return launch_locate_nt<5, 1, NP, H>(a, st);
+    default: return launch_locate_nt<6, 1, NP, H>(a, st);
+    }
+}
+
+hipError_t launch_ibf_locate(const LocateLaunch &a, hipStream_t st)
+{
+    if (a.n_items == 0) return hipSuccess;
+    if (!a.thr || a.thr_len == 0 || !a.part || a.n_slices == 0 || (a.wpl != 1 && a.wpl != 2) || a.lg < 0 || a.lg > 6) return hipErrorInvalidValue;
+    // every column the grid reaches lies inside the filter, every slice has a record
+    if (a.col_end > a.f.bin_width || a.col_begin > a.col_end ||
+        (uint64_t)a.n_slices * (uint64_t)((1u << a.lg) * (uint32_t)a.wpl) < (uint64_t)(a.col_end - a.col_begin))
+        return hipErrorInvalidValue;
+    if (a.f.n_hash == 3) return a.planes <= 10 ? dispatch_locate<10, 3>(a, st) : dispatch_locate<16, 3>(a, st);
+    return dispatch_locate<16, 0>(a, st);
+}
+
+hipError_t launch_reduce_locate_slices(const LocatePart *part, uint32_t n_slices, uint32_t n_items, const uint32_t *lens,
+                                       const uint8_t *pre_status, uint32_t max_len, uint32_t min_len, const LocateOut &out, uint32_t nf,
+                                       uint32_t fidx, hipStream_t st)
+{
+    if (n_items == 0) return hipSuccess;
+    hipLaunchKernelGGL(reduce_locate_slices_kernel, dim3((n_items + 255) / 256), dim3(256), 0, st, part, n_slices, n_items, lens, pre_status,
+                       max_len, min_len, out, nf, fidx);
     return hipGetLastError();
 }
 

@@ -42,6 +42,48 @@ struct ClassificationResults
     uint64_t readCounter = 0;
 } ClassificationResults_;
 
+// build --write-bin-map: beside <name>.ibf, <name>.bins.tsv with one line per bin -- the fragment of which record it holds.  A bin is a
+// fragment_size stretch of a reference record (src/IBF/IBFBuild.cpp:165-204), so the table turns the bin numbers of
+// classify --report-bins into loci.  No counterpart in the reference.
+static bool g_write_bin_map = false;
+static void write_bin_map(const std::string& path, const std::vector<interleave::RefSeq>& records, const interleave::IBFConfig& config)
+{
+    std::ofstream out(path);
+    if (!out) throw std::runtime_error("Unable to open the file: " + path);
+    out << "# start / end are positions in the record AFTER cutOutNNNs (every N removed): the sequence the reference fragments\n";
+    out << "bin\trecord_id\tstart\tend\n";
+    uint64_t bin = 0;
+    std::vector<uint64_t> s, e;
+    for (const interleave::RefSeq& r : records) {  // the records and the order of IBF::create_filter
+        if (r.seq.size() < config.kmer_size) continue;
+        std::string c(r.seq.size(), '\0');
+        c.resize(rb_cut_out_nnns(r.seq.data(), r.seq.size(), &c[0]));
+        const size_t n = rb_fragment_bounds(c.size(), config.fragment_length, config.kmer_size, config.overlap_length, nullptr, nullptr, 0);
+        s.resize(n);
+        e.resize(n);
+        rb_fragment_bounds(c.size(), config.fragment_length, config.kmer_size, config.overlap_length, s.data(), e.data(), n);
+        for (size_t i = 0; i < n; ++i) out << bin++ << '\t' << r.seqid << '\t' << s[i] << '\t' << e[i] << '\n';
+    }
+}
+
+// classify --bin-map: bin -> record id of one filter, from the table above
+static std::vector<std::string> read_bin_map(const std::string& path)
+{
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("Unable to open the file: " + path);
+    std::vector<std::string> rec;
+    std::string line;
+    while (std::getline(in, line)) {
+        if (line.empty() || line[0] == '#' || line.compare(0, 4, "bin\t") == 0) continue;
+        const size_t a = line.find('\t'), b = a == std::string::npos ? a : line.find('\t', a + 1);
+        if (b == std::string::npos) throw std::runtime_error("not a bin map: " + path);
+        const size_t bin = (size_t)std::stoull(line.substr(0, a));
+        if (bin >= rec.size()) rec.resize(bin + 1);
+        rec[bin] = line.substr(a + 1, b - a - 1);
+    }
+    return rec;
+}
+
 // buildIBF, src/main/ibfbuild.hpp:21-59
 static interleave::TIbf buildIBF(ConfigReader config_reader, const std::string reference_file,
                                  const std::string bloom_filter_output_path)
@@ -67,6 +109,11 @@ static interleave::TIbf buildIBF(ConfigReader config_reader, const std::string r
     const auto t0 = std::chrono::steady_clock::now();
     interleave::FilterStats stats = filter.create_filter(config, records);
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (g_write_bin_map) {
+        std::filesystem::path map_path(bloom_filter_output_path);
+        map_path.replace_extension("bins.tsv");
+        write_bin_map(map_path.string(), records, config);
+    }
     // where a build's time goes (profiles/cli_build.py reads this line): parsing the FASTA, cutOutNNNs + sizing, the filter's allocation
     // in HBM, the concatenation, rb_dibf_insert (H2D + the insert kernel), download + file
     std::cout << "BUILD_PHASES file=" << reference_file << " parse_s=" << parse_s << " load_seq_s=" << stats.timeLoadSeq
@@ -216,6 +263,7 @@ struct ReadState
 {
     bool classified = false, failed = false;
     int best = -1;
+    std::string bin_rows;  // --report-bins: this read's lines of classified_bins.tsv
 };
 
 // host pipeline knobs (command line)
@@ -237,6 +285,8 @@ struct IngestOptions
     size_t segment_mb = 32;      // file bytes per parsed segment (one GPU call of ~65 k reads of 250 bp; the page-locked staging blocks scale with it)
     size_t segment_bytes = 0;    // tests: segments far smaller than a megabyte (0 = segment_mb)
     size_t live_batch = 64;      // usage "target" replay: chunks per micro-batch
+    bool report_bins = false;    // --report-bins: locate the reads every chunk classified (rb_locate_batch) and write classified_bins.tsv
+    std::vector<std::string> bin_maps;  // --bin-map FILE (may repeat): <filter name>.bins.tsv of build --write-bin-map -> a record_id column
     size_t bytes() const { return segment_bytes ? segment_bytes : (segment_mb << 20); }
 };
 
@@ -290,6 +340,28 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                 std::cerr << "ERROR: Unable to open the file: " << outfile.string() << std::endl;
                 return;
             }
+        }
+        // --report-bins: <output_directory>/classified_bins.tsv, one line per (classified read, filter that matched it), in file order
+        std::ofstream bins_out;
+        std::vector<const interleave::IBFMeta*> all_filters;
+        std::vector<std::vector<std::string>> bin_records;  // per filter: bin -> record id (empty: no map given)
+        if (opt.report_bins) {
+            if (multi) throw std::runtime_error("--report-bins works on one device");
+            for (const interleave::IBFMeta& f : DepletionFilters) all_filters.push_back(&f);
+            for (const interleave::IBFMeta& f : TargetFilters) all_filters.push_back(&f);
+            bin_records.resize(all_filters.size());
+            for (const std::string& path : opt.bin_maps) {
+                std::string stem = std::filesystem::path(path).filename().string();
+                const size_t cut = stem.find(".bins.tsv");
+                if (cut != std::string::npos) stem.resize(cut);
+                bool used = false;
+                for (size_t fi = 0; fi < all_filters.size(); ++fi)
+                    if (all_filters[fi]->name == stem) { bin_records[fi] = read_bin_map(path); used = true; }
+                if (!used) throw std::runtime_error("--bin-map " + path + ": no filter named " + stem);
+            }
+            bins_out.open(std::filesystem::path(config.output_dir) / "classified_bins.tsv");
+            if (!bins_out) { std::cerr << "ERROR: Unable to open the file: classified_bins.tsv" << std::endl; return; }
+            bins_out << "read_id\tfilter\tbest_bin\tstrand\tmax_count\tthreshold\thit_bins\tchunk" << (opt.bin_maps.empty() ? "" : "\trecord_id") << '\n';
         }
         seqio::MappedFile mapped(read_file.string());
         if (!mapped.is_open()) {
@@ -419,14 +491,50 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                             multi ? multi->classify_flat(Conf, base, offs.data(), lens.data(), idx.size(), RB_MODE_CLASSIFY_CHUNK)
                                   : interleave::classify_batch_flat(DepletionFilters, TargetFilters, Conf, base, offs.data(),
                                                                     lens.data(), idx.size(), RB_MODE_CLASSIFY_CHUNK);
+                        std::vector<uint32_t> located;  // --report-bins: the work items this chunk classified
                         for (size_t j = 0; j < idx.size(); ++j) {
                             ReadState& st = state[idx[j]];
                             if (res.status[j] != RB_OK) { st.failed = true; continue; }  // exception -> failed++ (:306-316)
                             if (res.decision[j]) {
                                 st.classified = true;
                                 st.best = target ? res.best_target[j] : -1;
+                                if (opt.report_bins) located.push_back((uint32_t)j);
                             } else {
                                 next.push_back(idx[j]);
+                            }
+                        }
+                        if (!located.empty()) {
+                            const size_t nf = all_filters.size(), nl = located.size();
+                            std::vector<uint16_t> mc(nl * nf);
+                            std::vector<int32_t> bb(nl * nf);
+                            std::vector<uint8_t> bs(nl * nf), ls(nl);
+                            std::vector<uint32_t> hb(nl * nf);
+                            rb_locate_out lo{mc.data(), bb.data(), bs.data(), hb.data(), ls.data()};
+                            interleave::throw_status(rb_locate_batch(interleave::detail::engine_for(DepletionFilters, TargetFilters), base, offs.data(),
+                                                                     lens.data(), idx.size(), located.data(), nl, Conf.error_rate, Conf.significance, &lo),
+                                                     "rb_locate_batch");
+                            for (size_t q = 0; q < nl; ++q) {
+                                if (ls[q] != RB_OK) continue;
+                                const size_t j = located[q];
+                                const seqio::Record& r = recs[idx[j]];
+                                size_t w = 0;
+                                while (w < r.id_len && r.id[w] != ' ' && r.id[w] != '\t') ++w;
+                                std::string& rows = state[idx[j]].bin_rows;
+                                for (size_t fi = 0; fi < nf; ++fi) {
+                                    // a line per filter that matched the chunk: max_matches' predicate, count >= threshold (and a count at all)
+                                    const uint16_t t = rb_threshold(lens[j], all_filters[fi]->filter.kmerSize, Conf.error_rate, Conf.significance);
+                                    const uint16_t m = mc[q * nf + fi];
+                                    if (m == 0 || m < t) continue;
+                                    rows.append(r.id, w);
+                                    rows += '\t' + all_filters[fi]->name + '\t' + std::to_string(bb[q * nf + fi]) + '\t' + (bs[q * nf + fi] ? '-' : '+') + '\t' +
+                                            std::to_string(m) + '\t' + std::to_string(t) + '\t' + std::to_string(hb[q * nf + fi]) + '\t' + std::to_string(c);
+                                    if (!opt.bin_maps.empty()) {
+                                        const std::vector<std::string>& map = bin_records[fi];
+                                        const int32_t b = bb[q * nf + fi];
+                                        rows += '\t' + ((b >= 0 && (size_t)b < map.size() && !map[b].empty()) ? map[b] : std::string("-"));
+                                    }
+                                    rows += '\n';
+                                }
                             }
                         }
                     }
@@ -500,6 +608,8 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                         found += so.found;
                         failed += (uint16_t)so.failed;
                         for (const std::string& l : so.error_lines) log_line("error", l);
+                        if (opt.report_bins)
+                            for (const ReadState& rs : state) bins_out << rs.bin_rows;
                         for (size_t f = 0; f < TargetFilters.size(); ++f) TargetFilters[f].classified += so.per_target[f];
                         ++write_seq;
                     }
@@ -733,6 +843,9 @@ int main(int argc, char const* argv[])
         else if (!std::strcmp(argv[i], "--ingest-threads") && i + 1 < argc) opt.threads = (unsigned)std::max(1, std::stoi(argv[++i]));
         else if (!std::strcmp(argv[i], "--classify-threads") && i + 1 < argc) opt.classify_threads = (unsigned)std::max(1, std::stoi(argv[++i]));
         else if (!std::strcmp(argv[i], "--calibrate")) opt.calibrate = true;
+        else if (!std::strcmp(argv[i], "--report-bins")) opt.report_bins = true;
+        else if (!std::strcmp(argv[i], "--write-bin-map")) g_write_bin_map = true;
+        else if (!std::strcmp(argv[i], "--bin-map") && i + 1 < argc) opt.bin_maps.push_back(argv[++i]);
         // tables of 1 GiB and more are placed by trial (up to five allocations probed, 1-2 s at load time): 1 switches it off
         else if (!std::strcmp(argv[i], "--placement-tries") && i + 1 < argc) {
             if (rb_set_placement_tries(std::stoi(argv[++i])) != RB_OK) { std::cerr << "ERROR: --placement-tries 0 .. 8" << std::endl; return 1; }
@@ -769,6 +882,9 @@ int main(int argc, char const* argv[])
         else if (!std::strcmp(argv[i], "--help") || !std::strcmp(argv[i], "-h")) {
             std::cout << "readbouncer_amd --config <file.toml> [--dump-config] [--batch-reads N] [--ingest-threads N] [--classify-threads N] [--segment-mb N] [--mmap-output] [--calibrate] [--placement-tries N] [--revcomp-of-n 3|4] "
                          "[--devices 0,1,...] [--parse-stats file]\n"
+                         "  usage build:    [--write-bin-map]  beside every <name>.ibf, <name>.bins.tsv: bin -> record id and fragment bounds\n"
+                         "  usage classify: [--report-bins]  classified_bins.tsv: bin, strand, count and hit bins of every classified read\n"
+                         "                  [--bin-map <name>.bins.tsv ...]  adds the record id of the bin to that report\n"
                          "readbouncer_amd --verify-ibf <file.ibf> --reference <file.fasta> [--fragment-size N]" << std::endl;
             return 0;
         }
