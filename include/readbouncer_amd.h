@@ -156,6 +156,44 @@ typedef struct rb_ibf_compare {
     uint64_t payload_bits;  /* noOfBlocks * noOfBins: the positions insertKmer can reach */
 } rb_ibf_compare;
 RB_API int rb_dibf_compare(const rb_dibf *file_filter, const rb_dibf *rebuilt, rb_ibf_compare *out);
+
+/* ---- how full is each bin, and what false-positive rate does that mean -------------------------------
+ * The reference sizes a filter for max_fp = 0.01 (src/IBF/IBFConfig.hpp:77; calculate_filter_size_bits,
+ * src/IBF/IBFBuild.cpp:404-413) under the assumption that every bin holds fragment_size - k + 1 k-mers, and reports bins only
+ * by number (print_build_stats / print_load_stats, src/IBF/IBF.hpp:340-341); nothing holds a filter that was updated
+ * (update_filter, IBFBuild.cpp:223-321) or written elsewhere to that assumption.  One streaming pass over the resident table
+ * counts, per bin, the blocks whose bit is set:
+ *   out[j] = #{ b < noOfBlocks : bit (b, j) set },  j < noOfBins
+ * -- the block payload only (the positions rb_ibf_compare::payload_bits names): padding words of the HBM layout and bits at or
+ * beyond noOfBins are never counted.  It reads the filter's own table (never an engine's merged copy), needs no engine and
+ * touches no engine's workspace.  Host form: out_bits is host memory, u64 [n_bins]. */
+RB_API int rb_dibf_bin_occupancy(const rb_dibf *f, uint64_t *out_bits);
+/* Device form of the same count (what max_fp, src/IBF/IBFConfig.hpp:77, is to be held against): d_out_bits is a device pointer (u64 [n_bins]) on the filter's device; it is zeroed and filled asynchronously on
+ * `stream` (a hipStream_t).  stream == NULL: the pass runs on a stream of its own, which is synchronised before returning -- a non-blocking stream, NOT ordered
+ * after work the caller has pending on the default stream or anywhere else: such work must have completed before the call.  The
+ * filter's bits must be complete on `stream` (work that writes them on another stream -- rb_dibf_insert and the other builders
+ * synchronise by themselves -- has to be ordered before this call by the caller); d_out_bits may be read once `stream` has passed. */
+RB_API int rb_dibf_bin_occupancy_device(const rb_dibf *f, void *d_out_bits, void *stream);
+
+typedef struct rb_bin_occupancy_summary {
+    uint64_t n_bins, n_blocks, n_hash;
+    uint64_t bits_total;          /* == rb_ibf_compare::file_bits of the same filter */
+    uint64_t empty_bins;          /* bins with no bit set */
+    uint64_t max_bits;  uint64_t max_bin;     /* the fullest bin, lowest index on a tie */
+    uint64_t min_bits;  uint64_t min_bin;     /* the emptiest NON-empty bin, lowest index on a tie; 0 / 0 when all are empty */
+    double   mean_load, max_load; /* bits / n_blocks; the mean over non-empty bins */
+    double   mean_fpr,  max_fpr;  /* load ^ n_hash; the mean over non-empty bins */
+    uint64_t bins_over_max_fp;    /* bins with fpr > max_fp */
+} rb_bin_occupancy_summary;
+/* pure host arithmetic on a count vector: works without a GPU.  max_fp: the reference's default is 0.01 (IBFConfig.hpp:77).
+ * RB_ERR_INVALID_ARG when n_blocks or n_hash is 0. */
+RB_API int rb_bin_occupancy_summarize(const uint64_t *bits, uint64_t n_bins, uint64_t n_blocks, uint64_t n_hash,
+                                      double max_fp, rb_bin_occupancy_summary *out);
+/* per bin, the three derived figures (any pointer may be NULL): load = bits/n_blocks, fpr = load^h,
+ * est_kmers = -(n_blocks / h) * ln(1 - load)  (distinct k-mers the bin holds, the usual Bloom estimate -- the inverse of the
+ * sizing formula of IBFBuild.cpp:404-413; +inf at load 1) */
+RB_API int rb_bin_occupancy_derive(const uint64_t *bits, uint64_t n_bins, uint64_t n_blocks, uint64_t n_hash,
+                                   double *load, double *fpr, double *est_kmers);
 /* Text of what the last rb_ibf_open / rb_dibf_open / rb_is_ibf_file on this thread found odd about a file that still
  * parsed (non-zero spare metadata word, a hash-function count or k-mer size the reference never writes, tail bits set
  * beyond the last block); empty string when there was nothing. */

@@ -321,6 +321,27 @@ public:
         return rep;
     }
 
+    // Not in the reference, which prints a filter's statistics by bin NUMBER only (print_build_stats / print_load_stats,
+    // src/IBF/IBF.hpp:340-341): how full each bin of the loaded or built filter is -- per bin the blocks whose bit is set, taken in one
+    // pass over the table in HBM (rb_dibf_bin_occupancy) -- and what false-positive rate that means against config.max_fp.
+    struct BinOccupancy
+    {
+        std::vector<uint64_t> bits;  // [noOfBins]
+        rb_bin_occupancy_summary summary{};
+    };
+    BinOccupancy bin_occupancy(double max_fp = 0.01)
+    {
+        if (!filter.handle()) throw NullFilterException("bin_occupancy: no filter loaded or built");
+        BinOccupancy r;
+        r.bits.assign(filter.noOfBins, 0);
+        throw_status(rb_dibf_bin_occupancy(filter.handle(), r.bits.data()), "rb_dibf_bin_occupancy");
+        rb_ibf_info i;
+        throw_status(rb_dibf_get_info(filter.handle(), &i), "rb_dibf_get_info");
+        throw_status(rb_bin_occupancy_summarize(r.bits.data(), r.bits.size(), i.n_blocks, i.n_hash, max_fp, &r.summary),
+                     "rb_bin_occupancy_summarize");
+        return r;
+    }
+
     // IBF::update_filter, IBFBuild.cpp:223-321: load update_filter_file, resizeBins(old + new), add the new
     // sequences starting at bin id totalBinsFile, store back to update_filter_file
     FilterStats update_filter(IBFConfig& config, const std::vector<RefSeq>& records)

@@ -68,6 +68,15 @@ RB_API int rb_live_replay_arrivals(rb_live *lv, const uint32_t *read_ids, const 
  * Never done on a device where an engine of this process is alive (see rb_dibf_placement_cost).  Process-wide; results never depend on it.  rb_dibf_placement: how many allocations were probed for this filter (0: not placed by
  * trial), what the kept one and the slowest one delivered in GB/s. */
 RB_API int rb_set_placement_tries(int tries);
+/* How rb_dibf_bin_occupancy[_device] cuts a table, for every later pass of this process: at most max_workgroups_per_slice workgroups
+ * (16 waves each) per column slice and no chunk shorter than min_chunk_rows wave rows; 0 = the built-in rule (one workgroup per CU,
+ * chunks of at least 256 rows).  A wave flushes its counter planes after every chunk and a chunk never exceeds 4 080 rows, so with few
+ * workgroups a table of a hundred MiB walks full-length chunks, several per wave -- what a table of 16 GiB does by itself.  Counts
+ * never depend on it; tests and experiments. */
+RB_API void rb_set_bin_occupancy_grid(uint32_t max_workgroups_per_slice, uint32_t min_chunk_rows);
+/* table size beyond which the library reads with non-temporal loads: the default of rb_engine_set_nt_threshold and the rule of the
+ * passes that have no engine (rb_dibf_bin_occupancy) */
+RB_API uint64_t rb_nt_threshold_default(void);
 RB_API int rb_dibf_placement(const rb_dibf *f, uint32_t *tries, double *kept_gbps, double *worst_gbps);
 /* What the trial cost for this filter: seconds spent allocating and probing the candidates, seconds waited afterwards until the kept
  * table probed as in the trial (bounded by 3 s; the driver clears the freed candidates in the background), the most HBM the candidates

@@ -43,6 +43,13 @@ class IbfCompare(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("file_bits", "rebuilt_bits", "new_bits", "payload_bits")]
 
 
+class BinOccupancySummary(C.Structure):
+    """rb_bin_occupancy_summary"""
+    _fields_ = ([(n, C.c_uint64) for n in ("n_bins", "n_blocks", "n_hash", "bits_total", "empty_bins", "max_bits", "max_bin",
+                                           "min_bits", "min_bin")] +
+                [(n, C.c_double) for n in ("mean_load", "max_load", "mean_fpr", "max_fpr")] + [("bins_over_max_fp", C.c_uint64)])
+
+
 class IbfInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in
                 ("n_bins", "n_hash", "kmer_size", "n_bits", "bin_width", "n_blocks", "n_words")]
@@ -111,6 +118,12 @@ SIGNATURES = {
     "rb_pool_destroy": (None, [_vp]),
     "rb_dibf_clone_to": (_int, [_vp, _int, _pp]),
     "rb_dibf_compare": (_int, [_vp, _vp, C.POINTER(IbfCompare)]),
+    "rb_dibf_bin_occupancy": (_int, [_vp, _vp]),
+    "rb_dibf_bin_occupancy_device": (_int, [_vp, _vp, _vp]),
+    "rb_bin_occupancy_summarize": (_int, [_vp, _u64, _u64, _u64, _dbl, C.POINTER(BinOccupancySummary)]),
+    "rb_bin_occupancy_derive": (_int, [_vp, _u64, _u64, _u64, _vp, _vp, _vp]),
+    "rb_set_bin_occupancy_grid": (None, [_u32, _u32]),
+    "rb_nt_threshold_default": (_u64, []),
     "rb_last_warning": (C.c_char_p, []),
     "rb_pool_size": (_sz, [_vp]),
     "rb_pool_set_min_split": (_int, [_vp, _sz]),
@@ -304,6 +317,16 @@ class DeviceIBF:
         c = IbfCompare()
         _check(lib().rb_dibf_compare(self.h, rebuilt.h, C.byref(c)), "rb_dibf_compare")
         return {k: getattr(c, k) for k, _ in IbfCompare._fields_}
+
+    def bin_occupancy(self):
+        """-> np.uint64[n_bins]: blocks of the resident table whose bit for that bin is set (one streaming pass on the GPU)"""
+        out = np.zeros(self.info["n_bins"], dtype=np.uint64)
+        _check(lib().rb_dibf_bin_occupancy(self.h, _ptr(out)), "rb_dibf_bin_occupancy")
+        return out
+
+    def bin_occupancy_device(self, d_out, stream=None):
+        """the same into device memory (u64 [n_bins]); asynchronous on `stream`, synchronised when stream is None"""
+        _check(lib().rb_dibf_bin_occupancy_device(self.h, _ptr(d_out), _ptr(stream)), "rb_dibf_bin_occupancy_device")
 
     def device_words(self):
         return lib().rb_dibf_device_words(self.h)
@@ -799,6 +822,16 @@ class HostBlock:
             self.ptr = None
 
 
+def set_bin_occupancy_grid(max_workgroups_per_slice=0, min_chunk_rows=0):
+    """process-wide: how the per-bin occupancy pass cuts a table (0 / 0 = the built-in rule); counts never depend on it"""
+    lib().rb_set_bin_occupancy_grid(int(max_workgroups_per_slice), int(min_chunk_rows))
+
+
+def nt_threshold_default():
+    """table bytes beyond which the library reads with non-temporal loads"""
+    return int(lib().rb_nt_threshold_default())
+
+
 def set_placement_tries(tries):
     """process-wide: candidates a table of >= 1 GiB is allocated and probed as (default 5; 0 / 1 = off)"""
     _check(lib().rb_set_placement_tries(int(tries)), "rb_set_placement_tries")
@@ -849,6 +882,22 @@ def fragment_bounds(length, fragment_length, k, overlap=1500):
     e = np.zeros(n, dtype=np.uint64)
     lib().rb_fragment_bounds(length, fragment_length, k, overlap, _ptr(s), _ptr(e), n)
     return s, e
+
+
+def bin_occupancy_summary(bits, n_blocks, n_hash, max_fp=0.01):
+    """rb_bin_occupancy_summarize -> dict (host arithmetic, no GPU)"""
+    bits = np.ascontiguousarray(bits, dtype=np.uint64)
+    out = BinOccupancySummary()
+    _check(lib().rb_bin_occupancy_summarize(_ptr(bits), len(bits), n_blocks, n_hash, max_fp, C.byref(out)), "rb_bin_occupancy_summarize")
+    return {k: getattr(out, k) for k, _ in BinOccupancySummary._fields_}
+
+
+def bin_occupancy_derive(bits, n_blocks, n_hash):
+    """rb_bin_occupancy_derive -> (load, fpr, est_kmers), float64[n_bins] each (host arithmetic, no GPU)"""
+    bits = np.ascontiguousarray(bits, dtype=np.uint64)
+    load, fpr, est = (np.zeros(len(bits), dtype=np.float64) for _ in range(3))
+    _check(lib().rb_bin_occupancy_derive(_ptr(bits), len(bits), n_blocks, n_hash, _ptr(load), _ptr(fpr), _ptr(est)), "rb_bin_occupancy_derive")
+    return load, fpr, est
 
 
 def is_ibf_file(path):

@@ -7,6 +7,9 @@
 namespace rb {
 
 constexpr unsigned kMaxFilters = 16;
+// Tables beyond this size are read with non-temporal loads: 2x the 256 MiB Infinity Cache, beyond which caching cannot help.  The
+// default of an engine's nt_threshold_bytes (rb_engine_set_nt_threshold) and the rule of the passes that have no engine.
+constexpr uint64_t kNtThresholdBytes = 512ull << 20;
 
 // by-value kernel argument describing one HBM-resident IBF
 struct IbfDev {
@@ -248,6 +251,20 @@ hipError_t launch_insert(const IbfDev &f, uint64_t *words, const uint8_t *seq, c
 hipError_t launch_restride_blocks(const uint64_t *src, uint32_t s_src, uint64_t *dst, uint32_t s_dst, uint32_t w_copy,
                                   uint64_t n_blocks, hipStream_t st);
 hipError_t launch_compare_bits(const uint64_t *a, const uint64_t *b, uint64_t n_words, uint64_t *out3, hipStream_t st);
+// per-bin occupancy (rb_dibf_bin_occupancy; rb_kernels.hip, ibf_bin_occupancy_kernel): by-value kernel argument ...
+struct OccLaunch {
+    const uint64_t *words;
+    uint64_t n_blocks;
+    uint64_t stride;         // words from one block to the next
+    uint32_t bin_width, n_bins;
+    uint32_t chunk_rows;     // wave rows a wave walks between two flushes of its planes
+    uint32_t iters;          // chunks per wave
+    uint32_t wgs_per_slice;  // workgroups that share one column slice
+};
+// ... and the launch: out (u64 [n_bins]) is zeroed on `st`, then out[j] = blocks whose bit j is set.  nt: non-temporal loads
+void set_bin_occupancy_grid(uint32_t max_wgs_per_slice, uint32_t min_chunk_rows);
+hipError_t launch_bin_occupancy(const uint64_t *words, uint64_t n_blocks, uint64_t stride, uint32_t bin_width, uint32_t n_bins, int nt,
+                                uint64_t *out, hipStream_t st);
 hipError_t launch_fill_reads(uint8_t *seqs, uint64_t *offsets, uint32_t *lens, size_t n_reads, uint32_t read_len, uint64_t seed, hipStream_t st);
 hipError_t launch_fill_synth(uint64_t *words, uint64_t used_words, uint32_t bin_width, uint32_t stride_words,
                              uint64_t last_mask, uint64_t seed, hipStream_t st);

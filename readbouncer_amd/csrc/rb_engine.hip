@@ -310,7 +310,7 @@ struct rb_engine {
     bool merged_planned = false;
     uint64_t merge_max_bytes = 16ull << 30;  // a merged copy costs HBM beside its members: larger groups stay apart (RB_MERGE_MAX_BYTES)
     uint32_t revcomp_of_n = rbspec::kRevCompOfN;  // see ibf_spec.h: what the reverse strand holds for an N of the read
-    uint64_t nt_threshold_bytes = 512ull << 20;  // 2x the 256 MiB Infinity Cache: beyond it caching cannot help
+    uint64_t nt_threshold_bytes = kNtThresholdBytes;  // 2x the 256 MiB Infinity Cache: beyond it caching cannot help
     uint64_t serial_table_bytes = 128ull << 20;  // filters up to this size never run beside another filter (L2 share)
     // clock-phased gathers (rb_kernels.hip): tables between these sizes, batches of at least phase_min_reads reads
     uint64_t phase_min_bytes = 5ull << 18, phase_max_bytes = 128ull << 20;
@@ -836,6 +836,48 @@ int rb_dibf_compare(const rb_dibf *file_filter, const rb_dibf *rebuilt, rb_ibf_c
     out->rebuilt_bits = h[1];
     out->new_bits = h[2];
     out->payload_bits = a.n_blocks * a.n_bins;
+    return RB_OK;
+}
+
+// Per-bin occupancy of the resident table (ibf_bin_occupancy_kernel): the filter's own image, no engine, no workspace
+int rb_dibf_bin_occupancy_device(const rb_dibf *f, void *d_out_bits, void *stream)
+{
+    if (!f || !d_out_bits) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
+    int st = check_device(f->device);
+    if (st != RB_OK) return st;
+    hipStream_t s = (hipStream_t)stream;
+    if (!stream) RB_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    const int nt = f->geo.n_blocks * f->stride * 8 > kNtThresholdBytes;
+    hipError_t e = launch_bin_occupancy(f->d_words, f->geo.n_blocks, f->stride, (uint32_t)f->geo.bin_width, (uint32_t)f->geo.n_bins, nt,
+                                        (uint64_t *)d_out_bits, s);
+    if (!stream) {
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    if (e != hipSuccess) return rb::fail(RB_ERR_HIP, std::string("bin occupancy: ") + hipGetErrorString(e));
+    return RB_OK;
+}
+
+void rb_set_bin_occupancy_grid(uint32_t max_workgroups_per_slice, uint32_t min_chunk_rows)
+{
+    set_bin_occupancy_grid(max_workgroups_per_slice, min_chunk_rows);
+}
+
+uint64_t rb_nt_threshold_default(void) { return kNtThresholdBytes; }
+
+int rb_dibf_bin_occupancy(const rb_dibf *f, uint64_t *out_bits)
+{
+    if (!f || !out_bits) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
+    int st = check_device(f->device);
+    if (st != RB_OK) return st;
+    uint64_t *d_out = nullptr;
+    RB_HIP(hipMalloc((void **)&d_out, std::max<uint64_t>(f->geo.n_bins, 1) * 8));
+    st = rb_dibf_bin_occupancy_device(f, d_out, nullptr);
+    hipError_t e = hipSuccess;
+    if (st == RB_OK) e = hipMemcpy(out_bits, d_out, f->geo.n_bins * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d_out);
+    if (st != RB_OK) return st;
+    if (e != hipSuccess) return rb::fail(RB_ERR_HIP, std::string("bin occupancy: ") + hipGetErrorString(e));
     return RB_OK;
 }
 

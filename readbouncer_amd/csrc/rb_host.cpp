@@ -384,4 +384,57 @@ size_t rb_fragment_bounds(uint64_t len, uint64_t fragment_length, uint64_t kmer_
     return n;
 }
 
+// Figures of a per-bin bit count (rb_dibf_bin_occupancy): pure host arithmetic.  load = bits / noOfBlocks is the share of a bin's
+// positions that are set; a k-mer that is not in the bin tests positive with probability load^h -- the quantity the reference sizes a
+// filter for (max_fp, src/IBF/IBFConfig.hpp:77; calculate_filter_size_bits, src/IBF/IBFBuild.cpp:404-413).
+int rb_bin_occupancy_derive(const uint64_t *bits, uint64_t n_bins, uint64_t n_blocks, uint64_t n_hash, double *load, double *fpr,
+                            double *est_kmers)
+{
+    if ((n_bins && !bits) || n_blocks == 0 || n_hash == 0) return fail(RB_ERR_INVALID_ARG, "bin occupancy: null counts, no blocks or no hash functions");
+    const double m = (double)n_blocks, h = (double)n_hash;
+    for (uint64_t j = 0; j < n_bins; ++j) {
+        const double l = (double)bits[j] / m;
+        if (load) load[j] = l;
+        if (fpr) fpr[j] = std::pow(l, h);
+        if (est_kmers) est_kmers[j] = -(m / h) * std::log1p(-l);
+    }
+    return RB_OK;
+}
+
+int rb_bin_occupancy_summarize(const uint64_t *bits, uint64_t n_bins, uint64_t n_blocks, uint64_t n_hash, double max_fp,
+                               rb_bin_occupancy_summary *out)
+{
+    if (!out || (n_bins && !bits) || n_blocks == 0 || n_hash == 0)
+        return fail(RB_ERR_INVALID_ARG, "bin occupancy: null argument, no blocks or no hash functions");
+    rb_bin_occupancy_summary s;
+    std::memset(&s, 0, sizeof s);
+    s.n_bins = n_bins;
+    s.n_blocks = n_blocks;
+    s.n_hash = n_hash;
+    const double m = (double)n_blocks, h = (double)n_hash;
+    double fpr_sum = 0.0, fpr_comp = 0.0;  // (compensated: the mean of up to 2^31 terms)
+    uint64_t non_empty = 0;
+    for (uint64_t j = 0; j < n_bins; ++j) {
+        const uint64_t b = bits[j];
+        s.bits_total += b;
+        if (b == 0) { ++s.empty_bins; continue; }
+        if (b > s.max_bits) { s.max_bits = b; s.max_bin = j; }
+        if (non_empty == 0 || b < s.min_bits) { s.min_bits = b; s.min_bin = j; }
+        ++non_empty;
+        const double f = std::pow((double)b / m, h);
+        if (f > max_fp) ++s.bins_over_max_fp;
+        const double y = f - fpr_comp, t = fpr_sum + y;
+        fpr_comp = (t - fpr_sum) - y;
+        fpr_sum = t;
+    }
+    if (non_empty) {
+        s.mean_load = (double)s.bits_total / m / (double)non_empty;
+        s.mean_fpr = fpr_sum / (double)non_empty;
+        s.max_load = (double)s.max_bits / m;
+        s.max_fpr = std::pow(s.max_load, h);
+    }
+    *out = s;
+    return RB_OK;
+}
+
 }  // extern "C"

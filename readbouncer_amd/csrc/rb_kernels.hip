@@ -32,6 +32,7 @@
 // No MFMA anywhere: there is no multiply-accumulate structure in this path.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 
 #include "rb_device.h"
@@ -2177,6 +2178,152 @@ __global__ void fill_reads_kernel(uint8_t *__restrict__ seqs, uint64_t *__restri
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-bin occupancy of a resident filter (rb_dibf_bin_occupancy): out[j] += number of blocks whose bit j is set -- the column
+// sums of the block-major bit matrix, read once from the filter's own device image.  The vertical-counter problem of K1 without
+// the gathers: a lane keeps WPL word columns and walks DOWN the blocks; eight rows at a time go through the Harley-Seal tree of
+// Planes::add8 into lane-private planes (about one carry-save step per loaded word, no per-bit work, no LDS, no atomics in the loop).
+//   * A workgroup owns a column slice of 64 * WPL words of every block (WPL 2: 16-byte lanes for strides that are multiples of
+//     16 words; WPL 1: 8-byte lanes for the power-of-two strides below).  A slice narrower than a wave row -- strides of 1 to 8
+//     words, the 16 ... 112 words a stride leaves behind its last full slice -- is covered by 2^lg lanes per block, and the wave
+//     takes 64 >> lg blocks per load instruction: lane's column = (lane mod 2^lg) * WPL, fixed for the whole walk.
+//   * Loads: 16 / WPL wave rows (8 KiB per wave) go out together, no control flow between them, a schedule fence before the first use.
+//     Every 128-byte line of the table is requested once; a lane whose words are all padding loads nothing (its neighbours
+//     fetch the line), pad words and the bits at or beyond n_bins are masked when the planes are flushed.
+//   * Flush: a wave walks at most kOccMaxChunkRows < 2^kOccPlanes rows, then expands its planes (64 bins x kOccPlanes bits per lane
+//     word) into the workgroup's u32 counters in LDS and clears them.  When the workgroup has walked all its chunks, one 64-bit
+//     atomicAdd per non-empty bin carries the counters to `out` (integer sums: the order does not matter).  DESIGN 4.6 has the
+//     instruction shares.
+// The launcher sizes the grid to one workgroup of 16 waves per CU.
+constexpr int kOccPlanes = 12;
+constexpr int kOccWaves = 16;                  // waves per workgroup
+constexpr uint32_t kOccMaxChunkRows = 4080;    // wave rows between two flushes: the largest multiple of 16 below 2^kOccPlanes
+constexpr uint32_t kOccMinChunkRows = 256;     // ... and no grid so large that a wave walks fewer (the flush is a fixed cost per chunk)
+static_assert(kOccMaxChunkRows < (1u << kOccPlanes) && kOccMaxChunkRows % 16 == 0, "a chunk must not wrap the planes");
+
+// counters += one one-bit-per-bin word (ripple add; the rows behind the last full batch of a chunk)
+template <int NP>
+__device__ __forceinline__ void planes_add1(Planes<NP> &pl, uint64_t x)
+{
+    uint64_t carry = x;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const uint64_t t = pl.p[i] & carry;
+        pl.p[i] ^= carry;
+        carry = t;
+    }
+}
+
+template <int WPL, bool NT>
+__global__ __launch_bounds__(64 * kOccWaves) void ibf_bin_occupancy_kernel(OccLaunch a, unsigned long long *__restrict__ out)
+{
+    constexpr int RW = 64 * WPL;  // word columns of a slice
+    constexpr int B = 16 / WPL;   // wave rows per batch of loads
+    __shared__ uint32_t cnt[RW * 64];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (uniform: the walk below is scalar)
+    for (uint32_t i = threadIdx.x; i < (uint32_t)RW * 64u; i += blockDim.x) cnt[i] = 0;
+    __syncthreads();
+
+    const uint32_t slice = blockIdx.x / a.wgs_per_slice, wg = blockIdx.x - slice * a.wgs_per_slice;
+    const uint64_t col_begin = (uint64_t)slice * RW;
+    const uint32_t width = (uint32_t)min((uint64_t)RW, a.stride - col_begin);  // words of this slice per block, padding included
+    uint32_t lg = 0;
+    while ((uint32_t)WPL << lg < width) ++lg;  // lanes per block: the next power of two that holds the slice
+    const uint32_t ng = 64u >> lg;             // blocks per wave row
+    const uint32_t c = lane & ((1u << lg) - 1u), g = lane >> lg;
+    const uint64_t col0 = col_begin + (uint64_t)c * WPL;
+    uint64_t valid[WPL];
+    bool active = false;
+#pragma unroll
+    for (int w = 0; w < WPL; ++w) {
+        const uint64_t col = col0 + w;
+        const uint32_t rem = a.n_bins & 63u;
+        valid[w] = col >= a.bin_width ? 0ULL : (col == a.bin_width - 1 && rem) ? ((1ULL << rem) - 1) : ~0ULL;
+        active |= valid[w] != 0;
+    }
+    const uint64_t n_rows = (a.n_blocks + ng - 1) / ng;  // wave rows of this slice
+    const uint64_t n_full = a.n_blocks / ng;             // ... of which these hold a block for every lane group
+    const uint64_t step = (uint64_t)ng * a.stride;       // words from one wave row to the next
+    // a lane's place inside a wave row, in words: below 2^32 (g > 0 only for strides of at most 64 words; a block has fewer than 2^25)
+    const uint32_t lane_off = (uint32_t)(g * a.stride + col0);
+
+    for (uint32_t it = 0; it < a.iters; ++it) {
+        const uint64_t chunk = ((uint64_t)it * a.wgs_per_slice + wg) * kOccWaves + wave;
+        const uint64_t i0 = chunk * a.chunk_rows;
+        if (i0 >= n_rows) break;  // (wave-uniform)
+        const uint64_t i1 = min(i0 + a.chunk_rows, n_rows), f1 = min(i1, n_full);
+        if (!active) continue;
+        Planes<kOccPlanes> pl[WPL];
+#pragma unroll
+        for (int w = 0; w < WPL; ++w) pl[w].clear();
+        const uint64_t *p = a.words + i0 * step;  // (uniform) first word of wave row i
+        uint64_t i = i0;
+#pragma unroll 1
+        for (; i + B <= f1; i += B, p += B * step) {
+            if constexpr (WPL == 2) {
+                rb_u64x2 v[B];
+#pragma unroll
+                for (int j = 0; j < B; ++j) v[j] = load_word2<NT>(p + j * step + lane_off);
+                __builtin_amdgcn_sched_barrier(0);
+                uint64_t x0[8], x1[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    x0[j] = v[j].x;
+                    x1[j] = v[j].y;
+                }
+                pl[0].add8(x0);
+                pl[1].add8(x1);
+            } else {
+                uint64_t x[B];
+#pragma unroll
+                for (int j = 0; j < B; ++j) x[j] = load_word<NT>(p + j * step + lane_off);
+                __builtin_amdgcn_sched_barrier(0);
+                pl[0].add8(x);
+                pl[0].add8(x + 8);
+            }
+        }
+        // the rows behind the last full batch, and the wave row that holds fewer than ng blocks
+#pragma unroll 1
+        for (; i < i1; ++i, p += step) {
+            const bool ok = i * ng + g < a.n_blocks;
+#pragma unroll
+            for (int w = 0; w < WPL; ++w) planes_add1(pl[w], ok ? load_word<NT>(p + lane_off + w) : 0ULL);
+        }
+        // flush: planes -> the workgroup's counters.  Word column lc of the slice keeps its 64 bins at cnt[lc * 64 ...], rotated by
+        // the lane's column number so that the 64 lanes of a full-width slice hit 64 different banks
+#pragma unroll
+        for (int w = 0; w < WPL; ++w) {
+            uint32_t lo[kOccPlanes], hi[kOccPlanes];
+#pragma unroll
+            for (int q = 0; q < kOccPlanes; ++q) {
+                const uint64_t m = pl[w].p[q] & valid[w];
+                lo[q] = (uint32_t)m;
+                hi[q] = (uint32_t)(m >> 32);
+            }
+            uint32_t *dst = cnt + (c * WPL + w) * 64u;
+#pragma unroll 2
+            for (uint32_t b = 0; b < 32; ++b) {
+                uint32_t v0 = 0, v1 = 0;
+#pragma unroll
+                for (int q = 0; q < kOccPlanes; ++q) {
+                    v0 |= ((lo[q] >> b) & 1u) << q;
+                    v1 |= ((hi[q] >> b) & 1u) << q;
+                }
+                atomicAdd(dst + ((b + c) & 63u), v0);
+                atomicAdd(dst + ((b + 32u + c) & 63u), v1);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < (uint32_t)RW * 64u; i += blockDim.x) {
+        const uint32_t v = cnt[i];
+        const uint32_t lc = i >> 6;
+        const uint64_t bin = (col_begin + lc) * 64u + (((i & 63u) - lc / WPL) & 63u);
+        if (v != 0 && bin < a.n_bins) atomicAdd(out + bin, (unsigned long long)v);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 template <int LG, int WPL, int NP, int H, bool NT>
 static hipError_t launch_count_nt(const CountLaunch &a, hipStream_t st)
@@ -2726,6 +2873,62 @@ hipError_t launch_fill_synth(uint64_t *words, uint64_t used_words, uint32_t bin_
     if (blocks > 256 * 32) blocks = 256 * 32;
     hipLaunchKernelGGL(fill_synth_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, words, used_words, bin_width,
                        stride_words, last_mask, seed);
+    return hipGetLastError();
+}
+
+// rb_set_bin_occupancy_grid: workgroups per column slice at most, and the fewest rows of a chunk, for every later pass of this process
+// (0 = the rule below).  Counts never depend on it; a small table then walks chunks of the full length and several of them per wave.
+static std::atomic<uint32_t> g_occ_max_wgs{0}, g_occ_min_chunk_rows{0};
+void set_bin_occupancy_grid(uint32_t max_wgs_per_slice, uint32_t min_chunk_rows)
+{
+    g_occ_max_wgs.store(max_wgs_per_slice);
+    g_occ_min_chunk_rows.store(min_chunk_rows);
+}
+
+// One workgroup of kOccWaves waves per CU, shared out over the column slices; every wave walks `iters` chunks of `chunk_rows`
+// wave rows (a multiple of 16, at most kOccMaxChunkRows).  `out` (u64 [n_bins]) is zeroed on the stream first.
+hipError_t launch_bin_occupancy(const uint64_t *words, uint64_t n_blocks, uint64_t stride, uint32_t bin_width, uint32_t n_bins, int nt,
+                                uint64_t *out, hipStream_t st)
+{
+    if (n_bins == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(out, 0, (size_t)n_bins * 8, st);
+    if (e != hipSuccess || n_blocks == 0) return e;
+    if (stride < bin_width || (stride >= 16 && stride % 16 != 0) || (stride < 16 && (stride & (stride - 1)) != 0)) return hipErrorInvalidValue;
+    const int wpl = stride >= 16 ? 2 : 1;
+    const uint64_t rw = 64u * (uint64_t)wpl;
+    const uint64_t n_slices = (stride + rw - 1) / rw;
+    uint32_t lg = 0;
+    while (((uint64_t)wpl << lg) < std::min<uint64_t>(rw, stride)) ++lg;
+    const uint64_t ng = 64u >> lg;
+    const uint64_t n_rows = (n_blocks + ng - 1) / ng;  // wave rows of a full slice (a narrower last slice has fewer)
+    int dev = 0, cus = 0;
+    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
+    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+    uint64_t want = std::max<uint64_t>(1, ((uint64_t)std::max(cus, 1) + n_slices - 1) / n_slices);
+    if (const uint32_t cap = g_occ_max_wgs.load()) want = std::min<uint64_t>(want, cap);
+    const uint64_t min_rows = g_occ_min_chunk_rows.load() ? g_occ_min_chunk_rows.load() : kOccMinChunkRows;
+    const uint64_t useful = (n_rows + min_rows * kOccWaves - 1) / (min_rows * kOccWaves);
+    OccLaunch a;
+    a.words = words;
+    a.n_blocks = n_blocks;
+    a.stride = stride;
+    a.bin_width = bin_width;
+    a.n_bins = n_bins;
+    a.wgs_per_slice = (uint32_t)std::min(want, useful);
+    const uint64_t slots = (uint64_t)a.wgs_per_slice * kOccWaves;
+    const uint64_t per_slot = (n_rows + slots - 1) / slots;
+    a.iters = (uint32_t)((per_slot + kOccMaxChunkRows - 1) / kOccMaxChunkRows);
+    a.chunk_rows = (uint32_t)(((per_slot + a.iters - 1) / a.iters + 15) / 16 * 16);
+    if (a.chunk_rows > kOccMaxChunkRows || n_slices * a.wgs_per_slice > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)(n_slices * a.wgs_per_slice)), block(64 * kOccWaves);
+    unsigned long long *o = reinterpret_cast<unsigned long long *>(out);
+    if (wpl == 2) {
+        if (nt) hipLaunchKernelGGL((ibf_bin_occupancy_kernel<2, true>), grid, block, 0, st, a, o);
+        else hipLaunchKernelGGL((ibf_bin_occupancy_kernel<2, false>), grid, block, 0, st, a, o);
+    } else {
+        if (nt) hipLaunchKernelGGL((ibf_bin_occupancy_kernel<1, true>), grid, block, 0, st, a, o);
+        else hipLaunchKernelGGL((ibf_bin_occupancy_kernel<1, false>), grid, block, 0, st, a, o);
+    }
     return hipGetLastError();
 }
 

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <iomanip>
 #include <iostream>
 
 #include "../../include/readbouncer_amd.hpp"
@@ -66,22 +67,73 @@ static void write_bin_map(const std::string& path, const std::vector<interleave:
     }
 }
 
-// classify --bin-map: bin -> record id of one filter, from the table above
-static std::vector<std::string> read_bin_map(const std::string& path)
+// --bin-map: the table above read back, ONE parser for both reports: bin -> "record_id\tstart\tend" ...
+static std::vector<std::string> read_bin_map_rows(const std::string& path)
 {
     std::ifstream in(path);
     if (!in) throw std::runtime_error("Unable to open the file: " + path);
-    std::vector<std::string> rec;
+    std::vector<std::string> rows;
     std::string line;
     while (std::getline(in, line)) {
         if (line.empty() || line[0] == '#' || line.compare(0, 4, "bin\t") == 0) continue;
         const size_t a = line.find('\t'), b = a == std::string::npos ? a : line.find('\t', a + 1);
         if (b == std::string::npos) throw std::runtime_error("not a bin map: " + path);
         const size_t bin = (size_t)std::stoull(line.substr(0, a));
-        if (bin >= rec.size()) rec.resize(bin + 1);
-        rec[bin] = line.substr(a + 1, b - a - 1);
+        if (bin >= rows.size()) rows.resize(bin + 1);
+        rows[bin] = line.substr(a + 1);
     }
+    return rows;
+}
+// ... and its first column alone (classify --report-bins): bin -> record id of one filter
+static std::vector<std::string> read_bin_map(const std::string& path)
+{
+    std::vector<std::string> rec = read_bin_map_rows(path);
+    for (std::string& r : rec) r.resize(std::min(r.size(), r.find('\t')));
     return rec;
+}
+
+// --filter-stats <file.ibf> / build --filter-stats: how full is each bin of the filter in HBM, and what false-positive rate does that mean?
+// The reference sizes a filter for max_fp = 0.01 at fragment_size - k + 1 k-mers per bin (src/IBF/IBFConfig.hpp:77, IBFBuild.cpp:404-413) and
+// nothing holds an updated or foreign filter to it.  One pass over the resident table (rb_dibf_bin_occupancy), a summary on stdout and
+// <name>.binstats.tsv beside the filter: bin, bits, load, fpr, est_kmers and -- with a bin map of build --write-bin-map -- the record and
+// fragment bounds of the bin.  Returns 0, or 3 when a bin's false-positive rate is over max_fp.
+static bool g_filter_stats = false;
+static double g_stats_max_fp = 0.01;        // --max-fp
+static uint32_t g_stats_chunk_length = 360;  // --chunk-length: the read length the summary's noise floor is given for
+static int filter_stats(interleave::IBF& filter, const std::string& ibf_path, const std::string& bin_map_path, double error_rate)
+{
+    const interleave::IBF::BinOccupancy occ = filter.bin_occupancy(g_stats_max_fp);
+    const rb_bin_occupancy_summary& s = occ.summary;
+    const size_t n = occ.bits.size();
+    std::vector<double> load(n), fpr(n), est(n);
+    interleave::throw_status(rb_bin_occupancy_derive(occ.bits.data(), n, s.n_blocks, s.n_hash, load.data(), fpr.data(), est.data()),
+                             "rb_bin_occupancy_derive");
+    const std::vector<std::string> map_rows = bin_map_path.empty() ? std::vector<std::string>() : read_bin_map_rows(bin_map_path);
+    std::filesystem::path out_path(ibf_path);
+    out_path.replace_extension("binstats.tsv");
+    std::ofstream out(out_path);
+    if (!out) throw std::runtime_error("Unable to open the file: " + out_path.string());
+    out << std::setprecision(17);
+    out << "bin\tbits\tload\tfpr\test_kmers" << (bin_map_path.empty() ? "" : "\trecord_id\tstart\tend") << '\n';
+    for (size_t j = 0; j < n; ++j) {
+        out << j << '\t' << occ.bits[j] << '\t' << load[j] << '\t' << fpr[j] << '\t' << est[j];
+        if (!bin_map_path.empty()) out << '\t' << (j < map_rows.size() && !map_rows[j].empty() ? map_rows[j] : std::string("\t\t"));
+        out << '\n';
+    }
+    out.close();
+    if (!out) throw std::runtime_error("short write to " + out_path.string());
+    const uint64_t kmer_size = filter.getFilter().kmerSize;
+    const uint64_t n_kmers = g_stats_chunk_length >= kmer_size ? g_stats_chunk_length - kmer_size + 1 : 0;
+    std::cout << "FILTER_STATS file=" << ibf_path << " bins=" << s.n_bins << " blocks=" << s.n_blocks << " hash_functions=" << s.n_hash
+              << " bits_total=" << s.bits_total << " empty_bins=" << s.empty_bins << "\n"
+              << "  load   mean=" << s.mean_load << " max=" << s.max_load << " (over the non-empty bins)\n"
+              << "  fpr    mean=" << s.mean_fpr << " max=" << s.max_fpr << " max_fp=" << g_stats_max_fp << "\n"
+              << "  fullest_bin=" << s.max_bin << " bits=" << s.max_bits << " emptiest_bin=" << s.min_bin << " bits=" << s.min_bits << "\n"
+              << "  bins_over_max_fp=" << s.bins_over_max_fp << "\n"
+              << "  chunk_length=" << g_stats_chunk_length << " threshold=" << rb_threshold(g_stats_chunk_length, kmer_size, error_rate, 0.95)
+              << " at error_rate=" << error_rate << "; expected false-positive hits in the fullest bin=" << (double)n_kmers * s.max_fpr << "\n"
+              << "  written " << out_path.string() << std::endl;
+    return s.bins_over_max_fp ? 3 : 0;
 }
 
 // buildIBF, src/main/ibfbuild.hpp:21-59
@@ -113,6 +165,11 @@ static interleave::TIbf buildIBF(ConfigReader config_reader, const std::string r
         std::filesystem::path map_path(bloom_filter_output_path);
         map_path.replace_extension("bins.tsv");
         write_bin_map(map_path.string(), records, config);
+    }
+    if (g_filter_stats) {  // from the table while it is still in HBM
+        std::filesystem::path map_path(bloom_filter_output_path);
+        map_path.replace_extension("bins.tsv");
+        filter_stats(filter, bloom_filter_output_path, g_write_bin_map ? map_path.string() : std::string(), config_reader.IBF_Parsed.error_rate);
     }
     // where a build's time goes (profiles/cli_build.py reads this line): parsing the FASTA, cutOutNNNs + sizing, the filter's allocation
     // in HBM, the concatenation, rb_dibf_insert (H2D + the insert kernel), download + file
@@ -818,6 +875,8 @@ int main(int argc, char const* argv[])
     std::vector<int> devices{0};
     std::string verify_path, verify_ref;
     uint64_t verify_fragment = 100000;  // [IBF] fragment_size default (configReader.cpp)
+    std::string stats_path;
+    double stats_error_rate = 0.1;  // [IBF] exp_seq_error_rate default (configReader.cpp); --error-rate
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {  // e.g. --devices 0,1,2,3,4,5,6,7
             devices.clear();
@@ -845,6 +904,13 @@ int main(int argc, char const* argv[])
         else if (!std::strcmp(argv[i], "--calibrate")) opt.calibrate = true;
         else if (!std::strcmp(argv[i], "--report-bins")) opt.report_bins = true;
         else if (!std::strcmp(argv[i], "--write-bin-map")) g_write_bin_map = true;
+        else if (!std::strcmp(argv[i], "--filter-stats")) {  // with a file: the stand-alone report; bare (usage build): for every filter built
+            g_filter_stats = true;
+            if (i + 1 < argc && argv[i + 1][0] != '-') stats_path = argv[++i];
+        }
+        else if (!std::strcmp(argv[i], "--max-fp") && i + 1 < argc) g_stats_max_fp = std::stod(argv[++i]);
+        else if (!std::strcmp(argv[i], "--chunk-length") && i + 1 < argc) g_stats_chunk_length = (uint32_t)std::stoul(argv[++i]);
+        else if (!std::strcmp(argv[i], "--error-rate") && i + 1 < argc) stats_error_rate = std::stod(argv[++i]);
         else if (!std::strcmp(argv[i], "--bin-map") && i + 1 < argc) opt.bin_maps.push_back(argv[++i]);
         // tables of 1 GiB and more are placed by trial (up to five allocations probed, 1-2 s at load time): 1 switches it off
         else if (!std::strcmp(argv[i], "--placement-tries") && i + 1 < argc) {
@@ -885,7 +951,11 @@ int main(int argc, char const* argv[])
                          "  usage build:    [--write-bin-map]  beside every <name>.ibf, <name>.bins.tsv: bin -> record id and fragment bounds\n"
                          "  usage classify: [--report-bins]  classified_bins.tsv: bin, strand, count and hit bins of every classified read\n"
                          "                  [--bin-map <name>.bins.tsv ...]  adds the record id of the bin to that report\n"
-                         "readbouncer_amd --verify-ibf <file.ibf> --reference <file.fasta> [--fragment-size N]" << std::endl;
+                         "                  [--filter-stats]  per-bin occupancy of every filter built: a summary and <name>.binstats.tsv (give the flag last, or\n"
+                         "                                    before another flag: a bare word after it is taken as a file; a build's exit code stays 0 whatever the bins hold)\n"
+                         "readbouncer_amd --verify-ibf <file.ibf> --reference <file.fasta> [--fragment-size N]\n"
+                         "readbouncer_amd --filter-stats <file.ibf> [--bin-map <name>.bins.tsv] [--max-fp 0.01] [--chunk-length 360] [--error-rate 0.1]\n"
+                         "                  bits, load, false-positive rate and estimated k-mers per bin -> <name>.binstats.tsv; exit code 3 when a bin is over --max-fp" << std::endl;
             return 0;
         }
     }
@@ -893,6 +963,19 @@ int main(int argc, char const* argv[])
         if (verify_ref.empty()) { std::cerr << "ERROR: --verify-ibf <file.ibf> needs --reference <file.fasta> [--fragment-size N]" << std::endl; return 1; }
         try {
             return verify_ibf(verify_path, verify_ref, verify_fragment);
+        } catch (const std::exception& e) {
+            std::cerr << "ERROR: " << e.what() << std::endl;
+            return 1;
+        }
+    }
+    if (!stats_path.empty()) {
+        try {
+            interleave::IBFConfig cfg{};
+            cfg.input_filter_file = stats_path;
+            cfg.device = devices[0];
+            interleave::IBF f{};
+            f.load_filter(cfg);
+            return filter_stats(f, stats_path, opt.bin_maps.empty() ? std::string() : opt.bin_maps[0], stats_error_rate);
         } catch (const std::exception& e) {
             std::cerr << "ERROR: " << e.what() << std::endl;
             return 1;
