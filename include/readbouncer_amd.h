@@ -330,6 +330,49 @@ RB_API int rb_locate_batch(rb_engine *e, const char *seqs, const uint64_t *offse
                            const uint32_t *read_ids, size_t n_items, double error_rate, double significance,
                            const rb_locate_out *out);
 
+/* ---- hits: EVERY bin a read hit, per strand, with its k-mer count ---------------------------------
+ * The reference has no such call.  This is what seqan::count returns and select_matches walks (src/IBF/IBFClassify.cpp:16-38,
+ * 97-98, 149-150): which bins reached the threshold, on which strand, with what count -- the list behind the hit_bins of the
+ * locate pass.  An opt-in pass of its own, like locate: it always counts in full from each filter's own table, whatever the
+ * engine's pruning / early-decision / merge / phased settings are, and changes nothing any other call returns.
+ * Per (work item, filter), deplete filters first: fwd[b], rev[b] = the two uint16_t count vectors of seqan::count under the
+ * engine's N rule, t = the threshold; a HIT is a (bin b, strand s) with c_s[b] >= t.  Records are per (bin, strand): a bin that
+ * reaches t on both strands yields two.
+ *   min_count == 0 : t = rb_threshold(length, k, error_rate, significance) as the decision stage reads it -- the t of
+ *                    rb_locate_out's hit_bins (t == 0 lists every existing bin on both strands, a wrapped t of 65 5xx nothing)
+ *   min_count  > 0 : t = min_count for every filter; min_count = 1 with max_hits = 2 x n_bins is seqan::count in sparse form
+ *   hits      rb_hit [n_items x n_filters x max_hits]  the first min(n_hits, max_hits) hits in rising (bin, strand) order;
+ *                    slots beyond those are NOT written.  Order and truncation are deterministic
+ *   n_hits    u32 [n_items x n_filters]  the exact number of hits, whatever max_hits is: n_hits > max_hits = truncated
+ *   status    u8  [n_items]  the status rules of rb_locate_out; an item that is not RB_OK has n_hits == 0 and no record
+ *   bin_reads u64, one entry per bin of every filter, concatenated in filter order: the call ADDS 1 per distinct hit bin
+ *                    (either strand) of every RB_OK item, whatever max_hits is.  The caller zeroes it; it accumulates over calls
+ * The distinct bins of an untruncated list number rb_locate_out's hit_bins, and its highest count is max_count whenever that
+ * is >= t.  max_hits == 0 is legal (n_hits / bin_reads only).  A column-sharded engine refuses with RB_ERR_INVALID_ARG. */
+typedef struct rb_hit {
+    uint32_t bin;
+    uint16_t count;
+    uint8_t strand;   /* 0 forward, 1 reverse complement */
+    uint8_t reserved; /* 0 */
+} rb_hit;
+typedef struct rb_hits_out { /* any member may be NULL, but not hits, n_hits and bin_reads all at once */
+    void *hits;      /* rb_hit [n_items x n_filters x max_hits] */
+    void *n_hits;    /* u32 [n_items x n_filters] */
+    void *status;    /* u8  [n_items] */
+    void *bin_reads; /* u64 [sum of the filters' bins] */
+} rb_hits_out;
+/* Device pointers, asynchronous on `stream` (NULL = the engine's own stream, synchronised before returning); rb_batch_desc in
+ * full.  Allocates (and keeps, as the engine's) a workspace of n_items x S x 2 x max_hits records of 8 bytes plus
+ * n_items x S x 2 counters, S = the most column slices of any filter (ceil(bin_width / 128) beyond 64 words, else 1): a caller
+ * with a large max_hits bounds it by the size of its calls.  One stream per engine, as for rb_classify_batch_device. */
+RB_API int rb_hits_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance,
+                                uint16_t min_count, uint32_t max_hits, const rb_hits_out *d_out, void *stream);
+/* Host buffers; read_ids / n_items as in rb_locate_batch.  Large calls are processed in sub-batches so that the device
+ * workspace and the staged outputs together stay at or below 256 MiB (one work item at a time where a single item needs more). */
+RB_API int rb_hits_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads,
+                         const uint32_t *read_ids, size_t n_items, double error_rate, double significance, uint16_t min_count,
+                         uint32_t max_hits, const rb_hits_out *out);
+
 /* bin-sharded operation: restrict the engine to word columns
  * [rank*ceil(W/world) , ...) of every block; out_maxcount then holds PARTIAL maxima that the
  * caller combines with an all-reduce(max) before rb_decide_device. world=1 restores the default. */

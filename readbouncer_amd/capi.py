@@ -30,6 +30,20 @@ class LocateOut(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class Hit(C.Structure):
+    """rb_hit: one (bin, strand) at or above the threshold and its count -- 8 bytes"""
+    _fields_ = [("bin", C.c_uint32), ("count", C.c_uint16), ("strand", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+class HitsOut(C.Structure):
+    """rb_hits_out: any member may be NULL, but not hits, n_hits and bin_reads all at once"""
+    _fields_ = [("hits", C.c_void_p), ("n_hits", C.c_void_p), ("status", C.c_void_p), ("bin_reads", C.c_void_p)]
+
+
+# rb_hit as a numpy record
+HIT_DTYPE = np.dtype([("bin", "<u4"), ("count", "<u2"), ("strand", "u1"), ("reserved", "u1")])
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("table_bytes", C.c_uint64), ("block_words", C.c_uint32), ("stride_words", C.c_uint32),
                 ("merged_members", C.c_uint32), ("lanes_per_block_log2", C.c_uint32), ("words_per_lane", C.c_uint32),
@@ -103,6 +117,8 @@ SIGNATURES = {
     "rb_classify_batch_device_ex": (_int, [_vp, C.POINTER(BatchDesc), _dbl, _dbl, _int, _vp, _vp, _vp, _vp, _vp]),
     "rb_locate_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _dbl, _dbl, C.POINTER(LocateOut), _vp]),
     "rb_locate_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _dbl, _dbl, C.POINTER(LocateOut)]),
+    "rb_hits_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _dbl, _dbl, C.c_uint16, C.c_uint32, C.POINTER(HitsOut), _vp]),
+    "rb_hits_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _dbl, _dbl, C.c_uint16, C.c_uint32, C.POINTER(HitsOut)]),
     "rb_pack_reads": (_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "rb_host_alloc": (_int, [_sz, C.POINTER(_vp)]),
     "rb_host_free": (None, [_vp]),
@@ -498,6 +514,46 @@ class Engine:
         out = LocateOut(d_max_count, d_best_bin, d_best_strand, d_hit_bins, d_status)
         _check(lib().rb_locate_batch_device(self.h, C.byref(desc), error_rate, significance, C.byref(out), stream),
                "rb_locate_batch_device")
+
+    def hits(self, seqs, offsets, lens, read_ids=None, error_rate=0.1, significance=0.95, min_count=0, max_hits=64, bin_reads=None,
+             hits=None):
+        """every (bin, strand) of each selected read at or above the threshold, with its count (rb_hits_batch): host buffers in, a dict
+        of host numpy arrays out -- hits[n, nf, max_hits] of HIT_DTYPE (only the first min(n_hits, max_hits) of a list are written:
+        pass `hits` to keep what the rest held, else they are zero), n_hits[n, nf] u32 (exact, whatever max_hits), status[n] u8, and
+        bin_reads when an u64 array with one entry per bin of every filter is passed: the call ADDS to it.  min_count 0 = the decision
+        threshold; max_hits 0 = no records"""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        ids = None if read_ids is None else np.ascontiguousarray(read_ids, dtype=np.uint32)
+        n = len(lens) if ids is None else len(ids)
+        nf = self.nd + self.nt
+        res = {"n_hits": np.zeros((n, nf), dtype=np.uint32), "status": np.zeros(n, dtype=np.uint8)}
+        if max_hits:
+            if hits is None:
+                hits = np.zeros((n, nf, max_hits), dtype=HIT_DTYPE)
+            if hits.dtype != HIT_DTYPE or hits.shape != (n, nf, max_hits) or not hits.flags.c_contiguous:
+                raise ValueError("hits must be a C-contiguous HIT_DTYPE array of shape (n_items, n_filters, max_hits)")
+            res["hits"] = hits
+        if bin_reads is not None:
+            if bin_reads.dtype != np.uint64 or not bin_reads.flags.c_contiguous:
+                raise ValueError("bin_reads must be a C-contiguous uint64 array")
+            res["bin_reads"] = bin_reads
+        out = HitsOut(_ptr(res["hits"]) if max_hits else None, _ptr(res["n_hits"]), _ptr(res["status"]),
+                      None if bin_reads is None else _ptr(bin_reads))
+        _check(lib().rb_hits_batch(self.h, _ptr(seqs), _ptr(offsets), _ptr(lens), len(lens), None if ids is None else _ptr(ids), n,
+                                   error_rate, significance, min_count, max_hits, C.byref(out)), "rb_hits_batch")
+        return res
+
+    def hits_device(self, d_seqs, d_offsets, d_lens, n_items, max_len, d_nmask=None, d_nmask_offsets=None, chunk_start=0,
+                    chunk_length=0, d_read_ids=None, error_rate=0.1, significance=0.95, min_count=0, max_hits=0, d_hits=None,
+                    d_n_hits=None, d_status=None, d_bin_reads=None, stream=None):
+        """raw device pointers like locate_device (rb_hits_batch_device); d_hits, d_n_hits and d_bin_reads may be None, not all three"""
+        desc = BatchDesc(d_seqs, d_offsets, d_lens, n_items, max_len, d_nmask, d_nmask_offsets, chunk_start, chunk_length,
+                         d_read_ids)
+        out = HitsOut(d_hits, d_n_hits, d_status, d_bin_reads)
+        _check(lib().rb_hits_batch_device(self.h, C.byref(desc), error_rate, significance, min_count, max_hits, C.byref(out), stream),
+               "rb_hits_batch_device")
 
     def decide_device(self, d_maxcount, d_lens, n_reads, max_len, error_rate=0.1, significance=0.95,
                       mode=RB_MODE_CHECK_UNBLOCK, d_best=None, d_decision=None, d_status=None, stream=None):

@@ -226,6 +226,36 @@ hipError_t launch_reduce_locate_slices(const LocatePart *part, uint32_t n_slices
                                        const uint8_t *pre_status, uint32_t max_len, uint32_t min_len, const LocateOut &out, uint32_t nf,
                                        uint32_t fidx, hipStream_t st);
 
+// hits pass (rb_hits_batch_device; rb_kernels.hip, ibf_hits_kernel): a record as the kernels move it -- x = bin, y = count | strand << 16,
+// the eight bytes of rb_hit ...
+typedef unsigned int rb_u32x2 __attribute__((ext_vector_type(2)));
+// ... the caller's output arrays (any may be nullptr) ...
+struct HitsOut {
+    rb_u32x2 *hits;    // [n_items][nf][max_hits]
+    uint32_t *n_hits;  // [n_items][nf]
+    uint8_t *status;   // [n_items]
+};
+// ... and one filter's launch: the plain form over the filter's own table, counted in full, as the locate pass
+struct HitsLaunch {
+    IbfDev f;
+    ReadSrc src;
+    uint32_t n_items;
+    uint32_t col_begin, col_end;
+    uint32_t n_slices;
+    int lg, wpl, planes, nt;
+    const uint16_t *thr;  // the decision kernel's table [thr_len][nf][2]
+    uint32_t thr_len, nf, fi;
+    uint32_t min_count;   // 0: the table's entry; else the threshold itself
+    uint32_t max_hits;    // records kept per (item, slice, strand) segment and per (item, filter) list
+    uint32_t min_len;     // an item shorter than this is RB_ERR_SHORT_READ
+    const uint8_t *pre_status;  // chunk_prep's per-item status, or nullptr
+    void *seg;            // rb_u32x2 [n_items][n_slices][2][max_hits]
+    uint32_t *seg_count;  // [n_slices][2][n_items]: hits of the (slice, strand) run, whatever the cap
+    uint64_t *bin_reads;  // this filter's n_bins counters, or nullptr
+};
+hipError_t launch_ibf_hits(const HitsLaunch &a, hipStream_t st);
+hipError_t launch_finish_hits(const HitsLaunch &a, const uint32_t *lens, const HitsOut &out, hipStream_t st);
+
 hipError_t launch_ibf_count_max(const CountLaunch &a, hipStream_t st);
 hipError_t launch_ibf_count_max_merged(const CountLaunch &a, const MergeMap &map, hipStream_t st);
 // block b of a filter (width words at stride s_src, n_bins bins) -> bits [dst_bit, dst_bit + n_bins) of block b of dst (ORed in: dst starts zeroed)

@@ -409,6 +409,8 @@ struct rb_engine {
     DevBuf d_efflens, d_prestatus;  // on-GPU chunking: effective lengths and the bad-chunk status per item
     DevBuf d_locate_parts;          // locate pass: partial records of the column slices, all filters of a call
     DevBuf d_locate_io;             // rb_locate_batch: read ids in, the five outputs back
+    DevBuf d_hits_ws;               // hits pass: the (item, slice, strand) record segments and their counters, one filter at a time
+    DevBuf d_hits_io;               // rb_hits_batch: read ids in, records / n_hits / status / bin_reads back
     PinnedBuf h_in, h_out;
     // large host batches: slice i+1 is copied on this stream while slice i is counted on `stream`
     hipStream_t copy_stream = nullptr;
@@ -1034,7 +1036,7 @@ void rb_engine_destroy(rb_engine *e)
     }
     for (void *r : e->thr_retired_dev) (void)hipFree(r);
     for (PinnedBuf &h : e->thr_retired_host) h.release();
-    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_locate_parts, &e->d_locate_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
+    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_locate_parts, &e->d_locate_io, &e->d_hits_ws, &e->d_hits_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
                       &e->d_decision, &e->d_status})
         b->release();
     e->h_in.release();
@@ -2765,6 +2767,228 @@ int rb_locate_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, con
     if (out->hit_bins) RB_HIP(hipMemcpyAsync(out->hit_bins, io + o_hit, 4 * n * nf, hipMemcpyDeviceToHost, st));
     if (out->status) RB_HIP(hipMemcpyAsync(out->status, io + o_status, n, hipMemcpyDeviceToHost, st));
     RB_HIP(hipStreamSynchronize(st));
+    return RB_OK;
+}
+
+// ---- hits: every (bin, strand) at or above the threshold, with its count (no counterpart in the reference; see the boundary header).
+// The locate pass's shape: per filter one launch of ibf_hits_kernel over the filter's OWN table, counted in full, plus finish_hits_kernel,
+// in sequence on the call's stream -- so one workspace, sized for the filter with the most column slices, serves every filter.
+static int hits_device_impl(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, uint16_t min_count,
+                            uint32_t max_hits, const rb_hits_out *d_out, void *stream)
+{
+    if (!desc || !d_out) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor or output struct");
+    if (!d_out->hits && !d_out->n_hits && !d_out->bin_reads) return rb::fail(RB_ERR_INVALID_ARG, "rb_hits_out with no output");
+    if (d_out->hits && max_hits == 0) return rb::fail(RB_ERR_INVALID_ARG, "a hits buffer with max_hits == 0");
+    int rc = check_device(e ? e->device : 0);  // (argument shape first, then the device, then the handle: without a GPU nothing here can work)
+    if (rc != RB_OK) return rc;
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    const size_t n_items = desc->n_items;
+    if (n_items >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    if (n_items == 0) return RB_OK;
+    if (!desc->d_seqs || !desc->d_offsets || !desc->d_lens) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
+    if ((desc->d_nmask == nullptr) != (desc->d_nmask_offsets == nullptr))
+        return rb::fail(RB_ERR_INVALID_ARG, "packed input needs both the N bitmap and its offsets");
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (e->shard_world != 1) return rb::fail(RB_ERR_INVALID_ARG, "hits on a column-sharded engine: a shard sees only its own bins");
+    const size_t nf = e->filters.size();
+    if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
+    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+    const bool chunked = desc->chunk_start != 0 || desc->chunk_length != 0 || desc->d_read_ids != nullptr;
+    const void *d_lens = desc->d_lens;
+    const uint8_t *d_pre_status = nullptr;
+    uint32_t max_len = desc->max_len;
+    if (chunked) {
+        rc = e->d_efflens.ensure(n_items * 4);
+        if (rc == RB_OK) rc = e->d_prestatus.ensure(n_items);
+        if (rc != RB_OK) return rc;
+        RB_HIP(launch_chunk_prep((const uint32_t *)desc->d_lens, (const uint32_t *)desc->d_read_ids, (uint32_t)n_items, desc->chunk_start,
+                                 desc->chunk_length, (uint32_t *)e->d_efflens.p, (uint8_t *)e->d_prestatus.p, st));
+        d_lens = e->d_efflens.p;
+        d_pre_status = (const uint8_t *)e->d_prestatus.p;
+        if (desc->chunk_length && desc->chunk_length < max_len) max_len = desc->chunk_length;
+    }
+    // t for min_count == 0: the table the decision kernel reads, entry [len][filter][0] -- one definition of the threshold
+    const uint16_t *thr = nullptr;
+    uint32_t thr_len = 0;
+    if ((rc = ensure_thresholds(e, max_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
+    const uint32_t cap = d_out->hits ? max_hits : 0u;  // without a record buffer nothing is kept: the totals stay exact
+    std::vector<HitsLaunch> launches(nf);
+    uint32_t min_len = 0, max_slices = 0;
+    for (size_t fi = 0; fi < nf; ++fi) {
+        const rb_dibf *f = e->filters[fi];
+        HitsLaunch &a = launches[fi];
+        a = HitsLaunch{};
+        a.f = f->dev;
+        a.f.comp_n = e->revcomp_of_n;
+        a.src.seqs = (const uint8_t *)desc->d_seqs;
+        a.src.offsets = (const uint64_t *)desc->d_offsets;
+        a.src.lens = (const uint32_t *)d_lens;
+        a.src.nmask = (const uint8_t *)desc->d_nmask;
+        a.src.nmask_offsets = (const uint64_t *)desc->d_nmask_offsets;
+        a.src.ids = (const uint32_t *)desc->d_read_ids;
+        a.src.base_off = desc->chunk_start;
+        a.src.max_len = max_len;
+        a.n_items = (uint32_t)n_items;
+        const uint32_t W = (uint32_t)f->geo.bin_width;
+        a.col_begin = 0;
+        a.col_end = W;
+        if (W > 64) {
+            a.wpl = 2; a.lg = 6;
+        } else {
+            a.wpl = 1; a.lg = 0;
+            while ((1u << a.lg) < W) ++a.lg;
+        }
+        const uint32_t slice_words = (1u << a.lg) * a.wpl;
+        a.n_slices = (W + slice_words - 1) / slice_words;
+        const uint32_t kmers = max_len >= f->geo.kmer_size ? max_len - (uint32_t)f->geo.kmer_size + 1 : 0;
+        a.planes = kmers <= 1023 ? 10 : 16;
+        a.nt = f->geo.n_blocks * f->stride * 8 > e->nt_threshold_bytes;
+        a.thr = thr;
+        a.thr_len = thr_len;
+        a.nf = (uint32_t)nf;
+        a.fi = (uint32_t)fi;
+        a.min_count = min_count;
+        a.max_hits = cap;
+        a.pre_status = d_pre_status;
+        max_slices = std::max(max_slices, a.n_slices);
+        min_len = std::max<uint32_t>(min_len, (uint32_t)f->geo.kmer_size);
+    }
+    const size_t seg_bytes = n_items * (size_t)max_slices * 2 * (size_t)cap * 8;
+    if ((rc = e->d_hits_ws.ensure(seg_bytes + n_items * (size_t)max_slices * 2 * 4)) != RB_OK) return rc;
+    std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
+    if (e->timing && e->ev_used < ((size_t)1 << 16)) {
+        if (e->ev_used == e->ev_ring.size()) {
+            hipEvent_t a = nullptr, b = nullptr;
+            RB_HIP(hipEventCreate(&a));
+            RB_HIP(hipEventCreate(&b));
+            e->ev_ring.emplace_back(a, b);
+        }
+        evp = &e->ev_ring[e->ev_used++];
+        RB_HIP(hipEventRecord(evp->first, st));
+    }
+    HitsOut out;
+    out.hits = (rb_u32x2 *)d_out->hits;
+    out.n_hits = (uint32_t *)d_out->n_hits;
+    out.status = (uint8_t *)d_out->status;
+    uint64_t *bin_reads = (uint64_t *)d_out->bin_reads;
+    for (size_t fi = 0; fi < nf; ++fi) {
+        HitsLaunch &a = launches[fi];
+        a.min_len = min_len;
+        a.seg = e->d_hits_ws.p;
+        a.seg_count = (uint32_t *)((char *)e->d_hits_ws.p + seg_bytes);
+        a.bin_reads = bin_reads;
+        RB_HIP(launch_ibf_hits(a, st));
+        RB_HIP(launch_finish_hits(a, (const uint32_t *)d_lens, out, st));
+        if (bin_reads) bin_reads += e->filters[fi]->geo.n_bins;
+    }
+    if (evp) RB_HIP(hipEventRecord(evp->second, st));
+    if (!stream) RB_HIP(hipStreamSynchronize(st));
+    return RB_OK;
+}
+
+int rb_hits_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, uint16_t min_count, uint32_t max_hits,
+                         const rb_hits_out *d_out, void *stream)
+{
+    return hits_device_impl(e, desc, error_rate, significance, min_count, max_hits, d_out, stream);
+}
+
+int rb_hits_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *read_ids,
+                  size_t n_items, double error_rate, double significance, uint16_t min_count, uint32_t max_hits, const rb_hits_out *out)
+{
+    if (!out) return rb::fail(RB_ERR_INVALID_ARG, "null output struct");
+    if (!out->hits && !out->n_hits && !out->bin_reads) return rb::fail(RB_ERR_INVALID_ARG, "rb_hits_out with no output");
+    if (out->hits && max_hits == 0) return rb::fail(RB_ERR_INVALID_ARG, "a hits buffer with max_hits == 0");
+    int rc = check_device(e ? e->device : 0);
+    if (rc != RB_OK) return rc;
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    const size_t n = read_ids ? n_items : n_reads;  // without a selection the work items are the reads
+    if (n == 0) return RB_OK;
+    if (!seqs || !offsets || !lens || n_reads == 0) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
+    if (n >= (1ULL << 31) || n_reads >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    if (read_ids)
+        for (size_t i = 0; i < n; ++i)
+            if (read_ids[i] >= n_reads) return rb::fail(RB_ERR_INVALID_ARG, "read id beyond the batch");
+    uint64_t hi = 0, lo = ~0ULL;
+    uint32_t max_len = 0;
+    for (size_t i = 0; i < n_reads; ++i) {
+        hi = std::max<uint64_t>(hi, offsets[i] + lens[i]);
+        lo = std::min<uint64_t>(lo, offsets[i]);
+        max_len = std::max(max_len, lens[i]);
+    }
+    const uint64_t span = hi - lo;
+    hipStream_t st = e->stream;
+    std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
+    size_t nf = 0, total_bins = 0, max_slices = 1;
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        nf = e->filters.size();
+        for (const rb_dibf *f : e->filters) {
+            total_bins += f->geo.n_bins;
+            max_slices = std::max<size_t>(max_slices, f->geo.bin_width > 64 ? (f->geo.bin_width + 127) / 128 : 1);
+        }
+        if ((rc = e->d_seqs.ensure(span ? span : 1)) != RB_OK) return rc;
+        if ((rc = e->d_offsets.ensure(n_reads * 8)) != RB_OK) return rc;
+        if ((rc = e->d_lens.ensure(n_reads * 4)) != RB_OK) return rc;
+    }
+    if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
+    // sub-batches: workspace (S x 2 x cap records and S x 2 counters per item) plus staged outputs (nf x cap records, nf counters and a
+    // status byte per item) stay at or below kHitsBudget; a single item that needs more goes alone
+    constexpr size_t kHitsBudget = 256ull << 20;
+    const size_t cap = out->hits ? max_hits : 0;
+    const size_t per_item = max_slices * 2 * (cap * 8 + 4) + nf * (cap * 8 + 4) + 1 + 4;
+    const size_t sub_max = std::max<size_t>(1, std::min<size_t>(n, kHitsBudget / per_item));
+    // staging: u64 bin_reads[total_bins] | rb_hit hits[sub x nf x cap] | u32 n_hits[sub x nf] | u32 ids[sub] | u8 status[sub]
+    const size_t o_hits = 8 * total_bins, o_n = o_hits + sub_max * nf * cap * 8, o_ids = o_n + sub_max * nf * 4, o_status = o_ids + sub_max * 4;
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        if ((rc = e->d_hits_io.ensure(o_status + sub_max)) != RB_OK) return rc;
+    }
+    char *io = (char *)e->d_hits_io.p;
+    if (span) RB_HIP(hipMemcpyAsync(e->d_seqs.p, seqs + lo, span, hipMemcpyHostToDevice, st));
+    RB_HIP(hipMemcpyAsync(e->d_offsets.p, offsets, n_reads * 8, hipMemcpyHostToDevice, st));
+    RB_HIP(hipMemcpyAsync(e->d_lens.p, lens, n_reads * 4, hipMemcpyHostToDevice, st));
+    if (out->bin_reads) RB_HIP(hipMemsetAsync(io, 0, 8 * total_bins, st));
+    std::vector<uint32_t> h_n(sub_max * nf);
+    std::vector<rb_hit> h_hits(cap ? sub_max * nf * cap : 0);
+    for (size_t b0 = 0; b0 < n; b0 += sub_max) {
+        const size_t sub = std::min(sub_max, n - b0);
+        if (read_ids) RB_HIP(hipMemcpyAsync(io + o_ids, read_ids + b0, 4 * sub, hipMemcpyHostToDevice, st));
+        rb_batch_desc desc;
+        std::memset(&desc, 0, sizeof desc);
+        desc.d_seqs = (const char *)e->d_seqs.p - lo;  // device address of the caller's seqs[0]
+        // work item j of the sub-batch is read read_ids[b0 + j], or read b0 + j
+        desc.d_offsets = read_ids ? e->d_offsets.p : (const void *)((const uint64_t *)e->d_offsets.p + b0);
+        desc.d_lens = read_ids ? e->d_lens.p : (const void *)((const uint32_t *)e->d_lens.p + b0);
+        desc.n_items = sub;
+        desc.max_len = max_len;
+        desc.d_read_ids = read_ids ? io + o_ids : nullptr;
+        rb_hits_out d_out;
+        d_out.hits = cap ? io + o_hits : nullptr;
+        d_out.n_hits = io + o_n;  // (always: the copy below keeps to the records that were written)
+        d_out.status = out->status ? io + o_status : nullptr;
+        d_out.bin_reads = out->bin_reads ? io : nullptr;
+        rc = hits_device_impl(e, &desc, error_rate, significance, min_count, max_hits, &d_out, (void *)st);
+        if (rc != RB_OK) {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+        RB_HIP(hipMemcpyAsync(h_n.data(), io + o_n, 4 * sub * nf, hipMemcpyDeviceToHost, st));
+        if (cap) RB_HIP(hipMemcpyAsync(h_hits.data(), io + o_hits, 8 * sub * nf * cap, hipMemcpyDeviceToHost, st));
+        if (out->status) RB_HIP(hipMemcpyAsync((uint8_t *)out->status + b0, io + o_status, sub, hipMemcpyDeviceToHost, st));
+        RB_HIP(hipStreamSynchronize(st));
+        if (out->n_hits) std::memcpy((uint32_t *)out->n_hits + b0 * nf, h_n.data(), 4 * sub * nf);
+        if (cap)  // only what was written: the caller's slots beyond a list stay as they are
+            for (size_t q = 0; q < sub * nf; ++q) {
+                const size_t keep = std::min<size_t>(h_n[q], cap);
+                if (keep) std::memcpy((rb_hit *)out->hits + (b0 * nf + q) * cap, h_hits.data() + q * cap, keep * sizeof(rb_hit));
+            }
+    }
+    if (out->bin_reads) {  // ADD: the caller's profile accumulates over calls
+        std::vector<uint64_t> h_bins(total_bins);
+        RB_HIP(hipMemcpy(h_bins.data(), io, 8 * total_bins, hipMemcpyDeviceToHost));
+        uint64_t *dst = (uint64_t *)out->bin_reads;
+        for (size_t b = 0; b < total_bins; ++b) dst[b] += h_bins[b];
+    }
     return RB_OK;
 }
 

@@ -939,6 +939,173 @@ __global__ void reduce_locate_slices_kernel(const LocatePart *__restrict__ part,
     if (out.status && fidx == 0) out.status[i] = status;
 }
 
+// HITS: the opt-in pass (rb_hits_batch_device) that lists EVERY (bin, strand) whose count reached the threshold, with the count --
+// the sparse form of what seqan::count returns.  The kernel is ibf_locate_kernel up to the bit-sliced c > t-1 mask of a strand; then,
+// while that strand's planes are still live (records are per strand so that only one strand's planes ever are):
+//   * the wave walks the words that hold a hit in rising bin order (columns rise with the lane, words with w, bins with the bit): a
+//     ballot finds the lanes, the lane's mask and planes travel as scalars (readlane), and lane j of the wave handles bin j of the word;
+//   * a hit's number in the strand's run is the scalar count of the words before plus mbcnt within the word -- a prefix that needs no
+//     scan; the count is rebuilt from the planes (bit i of the count is bit j of plane i) and the 8-byte record goes out with one vector
+//     store into the (item, slice, strand) segment of the workspace while its number is below the cap.  The walk is wave-uniform, off
+//     the gather path and bounded by 2^LG x WPL words; beyond the cap nothing is stored and the totals stay exact.
+// No atomic decides a placement.  bin_reads (optional) takes one atomic add per distinct hit bin from the OR of the two masks.  An item
+// whose status is not RB_OK is left alone: finish_hits_kernel does not look at its segments.  t == 0: every existing bin on both strands;
+// t beyond what NP planes hold: none.
+template <int LG, int WPL, int NP, int H, bool NT>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(3, 8))) void ibf_hits_kernel(
+    IbfDev f, uint32_t col_begin, uint32_t col_end, ReadSrc src, uint32_t n_items, uint32_t n_slices, const uint16_t *__restrict__ thr,
+    uint32_t thr_len, uint32_t nf, uint32_t fi, uint32_t min_count, uint32_t max_hits, uint32_t min_len,
+    const uint8_t *__restrict__ pre_status, rb_u32x2 *__restrict__ seg, uint32_t *__restrict__ seg_count,
+    unsigned long long *__restrict__ bin_reads)
+{
+    __shared__ uint8_t s_stage[kWavesPerBlock][kStageBytes];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const uint64_t witem = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
+    // (scalar on purpose: the segment addresses below are then scalar arithmetic and cost no vector register across the gathers)
+    const uint32_t item = __builtin_amdgcn_readfirstlane((uint32_t)(witem / n_slices));
+    const uint32_t slice = __builtin_amdgcn_readfirstlane((uint32_t)(witem - (uint64_t)(uint32_t)(witem / n_slices) * n_slices));
+    if (item >= n_items) return;  // wave-uniform; there are no block-level barriers below
+    {  // the status rules of the locate pass (reduce_locate_slices_kernel): such an item has no hits and feeds no profile
+        const uint32_t raw = src.lens[item];
+        if ((pre_status && pre_status[item] != RB_OK) || raw > src.max_len || raw < min_len) return;  // wave-uniform
+    }
+
+    const LaneCols<WPL> lc = make_lane_cols<LG, WPL>(f, lane, col_begin, col_end, slice);
+    uint32_t len;
+    const BaseSrc seq = make_base_src(src, item, &len);
+    const uint32_t n = len >= f.k ? len - f.k + 1 : 0;
+    // the caller's threshold, or the one the decision kernel reads for this length and filter at the caller's error rate
+    const uint32_t tl = len < thr_len ? len : thr_len - 1;
+    const uint32_t t = min_count ? min_count : __builtin_amdgcn_readfirstlane((uint32_t)thr[((size_t)tl * nf + fi) * 2]);
+    const bool group0 = lane < (1 << LG);  // the lane group whose columns are reported (every group holds the same totals)
+
+    uint64_t seen[WPL];  // hit on either strand: the only per-lane state that lives across the strands
+#pragma unroll
+    for (int w = 0; w < WPL; ++w) seen[w] = 0ULL;
+    for (int strand = 0; strand < 2; ++strand) {
+        Planes<NP> pl[WPL];
+#pragma unroll
+        for (int w = 0; w < WPL; ++w) pl[w].clear();
+        count_strand<LG, WPL, NP, H, NT>(pl, f, lc, seq, len, n, strand, 0u, (uint32_t)TileShape<LG>::ITEMS, 0, TileShape<LG>::STEPS / 8,
+                                         s_stage[wave], lane);
+        // ---- bins with c >= t, i.e. c > t - 1
+        uint64_t hit[WPL];
+#pragma unroll
+        for (int w = 0; w < WPL; ++w) hit[w] = (t == 0 && group0) ? lc.valid[w] : 0ULL;
+        if (t > 0 && t <= (1u << NP) - 1u) {  // wave-uniform
+            const uint32_t tt = t - 1u;
+#pragma unroll
+            for (int w = 0; w < WPL; ++w) {
+                uint64_t gt = 0, eq = lc.valid[w];
+#pragma unroll
+                for (int i = NP - 1; i >= 0; --i) {
+                    if ((tt >> i) & 1u) {  // scalar branch
+                        eq &= pl[w].p[i];
+                    } else {
+                        gt |= eq & pl[w].p[i];
+                        eq &= ~pl[w].p[i];
+                    }
+                }
+                hit[w] = group0 ? gt : 0ULL;
+            }
+        }
+        bool mine = false;
+#pragma unroll
+        for (int w = 0; w < WPL; ++w) {
+            mine |= hit[w] != 0ULL;
+            seen[w] |= hit[w];
+        }
+        // ---- the records, one word of 64 bins at a time in rising bin order: the wave visits the lanes that hold a hit (lowest first;
+        // a strand without one, the common case, ends at the ballot), takes such a lane's mask and planes as scalars, and lane j writes
+        // bin j of the word.  The number of a hit is the scalar count of the words before plus mbcnt within the word.
+        uint32_t total = 0;
+        uint64_t who = __ballot(mine);
+        rb_u32x2 *out = seg + (((size_t)item * n_slices + slice) * 2 + (size_t)strand) * max_hits;
+        while (who != 0ULL) {  // wave-uniform, at most 2^LG rounds
+            const int from = (int)__builtin_amdgcn_readfirstlane((uint32_t)(__ffsll((unsigned long long)who) - 1));
+            who &= who - 1;
+#pragma unroll
+            for (int w = 0; w < WPL; ++w) {
+                const uint32_t mlo = readlane32((uint32_t)hit[w], from), mhi = readlane32((uint32_t)(hit[w] >> 32), from);
+                if ((mlo | mhi) == 0u) continue;  // scalar
+                if (total < max_hits) {  // scalar: past the cap a word is counted, not stored
+                    const uint32_t mhalf = lane < 32 ? mlo : mhi;
+                    const bool set = (mhalf >> (lane & 31)) & 1u;
+                    const uint32_t pos = total + __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
+                    uint32_t c = 0;
+#pragma unroll
+                    for (int i = NP - 1; i >= 0; --i) {  // bit i of the count is bit j of plane i
+                        const uint32_t half = lane < 32 ? readlane32((uint32_t)pl[w].p[i], from) : readlane32((uint32_t)(pl[w].p[i] >> 32), from);
+                        c = (c << 1) | ((half >> (lane & 31)) & 1u);
+                    }
+                    if (set && pos < max_hits) {  // pos < max_hits: inside the segment
+                        rb_u32x2 rec;
+                        rec.x = (col_begin + slice * (uint32_t)((1 << LG) * WPL) + (uint32_t)(from * WPL + w)) * 64u + (uint32_t)lane;
+                        rec.y = c | ((uint32_t)strand << 16);
+                        out[pos] = rec;
+                    }
+                }
+                total += (uint32_t)__builtin_popcount(mlo) + (uint32_t)__builtin_popcount(mhi);
+            }
+        }
+        if (lane == 0) seg_count[((size_t)slice * 2 + (size_t)strand) * n_items + item] = total;
+    }
+    if (bin_reads) {  // uniform: one add per distinct hit bin, word by word as above
+        bool mine = false;
+#pragma unroll
+        for (int w = 0; w < WPL; ++w) mine |= seen[w] != 0ULL;
+        uint64_t who = __ballot(mine);
+        while (who != 0ULL) {
+            const int from = (int)__builtin_amdgcn_readfirstlane((uint32_t)(__ffsll((unsigned long long)who) - 1));
+            who &= who - 1;
+#pragma unroll
+            for (int w = 0; w < WPL; ++w) {
+                const uint32_t mlo = readlane32((uint32_t)seen[w], from), mhi = readlane32((uint32_t)(seen[w] >> 32), from);
+                if (((lane < 32 ? mlo : mhi) >> (lane & 31)) & 1u)
+                    atomicAdd(bin_reads + ((size_t)(col_begin + slice * (uint32_t)((1 << LG) * WPL) + (uint32_t)(from * WPL + w)) * 64u + (uint32_t)lane), 1ULL);
+            }
+        }
+    }
+}
+
+// Finish one filter of a hits call: merge the column slices of an item (slices hold rising bins) and, inside a slice, the two strands'
+// sorted runs into (bin, strand) order; apply the per-item status (the locate pass's rules); write n_hits -- exact, whatever the cap --
+// and the first min(n_hits, max_hits) records.  Slots beyond those are not written.  A run longer than the cap was cut at the cap by the
+// kernel above: the first max_hits of the merge need no more than the first max_hits of either run.  One thread per work item.
+__global__ void finish_hits_kernel(const rb_u32x2 *__restrict__ seg, const uint32_t *__restrict__ seg_count, uint32_t n_slices, uint32_t n_items,
+                                   const uint32_t *__restrict__ lens, const uint8_t *__restrict__ pre_status, uint32_t max_len, uint32_t min_len,
+                                   uint32_t max_hits, HitsOut out, uint32_t nf, uint32_t fidx)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    uint8_t status = RB_OK;
+    const uint32_t len = lens[i];
+    if (pre_status && pre_status[i] != RB_OK) status = pre_status[i];
+    else if (len > max_len) status = RB_ERR_INVALID_ARG;
+    else if (len < min_len) status = RB_ERR_SHORT_READ;
+    const size_t o = (size_t)i * nf + fidx;
+    uint32_t total = 0, written = 0;
+    if (status == RB_OK) {
+        rb_u32x2 *dst = out.hits ? out.hits + o * max_hits : nullptr;
+        for (uint32_t s = 0; s < n_slices; ++s) {
+            const uint32_t na = seg_count[((size_t)s * 2) * n_items + i], nb = seg_count[((size_t)s * 2 + 1) * n_items + i];
+            total += na + nb;
+            if (!dst || written >= max_hits || na + nb == 0) continue;
+            const rb_u32x2 *a = seg + (((size_t)i * n_slices + s) * 2) * max_hits, *b = a + max_hits;
+            const uint32_t ma = na < max_hits ? na : max_hits, mb = nb < max_hits ? nb : max_hits;
+            uint32_t ia = 0, ib = 0;
+            while (written < max_hits && (ia < ma || ib < mb)) {
+                // forward first in an equal bin: (bin, strand) order
+                const bool take_a = ib >= mb || (ia < ma && a[ia].x <= b[ib].x);
+                dst[written++] = take_a ? a[ia++] : b[ib++];
+            }
+        }
+    }
+    if (out.n_hits) out.n_hits[o] = total;
+    if (out.status && fidx == 0) out.status[i] = status;
+}
+
 // Throughput form over a MERGED table: several narrow filters of one hash geometry (same noOfBlocks, k and h -- every filter
 // the reference builds with one fragment_size has them: noOfBits = BinSizeBits x 64 x binWidth, so noOfBlocks = BinSizeBits
 // whatever the bin count, src/IBF/IBFBuild.cpp:404-413) hash a k-mer to the SAME block number, so their blocks can sit side
@@ -2774,6 +2941,62 @@ hipError_t launch_reduce_locate_slices(const LocatePart *part, uint32_t n_slices
     if (n_items == 0) return hipSuccess;
     hipLaunchKernelGGL(reduce_locate_slices_kernel, dim3((n_items + 255) / 256), dim3(256), 0, st, part, n_slices, n_items, lens, pre_status,
                        max_len, min_len, out, nf, fidx);
+    return hipGetLastError();
+}
+
+// hits: the builds of the locate pass, case for case
+template <int LG, int WPL, int NP, int H>
+static hipError_t launch_hits_nt(const HitsLaunch &a, hipStream_t st)
+{
+    const uint64_t items = (uint64_t)a.n_items * a.n_slices;
+    dim3 grid((uint32_t)((items + kWavesPerBlock - 1) / kWavesPerBlock));
+    if constexpr (LG == 6) {
+        if (a.nt) {
+            hipLaunchKernelGGL((ibf_hits_kernel<LG, WPL, NP, H, true>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.col_begin, a.col_end, a.src,
+                               a.n_items, a.n_slices, a.thr, a.thr_len, a.nf, a.fi, a.min_count, a.max_hits, a.min_len, a.pre_status,
+                               (rb_u32x2 *)a.seg, a.seg_count, (unsigned long long *)a.bin_reads);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((ibf_hits_kernel<LG, WPL, NP, H, false>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.col_begin, a.col_end, a.src,
+                       a.n_items, a.n_slices, a.thr, a.thr_len, a.nf, a.fi, a.min_count, a.max_hits, a.min_len, a.pre_status,
+                       (rb_u32x2 *)a.seg, a.seg_count, (unsigned long long *)a.bin_reads);
+    return hipGetLastError();
+}
+
+template <int NP, int H>
+static hipError_t dispatch_hits(const HitsLaunch &a, hipStream_t st)
+{
+    if (a.wpl == 2) return launch_hits_nt<6, 2, NP, H>(a, st);
+    switch (a.lg) {
+    case 0: return launch_hits_nt<0, 1, NP, H>(a, st);
+    case 1: return launch_hits_nt<1, 1, NP, H>(a, st);
+    case 2: return launch_hits_nt<2, 1, NP, H>(a, st);
+    case 3: return launch_hits_nt<3, 1, NP, H>(a, st);
+    case 4: return launch_hits_nt<4, 1, NP, H>(a, st);
+    case 5: return launch_hits_nt<5, 1, NP, H>(a, st);
+    default: return launch_hits_nt<6, 1, NP, H>(a, st);
+    }
+}
+
+hipError_t launch_ibf_hits(const HitsLaunch &a, hipStream_t st)
+{
+    if (a.n_items == 0) return hipSuccess;
+    if (!a.thr || a.thr_len == 0 || !a.seg_count || (a.max_hits && !a.seg) || a.n_slices == 0 || (a.wpl != 1 && a.wpl != 2) || a.lg < 0 || a.lg > 6)
+        return hipErrorInvalidValue;
+    // every column the grid reaches lies inside the filter, every slice has its segments
+    if (a.col_end > a.f.bin_width || a.col_begin > a.col_end ||
+        (uint64_t)a.n_slices * (uint64_t)((1u << a.lg) * (uint32_t)a.wpl) < (uint64_t)(a.col_end - a.col_begin))
+        return hipErrorInvalidValue;
+    if (a.f.n_hash == 3) return a.planes <= 10 ? dispatch_hits<10, 3>(a, st) : dispatch_hits<16, 3>(a, st);
+    return dispatch_hits<16, 0>(a, st);
+}
+
+hipError_t launch_finish_hits(const HitsLaunch &a, const uint32_t *lens, const HitsOut &out, hipStream_t st)
+{
+    if (a.n_items == 0) return hipSuccess;
+    hipLaunchKernelGGL(finish_hits_kernel, dim3((a.n_items + 255) / 256), dim3(256), 0, st, (const rb_u32x2 *)a.seg, a.seg_count, a.n_slices,
+                       a.n_items, lens, a.pre_status, a.src.max_len, a.min_len, a.max_hits, out, a.nf, a.fi);
     return hipGetLastError();
 }
 

@@ -321,6 +321,7 @@ struct ReadState
     bool classified = false, failed = false;
     int best = -1;
     std::string bin_rows;  // --report-bins: this read's lines of classified_bins.tsv
+    std::string hit_rows;  // --report-hits: this read's lines of classified_hits.tsv
 };
 
 // host pipeline knobs (command line)
@@ -343,6 +344,8 @@ struct IngestOptions
     size_t segment_bytes = 0;    // tests: segments far smaller than a megabyte (0 = segment_mb)
     size_t live_batch = 64;      // usage "target" replay: chunks per micro-batch
     bool report_bins = false;    // --report-bins: locate the reads every chunk classified (rb_locate_batch) and write classified_bins.tsv
+    bool report_hits = false;    // --report-hits: list every (bin, strand) those reads hit (rb_hits_batch): classified_hits.tsv and bin_profile.tsv
+    uint32_t max_hits = 64;      // --max-hits N: records kept per (read, filter); n_hits in the report stays exact
     std::vector<std::string> bin_maps;  // --bin-map FILE (may repeat): <filter name>.bins.tsv of build --write-bin-map -> a record_id column
     size_t bytes() const { return segment_bytes ? segment_bytes : (segment_mb << 20); }
 };
@@ -402,8 +405,12 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
         std::ofstream bins_out;
         std::vector<const interleave::IBFMeta*> all_filters;
         std::vector<std::vector<std::string>> bin_records;  // per filter: bin -> record id (empty: no map given)
-        if (opt.report_bins) {
-            if (multi) throw std::runtime_error("--report-bins works on one device");
+        // --report-hits: classified_hits.tsv, one line per (bin, strand) such a read hit, in file order, and bin_profile.tsv, the number of
+        // those reads that hit each bin over the whole run
+        std::ofstream hits_out;
+        std::vector<uint64_t> bin_profile;  // one entry per bin of every filter, filter after filter (rb_hits_out.bin_reads)
+        if (opt.report_bins || opt.report_hits) {
+            if (multi) throw std::runtime_error("--report-bins and --report-hits work on one device");
             for (const interleave::IBFMeta& f : DepletionFilters) all_filters.push_back(&f);
             for (const interleave::IBFMeta& f : TargetFilters) all_filters.push_back(&f);
             bin_records.resize(all_filters.size());
@@ -416,9 +423,19 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                     if (all_filters[fi]->name == stem) { bin_records[fi] = read_bin_map(path); used = true; }
                 if (!used) throw std::runtime_error("--bin-map " + path + ": no filter named " + stem);
             }
+        }
+        if (opt.report_bins) {
             bins_out.open(std::filesystem::path(config.output_dir) / "classified_bins.tsv");
             if (!bins_out) { std::cerr << "ERROR: Unable to open the file: classified_bins.tsv" << std::endl; return; }
             bins_out << "read_id\tfilter\tbest_bin\tstrand\tmax_count\tthreshold\thit_bins\tchunk" << (opt.bin_maps.empty() ? "" : "\trecord_id") << '\n';
+        }
+        if (opt.report_hits) {
+            hits_out.open(std::filesystem::path(config.output_dir) / "classified_hits.tsv");
+            if (!hits_out) { std::cerr << "ERROR: Unable to open the file: classified_hits.tsv" << std::endl; return; }
+            hits_out << "read_id\tfilter\tbin" << (opt.bin_maps.empty() ? "" : "\trecord_id") << "\tstrand\tcount\tthreshold\tn_hits\n";
+            size_t total_bins = 0;
+            for (const interleave::IBFMeta* f : all_filters) total_bins += (size_t)f->filter.noOfBins;
+            bin_profile.assign(total_bins, 0);
         }
         seqio::MappedFile mapped(read_file.string());
         if (!mapped.is_open()) {
@@ -505,7 +522,7 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
         // the chunk loop of one segment (classify.hpp:262-299, batch-wise): the reads go to the GPU in calls of at most
         // batch_reads; chunk 0 comes ready-made from the parser threads, later chunks are gathered here for the reads that
         // are still unclassified
-        auto classify_segment = [&](const seqio::Segment& seg, std::vector<ReadState>& state) {
+        auto classify_segment = [&](const seqio::Segment& seg, std::vector<ReadState>& state, std::vector<uint64_t>& seg_profile) {
             const std::vector<seqio::Record>& recs = seg.batch.records;
             std::vector<char> flat;
             std::vector<uint64_t> offs;
@@ -555,12 +572,54 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                             if (res.decision[j]) {
                                 st.classified = true;
                                 st.best = target ? res.best_target[j] : -1;
-                                if (opt.report_bins) located.push_back((uint32_t)j);
+                                if (opt.report_bins || opt.report_hits) located.push_back((uint32_t)j);
                             } else {
                                 next.push_back(idx[j]);
                             }
                         }
-                        if (!located.empty()) {
+                        if (opt.report_hits && !located.empty()) {
+                            // every (bin, strand) at or above the decision threshold of the reads this chunk classified; the profile of
+                            // the segment is added to the run's when the segment's turn to write comes
+                            // the record buffer of a call stays at or below 64 MiB whatever --max-hits is: the reads go in pieces
+                            const size_t nf = all_filters.size(), cap = opt.max_hits;
+                            const size_t piece = std::max<size_t>(1, ((size_t)64 << 20) / (nf * cap * sizeof(rb_hit)));
+                            for (size_t p0 = 0; p0 < located.size(); p0 += piece) {
+                            const size_t nl = std::min(piece, located.size() - p0);
+                            std::vector<rb_hit> hv(nl * nf * cap);
+                            std::vector<uint32_t> nh(nl * nf);
+                            std::vector<uint8_t> hs(nl);
+                            rb_hits_out ho{hv.data(), nh.data(), hs.data(), seg_profile.data()};
+                            interleave::throw_status(rb_hits_batch(interleave::detail::engine_for(DepletionFilters, TargetFilters), base, offs.data(),
+                                                                   lens.data(), idx.size(), located.data() + p0, nl, Conf.error_rate, Conf.significance, 0,
+                                                                   opt.max_hits, &ho),
+                                                     "rb_hits_batch");
+                            for (size_t q = 0; q < nl; ++q) {
+                                if (hs[q] != RB_OK) continue;
+                                const size_t j = located[p0 + q];
+                                const seqio::Record& r = recs[idx[j]];
+                                size_t w = 0;
+                                while (w < r.id_len && r.id[w] != ' ' && r.id[w] != '\t') ++w;
+                                std::string& rows = state[idx[j]].hit_rows;
+                                for (size_t fi = 0; fi < nf; ++fi) {
+                                    const uint16_t t = rb_threshold(lens[j], all_filters[fi]->filter.kmerSize, Conf.error_rate, Conf.significance);
+                                    const uint32_t total = nh[q * nf + fi];
+                                    const size_t kept = std::min<size_t>(total, cap);
+                                    for (size_t h = 0; h < kept; ++h) {
+                                        const rb_hit& rec = hv[(q * nf + fi) * cap + h];
+                                        rows.append(r.id, w);
+                                        rows += '\t' + all_filters[fi]->name + '\t' + std::to_string(rec.bin);
+                                        if (!opt.bin_maps.empty()) {
+                                            const std::vector<std::string>& map = bin_records[fi];
+                                            rows += '\t' + ((rec.bin < map.size() && !map[rec.bin].empty()) ? map[rec.bin] : std::string("-"));
+                                        }
+                                        rows += std::string("\t") + (rec.strand ? '-' : '+') + '\t' + std::to_string(rec.count) + '\t' + std::to_string(t) + '\t' +
+                                                std::to_string(total) + '\n';
+                                    }
+                                }
+                            }
+                            }
+                        }
+                        if (opt.report_bins && !located.empty()) {
                             const size_t nf = all_filters.size(), nl = located.size();
                             std::vector<uint16_t> mc(nl * nf);
                             std::vector<int32_t> bb(nl * nf);
@@ -648,7 +707,8 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                     }
                     std::vector<ReadState> state(seg->batch.records.size());
                     const auto t0 = std::chrono::steady_clock::now();
-                    classify_segment(*seg, state);
+                    std::vector<uint64_t> seg_profile(bin_profile.size(), 0);
+                    classify_segment(*seg, state, seg_profile);
                     const double secs = seconds_since(t0);
                     SegmentOutput so = size_segment(*seg, state);
                     std::vector<uint64_t> at(n_out, 0);
@@ -667,6 +727,10 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                         for (const std::string& l : so.error_lines) log_line("error", l);
                         if (opt.report_bins)
                             for (const ReadState& rs : state) bins_out << rs.bin_rows;
+                        if (opt.report_hits) {
+                            for (const ReadState& rs : state) hits_out << rs.hit_rows;
+                            for (size_t b = 0; b < bin_profile.size(); ++b) bin_profile[b] += seg_profile[b];
+                        }
                         for (size_t f = 0; f < TargetFilters.size(); ++f) TargetFilters[f].classified += so.per_target[f];
                         ++write_seq;
                     }
@@ -712,6 +776,21 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
         for (auto& o : outputs) {
             o->close();
             if (!o->ok()) std::cerr << "ERROR: writing an output file failed: " << o->error() << std::endl;
+        }
+        if (opt.report_hits) {
+            std::ofstream prof(std::filesystem::path(config.output_dir) / "bin_profile.tsv");
+            if (!prof) std::cerr << "ERROR: Unable to open the file: bin_profile.tsv" << std::endl;
+            else prof << "filter\tbin\trecord_id\treads\n";
+            size_t at = 0;
+            for (size_t fi = 0; prof && fi < all_filters.size(); ++fi) {
+                const size_t nb = (size_t)all_filters[fi]->filter.noOfBins;
+                for (size_t b = 0; b < nb; ++b)
+                    if (bin_profile[at + b])
+                        prof << all_filters[fi]->name << '\t' << b << '\t'
+                             << ((b < bin_records[fi].size() && !bin_records[fi][b].empty()) ? bin_records[fi][b] : std::string("-")) << '\t'
+                             << bin_profile[at + b] << '\n';
+                at += nb;
+            }
         }
         const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
         const double avg = classify_reads_n ? classify_seconds / (double)classify_reads_n : 0.0;
@@ -903,6 +982,17 @@ int main(int argc, char const* argv[])
         else if (!std::strcmp(argv[i], "--classify-threads") && i + 1 < argc) opt.classify_threads = (unsigned)std::max(1, std::stoi(argv[++i]));
         else if (!std::strcmp(argv[i], "--calibrate")) opt.calibrate = true;
         else if (!std::strcmp(argv[i], "--report-bins")) opt.report_bins = true;
+        else if (!std::strcmp(argv[i], "--report-hits")) opt.report_hits = true;
+        else if (!std::strcmp(argv[i], "--max-hits")) {
+            char* end = nullptr;
+            const unsigned long long v = i + 1 < argc ? std::strtoull(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || argv[i + 1][0] == '-' || *end != '\0' || v < 1 || v > (1ull << 20)) {
+                std::cerr << "ERROR: --max-hits 1 .. 1048576" << std::endl;
+                return 1;
+            }
+            opt.max_hits = (uint32_t)v;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--write-bin-map")) g_write_bin_map = true;
         else if (!std::strcmp(argv[i], "--filter-stats")) {  // with a file: the stand-alone report; bare (usage build): for every filter built
             g_filter_stats = true;
@@ -950,7 +1040,9 @@ int main(int argc, char const* argv[])
                          "[--devices 0,1,...] [--parse-stats file]\n"
                          "  usage build:    [--write-bin-map]  beside every <name>.ibf, <name>.bins.tsv: bin -> record id and fragment bounds\n"
                          "  usage classify: [--report-bins]  classified_bins.tsv: bin, strand, count and hit bins of every classified read\n"
-                         "                  [--bin-map <name>.bins.tsv ...]  adds the record id of the bin to that report\n"
+                         "                  [--report-hits [--max-hits 64]]  classified_hits.tsv: every (bin, strand) at or above the threshold of those reads, with\n"
+                         "                                    its count, at most --max-hits per (read, filter) (n_hits stays exact); bin_profile.tsv: reads per bin\n"
+                         "                  [--bin-map <name>.bins.tsv ...]  adds the record id of the bin to these reports\n"
                          "                  [--filter-stats]  per-bin occupancy of every filter built: a summary and <name>.binstats.tsv (give the flag last, or\n"
                          "                                    before another flag: a bare word after it is taken as a file; a build's exit code stays 0 whatever the bins hold)\n"
                          "readbouncer_amd --verify-ibf <file.ibf> --reference <file.fasta> [--fragment-size N]\n"
