@@ -373,6 +373,56 @@ RB_API int rb_hits_batch(rb_engine *e, const char *seqs, const uint64_t *offsets
                          const uint32_t *read_ids, size_t n_items, double error_rate, double significance, uint16_t min_count,
                          uint32_t max_hits, const rb_hits_out *out);
 
+/* ---- spans: WHERE ALONG THE READ a bin matched: mask, span and longest run ---------------------------
+ * The reference has no such call.  seqan::count adds 1 per k-mer whose h words all hold the bin's bit (src/IBF/IBFClassify.cpp:97-98,
+ * 149-150) and nothing keeps WHICH k-mers of the read those were: max_matches and select_matches see the sums only (:48-71, :16-38).
+ * A bin is a fragment_size stretch of a reference record (src/IBF/IBFBuild.cpp:165-204); this is the other half of "the read matched
+ * record R around position P": which part of the read did.  An opt-in pass of its own, like locate and hits: it always reads the
+ * named filter's own table, whatever the engine's pruning / early-decision / merge / phased settings are, changes nothing any other
+ * call returns, and has no threshold (so no error_rate / significance).
+ * A QUERY is (work item, bin) against ONE filter of the engine (`filter`: deplete filters first).  With len = the bases rb_batch_desc
+ * selects for the item, k the filter's k-mer size and n_kmers = len - k + 1, POSITION p in [0, n_kmers) is the window of bases
+ * [p, p + k) of the chunk, in the read's own direction on both strands:
+ *   strand 0: p is a hit when all h words selected by the k-mer of that window have the bin's bit set -- the test by which seqan::count
+ *             adds 1 to fwd[bin]
+ *   strand 1: the same for the reverse complement of that window under the engine's N rule (rb_engine_set_revcomp_of_n) -- k-mer
+ *             n_kmers - 1 - p of the reverse-complemented chunk, so the hit positions of strand 1 number rev[bin]
+ * Per (query, strand) one rb_span; every slot of every output is written for every query (all mask_words words per (query, strand):
+ * zero beyond n_kmers, zero beyond what fits -- the caller clears nothing).  Positions at or beyond 64 x mask_words are left out of
+ * the MASK only: the record is exact whatever mask_words is, and mask_words == 0 is legal.
+ *   status   the item's status by the rules of rb_locate_out (RB_OK, RB_ERR_BAD_CHUNK, RB_ERR_INVALID_ARG for longer than max_len,
+ *            RB_ERR_SHORT_READ), and RB_ERR_INVALID_ARG when item >= n_items or bin >= the filter's n_bins -- both tested on the device
+ *            before anything is read through them: queries may come straight from another kernel's output
+ *   a query that is not RB_OK has n_kmers = 0, zero counts, 0xFFFFFFFF positions and a zero mask
+ * A column-sharded engine refuses with RB_ERR_INVALID_ARG, as locate does. */
+typedef struct rb_span {
+    uint32_t count;     /* hit positions, exact; its low 16 bits are seqan::count's uint16_t entry for this bin and strand */
+    uint32_t first;     /* lowest hit position;  0xFFFFFFFF when count == 0 */
+    uint32_t last;      /* highest hit position; 0xFFFFFFFF when count == 0 */
+    uint32_t run_start; /* start of the longest run of consecutive hit positions, the lowest such run on a tie; 0xFFFFFFFF when none */
+    uint32_t run_len;   /* its length; 0 when count == 0 */
+    uint32_t covered;   /* bases b of the chunk with a hit position p, p <= b < p + k */
+} rb_span;
+typedef struct rb_span_query { uint32_t item; uint32_t bin; } rb_span_query;
+typedef struct rb_spans_out {   /* any member may be NULL, not all */
+    void *spans;    /* rb_span [n_queries x 2]: strand 0, then strand 1 */
+    void *mask;     /* u64 [n_queries x 2 x mask_words]: bit p & 63 of word p >> 6 = position p is a hit */
+    void *n_kmers;  /* u32 [n_queries] */
+    void *status;   /* u8  [n_queries] */
+} rb_spans_out;
+/* Device pointers (d_queries: rb_span_query [n_queries]), asynchronous on `stream` (NULL = the engine's own stream, synchronised before
+ * returning); rb_batch_desc in full.  filter >= the engine's filters, a null descriptor or an rb_spans_out with no output is
+ * RB_ERR_INVALID_ARG.  No workspace beyond the chunk bookkeeping every descriptor call shares: one stream per engine, as for
+ * rb_classify_batch_device. */
+RB_API int rb_spans_batch_device(rb_engine *e, const rb_batch_desc *desc, size_t filter, const void *d_queries, size_t n_queries,
+                                 uint32_t mask_words, const rb_spans_out *d_out, void *stream);
+/* Host buffers; read_ids / n_items as in rb_locate_batch (queries name work items).  The reads are uploaded once; the queries are
+ * processed in sub-batches so that what they stage on the device (masks, records, n_kmers, status and the queries themselves) stays at or
+ * below 256 MiB (one query at a time where a single one needs more). */
+RB_API int rb_spans_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads,
+                          const uint32_t *read_ids, size_t n_items, size_t filter, const rb_span_query *queries, size_t n_queries,
+                          uint32_t mask_words, const rb_spans_out *out);
+
 /* bin-sharded operation: restrict the engine to word columns
  * [rank*ceil(W/world) , ...) of every block; out_maxcount then holds PARTIAL maxima that the
  * caller combines with an all-reduce(max) before rb_decide_device. world=1 restores the default. */

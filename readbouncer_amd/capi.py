@@ -44,6 +44,26 @@ class HitsOut(C.Structure):
 HIT_DTYPE = np.dtype([("bin", "<u4"), ("count", "<u2"), ("strand", "u1"), ("reserved", "u1")])
 
 
+class Span(C.Structure):
+    """rb_span: where along the read one (bin, strand) matched -- 24 bytes"""
+    _fields_ = [(n, C.c_uint32) for n in ("count", "first", "last", "run_start", "run_len", "covered")]
+
+
+class SpanQuery(C.Structure):
+    """rb_span_query: (work item, bin)"""
+    _fields_ = [("item", C.c_uint32), ("bin", C.c_uint32)]
+
+
+class SpansOut(C.Structure):
+    """rb_spans_out: any member may be NULL, not all"""
+    _fields_ = [("spans", C.c_void_p), ("mask", C.c_void_p), ("n_kmers", C.c_void_p), ("status", C.c_void_p)]
+
+
+# rb_span and rb_span_query as numpy records
+SPAN_DTYPE = np.dtype([(n, "<u4") for n in ("count", "first", "last", "run_start", "run_len", "covered")])
+SPAN_QUERY_DTYPE = np.dtype([("item", "<u4"), ("bin", "<u4")])
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("table_bytes", C.c_uint64), ("block_words", C.c_uint32), ("stride_words", C.c_uint32),
                 ("merged_members", C.c_uint32), ("lanes_per_block_log2", C.c_uint32), ("words_per_lane", C.c_uint32),
@@ -119,6 +139,8 @@ SIGNATURES = {
     "rb_locate_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _dbl, _dbl, C.POINTER(LocateOut)]),
     "rb_hits_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _dbl, _dbl, C.c_uint16, C.c_uint32, C.POINTER(HitsOut), _vp]),
     "rb_hits_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _dbl, _dbl, C.c_uint16, C.c_uint32, C.POINTER(HitsOut)]),
+    "rb_spans_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _sz, _vp, _sz, C.c_uint32, C.POINTER(SpansOut), _vp]),
+    "rb_spans_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp, _sz, C.c_uint32, C.POINTER(SpansOut)]),
     "rb_pack_reads": (_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "rb_host_alloc": (_int, [_sz, C.POINTER(_vp)]),
     "rb_host_free": (None, [_vp]),
@@ -554,6 +576,46 @@ class Engine:
         out = HitsOut(d_hits, d_n_hits, d_status, d_bin_reads)
         _check(lib().rb_hits_batch_device(self.h, C.byref(desc), error_rate, significance, min_count, max_hits, C.byref(out), stream),
                "rb_hits_batch_device")
+
+    def spans(self, seqs, offsets, lens, filter, queries, read_ids=None, mask_words=0, mask=None):
+        """where along the read each queried bin matched (rb_spans_batch): host buffers in, a dict of host numpy arrays out --
+        spans[n_queries, 2] of SPAN_DTYPE (strand 0, strand 1), n_kmers[n_queries] u32, status[n_queries] u8 and, with mask_words > 0,
+        mask[n_queries, 2, mask_words] u64 (bit p & 63 of word p >> 6 = position p is a hit; every word is written: pass `mask` to
+        see that over a fill of your own).  queries: SPAN_QUERY_DTYPE records or (item, bin) pairs against filter `filter` of the
+        engine (deplete filters first); an item is read_ids[item], or read `item` when read_ids is None"""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        ids = None if read_ids is None else np.ascontiguousarray(read_ids, dtype=np.uint32)
+        n = len(lens) if ids is None else len(ids)
+        q = np.asarray(queries)
+        if q.dtype != SPAN_QUERY_DTYPE:
+            pairs = np.asarray(queries, dtype=np.uint32).reshape(-1, 2)
+            q = np.zeros(len(pairs), dtype=SPAN_QUERY_DTYPE)
+            q["item"], q["bin"] = pairs[:, 0], pairs[:, 1]
+        q = np.ascontiguousarray(q)
+        nq = len(q)
+        res = {"spans": np.zeros((nq, 2), dtype=SPAN_DTYPE), "n_kmers": np.zeros(nq, dtype=np.uint32), "status": np.zeros(nq, dtype=np.uint8)}
+        if mask_words:
+            if mask is None:
+                mask = np.zeros((nq, 2, mask_words), dtype=np.uint64)
+            if mask.dtype != np.uint64 or mask.shape != (nq, 2, mask_words) or not mask.flags.c_contiguous:
+                raise ValueError("mask must be a C-contiguous uint64 array of shape (n_queries, 2, mask_words)")
+            res["mask"] = mask
+        out = SpansOut(_ptr(res["spans"]), _ptr(mask) if mask_words else None, _ptr(res["n_kmers"]), _ptr(res["status"]))
+        _check(lib().rb_spans_batch(self.h, _ptr(seqs), _ptr(offsets), _ptr(lens), len(lens), None if ids is None else _ptr(ids), n,
+                                    filter, _ptr(q), nq, mask_words, C.byref(out)), "rb_spans_batch")
+        return res
+
+    def spans_device(self, d_seqs, d_offsets, d_lens, n_items, max_len, filter, d_queries, n_queries, d_nmask=None, d_nmask_offsets=None,
+                     chunk_start=0, chunk_length=0, d_read_ids=None, mask_words=0, d_spans=None, d_mask=None, d_n_kmers=None, d_status=None,
+                     stream=None):
+        """raw device pointers like hits_device (rb_spans_batch_device); any output may be None, not all"""
+        desc = BatchDesc(d_seqs, d_offsets, d_lens, n_items, max_len, d_nmask, d_nmask_offsets, chunk_start, chunk_length,
+                         d_read_ids)
+        out = SpansOut(d_spans, d_mask, d_n_kmers, d_status)
+        _check(lib().rb_spans_batch_device(self.h, C.byref(desc), filter, d_queries, n_queries, mask_words, C.byref(out), stream),
+               "rb_spans_batch_device")
 
     def decide_device(self, d_maxcount, d_lens, n_reads, max_len, error_rate=0.1, significance=0.95,
                       mode=RB_MODE_CHECK_UNBLOCK, d_best=None, d_decision=None, d_status=None, stream=None):

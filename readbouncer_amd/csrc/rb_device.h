@@ -256,6 +256,28 @@ struct HitsLaunch {
 hipError_t launch_ibf_hits(const HitsLaunch &a, hipStream_t st);
 hipError_t launch_finish_hits(const HitsLaunch &a, const uint32_t *lens, const HitsOut &out, hipStream_t st);
 
+// spans pass (rb_spans_batch_device; rb_kernels.hip, ibf_spans_kernel): the caller's output arrays (any may be nullptr) ...
+struct SpansOut {
+    uint32_t *spans;    // rb_span [n_queries][2] as 32-bit words: count, first, last, run_start, run_len, covered
+    uint64_t *mask;     // [n_queries][2][mask_words]
+    uint32_t *n_kmers;  // [n_queries]
+    uint8_t *status;    // [n_queries]
+};
+// ... and the launch: one wave per query (x = work item, y = bin) against ONE filter's own table
+struct SpansLaunch {
+    IbfDev f;
+    ReadSrc src;
+    uint32_t n_items;
+    const rb_u32x2 *queries;
+    uint32_t n_queries;
+    uint32_t mask_words;
+    uint32_t min_len;           // an item shorter than this is RB_ERR_SHORT_READ (the locate pass's rule: the largest k of the engine)
+    const uint8_t *pre_status;  // chunk_prep's per-item status, or nullptr
+    int nt;
+    SpansOut out;
+};
+hipError_t launch_ibf_spans(const SpansLaunch &a, hipStream_t st);
+
 hipError_t launch_ibf_count_max(const CountLaunch &a, hipStream_t st);
 hipError_t launch_ibf_count_max_merged(const CountLaunch &a, const MergeMap &map, hipStream_t st);
 // block b of a filter (width words at stride s_src, n_bins bins) -> bits [dst_bit, dst_bit + n_bins) of block b of dst (ORed in: dst starts zeroed)

@@ -411,6 +411,7 @@ struct rb_engine {
     DevBuf d_locate_io;             // rb_locate_batch: read ids in, the five outputs back
     DevBuf d_hits_ws;               // hits pass: the (item, slice, strand) record segments and their counters, one filter at a time
     DevBuf d_hits_io;               // rb_hits_batch: read ids in, records / n_hits / status / bin_reads back
+    DevBuf d_spans_io;              // rb_spans_batch: read ids and queries in, masks / records / n_kmers / status back
     PinnedBuf h_in, h_out;
     // large host batches: slice i+1 is copied on this stream while slice i is counted on `stream`
     hipStream_t copy_stream = nullptr;
@@ -1036,7 +1037,7 @@ void rb_engine_destroy(rb_engine *e)
     }
     for (void *r : e->thr_retired_dev) (void)hipFree(r);
     for (PinnedBuf &h : e->thr_retired_host) h.release();
-    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_locate_parts, &e->d_locate_io, &e->d_hits_ws, &e->d_hits_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
+    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_locate_parts, &e->d_locate_io, &e->d_hits_ws, &e->d_hits_io, &e->d_spans_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
                       &e->d_decision, &e->d_status})
         b->release();
     e->h_in.release();
@@ -2988,6 +2989,173 @@ int rb_hits_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const
         RB_HIP(hipMemcpy(h_bins.data(), io, 8 * total_bins, hipMemcpyDeviceToHost));
         uint64_t *dst = (uint64_t *)out->bin_reads;
         for (size_t b = 0; b < total_bins; ++b) dst[b] += h_bins[b];
+    }
+    return RB_OK;
+}
+
+// ---- spans: where along a read a bin matched (no counterpart in the reference; see the boundary header).  One launch of ibf_spans_kernel
+// over the named filter's OWN table, one wave per query: no threshold, no workspace, and none of the engine's pruning / early-decision /
+// merge / phased settings reaches it.  Items and bins are vetted by the kernel: queries may be another kernel's output.
+static int spans_device_impl(rb_engine *e, const rb_batch_desc *desc, size_t filter, const void *d_queries, size_t n_queries, uint32_t mask_words,
+                             const rb_spans_out *d_out, void *stream)
+{
+    if (!desc || !d_out) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor or output struct");
+    if (!d_out->spans && !d_out->mask && !d_out->n_kmers && !d_out->status) return rb::fail(RB_ERR_INVALID_ARG, "rb_spans_out with no output");
+    int rc = check_device(e ? e->device : 0);  // (argument shape first, then the device, then the handle: without a GPU nothing here can work)
+    if (rc != RB_OK) return rc;
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    const size_t n_items = desc->n_items;
+    if (n_items >= (1ULL << 31) || n_queries >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (filter >= e->filters.size()) return rb::fail(RB_ERR_INVALID_ARG, "filter index beyond the engine's filters");
+    if (n_queries == 0) return RB_OK;
+    if (!d_queries) return rb::fail(RB_ERR_INVALID_ARG, "null query buffer");
+    if (n_items && (!desc->d_seqs || !desc->d_offsets || !desc->d_lens)) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
+    if ((desc->d_nmask == nullptr) != (desc->d_nmask_offsets == nullptr))
+        return rb::fail(RB_ERR_INVALID_ARG, "packed input needs both the N bitmap and its offsets");
+    if (e->shard_world != 1) return rb::fail(RB_ERR_INVALID_ARG, "spans on a column-sharded engine: a shard sees only its own bins");
+    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+    const bool chunked = n_items && (desc->chunk_start != 0 || desc->chunk_length != 0 || desc->d_read_ids != nullptr);
+    const void *d_lens = desc->d_lens;
+    const uint8_t *d_pre_status = nullptr;
+    uint32_t max_len = desc->max_len;
+    if (chunked) {
+        rc = e->d_efflens.ensure(n_items * 4);
+        if (rc == RB_OK) rc = e->d_prestatus.ensure(n_items);
+        if (rc != RB_OK) return rc;
+        RB_HIP(launch_chunk_prep((const uint32_t *)desc->d_lens, (const uint32_t *)desc->d_read_ids, (uint32_t)n_items, desc->chunk_start,
+                                 desc->chunk_length, (uint32_t *)e->d_efflens.p, (uint8_t *)e->d_prestatus.p, st));
+        d_lens = e->d_efflens.p;
+        d_pre_status = (const uint8_t *)e->d_prestatus.p;
+        if (desc->chunk_length && desc->chunk_length < max_len) max_len = desc->chunk_length;
+    }
+    const rb_dibf *f = e->filters[filter];
+    SpansLaunch a{};
+    a.f = f->dev;
+    a.f.comp_n = e->revcomp_of_n;
+    a.src.seqs = (const uint8_t *)desc->d_seqs;
+    a.src.offsets = (const uint64_t *)desc->d_offsets;
+    a.src.lens = (const uint32_t *)d_lens;
+    a.src.nmask = (const uint8_t *)desc->d_nmask;
+    a.src.nmask_offsets = (const uint64_t *)desc->d_nmask_offsets;
+    a.src.ids = (const uint32_t *)desc->d_read_ids;
+    a.src.base_off = desc->chunk_start;
+    a.src.max_len = max_len;
+    a.n_items = (uint32_t)n_items;
+    a.queries = (const rb_u32x2 *)d_queries;
+    a.n_queries = (uint32_t)n_queries;
+    a.mask_words = d_out->mask ? mask_words : 0u;
+    a.min_len = 0;  // the item's status is the locate pass's: shorter than the k of SOME filter of the engine is a short read
+    for (const rb_dibf *g : e->filters) a.min_len = std::max<uint32_t>(a.min_len, (uint32_t)g->geo.kmer_size);
+    a.pre_status = d_pre_status;
+    a.nt = f->geo.n_blocks * f->stride * 8 > e->nt_threshold_bytes;
+    a.out.spans = (uint32_t *)d_out->spans;
+    a.out.mask = (uint64_t *)d_out->mask;
+    a.out.n_kmers = (uint32_t *)d_out->n_kmers;
+    a.out.status = (uint8_t *)d_out->status;
+    std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
+    if (e->timing && e->ev_used < ((size_t)1 << 16)) {
+        if (e->ev_used == e->ev_ring.size()) {
+            hipEvent_t ea = nullptr, eb = nullptr;
+            RB_HIP(hipEventCreate(&ea));
+            RB_HIP(hipEventCreate(&eb));
+            e->ev_ring.emplace_back(ea, eb);
+        }
+        evp = &e->ev_ring[e->ev_used++];
+        RB_HIP(hipEventRecord(evp->first, st));
+    }
+    RB_HIP(launch_ibf_spans(a, st));
+    if (evp) RB_HIP(hipEventRecord(evp->second, st));
+    if (!stream) RB_HIP(hipStreamSynchronize(st));
+    return RB_OK;
+}
+
+int rb_spans_batch_device(rb_engine *e, const rb_batch_desc *desc, size_t filter, const void *d_queries, size_t n_queries, uint32_t mask_words,
+                          const rb_spans_out *d_out, void *stream)
+{
+    return spans_device_impl(e, desc, filter, d_queries, n_queries, mask_words, d_out, stream);
+}
+
+int rb_spans_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *read_ids,
+                   size_t n_items, size_t filter, const rb_span_query *queries, size_t n_queries, uint32_t mask_words, const rb_spans_out *out)
+{
+    if (!out) return rb::fail(RB_ERR_INVALID_ARG, "null output struct");
+    if (!out->spans && !out->mask && !out->n_kmers && !out->status) return rb::fail(RB_ERR_INVALID_ARG, "rb_spans_out with no output");
+    int rc = check_device(e ? e->device : 0);
+    if (rc != RB_OK) return rc;
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        if (filter >= e->filters.size()) return rb::fail(RB_ERR_INVALID_ARG, "filter index beyond the engine's filters");
+    }
+    if (n_queries == 0) return RB_OK;
+    if (!queries) return rb::fail(RB_ERR_INVALID_ARG, "null query buffer");
+    const size_t n = read_ids ? n_items : n_reads;  // without a selection the work items are the reads
+    if (n && (!seqs || !offsets || !lens || n_reads == 0)) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
+    if (n >= (1ULL << 31) || n_reads >= (1ULL << 31) || n_queries >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    if (read_ids)
+        for (size_t i = 0; i < n; ++i)
+            if (read_ids[i] >= n_reads) return rb::fail(RB_ERR_INVALID_ARG, "read id beyond the batch");
+    uint64_t hi = 0, lo = ~0ULL;
+    uint32_t max_len = 0;
+    for (size_t i = 0; n && i < n_reads; ++i) {
+        hi = std::max<uint64_t>(hi, offsets[i] + lens[i]);
+        lo = std::min<uint64_t>(lo, offsets[i]);
+        max_len = std::max(max_len, lens[i]);
+    }
+    if (!n) lo = 0;
+    const uint64_t span = hi - lo;
+    hipStream_t st = e->stream;
+    std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
+    // sub-batches of queries: what a query stages (its masks, its two records, n_kmers, status and the query itself) stays at or below
+    // kSpansBudget per call, one query at a time where a single one needs more; the reads and their ids are uploaded once
+    constexpr size_t kSpansBudget = 256ull << 20;
+    const size_t mw = out->mask ? mask_words : 0;
+    const size_t per_query = 16 * mw + sizeof(rb_span_query) + 2 * sizeof(rb_span) + 4 + 1;
+    const size_t sub_max = std::max<size_t>(1, std::min<size_t>(n_queries, kSpansBudget / per_query));
+    // staging: u64 mask[sub x 2 x mw] | rb_span_query q[sub] | rb_span spans[sub x 2] | u32 n_kmers[sub] | u32 ids[n] | u8 status[sub]
+    const size_t o_q = 16 * mw * sub_max, o_spans = o_q + 8 * sub_max, o_nk = o_spans + 48 * sub_max, o_ids = o_nk + 4 * sub_max,
+                 o_status = o_ids + 4 * (read_ids ? n : 0);
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        if ((rc = e->d_seqs.ensure(span ? span : 1)) != RB_OK) return rc;
+        if ((rc = e->d_offsets.ensure(n_reads ? n_reads * 8 : 8)) != RB_OK) return rc;
+        if ((rc = e->d_lens.ensure(n_reads ? n_reads * 4 : 4)) != RB_OK) return rc;
+        if ((rc = e->d_spans_io.ensure(o_status + sub_max)) != RB_OK) return rc;
+    }
+    char *io = (char *)e->d_spans_io.p;
+    if (span) RB_HIP(hipMemcpyAsync(e->d_seqs.p, seqs + lo, span, hipMemcpyHostToDevice, st));
+    if (n) {
+        RB_HIP(hipMemcpyAsync(e->d_offsets.p, offsets, n_reads * 8, hipMemcpyHostToDevice, st));
+        RB_HIP(hipMemcpyAsync(e->d_lens.p, lens, n_reads * 4, hipMemcpyHostToDevice, st));
+    }
+    if (read_ids && n) RB_HIP(hipMemcpyAsync(io + o_ids, read_ids, 4 * n, hipMemcpyHostToDevice, st));
+    rb_batch_desc desc;
+    std::memset(&desc, 0, sizeof desc);
+    desc.d_seqs = (const char *)e->d_seqs.p - lo;  // device address of the caller's seqs[0]
+    desc.d_offsets = e->d_offsets.p;
+    desc.d_lens = e->d_lens.p;
+    desc.n_items = n;
+    desc.max_len = max_len;
+    desc.d_read_ids = read_ids ? io + o_ids : nullptr;
+    for (size_t b0 = 0; b0 < n_queries; b0 += sub_max) {
+        const size_t sub = std::min(sub_max, n_queries - b0);
+        RB_HIP(hipMemcpyAsync(io + o_q, queries + b0, sizeof(rb_span_query) * sub, hipMemcpyHostToDevice, st));
+        rb_spans_out d_out;
+        d_out.spans = out->spans ? io + o_spans : nullptr;
+        d_out.mask = out->mask ? io : nullptr;
+        d_out.n_kmers = out->n_kmers ? io + o_nk : nullptr;
+        d_out.status = out->status ? io + o_status : nullptr;
+        rc = spans_device_impl(e, &desc, filter, io + o_q, sub, mask_words, &d_out, (void *)st);
+        if (rc != RB_OK) {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+        if (out->spans) RB_HIP(hipMemcpyAsync((rb_span *)out->spans + 2 * b0, io + o_spans, 48 * sub, hipMemcpyDeviceToHost, st));
+        if (out->mask && mw) RB_HIP(hipMemcpyAsync((uint64_t *)out->mask + 2 * mw * b0, io, 16 * mw * sub, hipMemcpyDeviceToHost, st));
+        if (out->n_kmers) RB_HIP(hipMemcpyAsync((uint32_t *)out->n_kmers + b0, io + o_nk, 4 * sub, hipMemcpyDeviceToHost, st));
+        if (out->status) RB_HIP(hipMemcpyAsync((uint8_t *)out->status + b0, io + o_status, sub, hipMemcpyDeviceToHost, st));
+        RB_HIP(hipStreamSynchronize(st));
     }
     return RB_OK;
 }

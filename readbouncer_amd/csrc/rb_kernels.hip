@@ -1106,6 +1106,267 @@ __global__ void finish_hits_kernel(const rb_u32x2 *__restrict__ seg, const uint3
     if (out.status && fidx == 0) out.status[i] = status;
 }
 
+// SPANS: the opt-in pass (rb_spans_batch_device) that says WHERE ALONG THE READ a bin matched.  A query is (work item, bin) against one
+// filter; position p is the window of bases [p, p + k) of the item, in the read's own direction on both strands: strand 0 hits at p
+// when all h words selected by that window's k-mer have the bin's bit -- the test by which seqan::count adds 1 to fwd[bin] -- and
+// strand 1 when the same holds for the window's reverse complement (k-mer n - 1 - p of the reverse-complemented item), so the hit
+// positions of the two strands number fwd[bin] and rev[bin].  One wave per query, built from the pieces of count_strand:
+//   * make_base_src and a per-wave LDS area with the bases of kSpanTiles tiles as Dna5 ordinals; lane l of tile j owns position
+//     64 j + l and evaluates both strands' base-5 values directly, reading every base once (the reverse complement's value is
+//     the sum of comp(b[i]) 5^i: the same ring arithmetic modulo 2^64 as the oracle's Horner form);
+//   * the bin is known, so a lookup is ONE 8-byte word, words[block * stride + (bin >> 6)]: 2 h kSpanTiles loads per lane go out
+//     back to back with no control flow around them (positions past the end read block 0 and are masked out: the rule of
+//     count_strand's phase B) and a schedule fence stands before the first use;
+//   * a tile's result per strand is __ballot(hit) -- the mask word the caller gets, stored by one lane -- and count, first, last, the
+//     longest run (the open run is carried from word to word) and the covered bases (the word smeared by k - 1 with doubling shifts
+//     over previous word : this word) are wave-uniform integer arithmetic on those words.  No atomics, no LDS beyond the staging.
+// Every output slot of a query is written, whatever its status: a query that is not RB_OK -- the item's status by the locate pass's
+// rules, or an item / bin that does not exist, which is tested here BEFORE anything is read through it -- gets n_kmers 0, a zero
+// record with 0xFFFFFFFF positions and a zero mask.  Positions at or beyond 64 mask_words are left out of the mask only.
+constexpr int kSpanTiles = 4;                                        // tiles of 64 positions per round: 2 h kSpanTiles loads in flight per lane
+constexpr int kSpanStage = 64 * kSpanTiles + rbspec::kMaxKmer;       // bases staged per round
+constexpr uint32_t kSpanNone = 0xFFFFFFFFu;
+
+// what a (query, strand) knows so far; every member is wave-uniform
+struct SpanAcc {
+    uint32_t count, first, last, run_start, run_len, covered;
+    uint32_t open_start, open_len;  // the run of hit positions that ends at the last position seen (open_len == 0: none)
+    uint64_t prev;                  // the mask word before this one
+};
+
+__device__ __forceinline__ void span_clear(SpanAcc &a)
+{
+    a.count = 0; a.first = kSpanNone; a.last = kSpanNone; a.run_start = kSpanNone; a.run_len = 0; a.covered = 0;
+    a.open_start = 0; a.open_len = 0; a.prev = 0ULL;
+}
+
+// bases of the word `cur` covers (64 bases from the word's first position on) that lie in [p, p + k) of a hit position p of prev : cur
+__device__ __forceinline__ uint32_t span_covered(uint64_t prev, uint64_t cur, uint32_t k)
+{
+    uint64_t lo = prev, hi = cur;
+    for (uint32_t c = 1; c < k;) {  // c: shifts 0 .. c - 1 are ORed in; k - 1 <= 31 never reaches beyond prev
+        const uint32_t sh = min(c, k - c);
+        hi |= (hi << sh) | (lo >> (64u - sh));
+        lo |= lo << sh;
+        c += sh;
+    }
+    return (uint32_t)__popcll(hi);
+}
+
+// the next mask word of a strand: positions base .. base + 63
+__device__ __forceinline__ void span_add_word(SpanAcc &a, uint64_t w, uint32_t base, uint32_t k)
+{
+    a.covered += span_covered(a.prev, w, k);
+    a.prev = w;
+    const uint32_t carry_start = a.open_start, carry_len = (w & 1ULL) ? a.open_len : 0u;
+    a.open_len = 0;
+    if (w == 0ULL) return;
+    if (a.count == 0) a.first = base + (uint32_t)(__ffsll((unsigned long long)w) - 1);
+    a.last = base + 63u - (uint32_t)__clzll((long long)w);
+    a.count += (uint32_t)__popcll(w);
+    uint64_t x = w;
+    uint32_t pos = 0;
+    while (x != 0ULL) {  // one turn per run of the word, lowest first: the lowest of equally long runs stays
+        const uint32_t tz = (uint32_t)(__ffsll((unsigned long long)x) - 1);
+        x >>= tz;  // (tz <= 63)
+        pos += tz;
+        const uint32_t ones = (~x == 0ULL) ? 64u : (uint32_t)(__ffsll((unsigned long long)~x) - 1);
+        const bool joins = pos == 0 && carry_len > 0;
+        const uint32_t start = joins ? carry_start : base + pos;
+        const uint32_t len = joins ? carry_len + ones : ones;
+        if (len > a.run_len) {
+            a.run_len = len;
+            a.run_start = start;
+        }
+        if (pos + ones >= 64u) {  // the run reaches the end of the word: it stays open
+            a.open_start = start;
+            a.open_len = len;
+            break;
+        }
+        x >>= ones;
+        pos += ones;
+    }
+}
+
+// One round's lookups: per (tile, strand, hash function) ONE word, the bin's column of the block the k-mer selects.  All loads of a batch
+// -- 2 h kSpanTiles with a compile-time h, 2 kSpanTiles per hash function otherwise -- go out back to back and a schedule fence stands
+// before the first use; a position that does not exist reads block 0 and is masked out.  POW2 names the modulus form of
+// rbspec::block_index at compile time (the engine's pow2_mask is 0xFFFFFFFF for a block count that is no power of two), so that its
+// test is not a branch between two loads.
+template <int H, bool NT, bool POW2>
+__device__ __forceinline__ void span_gather(bool (&hit)[kSpanTiles][2], const uint64_t (&kv)[kSpanTiles][2], const bool (&ok)[kSpanTiles],
+                                            const IbfDev &f, const uint64_t *col, uint64_t S, uint64_t bit)
+{
+    constexpr int T = kSpanTiles;
+    constexpr int HR = H > 0 ? H : 1;
+    if constexpr (POW2) __builtin_assume(f.pow2_mask != 0xFFFFFFFFu);
+    const uint32_t pm = POW2 ? f.pow2_mask : 0xFFFFFFFFu;
+    if constexpr (H > 0) {
+        uint64_t ld[T][2][HR];
+#pragma unroll
+        for (int j = 0; j < T; ++j)
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int h = 0; h < H; ++h) {
+                    const uint32_t b = rbspec::block_index(kv[j][s], f.precalc[h], f.n_blocks, f.magic, pm);
+                    ld[j][s][h] = load_word<NT>(col + (uint64_t)(ok[j] ? b : 0u) * S);
+                }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < T; ++j)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                uint64_t x = bit;
+#pragma unroll
+                for (int h = 0; h < H; ++h) x &= ld[j][s][h];
+                hit[j][s] = ok[j] && x != 0ULL;
+            }
+    } else {
+        uint64_t x[T][2];
+#pragma unroll
+        for (int j = 0; j < T; ++j) x[j][0] = x[j][1] = ok[j] ? bit : 0ULL;
+        for (uint32_t h = 0; h < f.n_hash; ++h) {  // wave-uniform
+            uint64_t ld[T][2];
+#pragma unroll
+            for (int j = 0; j < T; ++j)
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const uint32_t b = rbspec::block_index(kv[j][s], f.precalc[h], f.n_blocks, f.magic, pm);
+                    ld[j][s] = load_word<NT>(col + (uint64_t)(ok[j] ? b : 0u) * S);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < T; ++j) {
+                x[j][0] &= ld[j][0];
+                x[j][1] &= ld[j][1];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            hit[j][0] = x[j][0] != 0ULL;
+            hit[j][1] = x[j][1] != 0ULL;
+        }
+    }
+}
+
+template <int H, bool NT>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(4, 8))) void ibf_spans_kernel(
+    IbfDev f, ReadSrc src, uint32_t n_items, const rb_u32x2 *__restrict__ queries, uint32_t n_queries, uint32_t mask_words,
+    const uint8_t *__restrict__ pre_status, uint32_t min_len, SpansOut out)
+{
+    __shared__ uint8_t s_stage[kWavesPerBlock][kSpanStage];
+    constexpr int T = kSpanTiles;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const uint32_t qi = __builtin_amdgcn_readfirstlane(blockIdx.x * (uint32_t)kWavesPerBlock + (uint32_t)wave);
+    if (qi >= n_queries) return;  // wave-uniform; there are no block-level barriers below
+    const rb_u32x2 q = queries[qi];
+    const uint32_t item = __builtin_amdgcn_readfirstlane(q.x), bin = __builtin_amdgcn_readfirstlane(q.y);
+    uint64_t *const mask0 = out.mask ? out.mask + (size_t)qi * 2 * mask_words : nullptr;  // strand 1 follows mask_words later
+
+    // ---- the query's status: item and bin are tested before anything is read through them
+    uint32_t status = RB_OK;
+    if (item >= n_items || bin >= f.n_bins) {
+        status = RB_ERR_INVALID_ARG;
+    } else {  // the locate pass's rules (reduce_locate_slices_kernel)
+        const uint32_t raw = src.lens[item];
+        const uint32_t pre = pre_status ? (uint32_t)pre_status[item] : (uint32_t)RB_OK;
+        if (pre != RB_OK) status = pre;
+        else if (raw > src.max_len) status = RB_ERR_INVALID_ARG;
+        else if (raw < min_len) status = RB_ERR_SHORT_READ;
+    }
+    status = __builtin_amdgcn_readfirstlane(status);
+
+    SpanAcc acc[2];
+    span_clear(acc[0]);
+    span_clear(acc[1]);
+    uint32_t n = 0, words_done = 0;
+    if (status == RB_OK) {  // wave-uniform
+        uint32_t len;
+        const BaseSrc seq = make_base_src(src, item, &len);
+        const uint32_t k = f.k;
+        n = len >= k ? len - k + 1 : 0;  // (min_len >= k: n >= 1)
+        const uint64_t *const col = f.words + (bin >> 6);
+        const uint64_t bit = 1ULL << (bin & 63u);
+        const uint64_t S = f.stride;
+        uint8_t *const stage = s_stage[wave];
+        for (uint32_t mt = 0; mt < n; mt += 64u * T) {
+            // ---- stage the bases of this round as Dna5 ordinals
+            const uint32_t wlen = min((uint32_t)(64 * T) + k - 1u, len - mt);
+            __builtin_amdgcn_wave_barrier();
+            for (uint32_t i = lane; i < wlen; i += 64) stage[i] = (uint8_t)seq.ord(mt + i);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+
+            // ---- both strands' k-mer value of this lane's position in every tile
+            uint64_t kv[T][2];
+            bool ok[T];
+#pragma unroll
+            for (int j = 0; j < T; ++j) {
+                const uint32_t p = mt + (uint32_t)(j * 64 + lane);
+                ok[j] = p < n;
+                uint64_t vf = 0, vr = 0;
+                if (ok[j]) {
+                    const uint8_t *b = stage + (p - mt);
+                    uint64_t pw = 1;
+                    for (uint32_t i = 0; i < k; ++i) {
+                        const uint32_t o = b[i];
+                        vf = vf * 5u + o;
+                        vr += pw * rbspec::dna5_comp(o, f.comp_n);
+                        pw *= 5u;
+                    }
+                }
+                kv[j][0] = vf;
+                kv[j][1] = vr;
+            }
+
+            // ---- the gathers (span_gather): the modulus form is chosen here, outside the loads
+            bool hit[T][2];
+            if (f.pow2_mask != 0xFFFFFFFFu) span_gather<H, NT, true>(hit, kv, ok, f, col, S, bit);  // wave-uniform
+            else span_gather<H, NT, false>(hit, kv, ok, f, col, S, bit);
+
+            // ---- a tile's ballot is its mask word; the record follows from the words
+#pragma unroll
+            for (int j = 0; j < T; ++j) {
+                const uint32_t base = mt + (uint32_t)(j * 64);
+                if (base < n) {  // wave-uniform
+                    const uint32_t wi = base >> 6;
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        const uint64_t w = __ballot(hit[j][s]);
+                        span_add_word(acc[s], w, base, k);
+                        if (mask0 && wi < mask_words && lane == 0) mask0[(size_t)s * mask_words + wi] = w;
+                    }
+                    words_done = wi + 1;
+                }
+            }
+        }
+        // the bases beyond the last position word that its last k - 1 positions still cover
+        acc[0].covered += span_covered(acc[0].prev, 0ULL, k);
+        acc[1].covered += span_covered(acc[1].prev, 0ULL, k);
+    }
+
+    // ---- every slot of the query is written: the rest of the mask is zero ...
+    if (mask0) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            for (uint32_t wi = words_done + (uint32_t)lane; wi < mask_words; wi += 64) mask0[(size_t)s * mask_words + wi] = 0ULL;
+    }
+    // ... and the two records are twelve consecutive 32-bit words, one per lane
+    if (out.spans && lane < 12) {
+        const bool rev = lane >= 6;
+        const int m = rev ? lane - 6 : lane;
+        const uint32_t v0 = m == 0 ? acc[0].count : m == 1 ? acc[0].first : m == 2 ? acc[0].last : m == 3 ? acc[0].run_start : m == 4 ? acc[0].run_len : acc[0].covered;
+        const uint32_t v1 = m == 0 ? acc[1].count : m == 1 ? acc[1].first : m == 2 ? acc[1].last : m == 3 ? acc[1].run_start : m == 4 ? acc[1].run_len : acc[1].covered;
+        out.spans[(size_t)qi * 12 + (uint32_t)lane] = rev ? v1 : v0;
+    }
+    if (lane == 0) {
+        if (out.n_kmers) out.n_kmers[qi] = n;
+        if (out.status) out.status[qi] = (uint8_t)status;
+    }
+}
+
 // Throughput form over a MERGED table: several narrow filters of one hash geometry (same noOfBlocks, k and h -- every filter
 // the reference builds with one fragment_size has them: noOfBits = BinSizeBits x 64 x binWidth, so noOfBlocks = BinSizeBits
 // whatever the bin count, src/IBF/IBFBuild.cpp:404-413) hash a k-mer to the SAME block number, so their blocks can sit side
@@ -2998,6 +3259,33 @@ hipError_t launch_finish_hits(const HitsLaunch &a, const uint32_t *lens, const H
     hipLaunchKernelGGL(finish_hits_kernel, dim3((a.n_items + 255) / 256), dim3(256), 0, st, (const rb_u32x2 *)a.seg, a.seg_count, a.n_slices,
                        a.n_items, lens, a.pre_status, a.src.max_len, a.min_len, a.max_hits, out, a.nf, a.fi);
     return hipGetLastError();
+}
+
+// spans: the compile-time h = 3 build and the run-time-h build, each with its non-temporal twin
+template <int H>
+static hipError_t launch_spans_nt(const SpansLaunch &a, hipStream_t st)
+{
+    dim3 grid((a.n_queries + kWavesPerBlock - 1) / kWavesPerBlock);
+    if (a.nt)
+        hipLaunchKernelGGL((ibf_spans_kernel<H, true>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.src, a.n_items, a.queries, a.n_queries,
+                           a.mask_words, a.pre_status, a.min_len, a.out);
+    else
+        hipLaunchKernelGGL((ibf_spans_kernel<H, false>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.src, a.n_items, a.queries, a.n_queries,
+                           a.mask_words, a.pre_status, a.min_len, a.out);
+    return hipGetLastError();
+}
+
+hipError_t launch_ibf_spans(const SpansLaunch &a, hipStream_t st)
+{
+    if (a.n_queries == 0) return hipSuccess;
+    if (!a.queries || (!a.out.spans && !a.out.mask && !a.out.n_kmers && !a.out.status) || !a.f.words ||
+        (a.n_items && (!a.src.lens || !a.src.offsets || !a.src.seqs)))
+        return hipErrorInvalidValue;
+    // what the kernel's addressing relies on: the bin's word column lies inside a block, a round's bases fit the staging area
+    if (a.f.n_bins > (uint64_t)a.f.bin_width * 64u || a.f.bin_width > a.f.stride || a.f.k == 0 || a.f.k > rbspec::kMaxKmer || a.f.n_blocks == 0 ||
+        a.f.n_hash == 0 || a.f.n_hash > rbspec::kMaxHash || a.min_len < a.f.k)
+        return hipErrorInvalidValue;
+    return a.f.n_hash == 3 ? launch_spans_nt<3>(a, st) : launch_spans_nt<0>(a, st);
 }
 
 hipError_t launch_reduce_slices(const uint16_t *part, uint32_t n_slices, uint32_t n_reads, uint16_t *maxcount,

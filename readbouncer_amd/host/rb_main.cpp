@@ -322,6 +322,7 @@ struct ReadState
     int best = -1;
     std::string bin_rows;  // --report-bins: this read's lines of classified_bins.tsv
     std::string hit_rows;  // --report-hits: this read's lines of classified_hits.tsv
+    std::string span_rows; // --report-spans: this read's lines of classified_spans.tsv
 };
 
 // host pipeline knobs (command line)
@@ -345,6 +346,7 @@ struct IngestOptions
     size_t live_batch = 64;      // usage "target" replay: chunks per micro-batch
     bool report_bins = false;    // --report-bins: locate the reads every chunk classified (rb_locate_batch) and write classified_bins.tsv
     bool report_hits = false;    // --report-hits: list every (bin, strand) those reads hit (rb_hits_batch): classified_hits.tsv and bin_profile.tsv
+    bool report_spans = false;   // --report-spans: where along those reads the best bin of every matching filter matched (rb_spans_batch): classified_spans.tsv
     uint32_t max_hits = 64;      // --max-hits N: records kept per (read, filter); n_hits in the report stays exact
     std::vector<std::string> bin_maps;  // --bin-map FILE (may repeat): <filter name>.bins.tsv of build --write-bin-map -> a record_id column
     size_t bytes() const { return segment_bytes ? segment_bytes : (segment_mb << 20); }
@@ -409,8 +411,11 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
         // those reads that hit each bin over the whole run
         std::ofstream hits_out;
         std::vector<uint64_t> bin_profile;  // one entry per bin of every filter, filter after filter (rb_hits_out.bin_reads)
-        if (opt.report_bins || opt.report_hits) {
-            if (multi) throw std::runtime_error("--report-bins and --report-hits work on one device");
+        // --report-spans: classified_spans.tsv, one line per (classified read, filter that matched it), in file order: where along the read the
+        // locate pass's best bin matched on its best strand, positions in the read's coordinates
+        std::ofstream spans_out;
+        if (opt.report_bins || opt.report_hits || opt.report_spans) {
+            if (multi) throw std::runtime_error("--report-bins, --report-hits and --report-spans work on one device");
             for (const interleave::IBFMeta& f : DepletionFilters) all_filters.push_back(&f);
             for (const interleave::IBFMeta& f : TargetFilters) all_filters.push_back(&f);
             bin_records.resize(all_filters.size());
@@ -428,6 +433,12 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
             bins_out.open(std::filesystem::path(config.output_dir) / "classified_bins.tsv");
             if (!bins_out) { std::cerr << "ERROR: Unable to open the file: classified_bins.tsv" << std::endl; return; }
             bins_out << "read_id\tfilter\tbest_bin\tstrand\tmax_count\tthreshold\thit_bins\tchunk" << (opt.bin_maps.empty() ? "" : "\trecord_id") << '\n';
+        }
+        if (opt.report_spans) {
+            spans_out.open(std::filesystem::path(config.output_dir) / "classified_spans.tsv");
+            if (!spans_out) { std::cerr << "ERROR: Unable to open the file: classified_spans.tsv" << std::endl; return; }
+            spans_out << "read_id\tfilter\tbin" << (opt.bin_maps.empty() ? "" : "\trecord_id")
+                      << "\tstrand\tn_kmers\tcount\tfirst\tlast\trun_start\trun_len\tcovered\n";
         }
         if (opt.report_hits) {
             hits_out.open(std::filesystem::path(config.output_dir) / "classified_hits.tsv");
@@ -572,7 +583,7 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                             if (res.decision[j]) {
                                 st.classified = true;
                                 st.best = target ? res.best_target[j] : -1;
-                                if (opt.report_bins || opt.report_hits) located.push_back((uint32_t)j);
+                                if (opt.report_bins || opt.report_hits || opt.report_spans) located.push_back((uint32_t)j);
                             } else {
                                 next.push_back(idx[j]);
                             }
@@ -619,7 +630,7 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                             }
                             }
                         }
-                        if (opt.report_bins && !located.empty()) {
+                        if ((opt.report_bins || opt.report_spans) && !located.empty()) {
                             const size_t nf = all_filters.size(), nl = located.size();
                             std::vector<uint16_t> mc(nl * nf);
                             std::vector<int32_t> bb(nl * nf);
@@ -640,7 +651,8 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                                     // a line per filter that matched the chunk: max_matches' predicate, count >= threshold (and a count at all)
                                     const uint16_t t = rb_threshold(lens[j], all_filters[fi]->filter.kmerSize, Conf.error_rate, Conf.significance);
                                     const uint16_t m = mc[q * nf + fi];
-                                    if (m == 0 || m < t) continue;
+                                    if (m == 0 || m < t) { bb[q * nf + fi] = -1; continue; }  // (-1: the spans report below asks nothing of this filter)
+                                    if (!opt.report_bins) continue;
                                     rows.append(r.id, w);
                                     rows += '\t' + all_filters[fi]->name + '\t' + std::to_string(bb[q * nf + fi]) + '\t' + (bs[q * nf + fi] ? '-' : '+') + '\t' +
                                             std::to_string(m) + '\t' + std::to_string(t) + '\t' + std::to_string(hb[q * nf + fi]) + '\t' + std::to_string(c);
@@ -650,6 +662,46 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                                         rows += '\t' + ((b >= 0 && (size_t)b < map.size() && !map[b].empty()) ? map[b] : std::string("-"));
                                     }
                                     rows += '\n';
+                                }
+                            }
+                            if (opt.report_spans) {
+                                // per filter that matched: the located best bin of every such read, one query each; the record of the best strand
+                                std::vector<rb_span_query> qs;
+                                std::vector<rb_span> sp;
+                                std::vector<uint32_t> nk;
+                                std::vector<uint8_t> ss;
+                                for (size_t fi = 0; fi < nf; ++fi) {
+                                    qs.clear();
+                                    for (size_t q = 0; q < nl; ++q)
+                                        if (ls[q] == RB_OK && bb[q * nf + fi] >= 0) qs.push_back(rb_span_query{(uint32_t)q, (uint32_t)bb[q * nf + fi]});
+                                    if (qs.empty()) continue;
+                                    sp.resize(qs.size() * 2);
+                                    nk.resize(qs.size());
+                                    ss.resize(qs.size());
+                                    rb_spans_out so{sp.data(), nullptr, nk.data(), ss.data()};
+                                    interleave::throw_status(rb_spans_batch(interleave::detail::engine_for(DepletionFilters, TargetFilters), base, offs.data(),
+                                                                            lens.data(), idx.size(), located.data(), nl, fi, qs.data(), qs.size(), 0, &so),
+                                                             "rb_spans_batch");
+                                    const uint32_t at = c * chunk_length;  // positions in the read's coordinates
+                                    for (size_t x = 0; x < qs.size(); ++x) {
+                                        if (ss[x] != RB_OK) continue;
+                                        const size_t q = qs[x].item, j = located[q];
+                                        const seqio::Record& r = recs[idx[j]];
+                                        size_t w = 0;
+                                        while (w < r.id_len && r.id[w] != ' ' && r.id[w] != '\t') ++w;
+                                        const uint8_t strand = bs[q * nf + fi];
+                                        const rb_span& rec = sp[2 * x + strand];
+                                        std::string& rows = state[idx[j]].span_rows;
+                                        rows.append(r.id, w);
+                                        rows += '\t' + all_filters[fi]->name + '\t' + std::to_string(qs[x].bin);
+                                        if (!opt.bin_maps.empty()) {
+                                            const std::vector<std::string>& map = bin_records[fi];
+                                            rows += '\t' + ((qs[x].bin < map.size() && !map[qs[x].bin].empty()) ? map[qs[x].bin] : std::string("-"));
+                                        }
+                                        rows += std::string("\t") + (strand ? '-' : '+') + '\t' + std::to_string(nk[x]) + '\t' + std::to_string(rec.count) + '\t' +
+                                                std::to_string(rec.first + at) + '\t' + std::to_string(rec.last + at) + '\t' + std::to_string(rec.run_start + at) + '\t' +
+                                                std::to_string(rec.run_len) + '\t' + std::to_string(rec.covered) + '\n';
+                                    }
                                 }
                             }
                         }
@@ -727,6 +779,8 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                         for (const std::string& l : so.error_lines) log_line("error", l);
                         if (opt.report_bins)
                             for (const ReadState& rs : state) bins_out << rs.bin_rows;
+                        if (opt.report_spans)
+                            for (const ReadState& rs : state) spans_out << rs.span_rows;
                         if (opt.report_hits) {
                             for (const ReadState& rs : state) hits_out << rs.hit_rows;
                             for (size_t b = 0; b < bin_profile.size(); ++b) bin_profile[b] += seg_profile[b];
@@ -983,6 +1037,7 @@ int main(int argc, char const* argv[])
         else if (!std::strcmp(argv[i], "--calibrate")) opt.calibrate = true;
         else if (!std::strcmp(argv[i], "--report-bins")) opt.report_bins = true;
         else if (!std::strcmp(argv[i], "--report-hits")) opt.report_hits = true;
+        else if (!std::strcmp(argv[i], "--report-spans")) opt.report_spans = true;
         else if (!std::strcmp(argv[i], "--max-hits")) {
             char* end = nullptr;
             const unsigned long long v = i + 1 < argc ? std::strtoull(argv[i + 1], &end, 10) : 0;
@@ -1042,6 +1097,8 @@ int main(int argc, char const* argv[])
                          "  usage classify: [--report-bins]  classified_bins.tsv: bin, strand, count and hit bins of every classified read\n"
                          "                  [--report-hits [--max-hits 64]]  classified_hits.tsv: every (bin, strand) at or above the threshold of those reads, with\n"
                          "                                    its count, at most --max-hits per (read, filter) (n_hits stays exact); bin_profile.tsv: reads per bin\n"
+                         "                  [--report-spans]  classified_spans.tsv: where along the read the best bin of every matching filter matched, on its best\n"
+                         "                                    strand: n_kmers, count, first, last, run_start, run_len, covered; positions in the read's coordinates\n"
                          "                  [--bin-map <name>.bins.tsv ...]  adds the record id of the bin to these reports\n"
                          "                  [--filter-stats]  per-bin occupancy of every filter built: a summary and <name>.binstats.tsv (give the flag last, or\n"
                          "                                    before another flag: a bare word after it is taken as a file; a build's exit code stays 0 whatever the bins hold)\n"
