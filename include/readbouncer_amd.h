@@ -133,6 +133,29 @@ RB_API void rb_dibf_free(rb_dibf *f);
 /* resizeBins of IBF::update_filter (src/IBF/IBFBuild.cpp:274): same blocks and hash positions, every block widened
  * to ceil(new_bins/64) words, new bins empty, noOfBits = noOfBlocks * new block size.  Returns a new filter. */
 RB_API int rb_dibf_resize_bins(const rb_dibf *f, uint64_t new_bins, rb_dibf **out);
+/* ---- assemble: a new resident filter from bins of others (select, reorder, drop, merge, join) ---------
+ * The reference only appends (IBF::update_filter, src/IBF/IBFBuild.cpp:223-321); everything else is a rebuild from the FASTA.
+ * Every bin of the new filter is the OR of a list of (filter, bin) pairs of resident filters that share noOfBlocks, noOfHashFunc
+ * and kmerSize -- a block number depends on the k-mer, the hash number and noOfBlocks only, so the result is bit for bit what
+ * the builder writes when those fragments are inserted into those bins at that block count (the argument of resizeBins):
+ *   out bin j = OR of srcs[refs[i].filter] bin refs[i].bin for i in [offsets[j], offsets[j+1]); an empty list = an empty bin
+ * One ref per list selects, reorders or drops; several merge fragments into coarser bins; refs into several sources join
+ * filters.  A ref may repeat.  The result is a fresh filter on the sources' device with noOfBins = n_out_bins and noOfBits =
+ * noOfBlocks * ceil(n_out_bins / 64) * 64 (as rb_dibf_resize_bins makes it); the sources are not written and engines that
+ * hold them see no change.  The plan is vetted on the host before anything is launched -- RB_ERR_INVALID_ARG, with
+ * rb_last_error() naming the out bin or source at fault, for: a null argument, n_srcs of 0 or above
+ * RB_ASSEMBLE_MAX_SOURCES, n_out_bins of 0, sources on different devices or of different noOfBlocks / noOfHashFunc / kmerSize,
+ * offsets[0] != 0 or a descending offset, a ref whose filter >= n_srcs or whose bin is at or beyond that source's noOfBins.
+ * RB_ERR_UNSUPPORTED: 2^32 refs or more, or 4 096 consecutive out bins whose lists together span more than 60 KiB of one
+ * block of the sources (some 490 000 source bins). */
+#define RB_ASSEMBLE_MAX_SOURCES 8
+#define RB_BIN_NONE UINT64_MAX
+typedef struct rb_bin_ref { uint32_t filter; uint32_t bin; } rb_bin_ref;   /* 8 bytes */
+RB_API int rb_dibf_assemble(const rb_dibf *const *srcs, size_t n_srcs, const uint64_t *offsets, const rb_bin_ref *refs,
+                            uint64_t n_out_bins, rb_dibf **out);
+/* the one-source, one-ref-per-bin case: out bin j = src bin bins[j], RB_BIN_NONE = empty */
+RB_API int rb_dibf_select_bins(const rb_dibf *src, const uint64_t *bins, uint64_t n_out_bins, rb_dibf **out);
+
 /* seqan::insertKmer for a batch of fragments (src/IBF/IBFBuild.cpp:189-190) on the GPU:
  * fragment i = seq[starts[i], ends[i]) goes to bin bins[i]. seq is host ASCII. */
 RB_API int rb_dibf_insert(rb_dibf *f, const char *seq, size_t len, const uint64_t *starts,

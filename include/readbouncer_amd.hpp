@@ -376,6 +376,25 @@ public:
         return stats;
     }
 
+    // Not in the reference, which only appends (update_filter above): this object's filter becomes a NEW filter whose bin j is the OR of
+    // the (filter, bin) pairs of plan[j], `filter` indexing `sources` -- resident filters of one noOfBlocks, noOfHashFunc and kmerSize
+    // (rb_dibf_assemble: select, reorder, drop, merge, join).  An empty list is an empty bin.  The sources are left as they are.
+    TIbf assemble(const std::vector<TIbf>& sources, const std::vector<std::vector<rb_bin_ref>>& plan)
+    {
+        std::vector<const rb_dibf*> srcs;
+        for (const TIbf& s : sources) srcs.push_back(s.handle());
+        std::vector<uint64_t> offsets(plan.size() + 1, 0);
+        std::vector<rb_bin_ref> refs;
+        for (size_t j = 0; j < plan.size(); ++j) {
+            refs.insert(refs.end(), plan[j].begin(), plan[j].end());
+            offsets[j + 1] = refs.size();
+        }
+        rb_dibf* raw = nullptr;
+        throw_status(rb_dibf_assemble(srcs.data(), srcs.size(), offsets.data(), refs.data(), plan.size(), &raw), "rb_dibf_assemble");
+        filter = TIbf(raw);
+        return filter;
+    }
+
     inline TIbf getFilter() { return filter; }
 };
 

@@ -74,6 +74,15 @@ RB_API int rb_set_placement_tries(int tries);
  * workgroups a table of a hundred MiB walks full-length chunks, several per wave -- what a table of 16 GiB does by itself.  Counts
  * never depend on it; tests and experiments. */
 RB_API void rb_set_bin_occupancy_grid(uint32_t max_workgroups_per_slice, uint32_t min_chunk_rows);
+/* How rb_dibf_assemble / rb_dibf_select_bins cut a table, for every later call of this process: at most max_workgroups workgroups
+ * (8 waves each) in all, and chunks of blocks_per_chunk blocks; 0 = the built-in rule (four workgroups per CU, chunks of 1 024 blocks).
+ * A workgroup reads its part of the plan once and then walks chunk after chunk, so with one workgroup and chunks of 1 or 5 blocks a
+ * table of a few thousand blocks goes through many chunks, short last ones and short steps included.  The bits never depend on it;
+ * tests and experiments.  The counterpart of rb_set_bin_occupancy_grid. */
+RB_API void rb_set_assemble_grid(uint32_t max_workgroups, uint32_t blocks_per_chunk);
+/* seconds the kernel of the last successful rb_dibf_assemble / rb_dibf_select_bins of the calling thread ran (a hipEvent pair around
+ * the launch; 0.0 before the first) -- what `--edit-ibf` prints and profiles/assemble_cost.py measures */
+RB_API double rb_assemble_last_seconds(void);
 /* table size beyond which the library reads with non-temporal loads: the default of rb_engine_set_nt_threshold and the rule of the
  * passes that have no engine (rb_dibf_bin_occupancy) */
 RB_API uint64_t rb_nt_threshold_default(void);

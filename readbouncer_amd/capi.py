@@ -73,6 +73,17 @@ class PlanInfo(C.Structure):
                 ("phase_rule_ticks", C.c_uint32), ("reserved0", C.c_uint32), ("phase_slice_bytes", C.c_uint64)]
 
 
+class BinRef(C.Structure):
+    """rb_bin_ref: one (source filter, bin) of an assemble plan -- 8 bytes"""
+    _fields_ = [("filter", C.c_uint32), ("bin", C.c_uint32)]
+
+
+# rb_bin_ref as a numpy record
+BIN_REF_DTYPE = np.dtype([("filter", "<u4"), ("bin", "<u4")])
+RB_ASSEMBLE_MAX_SOURCES = 8
+RB_BIN_NONE = 2**64 - 1
+
+
 class IbfCompare(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("file_bits", "rebuilt_bits", "new_bits", "payload_bits")]
 
@@ -127,6 +138,10 @@ SIGNATURES = {
     "rb_dibf_device": (_int, [_vp]),
     "rb_dibf_free": (None, [_vp]),
     "rb_dibf_resize_bins": (_int, [_vp, _u64, _pp]),
+    "rb_dibf_assemble": (_int, [_pp, _sz, _vp, _vp, _u64, _pp]),
+    "rb_dibf_select_bins": (_int, [_vp, _vp, _u64, _pp]),
+    "rb_set_assemble_grid": (None, [_u32, _u32]),
+    "rb_assemble_last_seconds": (_dbl, []),
     "rb_dibf_fill_synth": (_int, [_vp, _u64]),
     "rb_dibf_insert": (_int, [_vp, _vp, _sz, _vp, _vp, _vp, _sz]),
     "rb_dibf_add_sequence": (_int, [_vp, _vp, _sz, _u64, _u64, _u64, C.POINTER(_u64)]),
@@ -394,6 +409,23 @@ class DeviceIBF:
     def resize_bins(self, new_bins):
         h = C.c_void_p()
         _check(lib().rb_dibf_resize_bins(self.h, new_bins, C.byref(h)), "rb_dibf_resize_bins")
+        return DeviceIBF(h)
+
+    @classmethod
+    def assemble(cls, sources, plan):
+        """a new filter whose bin j is the OR of the (filter, bin) pairs of plan[j], filter indexing `sources` (resident filters of one
+        n_blocks, n_hash and kmer_size); plan: a list of lists of (filter, bin), or an (offsets, refs) pair (assemble_plan)"""
+        offsets, refs = assemble_plan(plan)
+        h = C.c_void_p()
+        _check(lib().rb_dibf_assemble(_handle_array(sources), len(sources), _ptr(offsets), _ptr(refs), len(offsets) - 1, C.byref(h)),
+               "rb_dibf_assemble")
+        return cls(h)
+
+    def select_bins(self, bins):
+        """a new filter whose bin j is this filter's bin bins[j]; RB_BIN_NONE (or None) = an empty bin"""
+        b = np.ascontiguousarray([RB_BIN_NONE if x is None else int(x) for x in bins], dtype=np.uint64)
+        h = C.c_void_p()
+        _check(lib().rb_dibf_select_bins(self.h, _ptr(b), len(b), C.byref(h)), "rb_dibf_select_bins")
         return DeviceIBF(h)
 
     def fill_synth(self, seed):
@@ -943,6 +975,50 @@ class HostBlock:
 def set_bin_occupancy_grid(max_workgroups_per_slice=0, min_chunk_rows=0):
     """process-wide: how the per-bin occupancy pass cuts a table (0 / 0 = the built-in rule); counts never depend on it"""
     lib().rb_set_bin_occupancy_grid(int(max_workgroups_per_slice), int(min_chunk_rows))
+
+
+def set_assemble_grid(max_workgroups=0, blocks_per_chunk=0):
+    """rb_set_assemble_grid: how every later assemble of this process cuts a table (0, 0 = the built-in rule)"""
+    lib().rb_set_assemble_grid(int(max_workgroups), int(blocks_per_chunk))
+
+
+def assemble_last_seconds():
+    """seconds the kernel of this thread's last assemble / select_bins ran"""
+    return float(lib().rb_assemble_last_seconds())
+
+
+def assemble_plan(plan):
+    """an assemble plan in either form -> (offsets np.uint64[n_out_bins + 1], refs BIN_REF_DTYPE[n_refs]), the CSR arrays of
+    rb_dibf_assemble.  `plan` is a list with one list of (filter, bin) pairs per out bin, or an (offsets, refs) pair of arrays,
+    refs as BIN_REF_DTYPE records or an [n, 2] integer array.  Pure Python: no library call, no GPU."""
+    if isinstance(plan, tuple) and len(plan) == 2 and isinstance(plan[0], np.ndarray):
+        offsets = np.ascontiguousarray(plan[0], dtype=np.uint64)
+        r = np.asarray(plan[1])
+        if r.dtype != BIN_REF_DTYPE:
+            r = np.asarray(r, dtype=np.int64).reshape(-1, 2)
+            if r.size and (r.min() < 0 or r.max() >= 2**32):
+                raise ValueError("assemble plan: a ref does not fit 32 bits")
+            rec = np.zeros(len(r), dtype=BIN_REF_DTYPE)
+            rec["filter"], rec["bin"] = r[:, 0], r[:, 1]
+            r = rec
+        refs = np.ascontiguousarray(r)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError("assemble plan: offsets needs n_out_bins + 1 entries")
+        if int(offsets[-1]) != len(refs):
+            raise ValueError("assemble plan: offsets end at %d, there are %d refs" % (int(offsets[-1]), len(refs)))
+        return offsets, refs
+    lists = [list(l) for l in plan]
+    offsets = np.zeros(len(lists) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(l) for l in lists], dtype=np.uint64)
+    refs = np.zeros(int(offsets[-1]), dtype=BIN_REF_DTYPE)
+    i = 0
+    for l in lists:
+        for f, b in l:
+            if not (0 <= int(f) < 2**32 and 0 <= int(b) < 2**32):
+                raise ValueError("assemble plan: ref (%r, %r) does not fit 32 bits" % (f, b))
+            refs[i] = (int(f), int(b))
+            i += 1
+    return offsets, refs
 
 
 def nt_threshold_default():

@@ -317,6 +317,35 @@ struct OccLaunch {
 void set_bin_occupancy_grid(uint32_t max_wgs_per_slice, uint32_t min_chunk_rows);
 hipError_t launch_bin_occupancy(const uint64_t *words, uint64_t n_blocks, uint64_t stride, uint32_t bin_width, uint32_t n_bins, int nt,
                                 uint64_t *out, hipStream_t st);
+// assembling a filter from bins of others (rb_dibf_assemble; rb_kernels.hip, ibf_assemble_kernel): the source tables by value, the
+// plan (CSR: offsets u64 [n_out_bins + 1], refs {u32 filter, u32 bin}) and the per-tile staging windows in device memory
+constexpr uint32_t kAsmMaxSources = 8;     // == RB_ASSEMBLE_MAX_SOURCES
+constexpr uint32_t kAsmWaves = 8;          // waves per workgroup
+constexpr uint32_t kAsmOutWords = 8;       // out words a wave holds the lists of
+constexpr uint32_t kAsmHeld = 8;           // refs per out bin held in registers; longer lists walk the plan in memory
+constexpr uint32_t kAsmTileWords = kAsmWaves * kAsmOutWords;  // out words of a tile: 64 (4 096 bins)
+constexpr uint32_t kAsmMaxLdsWords = 7680; // 60 KiB: the staged source windows of one step (the kernel's small tables fit beside them below 64 KiB)
+constexpr uint32_t kAsmStepLdsWords = 4096; // ... and what a step is sized to when a block's windows leave the choice
+struct AsmWindow { uint32_t lo, n; };      // words [lo, lo + n) of a source's block are what a tile's lists name
+struct AsmLaunch {
+    const uint64_t *src[kAsmMaxSources];
+    uint64_t src_stride[kAsmMaxSources];
+    uint64_t *out;
+    uint64_t out_stride;         // words; the tiles cover all of it, so pad words are written (zero: no list names them)
+    uint64_t n_blocks;
+    uint64_t n_out_bins;
+    const uint64_t *offsets;
+    const uint2 *refs;           // .x = filter, .y = bin
+    const AsmWindow *windows;    // [n_tiles][kAsmMaxSources]
+    uint32_t n_srcs;
+    uint32_t n_tiles;
+    uint32_t wgs_per_tile;
+    uint32_t blocks_per_chunk;   // a workgroup walks chunks of that many blocks, chunk = iteration * wgs_per_tile + workgroup
+    uint32_t iters;
+};
+void set_assemble_grid(uint32_t max_workgroups, uint32_t blocks_per_chunk);
+// windows_host: the same table the launch reads on the device (the launcher sizes every tile's step from it)
+hipError_t launch_assemble(AsmLaunch a, const AsmWindow *windows_host, int nt, hipStream_t st);
 hipError_t launch_fill_reads(uint8_t *seqs, uint64_t *offsets, uint32_t *lens, size_t n_reads, uint32_t read_len, uint64_t seed, hipStream_t st);
 hipError_t launch_fill_synth(uint64_t *words, uint64_t used_words, uint32_t bin_width, uint32_t stride_words,
                              uint64_t last_mask, uint64_t seed, hipStream_t st);

@@ -799,6 +799,139 @@ int rb_dibf_resize_bins(const rb_dibf *f, uint64_t new_bins, rb_dibf **out)
     return RB_OK;
 }
 
+// A new filter from bins of resident ones (ibf_assemble_kernel).  Everything the kernel indexes with is vetted here: nothing out of
+// range reaches it.  Per tile of kAsmTileWords out words the plan also gives the window of each source's block that the tile's lists
+// name -- what the kernel stages in LDS.
+static thread_local double g_assemble_seconds = 0.0;
+double rb_assemble_last_seconds(void) { return g_assemble_seconds; }
+void rb_set_assemble_grid(uint32_t max_workgroups, uint32_t blocks_per_chunk) { set_assemble_grid(max_workgroups, blocks_per_chunk); }
+
+int rb_dibf_assemble(const rb_dibf *const *srcs, size_t n_srcs, const uint64_t *offsets, const rb_bin_ref *refs, uint64_t n_out_bins,
+                     rb_dibf **out)
+{
+    if (!srcs || !offsets || !out) return rb::fail(RB_ERR_INVALID_ARG, "assemble: null argument");
+    if (n_srcs == 0 || n_srcs > RB_ASSEMBLE_MAX_SOURCES)
+        return rb::fail(RB_ERR_INVALID_ARG, "assemble: " + std::to_string(n_srcs) + " sources (1 to " + std::to_string(RB_ASSEMBLE_MAX_SOURCES) + ")");
+    if (n_out_bins == 0) return rb::fail(RB_ERR_INVALID_ARG, "assemble: n_out_bins is 0");
+    for (size_t s = 0; s < n_srcs; ++s) {
+        if (!srcs[s]) return rb::fail(RB_ERR_INVALID_ARG, "assemble: source " + std::to_string(s) + " is null");
+        const rb_dibf *f = srcs[s], *f0 = srcs[0];
+        if (f->device != f0->device) return rb::fail(RB_ERR_INVALID_ARG, "assemble: source " + std::to_string(s) + " is on another device than source 0");
+        if (f->geo.n_blocks != f0->geo.n_blocks || f->geo.n_hash != f0->geo.n_hash || f->geo.kmer_size != f0->geo.kmer_size)
+            return rb::fail(RB_ERR_INVALID_ARG, "assemble: source " + std::to_string(s) + " differs from source 0 in n_blocks, n_hash or kmer_size");
+    }
+    if (n_out_bins >= (1ULL << 31)) return rb::fail(RB_ERR_UNSUPPORTED, "too many bins");
+    if (offsets[0] != 0) return rb::fail(RB_ERR_INVALID_ARG, "assemble: offsets[0] is not 0");
+    for (uint64_t j = 0; j < n_out_bins; ++j)
+        if (offsets[j + 1] < offsets[j]) return rb::fail(RB_ERR_INVALID_ARG, "assemble: the offsets descend at out bin " + std::to_string(j));
+    const uint64_t n_refs = offsets[n_out_bins];
+    if (n_refs && !refs) return rb::fail(RB_ERR_INVALID_ARG, "assemble: null refs");
+    if (n_refs >= (1ULL << 32)) return rb::fail(RB_ERR_UNSUPPORTED, "assemble: 2^32 refs or more");
+    const rb_ibf_info &g0 = srcs[0]->geo;
+    const uint64_t out_width = (n_out_bins + rbspec::kIntSize - 1) / rbspec::kIntSize;
+    rb_ibf_info g;
+    if (!geometry_from(n_out_bins, g0.n_hash, g0.kmer_size, g0.n_blocks * out_width * 64, &g)) return rb::fail(RB_ERR_INVALID_ARG, "bad IBF geometry");
+    const uint64_t out_stride = hbm_stride(out_width);
+    const uint64_t n_tiles = (out_stride + kAsmTileWords - 1) / kAsmTileWords;
+    std::vector<AsmWindow> win(n_tiles * kAsmMaxSources, AsmWindow{0, 0});
+    std::vector<uint32_t> hi(kAsmMaxSources);
+    for (uint64_t t = 0; t < n_tiles; ++t) {
+        AsmWindow *w = win.data() + t * kAsmMaxSources;
+        std::fill(hi.begin(), hi.end(), 0u);
+        const uint64_t j1 = std::min<uint64_t>(n_out_bins, (t + 1) * kAsmTileWords * 64);
+        for (uint64_t j = t * kAsmTileWords * 64; j < j1; ++j) {
+            for (uint64_t i = offsets[j]; i < offsets[j + 1]; ++i) {
+                const rb_bin_ref r = refs[i];
+                if (r.filter >= n_srcs)
+                    return rb::fail(RB_ERR_INVALID_ARG, "assemble: out bin " + std::to_string(j) + " names filter " + std::to_string(r.filter) + " of " + std::to_string(n_srcs));
+                if (r.bin >= srcs[r.filter]->geo.n_bins)
+                    return rb::fail(RB_ERR_INVALID_ARG, "assemble: out bin " + std::to_string(j) + " names bin " + std::to_string(r.bin) + " of source " +
+                                                            std::to_string(r.filter) + ", which has " + std::to_string(srcs[r.filter]->geo.n_bins));
+                const uint32_t word = r.bin >> 6;
+                if (w[r.filter].n == 0) { w[r.filter].lo = word; hi[r.filter] = word; w[r.filter].n = 1; }
+                else { w[r.filter].lo = std::min(w[r.filter].lo, word); hi[r.filter] = std::max(hi[r.filter], word); }
+            }
+        }
+        uint64_t staged = 1;
+        for (size_t s = 0; s < n_srcs; ++s) {
+            if (w[s].n) w[s].n = hi[s] - w[s].lo + 1;
+            staged += w[s].n;
+        }
+        if (staged > kAsmMaxLdsWords)
+            return rb::fail(RB_ERR_UNSUPPORTED, "assemble: the lists of out bins " + std::to_string(t * kAsmTileWords * 64) + " to " + std::to_string(j1 - 1) + " span " +
+                                                    std::to_string(staged * 8) + " bytes of a source block (at most " + std::to_string(kAsmMaxLdsWords * 8) + ")");
+    }
+    rb_dibf *n = nullptr;
+    int st = dibf_alloc(srcs[0]->device, g, false, &n);  // (the kernel writes every word of every block, pad words included; the tail is zeroed here)
+    if (st != RB_OK) return st;
+    if (n->stride != out_stride) { rb_dibf_free(n); return rb::fail(RB_ERR_HIP, "assemble: stride rule mismatch"); }
+    uint64_t *d_offsets = nullptr;
+    rb_bin_ref *d_refs = nullptr;
+    AsmWindow *d_win = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipError_t e = hipMalloc((void **)&d_offsets, (n_out_bins + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_refs, std::max<uint64_t>(n_refs, 1) * sizeof(rb_bin_ref));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_win, win.size() * sizeof(AsmWindow));
+    if (e == hipSuccess) e = hipMemcpy(d_offsets, offsets, (n_out_bins + 1) * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_refs) e = hipMemcpy(d_refs, refs, n_refs * sizeof(rb_bin_ref), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_win, win.data(), win.size() * sizeof(AsmWindow), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipEventCreate(&ev0);
+    if (e == hipSuccess) e = hipEventCreate(&ev1);
+    float ms = 0.0f;
+    if (e == hipSuccess) {
+        AsmLaunch a{};
+        uint64_t src_bytes = 0;
+        for (size_t s = 0; s < n_srcs; ++s) {
+            a.src[s] = srcs[s]->d_words;
+            a.src_stride[s] = srcs[s]->stride;
+            src_bytes += srcs[s]->geo.n_blocks * srcs[s]->stride * 8;
+        }
+        a.out = n->d_words;
+        a.out_stride = out_stride;
+        a.n_blocks = g.n_blocks;
+        a.n_out_bins = n_out_bins;
+        a.offsets = d_offsets;
+        a.refs = reinterpret_cast<const uint2 *>(d_refs);
+        a.windows = d_win;
+        a.n_srcs = (uint32_t)n_srcs;
+        const int nt = src_bytes + g.n_blocks * out_stride * 8 > kNtThresholdBytes;
+        e = hipEventRecord(ev0, nullptr);
+        if (e == hipSuccess) e = launch_assemble(a, win.data(), nt, nullptr);
+        if (e == hipSuccess) e = hipEventRecord(ev1, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
+    }
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (d_offsets) (void)hipFree(d_offsets);
+    if (d_refs) (void)hipFree(d_refs);
+    if (d_win) (void)hipFree(d_win);
+    if (e != hipSuccess) { rb_dibf_free(n); return rb::fail(RB_ERR_HIP, std::string("assemble: ") + hipGetErrorString(e)); }
+    g_assemble_seconds = (double)ms * 1e-3;
+    *out = n;
+    return RB_OK;
+}
+
+int rb_dibf_select_bins(const rb_dibf *src, const uint64_t *bins, uint64_t n_out_bins, rb_dibf **out)
+{
+    if (!src || !bins || !out) return rb::fail(RB_ERR_INVALID_ARG, "select_bins: null argument");
+    if (n_out_bins == 0) return rb::fail(RB_ERR_INVALID_ARG, "select_bins: n_out_bins is 0");
+    if (n_out_bins >= (1ULL << 31)) return rb::fail(RB_ERR_UNSUPPORTED, "too many bins");
+    std::vector<uint64_t> offsets(n_out_bins + 1, 0);
+    std::vector<rb_bin_ref> refs;
+    refs.reserve(n_out_bins);
+    for (uint64_t j = 0; j < n_out_bins; ++j) {
+        if (bins[j] != RB_BIN_NONE) {
+            if (bins[j] >= src->geo.n_bins)
+                return rb::fail(RB_ERR_INVALID_ARG, "select_bins: out bin " + std::to_string(j) + " names bin " + std::to_string(bins[j]) + " of a source with " +
+                                                        std::to_string(src->geo.n_bins));
+            refs.push_back(rb_bin_ref{0u, (uint32_t)bins[j]});
+        }
+        offsets[j + 1] = refs.size();
+    }
+    return rb_dibf_assemble(&src, 1, offsets.data(), refs.data(), n_out_bins, out);
+}
+
 int rb_dibf_fill_synth(rb_dibf *f, uint64_t seed)
 {
     if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");

@@ -2752,6 +2752,252 @@ __global__ __launch_bounds__(64 * kOccWaves) void ibf_bin_occupancy_kernel(OccLa
 }
 
 // ---------------------------------------------------------------------------------------------
+// Assembling a filter from bins of others (rb_dibf_assemble): out bin j of every block = OR of the source bits its list names.
+// The plan is the same for every block, so it is read ONCE per workgroup and held in registers while the workgroup walks blocks:
+//   * A workgroup (kAsmWaves waves) owns a TILE of up to kAsmTileWords out words (4 096 out bins) of every block of its chunks.
+//     A wave holds the lists of `ow` = ceil(tile words / kAsmWaves) consecutive out words: lane = out bin of the word, up to
+//     kAsmHeld refs per bin, each already translated to (word of the staged image << 6 | bit) -- 0 names the image's zero word,
+//     so an absent ref needs no test.  A tile narrower than kAsmWaves words leaves waves over: they take further blocks
+//     (`gpw` block groups per workgroup), every wave takes `kb` consecutive blocks per round, and a step has as many
+//     rounds as its LDS image (about 32 KiB) holds: the loads of a whole step are in flight together.
+//   * Per step the workgroup stages, for each of its gpw * kb blocks, the WINDOW of every source block that the tile's lists name
+//     (AsmWindow: words [lo, lo + n); the host derives it from the plan, so an identity, a merge or a reversal stage exactly the
+//     words they use and a source block is fetched once) into LDS: one global load per word, 2^lg lanes per block like the
+//     occupancy pass.  Then lane ORs its refs' bits out of LDS (the r loop runs to the wave's longest held list, uniform), one
+//     __ballot per out word -- every lane of the wave is inside it: all control flow around it is wave-uniform -- is the out
+//     word, which lane k * ow + j keeps; one store per wave and step writes ow * kb words.
+//   * Lists longer than kAsmHeld walk refs[] in memory behind the held part, to the wave's longest list (a ballot is the loop
+//     condition; the loads are predicated per lane).
+//   * Out words at or beyond ceil(n_out_bins / 64) (the pad of the stride) and bins at or beyond n_out_bins have no list: their
+//     ballots are zero, so the image comes out padded with zeros without a pass of its own.
+// All table addresses are 64-bit word numbers.  DESIGN 4.9 has the resources.
+struct AsmShape { uint32_t ow, wpb, gpw, kb, rounds; };
+__host__ __device__ inline AsmShape asm_shape(uint32_t tile_words, uint32_t staged_words)
+{
+    AsmShape s;
+    s.ow = (tile_words + kAsmWaves - 1) / kAsmWaves;
+    s.wpb = (tile_words + s.ow - 1) / s.ow;
+    s.gpw = kAsmWaves / s.wpb;
+    const uint32_t room = kAsmMaxLdsWords / staged_words;  // (>= 1: the host refuses wider windows)
+    if (s.gpw > room) s.gpw = room;
+    uint32_t kb = kAsmStepLdsWords / (s.gpw * staged_words);
+    if (kb < 1) kb = 1;
+    if (kb > 64u / s.ow) kb = 64u / s.ow;
+    s.kb = kb;
+    // ... and as many rounds of gpw * kb blocks per step as the step's LDS holds: the loads of a step are what is in flight
+    uint32_t rounds = kAsmStepLdsWords / (s.gpw * kb * staged_words);
+    if (rounds < 1) rounds = 1;
+    if (rounds > 16) rounds = 16;
+    s.rounds = rounds;
+    return s;
+}
+
+template <bool NT>
+__device__ __forceinline__ void store_word(uint64_t *p, uint64_t v)
+{
+    if constexpr (NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+
+// the OR phase of a full-width wave (kAsmOutWords out words), lists of at most R held refs: all R * kAsmOutWords LDS reads of a block
+// go out with no control flow between them, so the out words do not wait for one another's read.  An absent ref is 0 = the zero word.
+template <int R>
+__device__ __forceinline__ void asm_or_words(const uint64_t *blk, const uint32_t (&held)[kAsmOutWords][kAsmHeld], uint64_t (&acc)[kAsmOutWords])
+{
+#pragma unroll
+    for (uint32_t j = 0; j < kAsmOutWords; ++j) acc[j] = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        // ref r of all the out words: the refs are decoded here, every time (hoisted out of the block loop the word numbers and shifts
+        // would triple the registers), behind empty asm statements that come BEFORE the batch's reads, not between them
+        // (four reads at a time: eight more live words spill)
+#pragma unroll
+        for (uint32_t j0 = 0; j0 < kAsmOutWords; j0 += 4) {
+            uint32_t e[4];
+            uint64_t w[4];
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                e[j] = held[j0 + j][r];
+                asm volatile("" : "+v"(e[j]));
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) w[j] = blk[e[j] >> 6];
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) acc[j0 + j] |= w[j] >> (e[j] & 63u);
+        }
+    }
+}
+
+template <bool NT>
+__global__ __launch_bounds__(64 * kAsmWaves, 4) void ibf_assemble_kernel(AsmLaunch a)
+{
+    extern __shared__ uint64_t asm_img[];  // gpw * kb staged blocks of `sw` words: [zero word | window of source 0 | window of source 1 ...]
+    __shared__ uint32_t s_base[kAsmMaxSources], s_lo[kAsmMaxSources], s_n[kAsmMaxSources], s_lg[kAsmMaxSources], s_sw;
+    __shared__ const uint64_t *s_src[kAsmMaxSources];
+    __shared__ uint64_t s_stride[kAsmMaxSources];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t tile = blockIdx.x % a.n_tiles, wg = blockIdx.x / a.n_tiles;
+    const uint64_t t0 = (uint64_t)tile * kAsmTileWords;
+    const uint32_t tw = (uint32_t)min((uint64_t)kAsmTileWords, a.out_stride - t0);
+    if (threadIdx.x == 0) {
+        uint32_t base = 1;
+#pragma unroll
+        for (uint32_t s = 0; s < kAsmMaxSources; ++s) {
+            AsmWindow w{0, 0};
+            if (s < a.n_srcs) w = a.windows[(uint64_t)tile * kAsmMaxSources + s];
+            uint32_t lg = 0;
+            while ((1u << lg) < w.n && lg < 6) ++lg;
+            s_base[s] = base;
+            s_lo[s] = w.lo;
+            s_n[s] = w.n;
+            s_lg[s] = lg;
+            s_src[s] = a.src[s];
+            s_stride[s] = a.src_stride[s];
+            base += w.n;
+        }
+        s_sw = base;
+    }
+    __syncthreads();
+    const uint32_t sw = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_sw);
+    const AsmShape sh = asm_shape(tw, sw);
+    const uint32_t ow = sh.ow, kb = sh.kb, nb = sh.gpw * sh.kb * sh.rounds;
+    for (uint32_t i = threadIdx.x; i < nb; i += blockDim.x) asm_img[(uint64_t)i * sw] = 0ULL;
+
+    // the wave's lists, once for all blocks
+    const uint32_t grp = wave / sh.wpb, wq_in = (wave - grp * sh.wpb) * ow;  // (uniform)
+    const bool wave_on = grp < sh.gpw;
+    uint32_t held[kAsmOutWords][kAsmHeld];
+    uint32_t held_len = 0;    // 4 bits per out word: the wave's longest held list
+    uint32_t spill_mask = 0;  // out words with a list beyond kAsmHeld somewhere in the wave
+#pragma unroll
+    for (uint32_t j = 0; j < kAsmOutWords; ++j) {
+        const uint64_t bin = (t0 + wq_in + j) * 64u + lane;
+        uint64_t o0 = 0;
+        uint32_t n = 0;
+        if (wave_on && j < ow && wq_in + j < tw && bin < a.n_out_bins) {
+            o0 = a.offsets[bin];
+            n = (uint32_t)(a.offsets[bin + 1] - o0);
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < kAsmHeld; ++r) {
+            held[j][r] = 0;
+            if (r < n) {
+                const uint2 rf = a.refs[o0 + r];
+                held[j][r] = ((s_base[rf.x] + (rf.y >> 6) - s_lo[rf.x]) << 6) | (rf.y & 63u);
+            }
+            if (__ballot(r < n) != 0ULL) held_len += 1u << (4u * j);
+        }
+        if (__ballot(n > kAsmHeld) != 0ULL) spill_mask |= 1u << j;
+    }
+    held_len = (uint32_t)__builtin_amdgcn_readfirstlane((int)held_len);
+    spill_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)spill_mask);
+    uint32_t max_len = 0;  // the longest held list of the wave's out words
+#pragma unroll
+    for (uint32_t j = 0; j < kAsmOutWords; ++j) max_len = max(max_len, (held_len >> (4u * j)) & 15u);
+    const bool full_wave = ow == kAsmOutWords;
+    const uint32_t lane_k = lane / ow, lane_j = lane - lane_k * ow;  // the (block, out word) whose result this lane stores
+
+    for (uint32_t it = 0; it < a.iters; ++it) {
+        const uint64_t chunk = (uint64_t)it * a.wgs_per_tile + wg;
+        const uint64_t cb = chunk * a.blocks_per_chunk;
+        if (cb >= a.n_blocks) break;
+        const uint64_t ce = min(cb + a.blocks_per_chunk, a.n_blocks);
+#pragma unroll 1
+        for (uint64_t b0 = cb; b0 < ce; b0 += nb) {
+            const uint32_t nbe = (uint32_t)min((uint64_t)nb, ce - b0);
+            __syncthreads();  // the step before has been read
+            for (uint32_t s = 0; s < a.n_srcs; ++s) {
+                const uint32_t ns = s_n[s];
+                if (ns == 0) continue;
+                const uint32_t lg = s_lg[s], per_row = 64u >> lg;
+                const uint32_t q = lane >> lg, c0 = lane & ((1u << lg) - 1u);
+                const uint64_t stride = s_stride[s];
+                const uint64_t *sp = s_src[s] + s_lo[s];
+                uint64_t *dp = asm_img + s_base[s];
+                // four loads per lane go out before the first of them is written to LDS
+                for (uint32_t c = c0; c < ns; c += 1u << lg) {
+                    for (uint32_t bb = wave * per_row + q; bb < nbe; bb += 4u * kAsmWaves * per_row) {
+                        uint64_t v[4];
+#pragma unroll
+                        for (uint32_t u = 0; u < 4; ++u) {
+                            const uint32_t b = bb + u * kAsmWaves * per_row;
+                            v[u] = b < nbe ? load_word<NT>(sp + (b0 + b) * stride + c) : 0ULL;
+                        }
+#pragma unroll
+                        for (uint32_t u = 0; u < 4; ++u) {
+                            const uint32_t b = bb + u * kAsmWaves * per_row;
+                            if (b < nbe) dp[(uint64_t)b * sw + c] = v[u];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (!wave_on) continue;
+#pragma unroll 1
+            for (uint32_t round = 0; round < sh.rounds; ++round) {
+            const uint32_t first = (round * sh.gpw + grp) * kb;  // the kb consecutive blocks of this wave in this round
+            if (first >= nbe) break;  // (uniform)
+            uint64_t keep = 0;
+#pragma unroll 1
+            for (uint32_t k = 0; k < kb; ++k) {
+                const uint32_t bsub = first + k;
+                if (bsub >= nbe) break;  // (uniform)
+                const uint64_t *blk = asm_img + (uint64_t)bsub * sw;
+                uint64_t accs[kAsmOutWords];
+                if (full_wave) {  // (uniform) one branch per block, none between the reads
+                    if (max_len <= 1) asm_or_words<1>(blk, held, accs);
+                    else if (max_len <= 2) asm_or_words<2>(blk, held, accs);
+                    else if (max_len <= 4) asm_or_words<4>(blk, held, accs);
+                    else asm_or_words<8>(blk, held, accs);
+                } else {
+#pragma unroll
+                    for (uint32_t j = 0; j < kAsmOutWords; ++j) {
+                        accs[j] = 0;
+                        if (j >= ow) continue;  // (uniform)
+                        const uint32_t len = (held_len >> (4u * j)) & 15u;
+#pragma unroll
+                        for (uint32_t r = 0; r < kAsmHeld; ++r) {
+                            if (r < len) {  // (uniform guard: the wave's longest list)
+                                uint32_t e = held[j][r];
+                                asm volatile("" : "+v"(e));
+                                accs[j] |= blk[e >> 6] >> (e & 63u);
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < kAsmOutWords; ++j) {
+                    if (j >= ow) continue;  // (uniform)
+                    uint64_t acc = accs[j];
+                    if ((spill_mask >> j) & 1u) {  // (uniform) the lists' tails, from the plan in memory
+                        const uint64_t bin = (t0 + wq_in + j) * 64u + lane;
+                        uint64_t o0 = 0;
+                        uint32_t n = 0;
+                        if (wq_in + j < tw && bin < a.n_out_bins) {
+                            o0 = a.offsets[bin];
+                            n = (uint32_t)(a.offsets[bin + 1] - o0);
+                        }
+                        for (uint32_t i = kAsmHeld; __ballot(i < n) != 0ULL; ++i) {
+                            if (i < n) {
+                                const uint2 rf = a.refs[o0 + i];
+                                acc |= blk[s_base[rf.x] + (rf.y >> 6) - s_lo[rf.x]] >> (rf.y & 63u);
+                            }
+                        }
+                    }
+                    const uint64_t word = __ballot((acc & 1ULL) != 0ULL);
+                    if (lane == k * ow + j) keep = word;
+                }
+            }
+            const uint32_t bsub = first + lane_k;
+            if (lane_k < kb && bsub < nbe && wq_in + lane_j < tw)
+                store_word<NT>(a.out + (b0 + bsub) * a.out_stride + t0 + wq_in + lane_j, keep);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 template <int LG, int WPL, int NP, int H, bool NT>
 static hipError_t launch_count_nt(const CountLaunch &a, hipStream_t st)
@@ -3440,6 +3686,56 @@ hipError_t launch_bin_occupancy(const uint64_t *words, uint64_t n_blocks, uint64
         if (nt) hipLaunchKernelGGL((ibf_bin_occupancy_kernel<1, true>), grid, block, 0, st, a, o);
         else hipLaunchKernelGGL((ibf_bin_occupancy_kernel<1, false>), grid, block, 0, st, a, o);
     }
+    return hipGetLastError();
+}
+
+// rb_set_assemble_grid: workgroups per launch at most, and the blocks of a chunk, for every later assemble of this process (0 = the
+// rule below).  The bits never depend on it; a small table then walks several chunks per workgroup, short last chunks included.
+static std::atomic<uint32_t> g_asm_max_wgs{0}, g_asm_blocks_per_chunk{0};
+void set_assemble_grid(uint32_t max_workgroups, uint32_t blocks_per_chunk)
+{
+    g_asm_max_wgs.store(max_workgroups);
+    g_asm_blocks_per_chunk.store(blocks_per_chunk);
+}
+
+// Four workgroups of kAsmWaves waves per CU, shared out over the tiles (workgroup = tile + n_tiles * slot, so the tiles of one chunk
+// are dispatched side by side and meet each other's source lines in cache); a slot walks `iters` chunks of `blocks_per_chunk` blocks.
+hipError_t launch_assemble(AsmLaunch a, const AsmWindow *windows_host, int nt, hipStream_t st)
+{
+    if (a.n_blocks == 0 || a.out_stride == 0) return hipSuccess;
+    if (a.n_srcs == 0 || a.n_srcs > kAsmMaxSources) return hipErrorInvalidValue;
+    const uint64_t n_tiles = (a.out_stride + kAsmTileWords - 1) / kAsmTileWords;
+    if (n_tiles > 0x00FFFFFFull) return hipErrorInvalidValue;
+    a.n_tiles = (uint32_t)n_tiles;
+    uint64_t lds_words = 0;
+    for (uint64_t t = 0; t < n_tiles; ++t) {
+        uint64_t sw = 1;
+        for (uint32_t s = 0; s < a.n_srcs; ++s) sw += windows_host[t * kAsmMaxSources + s].n;
+        if (sw > kAsmMaxLdsWords) return hipErrorInvalidValue;
+        const uint32_t tw = (uint32_t)std::min<uint64_t>(kAsmTileWords, a.out_stride - t * kAsmTileWords);
+        const AsmShape sh = asm_shape(tw, (uint32_t)sw);
+        lds_words = std::max<uint64_t>(lds_words, (uint64_t)sh.gpw * sh.kb * sh.rounds * sw);
+    }
+    int dev = 0, cus = 0;
+    hipError_t e;
+    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
+    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+    const uint32_t bpc = g_asm_blocks_per_chunk.load() ? g_asm_blocks_per_chunk.load() : 1024u;
+    const uint64_t n_chunks = (a.n_blocks + bpc - 1) / bpc;
+    uint64_t wgs = std::max<uint64_t>(1, 4ull * (uint64_t)std::max(cus, 1));
+    if (const uint32_t cap = g_asm_max_wgs.load()) wgs = std::min<uint64_t>(wgs, cap);
+    uint64_t per_tile = std::max<uint64_t>(1, wgs / n_tiles);
+    per_tile = std::min(per_tile, n_chunks);
+    if (per_tile * n_tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    a.wgs_per_tile = (uint32_t)per_tile;
+    a.blocks_per_chunk = bpc;
+    const uint64_t iters = (n_chunks + per_tile - 1) / per_tile;
+    if (iters > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    a.iters = (uint32_t)iters;
+    const dim3 grid((uint32_t)(per_tile * n_tiles)), block(64 * kAsmWaves);
+    const size_t lds_bytes = (size_t)lds_words * 8;
+    if (nt) hipLaunchKernelGGL((ibf_assemble_kernel<true>), grid, block, lds_bytes, st, a);
+    else hipLaunchKernelGGL((ibf_assemble_kernel<false>), grid, block, lds_bytes, st, a);
     return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 // through rb_live_*); the MinKNOW client, the basecallers and usage "test" (connection test) are out of scope.
 #include <sys/resource.h>
 
+#include <algorithm>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -47,12 +48,17 @@ struct ClassificationResults
 // fragment_size stretch of a reference record (src/IBF/IBFBuild.cpp:165-204), so the table turns the bin numbers of
 // classify --report-bins into loci.  No counterpart in the reference.
 static bool g_write_bin_map = false;
+// the two head lines of every <name>.bins.tsv, whoever writes it (build --write-bin-map, --edit-ibf)
+static void write_bin_map_head(std::ostream& out)
+{
+    out << "# start / end are positions in the record AFTER cutOutNNNs (every N removed): the sequence the reference fragments\n";
+    out << "bin\trecord_id\tstart\tend\n";
+}
 static void write_bin_map(const std::string& path, const std::vector<interleave::RefSeq>& records, const interleave::IBFConfig& config)
 {
     std::ofstream out(path);
     if (!out) throw std::runtime_error("Unable to open the file: " + path);
-    out << "# start / end are positions in the record AFTER cutOutNNNs (every N removed): the sequence the reference fragments\n";
-    out << "bin\trecord_id\tstart\tend\n";
+    write_bin_map_head(out);
     uint64_t bin = 0;
     std::vector<uint64_t> s, e;
     for (const interleave::RefSeq& r : records) {  // the records and the order of IBF::create_filter
@@ -134,6 +140,185 @@ static int filter_stats(interleave::IBF& filter, const std::string& ibf_path, co
               << " at error_rate=" << error_rate << "; expected false-positive hits in the fullest bin=" << (double)n_kmers * s.max_fpr << "\n"
               << "  written " << out_path.string() << std::endl;
     return s.bins_over_max_fp ? 3 : 0;
+}
+
+// --edit-ibf <a.ibf> [--with <b.ibf> ...] --output <out.ibf> with one of --plan / --merge-every / --drop-records: a new filter whose bins are
+// ORs of bins of the loaded ones (rb_dibf_assemble) -- drop a record, merge fragments into coarser bins, join filters -- without the FASTA.
+// The reference only appends (IBF::update_filter, src/IBF/IBFBuild.cpp:223-321).  The plan is a list of (filter, bin) per out bin, filter
+// 0 = --edit-ibf, the --with files follow in order.
+struct EditOptions
+{
+    std::string input, output, plan_path, drop_records;
+    std::vector<std::string> with;
+    uint64_t merge_every = 0;
+    bool merge_given = false;
+};
+static std::vector<std::string> split_commas(const std::string& list)
+{
+    std::vector<std::string> out;
+    size_t pos = 0;
+    while (pos <= list.size()) {
+        const size_t comma = list.find(',', pos);
+        const std::string tok = list.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
+        if (!tok.empty()) out.push_back(tok);
+        if (comma == std::string::npos) break;
+        pos = comma + 1;
+    }
+    return out;
+}
+// rows `out_bin<TAB>filter<TAB>bin`; `#` starts a comment; `# bins=N` fixes the bin count, otherwise it is the highest out bin + 1
+static std::vector<std::vector<rb_bin_ref>> read_plan(const std::string& path)
+{
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("Unable to open the file: " + path);
+    struct Row { uint64_t out_bin; rb_bin_ref ref; size_t line_no; };
+    std::vector<Row> rows;  // the plan is sized only when every row has been read and held against `# bins=N`
+    uint64_t fixed = 0, highest = 0;
+    bool have_fixed = false;
+    std::string line;
+    size_t line_no = 0;
+    while (std::getline(in, line)) {
+        ++line_no;
+        const std::string where = path + ":" + std::to_string(line_no) + ": ";
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) {
+            const size_t b = line.find("bins=", hash);
+            if (line.find_first_not_of(" \t") == hash && b != std::string::npos && line.find_first_not_of(" \t", hash + 1) == b) {
+                char* end = nullptr;
+                const unsigned long long v = std::strtoull(line.c_str() + b + 5, &end, 10);
+                if (end == line.c_str() + b + 5 || v == 0 || v >= (1ull << 31)) throw std::runtime_error(where + "malformed bins=N");
+                fixed = v;
+                have_fixed = true;
+            }
+            line.resize(hash);
+        }
+        if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+        unsigned long long v[3];
+        const char* p = line.c_str();
+        for (int i = 0; i < 3; ++i) {
+            while (*p == ' ' || *p == '\t') ++p;
+            char* end = nullptr;
+            if (*p < '0' || *p > '9') throw std::runtime_error(where + "malformed plan row (out_bin<TAB>filter<TAB>bin)");
+            v[i] = std::strtoull(p, &end, 10);
+            p = end;
+        }
+        while (*p == ' ' || *p == '\t' || *p == '\r') ++p;
+        if (*p != '\0') throw std::runtime_error(where + "malformed plan row (out_bin<TAB>filter<TAB>bin)");
+        if (v[0] >= (1ull << 31) || v[1] > 0xFFFFFFFFull || v[2] > 0xFFFFFFFFull) throw std::runtime_error(where + "plan row out of range");
+        rows.push_back(Row{v[0], rb_bin_ref{(uint32_t)v[1], (uint32_t)v[2]}, line_no});
+        highest = std::max<uint64_t>(highest, v[0]);
+    }
+    if (have_fixed)
+        for (const Row& r : rows)
+            if (r.out_bin >= fixed)
+                throw std::runtime_error(path + ":" + std::to_string(r.line_no) + ": plan row out of range: out bin " + std::to_string(r.out_bin) + " with bins=" + std::to_string(fixed));
+    if (!have_fixed && rows.empty()) throw std::runtime_error(path + ": the plan has no out bin");
+    // without `# bins=N` the bin count is the highest out bin + 1: a number far beyond what the rows could fill is a typo, not a plan
+    if (!have_fixed && highest >= (1ull << 24) && highest >= 1024 * (uint64_t)rows.size())
+        throw std::runtime_error(path + ": plan row out of range: out bin " + std::to_string(highest) + " with " + std::to_string(rows.size()) + " rows and no `# bins=N` line");
+    std::vector<std::vector<rb_bin_ref>> plan(have_fixed ? fixed : highest + 1);
+    for (const Row& r : rows) plan[r.out_bin].push_back(r.ref);
+    return plan;
+}
+static int edit_ibf(const EditOptions& eo, const std::vector<std::string>& bin_map_args, int device, bool with_stats, double error_rate)
+{
+    if (eo.output.empty()) throw std::runtime_error("--edit-ibf needs --output <out.ibf>");
+    if ((eo.plan_path.empty() ? 0 : 1) + (eo.merge_given ? 1 : 0) + (eo.drop_records.empty() ? 0 : 1) != 1)
+        throw std::runtime_error("--edit-ibf needs exactly one of --plan <plan.tsv>, --merge-every N, --drop-records id[,id...]");
+    std::vector<std::string> map_paths;
+    for (const std::string& a : bin_map_args)
+        for (const std::string& m : split_commas(a)) map_paths.push_back(m);
+    std::vector<std::string> paths{eo.input};
+    paths.insert(paths.end(), eo.with.begin(), eo.with.end());
+    if (paths.size() > RB_ASSEMBLE_MAX_SOURCES) throw std::runtime_error("--edit-ibf: at most " + std::to_string(RB_ASSEMBLE_MAX_SOURCES) + " filters");
+    if (!map_paths.empty() && map_paths.size() != paths.size())
+        throw std::runtime_error("--bin-map: " + std::to_string(map_paths.size()) + " bin maps for " + std::to_string(paths.size()) + " filters");
+    if (eo.merge_given && (eo.merge_every == 0 || paths.size() != 1)) throw std::runtime_error("--merge-every N: N >= 1, one filter only");
+    if (!eo.drop_records.empty() && map_paths.empty()) throw std::runtime_error("--drop-records needs --bin-map");
+    std::vector<interleave::TIbf> sources;
+    uint64_t bins_in = 0;
+    for (const std::string& p : paths) {
+        interleave::IBFConfig cfg{};
+        cfg.input_filter_file = p;
+        cfg.device = device;
+        interleave::IBF f{};
+        f.load_filter(cfg);
+        sources.push_back(f.getFilter());
+        bins_in += sources.back().noOfBins;
+    }
+    std::vector<std::vector<std::string>> maps;  // per source: bin -> "record_id\tstart\tend"
+    for (const std::string& m : map_paths) maps.push_back(read_bin_map_rows(m));
+    auto record_of = [&](const rb_bin_ref& r) {
+        if (r.filter >= maps.size() || r.bin >= maps[r.filter].size()) return std::string();
+        const std::string& row = maps[r.filter][r.bin];
+        return row.substr(0, row.find('\t'));
+    };
+    std::vector<std::vector<rb_bin_ref>> plan;
+    if (!eo.plan_path.empty()) plan = read_plan(eo.plan_path);
+    else if (eo.merge_given) {
+        for (uint64_t j = 0; j < sources[0].noOfBins; j += eo.merge_every) {
+            plan.emplace_back();
+            for (uint64_t b = j; b < std::min<uint64_t>(j + eo.merge_every, sources[0].noOfBins); ++b) plan.back().push_back(rb_bin_ref{0u, (uint32_t)b});
+        }
+    } else {
+        const std::vector<std::string> drop = split_commas(eo.drop_records);
+        std::vector<bool> seen(drop.size(), false);
+        for (uint32_t f = 0; f < sources.size(); ++f)
+            for (uint64_t b = 0; b < sources[f].noOfBins; ++b) {
+                const rb_bin_ref r{f, (uint32_t)b};
+                const std::string rec = record_of(r);
+                bool dropped = false;
+                for (size_t d = 0; d < drop.size(); ++d)
+                    if (!rec.empty() && rec == drop[d]) dropped = seen[d] = true;
+                if (!dropped) plan.push_back(std::vector<rb_bin_ref>{r});
+            }
+        for (size_t d = 0; d < drop.size(); ++d)
+            if (!seen[d]) throw std::runtime_error("--drop-records: no bin of record " + drop[d]);
+        if (drop.empty()) throw std::runtime_error("--drop-records: no record id given");
+        if (plan.empty()) throw std::runtime_error("--drop-records: no bin is left");
+    }
+    uint64_t n_refs = 0;
+    for (const auto& l : plan) n_refs += l.size();
+    interleave::IBF result{};
+    result.assemble(sources, plan);
+    const double kernel_s = rb_assemble_last_seconds();
+    try {
+        result.getFilter().store(eo.output);
+    } catch (const interleave::IBFBuildException& e) {
+        throw std::runtime_error("Could not store IBF to " + eo.output + ": " + e.what());
+    }
+    std::filesystem::path map_out(eo.output);
+    map_out.replace_extension("bins.tsv");
+    if (!maps.empty()) {
+        std::ofstream out(map_out);
+        if (!out) throw std::runtime_error("Unable to open the file: " + map_out.string());
+        write_bin_map_head(out);
+        for (size_t j = 0; j < plan.size(); ++j) {
+            if (plan[j].empty()) continue;
+            std::vector<std::string> ids;
+            uint64_t lo = UINT64_MAX, hi = 0;
+            bool bounds = true;
+            for (const rb_bin_ref& r : plan[j]) {
+                const std::string rec = record_of(r);
+                if (std::find(ids.begin(), ids.end(), rec) == ids.end()) ids.push_back(rec);
+                const std::string& row = maps[r.filter].size() > r.bin ? maps[r.filter][r.bin] : std::string();
+                const size_t a = row.find('\t'), b = a == std::string::npos ? a : row.find('\t', a + 1);
+                if (b == std::string::npos || b + 1 >= row.size() || a + 1 == b) { bounds = false; continue; }
+                lo = std::min<uint64_t>(lo, std::stoull(row.substr(a + 1, b - a - 1)));
+                hi = std::max<uint64_t>(hi, std::stoull(row.substr(b + 1)));
+            }
+            out << j << '\t';
+            for (size_t i = 0; i < ids.size(); ++i) out << (i ? "," : "") << ids[i];
+            if (ids.size() == 1 && bounds) out << '\t' << lo << '\t' << hi << '\n';
+            else out << "\t\t\n";
+        }
+        out.close();
+        if (!out) throw std::runtime_error("short write to " + map_out.string());
+    }
+    std::cout << "EDIT_IBF sources=" << sources.size() << " bins_in=" << bins_in << " bins_out=" << plan.size() << " refs=" << n_refs
+              << " kernel_seconds=" << kernel_s << " output=" << eo.output << std::endl;
+    if (with_stats) return filter_stats(result, eo.output, maps.empty() ? std::string() : map_out.string(), error_rate);
+    return 0;
 }
 
 // buildIBF, src/main/ibfbuild.hpp:21-59
@@ -1010,6 +1195,7 @@ int main(int argc, char const* argv[])
     uint64_t verify_fragment = 100000;  // [IBF] fragment_size default (configReader.cpp)
     std::string stats_path;
     double stats_error_rate = 0.1;  // [IBF] exp_seq_error_rate default (configReader.cpp); --error-rate
+    EditOptions edit;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--devices") && i + 1 < argc) {  // e.g. --devices 0,1,2,3,4,5,6,7
             devices.clear();
@@ -1049,6 +1235,17 @@ int main(int argc, char const* argv[])
             ++i;
         }
         else if (!std::strcmp(argv[i], "--write-bin-map")) g_write_bin_map = true;
+        else if (!std::strcmp(argv[i], "--edit-ibf") && i + 1 < argc) edit.input = argv[++i];
+        else if (!std::strcmp(argv[i], "--with") && i + 1 < argc) edit.with.push_back(argv[++i]);
+        else if (!std::strcmp(argv[i], "--output") && i + 1 < argc) edit.output = argv[++i];
+        else if (!std::strcmp(argv[i], "--plan") && i + 1 < argc) edit.plan_path = argv[++i];
+        else if (!std::strcmp(argv[i], "--drop-records") && i + 1 < argc) edit.drop_records = argv[++i];
+        else if (!std::strcmp(argv[i], "--merge-every") && i + 1 < argc) {
+            char* end = nullptr;
+            edit.merge_every = std::strtoull(argv[++i], &end, 10);
+            edit.merge_given = true;
+            if (*end != '\0' || argv[i][0] == '-') { std::cerr << "ERROR: --merge-every N" << std::endl; return 1; }
+        }
         else if (!std::strcmp(argv[i], "--filter-stats")) {  // with a file: the stand-alone report; bare (usage build): for every filter built
             g_filter_stats = true;
             if (i + 1 < argc && argv[i + 1][0] != '-') stats_path = argv[++i];
@@ -1104,7 +1301,13 @@ int main(int argc, char const* argv[])
                          "                                    before another flag: a bare word after it is taken as a file; a build's exit code stays 0 whatever the bins hold)\n"
                          "readbouncer_amd --verify-ibf <file.ibf> --reference <file.fasta> [--fragment-size N]\n"
                          "readbouncer_amd --filter-stats <file.ibf> [--bin-map <name>.bins.tsv] [--max-fp 0.01] [--chunk-length 360] [--error-rate 0.1]\n"
-                         "                  bits, load, false-positive rate and estimated k-mers per bin -> <name>.binstats.tsv; exit code 3 when a bin is over --max-fp" << std::endl;
+                         "                  bits, load, false-positive rate and estimated k-mers per bin -> <name>.binstats.tsv; exit code 3 when a bin is over --max-fp\n"
+                         "readbouncer_amd --edit-ibf <a.ibf> [--with <b.ibf> ...] --output <out.ibf> (--plan <plan.tsv> | --merge-every N | --drop-records id[,id...])\n"
+                         "                  [--bin-map <a.bins.tsv>[,<b.bins.tsv>...]] [--filter-stats]\n"
+                         "                  a new filter whose bins are ORs of bins of the loaded ones, in HBM, without the FASTA; prints one EDIT_IBF line\n"
+                         "                  --plan: rows out_bin<TAB>filter<TAB>bin (filter 0 = --edit-ibf, the --with files follow), # comments, `# bins=N` fixes the bin count\n"
+                         "                  --merge-every N: out bin j = bins [jN, jN+N) of one filter; --drop-records (needs --bin-map): every bin of the other records, in order\n"
+                         "                  --bin-map: also writes <out>.bins.tsv; --filter-stats: the report of the assembled table while it is in HBM (exit code 3)" << std::endl;
             return 0;
         }
     }
@@ -1112,6 +1315,19 @@ int main(int argc, char const* argv[])
         if (verify_ref.empty()) { std::cerr << "ERROR: --verify-ibf <file.ibf> needs --reference <file.fasta> [--fragment-size N]" << std::endl; return 1; }
         try {
             return verify_ibf(verify_path, verify_ref, verify_fragment);
+        } catch (const std::exception& e) {
+            std::cerr << "ERROR: " << e.what() << std::endl;
+            return 1;
+        }
+    }
+    if (edit.input.empty() && (!edit.with.empty() || !edit.output.empty() || !edit.plan_path.empty() || edit.merge_given || !edit.drop_records.empty())) {
+        std::cerr << "ERROR: --with, --output, --plan, --merge-every and --drop-records belong to --edit-ibf <a.ibf>" << std::endl;
+        return 1;
+    }
+    if (!edit.input.empty()) {
+        try {
+            if (!stats_path.empty()) throw std::runtime_error("--edit-ibf: give --filter-stats without a file (last, or before another flag)");
+            return edit_ibf(edit, opt.bin_maps, devices[0], g_filter_stats, stats_error_rate);
         } catch (const std::exception& e) {
             std::cerr << "ERROR: " << e.what() << std::endl;
             return 1;
