@@ -234,6 +234,41 @@ RB_API int rb_engine_set_early_decision(rb_engine *e, int enabled);
  * runs, tests).  Results are identical. */
 RB_API int rb_engine_set_bound_pruning(rb_engine *e, int enabled);
 
+/* Refinements of bound pruning, all on by default; they change which gathers are skipped, never a result.  Bit 0 of `mask`: the
+ * bound is checked after every eight k-mers instead of after every 64 (behind a scalar gate that opens once the best count so far
+ * reaches the k-mers still to come).  Bit 1: both strands are counted for their first 64 k-mers, the one with the larger maximum so
+ * far is finished first (a tie: forward) and the other continues against that maximum -- a read given as its reverse complement no
+ * longer counts its forward strand in full against nothing.  Bit 2 (needs bit 1): before the second strand is continued, its remaining
+ * k-mers are gathered for the FIRST hash only, on top of its 64-k-mer counts -- a k-mer counts for a bin only where all hashes have
+ * the bit, so this is an upper bound at a third of the lines; if its maximum does not pass the first strand's maximum the strand is
+ * done, otherwise it is counted in full.  Attempted where the first strand's maximum makes it promising (rb_engine_set_cert_load);
+ * never in a launch that several filters share (fused micro-batches).
+ * 0 = the bound as rb_engine_set_bound_pruning alone gives it; ignored while bound pruning is off.  Applies to the plain count kernel's builds that take the bound (wide filters, throughput form, no early
+ * decision). */
+RB_API int rb_engine_set_prune_parts(rb_engine *e, uint32_t mask);
+
+/* When the certificate of rb_engine_set_prune_parts (bit 2) is attempted for filter `filter_index` (deplete filters first, as in
+ * rb_engine_plan): when the first strand's maximum is at least the other strand's 64-k-mer maximum + ceil(d rem + 4.5 sqrt(d (1 - d) rem)),
+ * rem = the k-mers behind the first 64 and d = `load`, a bit load (set bits / blocks of a bin).  load < 0 (the default): d is the
+ * load of the filter's FULLEST bin -- an attempt fails on the one bin that passes the allowance, so it has to cover every bin --
+ * measured with the occupancy pass (rb_dibf_bin_occupancy_device, into memory the engine owns) by the first call that can attempt
+ * a certificate on the filter, and again after its bits have changed; a call whose stream is being captured does not measure and
+ * goes without the certificate.  0: always attempt; >= 1: never.  The rule only picks the attempts: results never depend on it. */
+RB_API int rb_engine_set_cert_load(rb_engine *e, size_t filter_index, double load);
+
+/* Measurement and test aid, NULL by default: device memory into which every wave of the plain count kernel (throughput form) writes one
+ * 8-byte record when it has finished its (read, column slice) -- bit 0: the strand finished first (0 forward, 1 reverse); bit 1: both
+ * strands were probed and the lead chosen; bit 2: a certificate was attempted for the other strand; bit 3: it held; bit 15: always set; bits 16-31 and 32-47: the k-mer position at which the gathers of the
+ * forward and of the reverse strand ended (the number of k-mers: counted to the end; less: no lane could reach the maximum any more,
+ * or the strand was not continued behind its 64-k-mer probe; 0: not counted).  Records lie filter after filter in engine order,
+ * within a filter [read][column slice] (rb_engine_plan names the slices); a filter that the call does not launch on its own takes NO
+ * room in that order -- one served by a merged table of several narrow filters, and, on a column-sharded engine, one of which this
+ * rank holds no column; the caller sizes and zeroes the memory and keeps it alive
+ * while set.  Calls of other kernel forms write nothing, and neither do micro-batches in which several filters of one kernel geometry
+ * share a launch (batches up to rb_engine_set_split_threshold on an engine with several filters): a fused launch writes no record and
+ * never attempts the certificate of rb_engine_set_prune_parts. */
+RB_API int rb_engine_set_prune_trace(rb_engine *e, void *d_trace);
+
 /* How the eight XCDs walk the slices of a phased table (each has an L2 of its own, so each reloads every slice): bit 0 of `mode` -- at
  * any time every XCD works on a different slice (slice = (window + XCD number) mod slices); bit 1 -- the XCDs' windows start an eighth
  * of a window apart, so that they refill their L2s one after the other instead of all in the same instant.  0 (default): one clock, one

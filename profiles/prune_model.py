@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""CPU model of the plain count kernel's fabric lines per read under bound pruning (rb_kernels.hip, count_strand), numpy only.
+
+The filter is config 3's: 8192 bins = 64 lanes of 128 bins (16 bytes) = 8 lines of 128 bytes per block, three hashes, random fill at
+rbspec::synth_word's bit density (55/256 per bit).  A read is 360 bp = 348 13-mers.  Read kinds follow synth.make_reads: negatives
+(uniform), positives at 10 % nominal substitutions (a quarter restore the base: 7.5 % effective), a tenth of the positives at
+19-23 % nominal, every second positive given as its reverse complement.  Per k-mer and bin a chance hit is Bernoulli(d) for hash 0
+and Bernoulli(d^2) more for the other two; a planted k-mer (no error in its 13 bases) hits its bin on its strand.
+
+What is counted: per k-mer step, h (3, or 1 in a certificate pass) times the 128-byte lines that still have a live lane.  A lane is
+live while one of its bins has count > M - rem; M is the best count the wave holds (fresh at a tile boundary, stale in between).
+Dead lanes read block 0, which never leaves the cache.
+
+States: no pruning; today (checks at 64-k-mer tile boundaries, forward strand first); and the combinations of
+  part 1  a check after every 8 k-mers (M stale since the tile boundary),
+  part 2  both strands probed for 64 k-mers, the one with the larger probe maximum finished first (tie: forward),
+  part 3  the trailing strand certified from hash 0 alone when the leader's maximum is at least
+          probe maximum + ceil(d rem + z sqrt(d (1 - d) rem)), z = 4.5.  (The kernel also prunes inside that pass and leaves it at the
+          first counter above the leader's maximum; the model gathers it with the lanes alive on entry, so it reads a little high there.)
+
+  python3 profiles/prune_model.py [reads per kind, default 500] [seed, default 1]
+"""
+import math
+import sys
+
+import numpy as np
+
+N, TILE, LANES, BPL, LPL, H = 348, 64, 64, 128, 8, 3  # k-mers, tile, lanes, bins per lane, lanes per line, hashes
+D = 55.0 / 256.0
+Z = 4.5
+MEASURED_TODAY = 15698.1  # TCC_EA0_RDREQ per read, profiles/bound_pruning/bench_ab.txt
+
+
+def strand_counts(rng, planted):
+    """per-bin cumulative counts of one strand, all hashes and hash 0 alone: two arrays [N + 1][bins]; planted = bool[N] or None"""
+    h0 = rng.random((N, LANES * BPL), dtype=np.float32) < D
+    full = h0 & (rng.random((N, LANES * BPL), dtype=np.float32) < D * D)
+    if planted is not None:
+        b = int(rng.integers(0, LANES * BPL))
+        full[:, b] |= planted
+        h0[:, b] |= planted
+    out = []
+    for hits in (full, h0):
+        c = np.zeros((N + 1, LANES * BPL), dtype=np.int32)
+        np.cumsum(hits, axis=0, out=c[1:])
+        out.append(c)
+    return out  # per-bin cumulative counts (full, hash 0)
+
+
+def lines_of(live):
+    return int(live.reshape(LANES // LPL, LPL).any(axis=1).sum())
+
+
+def run_strand(c, start, bb, sub):
+    """full pass over k-mers [start, N) with bound bb; returns (lines, held maximum).  c = per-bin cumulative counts"""
+    live = np.ones(LANES, dtype=bool)
+    held = np.zeros(LANES * BPL, dtype=np.int32)  # counters of dead lanes, frozen
+    lanes_of_bin = np.repeat(np.arange(LANES), BPL)
+    lines, pos, m_stale = 0, start, bb
+
+    def check(q, m):
+        nonlocal live, held
+        rem = N - q
+        if m < rem:
+            return
+        cur = c[q]
+        alive_bin = cur > (m - rem)
+        lane_alive = alive_bin.reshape(LANES, BPL).any(axis=1)
+        dying = live & ~lane_alive
+        if dying.any():
+            sel = dying[lanes_of_bin]
+            held[sel] = cur[sel]
+            live &= lane_alive
+
+    def held_max(q):
+        cur = np.where(live[lanes_of_bin], c[q], held)
+        return int(cur.max())
+
+    if start > 0:  # entry check at the probe's end
+        m_stale = max(bb, held_max(start))
+        check(start, m_stale)
+    while pos < N and live.any():
+        nxt = min(N, (pos // TILE + 1) * TILE)
+        if sub:
+            nxt = min(nxt, pos + 8)
+        lines += H * lines_of(live) * (nxt - pos)
+        pos = nxt
+        if pos >= N:
+            break
+        if pos % TILE == 0:
+            m_stale = max(bb, held_max(pos))
+            check(pos, m_stale)
+        else:
+            check(pos, m_stale)
+    return lines, held_max(min(pos, N))
+
+
+def allowance(rem):
+    return math.ceil(D * rem + Z * math.sqrt(D * (1 - D) * rem))
+
+
+def read_lines(rng, kind):
+    """lines per read under every state for one read of `kind` = (planted strand or None, effective error rate)"""
+    strand, e = kind
+    planted = None
+    if strand is not None:
+        err = rng.random(N + 12) < e
+        bad = np.convolve(err.astype(np.int32), np.ones(13, dtype=np.int32), mode="valid") > 0
+        planted = ~bad
+    cs = [strand_counts(rng, planted if strand == s else None) for s in (0, 1)]
+    res = {"none": 2 * N * H * (LANES // LPL)}
+    for sub in (0, 1):  # forward first (today, and part 1 alone)
+        l0, m0 = run_strand(cs[0][0], 0, 0, sub)
+        l1, m1 = (0, 0) if m0 >= N else run_strand(cs[1][0], 0, m0, sub)
+        res["today" if not sub else "1"] = l0 + l1
+        assert max(m0, m1) == max(int(cs[0][0][N].max()), int(cs[1][0][N].max()))
+    probe = 2 * TILE * H * (LANES // LPL)
+    p = [int(cs[s][0][TILE].max()) for s in (0, 1)]
+    lead = 1 if p[1] > p[0] else 0
+    trail = lead ^ 1
+    for sub in (0, 1):
+        ll, m = run_strand(cs[lead][0], TILE, 0, sub)
+        lt, mt = (0, 0) if m >= N else run_strand(cs[trail][0], TILE, m, sub)
+        res["2" if not sub else "12"] = probe + ll + lt
+        assert max(m, mt) == max(int(cs[0][0][N].max()), int(cs[1][0][N].max()))
+        # part 3: hash 0 alone over [TILE, N) on top of the trailing probe's counters
+        rem = N - TILE
+        tot = probe + ll + lt
+        tried = held = False
+        if m < N and m >= p[trail] + allowance(rem):
+            tried = True
+            ub = cs[trail][0][TILE] + (cs[trail][1][N] - cs[trail][1][TILE])
+            # lanes that the entry check kills are not gathered in the certificate pass either
+            live = (cs[trail][0][TILE] > (m - rem)).reshape(LANES, BPL).any(axis=1) if m >= rem else np.ones(LANES, dtype=bool)
+            cert = lines_of(live) * rem
+            ub_max = int(np.where(np.repeat(live, BPL), ub, 0).max())
+            held = ub_max <= m
+            tot = probe + ll + cert + (0 if held else lt)
+        res["23" if not sub else "123"] = tot
+        res["cert_tried"], res["cert_held"] = int(tried), int(held)
+    return res
+
+
+def main():
+    per_kind = int(sys.argv[1]) if len(sys.argv) > 1 else 500
+    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    rng = np.random.default_rng(seed)
+    kinds = {"neg": (None, 0.0), "pos_fwd": (0, 0.075), "pos_rev": (1, 0.075), "near_fwd": (0, None), "near_rev": (1, None)}
+    means = {}
+    for name, (strand, e) in kinds.items():
+        acc = {}
+        for _ in range(per_kind):
+            ee = e if e is not None else 0.75 * rng.uniform(0.19, 0.23)
+            for k, v in read_lines(rng, (strand, ee)).items():
+                acc[k] = acc.get(k, 0) + v
+        means[name] = {k: v / per_kind for k, v in acc.items()}
+        print(name, {k: round(v, 1) for k, v in means[name].items()}, flush=True)
+    pos = {k: 0.45 * (means["pos_fwd"][k] + means["pos_rev"][k]) + 0.05 * (means["near_fwd"][k] + means["near_rev"][k]) for k in means["neg"]}
+    mixes = {"bench": {k: 0.5 * means["neg"][k] + 0.5 * pos[k] for k in pos}, "positive": pos, "negative": means["neg"]}
+    print("\nfabric lines per read (model, %d reads per kind, seed %d)" % (per_kind, seed))
+    states = ("none", "today", "1", "2", "12", "23", "123")
+    print("%-10s" % "mix" + "".join("%10s" % ("parts " + s if s[0].isdigit() else s) for s in states) + "  cert tried/held")
+    for mix, v in mixes.items():
+        print("%-10s" % mix + "".join("%10.0f" % v[s] for s in states) + "  %.3f / %.3f" % (v["cert_tried"], v["cert_held"]))
+    today = mixes["bench"]["today"]
+    off = today / MEASURED_TODAY - 1.0
+    print("\ntoday's state on the bench mix: model %.0f, measured %.1f (%+.2f %%)" % (today, MEASURED_TODAY, 100 * off))
+    if abs(off) > 0.002:
+        print("MODEL NOT CALIBRATED: today's state is more than 0.2 % off the measurement; do not quote the predictions")
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -215,6 +215,9 @@ SIGNATURES = {
     "rb_engine_set_phase_xcd_skew": (_int, [_vp, _u32]),
     "rb_engine_set_early_decision": (_int, [_vp, _int]),
     "rb_engine_set_bound_pruning": (_int, [_vp, _int]),
+    "rb_engine_set_prune_parts": (_int, [_vp, C.c_uint32]),
+    "rb_engine_set_prune_trace": (_int, [_vp, _vp]),
+    "rb_engine_set_cert_load": (_int, [_vp, C.c_size_t, C.c_double]),
     "rb_engine_set_phased": (_int, [_vp, _u64, _u64, _u32, _u32, _u32]),
     "rb_engine_set_timing": (_int, [_vp, _int]),
     "rb_engine_kernel_time": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_u64)]),
@@ -753,6 +756,19 @@ class Engine:
     def set_bound_pruning(self, on):
         """plain count kernel: skip the gathers of bins that can no longer reach the read's maximum (default on; results identical)"""
         _check(lib().rb_engine_set_bound_pruning(self.h, int(on)), "rb_engine_set_bound_pruning")
+
+    def set_prune_parts(self, mask):
+        """refinements of bound pruning: bit 0 checks after every eight k-mers, bit 1 the stronger strand first, bit 2 the other strand
+        certified from the first hash alone (default 7; results identical)"""
+        _check(lib().rb_engine_set_prune_parts(self.h, int(mask)), "rb_engine_set_prune_parts")
+
+    def set_cert_load(self, filter_index, load):
+        """bit load (of the fullest bin) the certificate's attempt rule assumes for a filter: < 0 measure (default), 0 always attempt, >= 1 never"""
+        _check(lib().rb_engine_set_cert_load(self.h, filter_index, float(load)), "rb_engine_set_cert_load")
+
+    def set_prune_trace(self, device_ptr):
+        """device memory for one 8-byte record per (filter, read, column slice) of the plain count kernel's waves, or 0 / None: none"""
+        _check(lib().rb_engine_set_prune_trace(self.h, C.c_void_p(device_ptr or None)), "rb_engine_set_prune_trace")
 
     def set_phase_xcd_skew(self, mode):
         """bit 0: every XCD on a different slice at any time; bit 1: the XCDs' windows start an eighth of a window apart"""

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -337,6 +338,19 @@ struct rb_engine {
     // rb_engine_set_bound_pruning (on by default): the plain count kernel stops gathering for bins that can no longer reach the read's
     // maximum (rb_kernels.hip, count_strand); outputs are identical either way
     bool bound_pruning = true;
+    // rb_engine_set_prune_parts: its refinements (bit 0: checks after every eight k-mers; bit 1: both strands probed, the stronger one
+    // finished first), and rb_engine_set_prune_trace: where the waves of the plain count kernel say which path they took (nullptr: nowhere)
+    // bit 2: the trailing strand certified from hash 0 alone where the load of the filter's fullest bin says that is promising -- rb_engine_set_cert_load:
+    // the load per filter index (< 0 or none: measured with the occupancy pass when the filter is first planned, and again when its bits change)
+    uint32_t prune_parts = 7;
+    uint64_t *prune_trace = nullptr;
+    struct CertLoad {
+        double set = -1.0;       // what the caller gave (< 0: measure)
+        double measured = -1.0;  // load of the filter's fullest bin at `version` (< 0: not measured yet)
+        uint64_t version = 0;
+    };
+    std::vector<CertLoad> cert_loads;  // by filter index
+    DevBuf d_occupancy;                // ... where the occupancy pass counts for it
     bool multi_one_word = true;  // ... for one-word blocks of up to 2^22 - 2 of them (32 MiB) (RB_MULTI_ONE_WORD=0: the register builds)
     bool multi_wide = true;      // ... and for blocks of three and four words (RB_MULTI_WIDE=0: those keep the register builds)
     bool multi_wide_six = true;  // ... six tiles in one round for their reads of 257-384 k-mers (RB_MULTI_WIDE_SIX=0: rounds of three tiles)
@@ -1162,6 +1176,7 @@ void rb_engine_destroy(rb_engine *e)
     if (e->copy_stream) { (void)hipStreamSynchronize(e->copy_stream); (void)hipStreamDestroy(e->copy_stream); }
     for (hipEvent_t ev : e->copy_ev) (void)hipEventDestroy(ev);
     for (DevBuf &b : e->d_parts) b.release();
+    e->d_occupancy.release();
     for (MergedGroup *g : e->merged) delete g;
     for (auto &t : e->thr) {
         if (t.d) (void)hipFree(t.d);
@@ -1380,6 +1395,72 @@ int rb_engine_set_bound_pruning(rb_engine *e, int enabled)
     if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
     std::lock_guard<std::mutex> lock(e->mu);
     e->bound_pruning = enabled != 0;
+    return RB_OK;
+}
+
+int rb_engine_set_prune_parts(rb_engine *e, uint32_t mask)
+{
+    if (!e || mask > 7) return rb::fail(RB_ERR_INVALID_ARG, "mask 0..7 (bit 0: sub-tile checks, bit 1: strand lead, bit 2: certificate)");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->prune_parts = mask;
+    return RB_OK;
+}
+
+int rb_engine_set_cert_load(rb_engine *e, size_t filter_index, double load)
+{
+    if (!e || load != load) return rb::fail(RB_ERR_INVALID_ARG, "null engine, or not a number");
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (filter_index >= e->filters.size()) return rb::fail(RB_ERR_INVALID_ARG, "no such filter");
+    if (e->cert_loads.size() < e->filters.size()) e->cert_loads.resize(e->filters.size());
+    e->cert_loads[filter_index].set = load;
+    return RB_OK;
+}
+
+// The certificate's allowance for filter fi (kernel: cert_d * rem + cert_c * sqrt(rem)); *on = false: no attempt in this call.
+// Called only for launches that can attempt one (the plain kernel, unfused).  d is the load of the filter's FULLEST bin: the
+// certificate fails on the one bin that passes the allowance, so the allowance has to cover every bin (a filter whose bins are
+// evenly loaded has its mean there; one with a few overloaded bins would fail attempt after attempt against the mean).  Measured
+// with the occupancy pass into the engine's own buffer when the filter is first used and again after its bits have changed: about
+// a millisecond on 8 GiB plus one synchronising copy of n_bins words; never while `st` is being captured -- such a call goes
+// without the certificate until an uncaptured one has measured.
+static int cert_allowance(rb_engine *e, size_t fi, hipStream_t st, float *cert_d, float *cert_c, bool *on)
+{
+    constexpr double kCertZ = 4.5;  // the 8192-bin tail of the hash-0 counts sits near 3.8 sigma
+    if (e->cert_loads.size() < e->filters.size()) e->cert_loads.resize(e->filters.size());
+    rb_engine::CertLoad &c = e->cert_loads[fi];
+    double d = c.set;
+    if (d < 0.0) {
+        const rb_dibf *f = e->filters[fi];
+        const uint64_t v = f->version.load();
+        if (c.measured < 0.0 || c.version != v) {
+            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+            if (st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+                *on = false;
+                return RB_OK;
+            }
+            std::vector<uint64_t> bits(std::max<uint64_t>(f->geo.n_bins, 1));
+            int rc = e->d_occupancy.ensure(bits.size() * 8);
+            if (rc != RB_OK) return rc;
+            if ((rc = rb_dibf_bin_occupancy_device(f, e->d_occupancy.p, nullptr)) != RB_OK) return rc;  // (a stream of its own, synchronised)
+            RB_HIP(hipMemcpy(bits.data(), e->d_occupancy.p, f->geo.n_bins * 8, hipMemcpyDeviceToHost));
+            uint64_t fullest = 0;
+            for (uint64_t b = 0; b < f->geo.n_bins; ++b) fullest = std::max(fullest, bits[b]);
+            c.measured = f->geo.n_blocks ? (double)fullest / (double)f->geo.n_blocks : 1.0;
+            c.version = v;
+        }
+        d = c.measured;
+    }
+    *on = d < 1.0;
+    *cert_d = (float)d;
+    *cert_c = (float)(kCertZ * std::sqrt(std::max(0.0, d * (1.0 - d))));
+    return RB_OK;
+}
+
+int rb_engine_set_prune_trace(rb_engine *e, void *d_trace)
+{
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->prune_trace = (uint64_t *)d_trace;
     return RB_OK;
 }
 
@@ -2186,6 +2267,7 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
     size_t n_big = 0, n_small = 0;
     for (const rb_dibf *f : e->filters) (l2_sensitive(f) ? n_small : n_big) += 1;
     size_t next_aux = 0;
+    size_t trace_off = 0;
     bool big_on_main = false;
     for (size_t fi = 0; fi < nf; ++fi) {
         if (use_merged && e->merged_of[fi] >= 0) continue;  // counted by its group's launch above
@@ -2215,6 +2297,19 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
         }
         if (a.n_slices != 1 || a.split_waves < 2) fold_ok = false;
         a.bound_prune = e->bound_pruning ? 1 : 0;
+        a.prune_parts = (int)e->prune_parts;
+        // (only where the launch can attempt a certificate: the plain kernel on its own -- not the latency form, not the phased forms,
+        // not a micro-batch that is fused with other filters below)
+        const bool fuses = a.n_slices == 1 && !fan_out && nf > 1 && n_reads <= e->split_threshold;
+        if (a.bound_prune && (a.prune_parts & 4) && a.lg == 6 && a.split_waves < 2 && a.phase.n_slices == 0 && !fuses) {
+            bool cert_on = false;
+            if ((rc = cert_allowance(e, fi, fs, &a.cert_d, &a.cert_c, &cert_on)) != RB_OK) return rc;
+            if (!cert_on) a.prune_parts &= ~4;
+        }
+        if (e->prune_trace) {  // records lie filter after filter, [read][slice] within a filter
+            a.prune_trace = e->prune_trace + trace_off;
+            trace_off += (size_t)n_reads * a.n_slices;
+        }
         // (a target filter's count also picks best_target -- the strictly-greater argmax of IBFClassify.cpp:262-273 -- so target filters stop
         // early only when the caller does not ask for best_target; a deplete filter's count is seen through the two predicates alone)
         if (early_thr && a.split_waves < 2 && (fi < e->nd || !d_best_target)) {

@@ -485,13 +485,56 @@ __device__ __forceinline__ void phased_gather_x4(uint64_t (&x0)[N], uint64_t (&x
 // is a bit-sliced compare of the planes against that constant, MSB first, with a scalar branch per plane.  The caller passes
 // kNoBound where counters can wrap (n >= 2^NP: the 16-plane builds reproduce the reference's uint16_t wrap, and the bound is false
 // there) and where the engine switched pruning off (rb_engine_set_bound_pruning).
+//
+// Three refinements of the bound (ibf_count_max_kernel's `prune` word, rb_engine_set_prune_parts), and why the maximum stays exact:
+//   * SUB-TILE CHECKS (`sub_checks`): the same compare after every eight-step block of a tile, behind a scalar gate, with rem taken at that
+//     point and M_stale = the M of the last tile boundary.  It is the argument above with a smaller rem and an M that is never above the
+//     true one (counters never shrink): a smaller M only kills later.  For a negative read the gate opens in the last ~13 k-mers only.
+//   * STRAND LEAD (the caller's doing: `mt_first` > 0, `mt_end`): both strands are counted for their first tile, the one with the larger
+//     probe maximum is finished first and the other continues from k-mer 64 against the leader's maximum.  The output is the maximum
+//     over the strands and the strands' counters are separate, so the order is free.  A strand that continues (mt_first > 0) is checked
+//     on entry like at a tile boundary: its counters hold the first mt_first k-mers.
+//   * CERTIFICATE (the caller again; H == 1, EARLY, stop_at = M + 1, bound_best = M): a k-mer counts for a bin only where ALL h blocks
+//     have the bit, so the count of hash-0 bits alone is an upper bound of the count.  On top of the trailing strand's probe counters
+//     the rest of the strand is gathered for hash 0 only -- a third of the lines; for every bin, probe count + hash-0 hits of the rest
+//     >= true count, so if the maximum of that stays <= M (the leader's maximum) the strand's maximum is <= M and the read's result
+//     is M.  The bound prunes this pass too (an upper bound that cannot pass M any more need not be followed); the pass is left as
+//     failed the moment a counter exceeds M, and the strand is then counted in full from its probe counters.
+//   * `stop_pos` reports the k-mer position at which this call's gathers ended (n, or where the whole wave was dead).
 constexpr uint32_t kNoBound = 0xFFFFFFFFu;
+
+// bit-sliced "some valid bin of this lane has c > t", MSB plane first (t wave-uniform: one scalar branch per plane): gt = bins already
+// above t, eq = bins equal to t's leading bits so far
+template <int NP, int WPL>
+__device__ __forceinline__ bool bound_alive(const Planes<NP> (&pl)[WPL], const uint64_t (&valid)[WPL], uint32_t t)
+{
+    bool alive = false;
+    if (t < (1u << NP) - 1u) {
+#pragma unroll
+        for (int w = 0; w < WPL; ++w) {
+            uint64_t gt = 0, eq = valid[w];
+#pragma unroll
+            for (int i = NP - 1; i >= 0; --i) {
+                if ((t >> i) & 1u) {  // scalar branch
+                    eq &= pl[w].p[i];
+                } else {
+                    gt |= eq & pl[w].p[i];
+                    eq &= ~pl[w].p[i];
+                }
+            }
+            alive |= gt != 0ULL;
+        }
+    }
+    return alive;
+}
+
 template <int LG, int WPL, int NP, int H, bool NT, bool PH = false, bool EARLY = false>
 __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev &f, const LaneCols<WPL> &lc,
                                              const BaseSrc &seq, uint32_t len, uint32_t n, int strand,
                                              uint32_t mt_first, uint32_t mt_step, int blk_first, int blk_end,
                                              uint8_t *stage, int lane, const PhaseCfg ph = PhaseCfg{0, 0, 0, 0, 0}, uint32_t stop_at = 0xFFFFFFFFu,
-                                             uint32_t bound_best = kNoBound)
+                                             uint32_t bound_best = kNoBound, uint32_t mt_end = 0xFFFFFFFFu, bool sub_checks = false,
+                                             uint32_t *stop_pos = nullptr)
 {
     using T = TileShape<LG>;
     constexpr int NG = T::NG, SPT = T::SPT, J = T::J, ITEMS = T::ITEMS;
@@ -502,8 +545,26 @@ __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev
     const uint32_t S = f.stride;  // words between consecutive blocks in HBM (>= bin_width, see rb_engine.hip)
     const uint32_t k = f.k;
     bool lane_on = lc.colok;  // lane gathers (BOUND: and is not dead yet)
+    const uint32_t n_end = min(n, mt_end);  // k-mers this call counts up to
+    uint32_t m_stale = bound_best;          // BOUND: the M of the last boundary check (scalar)
+    uint32_t stopped = n_end;               // where the gathers ended: n_end, or the check that found the whole wave dead
+    if constexpr (BOUND) {
+        // a strand that continues behind its probe tile: the check of the tile boundary it starts at
+        if (bound_best != kNoBound && mt_first > 0 && mt_first < n_end) {
+            const uint32_t M = __builtin_amdgcn_readfirstlane(max(planes_max<NP, WPL>(pl, lc.valid), bound_best));
+            const uint32_t rem = __builtin_amdgcn_readfirstlane(n - mt_first);
+            m_stale = M;
+            if (M >= rem) {
+                lane_on = lane_on && bound_alive<NP, WPL>(pl, lc.valid, M - rem);
+                if (__ballot(lane_on) == 0ULL) {
+                    if (stop_pos) *stop_pos = mt_first;
+                    return false;  // wave-uniform (NG == 1: no butterfly below)
+                }
+            }
+        }
+    }
 
-    for (uint32_t mt = mt_first; mt < n; mt += mt_step) {
+    for (uint32_t mt = mt_first; mt < n_end; mt += mt_step) {
         // ---- stage the bases of this macro tile as Dna5 ordinals ((Dna5String) conversion)
         const uint32_t wlen = min((uint32_t)(ITEMS + k - 1), len - mt);
         __builtin_amdgcn_wave_barrier();
@@ -576,7 +637,8 @@ __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev
                 }
                 phased_gather<8, H, NT, RB_GATHER_BG>(x[0], bn, f.words, slice_shift, ph);
             } else if constexpr (H > 0) {
-                constexpr int HALF = (WPL == 1) ? RB_HALF1 : RB_HALF2;  // steps per load batch
+                // steps per load batch (the one-hash pass of the certificate, H == 1, has a third of the loads per step: eight steps at once)
+                constexpr int HALF = (WPL == 1 || H == 1) ? RB_HALF1 : RB_HALF2;
 #pragma unroll
                 for (int half = 0; half < 8 / HALF; ++half) {
                     uint64_t ld[HALF][H][WPL];
@@ -647,6 +709,23 @@ __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev
             }
 #pragma unroll
             for (int w = 0; w < WPL; ++w) pl[w].add8(x[w]);
+            if constexpr (BOUND) {
+                // sub-tile check (behind the batch's last use: no control flow between its loads); the tile's last block is the boundary's
+                const uint32_t donek = mt + (uint32_t)(blk + 1) * 8u;
+                if (sub_checks && bound_best != kNoBound && blk + 1 < T::STEPS / 8 && donek < n) {
+                    const uint32_t rem = __builtin_amdgcn_readfirstlane(n - donek);
+                    if (m_stale >= rem) {  // the scalar gate: below it every bin is still within reach
+                        lane_on = lane_on && bound_alive<NP, WPL>(pl, lc.valid, m_stale - rem);
+                        if (__ballot(lane_on) == 0ULL) {
+                            stopped = donek;
+                            break;  // wave-uniform
+                        }
+                    }
+                }
+            }
+        }
+        if constexpr (BOUND) {
+            if (stopped != n_end) break;
         }
         if constexpr (EARLY && !BOUND) {
             // (with several lane groups per block every group holds the counts of ITS k-mers only: a lower bound of a lower bound, still
@@ -661,28 +740,13 @@ __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev
             if (bound_best != kNoBound && done < n) {  // (after the last tile there is nothing left to skip)
                 const uint32_t M = __builtin_amdgcn_readfirstlane(max(m, bound_best));
                 const uint32_t rem = __builtin_amdgcn_readfirstlane(n - done);
+                m_stale = M;
                 if (M >= rem) {
-                    const uint32_t t = M - rem;  // a bin stays alive while its count exceeds t
-                    bool alive = false;
-                    if (t < (1u << NP) - 1u) {
-                        // bit-sliced c > t, MSB plane first: gt = bins already above t, eq = bins equal to t's leading bits so far
-#pragma unroll
-                        for (int w = 0; w < WPL; ++w) {
-                            uint64_t gt = 0, eq = lc.valid[w];
-#pragma unroll
-                            for (int i = NP - 1; i >= 0; --i) {
-                                if ((t >> i) & 1u) {  // scalar branch
-                                    eq &= pl[w].p[i];
-                                } else {
-                                    gt |= eq & pl[w].p[i];
-                                    eq &= ~pl[w].p[i];
-                                }
-                            }
-                            alive |= gt != 0ULL;
-                        }
+                    lane_on = lane_on && bound_alive<NP, WPL>(pl, lc.valid, M - rem);  // a bin stays alive while its count exceeds M - rem
+                    if (__ballot(lane_on) == 0ULL) {  // wave-uniform: the rest of this strand cannot change the maximum
+                        stopped = done;
+                        break;
                     }
-                    lane_on = lane_on && alive;
-                    if (__ballot(lane_on) == 0ULL) break;  // wave-uniform: the rest of this strand cannot change the maximum
                 }
             }
         }
@@ -696,6 +760,7 @@ __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev
             for (int w = 0; w < WPL; ++w) pl[w].add_from_lane_xor(lane, m);
         }
     }
+    if (stop_pos) *stop_pos = stopped;
     return false;
 }
 
@@ -735,17 +800,33 @@ struct EarlyCfg {
     uint32_t fi[kMaxFused];  // blockIdx.y -> filter index in the table
 };
 
+// STRAND LEAD (prune.flags, kPruneLead; plain builds with the bound, reads of more than one tile): the forward strand always going first
+// wastes the bound on reads given as reverse complements -- their forward strand is counted in full against nothing, and the strand
+// that holds the maximum then has nobody left to prune.  So both strands are PROBED for their first tile (64 k-mers), the forward
+// probe's counters wait in LDS meanwhile (after 64 k-mers only planes 0-6 can be set: kParkPlanes x WPL x 64 lanes x 8 bytes per
+// wave), the strand with the larger probe maximum LEADS (a tie: forward, so a read always takes the same path), and the other one
+// continues from k-mer 64 against the leader's maximum, its probe counters back from LDS -- after an attempt to CERTIFY it from hash 0
+// alone (count_strand) where the leader's maximum makes that promising.  The four passes are one loop around one count_strand call, so
+// the three-hash gather schedule exists once.
+constexpr int kParkPlanes = 7;
+constexpr bool plain_leads(int lg, int h, bool early) { return lg == 6 && h > 0 && !early; }
+
 template <int LG, int WPL, int NP, int H, bool NT, bool EARLY = false>
 __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu((WPL == 1 && NP == 10 && H == 3) ? RB_WAVES_PLAIN : 3, 8))) void ibf_count_max_kernel(
     FilterSet set, ReadSrc src, uint32_t n_reads, uint32_t n_slices, uint16_t *__restrict__ out_base,
-    uint32_t out_read_stride, uint32_t out_slice_stride, EarlyCfg early, uint32_t prune)
+    uint32_t out_read_stride, uint32_t out_slice_stride, EarlyCfg early, PruneCfg prune)
 {
+    constexpr bool LEADS = plain_leads(LG, H, EARLY);
+    constexpr uint32_t TILE = (uint32_t)TileShape<LG>::ITEMS;
     __shared__ uint8_t s_stage[kWavesPerBlock][kStageBytes];
+    __shared__ uint64_t s_park[LEADS ? kWavesPerBlock : 1][LEADS ? kParkPlanes * WPL : 1][64];
     const IbfDev &f = set.f[blockIdx.y];  // filters of equal kernel geometry may share a launch (micro-batches)
     const uint32_t col_begin = set.col_begin[blockIdx.y], col_end = set.col_end[blockIdx.y];
     uint16_t *__restrict__ out = out_base + set.out_offset[blockIdx.y];
     const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
+    // (scalar in the builds that carry the strand lead's state: so are the item, its read and its slice, which leaves them the registers; the
+    // other builds -- config 2's among them -- are compiled as they were)
+    const int wave = LG == 6 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x >> 6);
     // work item = (read, column slice), slice fastest: the waves of a workgroup gather neighbouring parts of the same
     // blocks at about the same time (DRAM page locality for wide filters)
     const uint64_t item = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
@@ -767,22 +848,97 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
         stop_at = max(max((uint32_t)t[0], (uint32_t)t[1]), 1u);
     }
     // bound pruning (see count_strand): on when asked for and no counter can wrap
-    const bool bound = prune && n < (1u << NP);
-    uint32_t best = 0;
-    for (int strand = 0; strand < 2; ++strand) {
+    const bool bound = (prune.flags & kPruneBound) && n < (1u << NP);
+    const bool sub = LEADS && bound && (prune.flags & kPruneSubTile);
+    const bool leads = LEADS && bound && (prune.flags & kPruneLead) && n > TILE;
+    const bool cert = leads && (prune.flags & kPruneCert);
+    // passes (all wave-uniform): without the lead 0 = forward, 1 = reverse, each whole; with it 0 / 1 = the probes, 2 = the leader
+    // from k-mer 64, 3 = the other strand from k-mer 64
+    const int n_pass = leads ? 4 : 2;
+    uint32_t best = 0, probe0 = 0, lead = 0, cert_bits = 0;  // (probe0: the forward probe's maximum, then the trailing strand's)
+    uint32_t stops = 0;  // per strand, 16 bits each: where its gathers ended (the trace)
+    Planes<NP> pl[WPL];
+#pragma unroll 1
+    for (int pass = 0; pass < n_pass; ++pass) {
+        const bool probe = leads && pass < 2;
+        const int strand = (!leads || pass < 2) ? pass : (int)(lead ^ (uint32_t)(pass & 1));
         // a strand counts at most n per bin: once the first strand's maximum has reached n the second cannot exceed it
-        if (bound && strand == 1 && best >= n) break;  // wave-uniform
-        Planes<NP> pl[WPL];
+        if (bound && (pass & 1) && !probe && best >= n) break;  // wave-uniform
+        if constexpr (LEADS) {
+            if (leads && pass == 1) {  // the forward probe waits in LDS
 #pragma unroll
-        for (int w = 0; w < WPL; ++w) pl[w].clear();
-        const bool left = count_strand<LG, WPL, NP, H, NT, false, EARLY>(pl, f, lc, seq, len, n, strand, 0u, (uint32_t)TileShape<LG>::ITEMS, 0,
+                for (int w = 0; w < WPL; ++w)
+#pragma unroll
+                    for (int i = 0; i < kParkPlanes; ++i) s_park[wave][w * kParkPlanes + i][lane] = pl[w].p[i];
+            }
+        }
+        if (!leads || pass < 2) {
+#pragma unroll
+            for (int w = 0; w < WPL; ++w) pl[w].clear();
+        }
+        if constexpr (LEADS) {
+            if (leads && pass == 3) {  // the other strand's probe comes back (its planes above 6 are zero)
+#pragma unroll
+                for (int w = 0; w < WPL; ++w) {
+                    pl[w].clear();
+#pragma unroll
+                    for (int i = 0; i < kParkPlanes; ++i) pl[w].p[i] = s_park[wave][w * kParkPlanes + i][lane];
+                }
+                // the certificate: worth a third of a strand when the leader's maximum clears the trailing probe's maximum plus the hash-0
+                // hits a bin of load d (the filter's fullest) is expected to add over the rest, z sigma up (cert_c = z sqrt(d (1 - d))).  The rule only
+                // picks the attempts; a failed one costs lines, never a result.
+                const float rem = (float)(n - TILE);
+                if (cert && (float)(best - min(best, probe0)) >= prune.cert_d * rem + prune.cert_c * __builtin_sqrtf(rem)) {
+                    cert_bits = 1u;
+                    const bool over = count_strand<LG, WPL, NP, 1, NT, false, true>(pl, f, lc, seq, len, n, strand, TILE, TILE, 0, TileShape<LG>::STEPS / 8,
+                                                                                    s_stage[wave], lane, PhaseCfg{0, 0, 0, 0, 0}, best + 1u, best,
+                                                                                    0xFFFFFFFFu, sub);
+                    if (!over && planes_max<NP, WPL>(pl, lc.valid) <= best) {  // wave-uniform
+                        cert_bits = 3u;
+                        break;
+                    }
+#pragma unroll
+                    for (int w = 0; w < WPL; ++w) {
+                        pl[w].clear();
+#pragma unroll
+                        for (int i = 0; i < kParkPlanes; ++i) pl[w].p[i] = s_park[wave][w * kParkPlanes + i][lane];
+                    }
+                }
+            }
+        }
+        uint32_t stopped = 0;
+        const bool left = count_strand<LG, WPL, NP, H, NT, false, EARLY>(pl, f, lc, seq, len, n, strand, leads && pass >= 2 ? TILE : 0u, TILE, 0,
                                                                          TileShape<LG>::STEPS / 8, s_stage[wave], lane, PhaseCfg{0, 0, 0, 0, 0}, stop_at,
-                                                                         bound ? best : kNoBound);
+                                                                         !bound || probe ? kNoBound : best,
+                                                                         probe ? TILE : 0xFFFFFFFFu, sub, &stopped);
+        stops = strand == 0 ? (stops & 0xFFFF0000u) | (stopped & 0xFFFFu) : (stops & 0xFFFFu) | (stopped << 16);
         const uint32_t m = planes_max<NP, WPL>(pl, lc.valid);
-        best = m > best ? m : best;
+        if (!probe) best = m > best ? m : best;
+        if constexpr (LEADS) {
+            if (leads && pass == 0) probe0 = m;
+            if (leads && pass == 1) {
+                lead = m > probe0 ? 1u : 0u;  // a tie: forward
+                probe0 = min(m, probe0);      // the trailing strand's probe maximum
+                if (lead == 0) {  // the registers hold the reverse probe: change places with the forward one
+#pragma unroll
+                    for (int w = 0; w < WPL; ++w)
+#pragma unroll
+                        for (int i = 0; i < kParkPlanes; ++i) {
+                            const uint64_t t = s_park[wave][w * kParkPlanes + i][lane];
+                            s_park[wave][w * kParkPlanes + i][lane] = pl[w].p[i];
+                            pl[w].p[i] = t;
+                        }
+                }
+            }
+        }
         if (EARLY && left) break;  // wave-uniform
     }
     if (lane == 0) out[(size_t)read * out_read_stride + (size_t)slice * out_slice_stride] = (uint16_t)best;
+    if (prune.trace) {  // (one scalar branch when there is none)
+        if (lane == 0)
+            prune.trace[(size_t)blockIdx.y * n_reads * n_slices + item] =
+                prune_trace_record(lead, leads, cert_bits, stops & 0xFFFFu, stops >> 16);
+    }
 }
 
 // LOCATE: the opt-in second pass (rb_locate_batch_device) that says WHERE a read matched.  One wave per (work item, column slice) as
@@ -3020,6 +3176,12 @@ static hipError_t launch_count_nt(const CountLaunch &a, hipStream_t st)
     const uint64_t items = (uint64_t)a.n_reads * a.n_slices;
     dim3 grid((uint32_t)((items + kWavesPerBlock - 1) / kWavesPerBlock), set.n);
     EarlyCfg early{};
+    PruneCfg prune{};
+    prune.flags = a.bound_prune ? (kPruneBound | ((uint32_t)a.prune_parts << 1)) : 0u;
+    prune.trace = a.n_fused == 0 ? a.prune_trace : nullptr;
+    prune.cert_d = a.cert_d;
+    prune.cert_c = a.cert_c;
+    if (a.n_fused > 0) prune.flags &= ~kPruneCert;  // (the allowance is one filter's)
     if constexpr (H == 3 && NP == 10) {  // (the early-decision builds exist for three hash functions and ten counter planes: what config 3 / 4 take)
         if (a.early_thr && a.n_fused == 0) {
             early.thr = a.early_thr;
@@ -3027,12 +3189,12 @@ static hipError_t launch_count_nt(const CountLaunch &a, hipStream_t st)
             early.nf = a.early_nf;
             early.fi[0] = a.early_fi;
             hipLaunchKernelGGL((ibf_count_max_kernel<LG, WPL, NP, H, NT, true>), grid, dim3(64 * kWavesPerBlock), 0, st, set, a.src,
-                               a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, early, (uint32_t)a.bound_prune);
+                               a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, early, prune);
             return hipGetLastError();
         }
     }
     hipLaunchKernelGGL((ibf_count_max_kernel<LG, WPL, NP, H, NT>), grid, dim3(64 * kWavesPerBlock), 0, st, set, a.src,
-                       a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, early, (uint32_t)a.bound_prune);
+                       a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, early, prune);
     return hipGetLastError();
 }
 
