@@ -233,8 +233,8 @@ struct LocateOut {
     uint32_t *hit_bins;
     uint8_t *status;
 };
-// ... and one filter's launch: always the plain form over the filter's own table, counted in full
-struct LocateLaunch {
+// ... and one filter's launch.  What locate and hits share: always the plain form over the filter's own table, counted in full
+struct PlainPassLaunch {
     IbfDev f;
     ReadSrc src;
     uint32_t n_items;
@@ -243,6 +243,8 @@ struct LocateLaunch {
     int lg, wpl, planes, nt;
     const uint16_t *thr;  // the decision kernel's table [thr_len][nf][2]
     uint32_t thr_len, nf, fi;
+};
+struct LocateLaunch : PlainPassLaunch {
     LocatePart *part;     // [n_slices][n_items]
 };
 hipError_t launch_ibf_locate(const LocateLaunch &a, hipStream_t st);
@@ -259,16 +261,8 @@ struct HitsOut {
     uint32_t *n_hits;  // [n_items][nf]
     uint8_t *status;   // [n_items]
 };
-// ... and one filter's launch: the plain form over the filter's own table, counted in full, as the locate pass
-struct HitsLaunch {
-    IbfDev f;
-    ReadSrc src;
-    uint32_t n_items;
-    uint32_t col_begin, col_end;
-    uint32_t n_slices;
-    int lg, wpl, planes, nt;
-    const uint16_t *thr;  // the decision kernel's table [thr_len][nf][2]
-    uint32_t thr_len, nf, fi;
+// ... and one filter's launch
+struct HitsLaunch : PlainPassLaunch {
     uint32_t min_count;   // 0: the table's entry; else the threshold itself
     uint32_t max_hits;    // records kept per (item, slice, strand) segment and per (item, filter) list
     uint32_t min_len;     // an item shorter than this is RB_ERR_SHORT_READ
@@ -295,7 +289,7 @@ struct SpansLaunch {
     const rb_u32x2 *queries;
     uint32_t n_queries;
     uint32_t mask_words;
-    uint32_t min_len;           // an item shorter than this is RB_ERR_SHORT_READ (the locate pass's rule: the largest k of the engine)
+    uint32_t min_len;           // an item shorter than this is RB_ERR_SHORT_READ (item_status: the largest k of the engine)
     const uint8_t *pre_status;  // chunk_prep's per-item status, or nullptr
     int nt;
     SpansOut out;

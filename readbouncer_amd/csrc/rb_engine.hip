@@ -2081,6 +2081,135 @@ static int ensure_merged_table(rb_engine *e, MergedGroup *g, hipStream_t st)
     return RB_OK;
 }
 
+// ---- what the device-form passes (classify, locate, hits, spans) share
+// The descriptor's buffers: present (a pass that may run without work items says so) and, for packed input, paired.
+static int check_desc_buffers(const rb_batch_desc *desc, bool items_optional)
+{
+    if ((desc->n_items || !items_optional) && (!desc->d_seqs || !desc->d_offsets || !desc->d_lens))
+        return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
+    if ((desc->d_nmask == nullptr) != (desc->d_nmask_offsets == nullptr))
+        return rb::fail(RB_ERR_INVALID_ARG, "packed input needs both the N bitmap and its offsets");
+    return RB_OK;
+}
+
+// The query passes, after their own argument-shape checks: the device, then the handle, then the sizes (n_extra: the queries of spans) --
+// without a GPU nothing here can work, so the device comes before the handle.
+static int check_pass_call(const rb_engine *e, const rb_batch_desc *desc, size_t n_extra)
+{
+    const int rc = check_device(e ? e->device : 0);
+    if (rc != RB_OK) return rc;
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    if (desc->n_items >= (1ULL << 31) || n_extra >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    return RB_OK;
+}
+
+// A query pass reads a filter's own table in full: a column shard sees only its own bins.
+static int refuse_sharded(const rb_engine *e, const char *pass)
+{
+    if (e->shard_world == 1) return RB_OK;
+    return rb::fail(RB_ERR_INVALID_ARG, std::string(pass) + " on a column-sharded engine: a shard sees only its own bins");
+}
+
+// What a pass makes of its descriptor: the read source its kernels take, after the on-GPU chunking / read indirection -- effective
+// per-item lengths and the bad-chunk status are made on the device, on the call's stream, and the declared bound is clipped to the chunk.
+struct PassInput {
+    ReadSrc src;                  // src.lens: the effective lengths; src.max_len: the clipped bound
+    const uint32_t *d_lens;       // == src.lens
+    const uint8_t *d_pre_status;  // chunk_prep's per-item status, or nullptr
+    uint32_t max_len;             // == src.max_len
+    size_t n_items;
+};
+static int prepare_pass_input(rb_engine *e, const rb_batch_desc *desc, hipStream_t st, PassInput *in)
+{
+    const size_t n = desc->n_items;
+    in->n_items = n;
+    in->d_lens = (const uint32_t *)desc->d_lens;
+    in->d_pre_status = nullptr;
+    in->max_len = desc->max_len;
+    if (n && (desc->chunk_start != 0 || desc->chunk_length != 0 || desc->d_read_ids != nullptr)) {
+        int rc = e->d_efflens.ensure(n * 4);
+        if (rc == RB_OK) rc = e->d_prestatus.ensure(n);
+        if (rc != RB_OK) return rc;
+        RB_HIP(launch_chunk_prep((const uint32_t *)desc->d_lens, (const uint32_t *)desc->d_read_ids, (uint32_t)n, desc->chunk_start,
+                                 desc->chunk_length, (uint32_t *)e->d_efflens.p, (uint8_t *)e->d_prestatus.p, st));
+        in->d_lens = (const uint32_t *)e->d_efflens.p;
+        in->d_pre_status = (const uint8_t *)e->d_prestatus.p;
+        if (desc->chunk_length && desc->chunk_length < in->max_len) in->max_len = desc->chunk_length;
+    }
+    in->src = ReadSrc{};
+    in->src.seqs = (const uint8_t *)desc->d_seqs;
+    in->src.offsets = (const uint64_t *)desc->d_offsets;
+    in->src.lens = in->d_lens;
+    in->src.nmask = (const uint8_t *)desc->d_nmask;
+    in->src.nmask_offsets = (const uint64_t *)desc->d_nmask_offsets;
+    in->src.ids = (const uint32_t *)desc->d_read_ids;
+    in->src.base_off = desc->chunk_start;
+    in->src.max_len = in->max_len;
+    return RB_OK;
+}
+
+// Kernel time of a device-form call (rb_engine_set_timing): one pair of events per call, from a ring that grows on demand.  Bounded: a
+// caller that never collects stops being timed.  *evp stays nullptr when the call is not timed.
+static int begin_timed(rb_engine *e, hipStream_t st, std::pair<hipEvent_t, hipEvent_t> **evp)
+{
+    *evp = nullptr;
+    if (!e->timing || e->ev_used >= ((size_t)1 << 16)) return RB_OK;
+    if (e->ev_used == e->ev_ring.size()) {
+        hipEvent_t a = nullptr, b = nullptr;
+        RB_HIP(hipEventCreate(&a));
+        RB_HIP(hipEventCreate(&b));
+        e->ev_ring.emplace_back(a, b);
+    }
+    *evp = &e->ev_ring[e->ev_used++];
+    RB_HIP(hipEventRecord((*evp)->first, st));
+    return RB_OK;
+}
+static int end_timed(std::pair<hipEvent_t, hipEvent_t> *evp, hipStream_t st)
+{
+    if (evp) RB_HIP(hipEventRecord(evp->second, st));
+    return RB_OK;
+}
+
+// The plain form over a WHOLE filter (no shard), as locate and hits launch it: blocks of up to 64 word columns on 2^lg lanes, wider ones
+// on a whole wave with two words per lane and as many column slices as that takes; ten counter planes while a read's k-mers fit them.
+static void plain_geometry(const rb_engine *e, const rb_dibf *f, uint32_t max_len, int *lg, int *wpl, uint32_t *n_slices, int *planes, int *nt)
+{
+    const uint32_t W = (uint32_t)f->geo.bin_width;
+    *wpl = W > 64 ? 2 : 1;
+    *lg = W > 64 ? 6 : 0;
+    while ((1u << *lg) < W && *lg < 6) ++*lg;
+    const uint32_t slice_words = (1u << *lg) * (uint32_t)*wpl;
+    *n_slices = (W + slice_words - 1) / slice_words;
+    const uint32_t kmers = max_len >= f->geo.kmer_size ? max_len - (uint32_t)f->geo.kmer_size + 1 : 0;
+    *planes = kmers <= 1023 ? 10 : 16;
+    *nt = f->geo.n_blocks * f->stride * 8 > e->nt_threshold_bytes;
+}
+
+// an item shorter than the k of SOME filter of the engine is a short read: that filter has nothing to count
+static uint32_t engine_min_len(const rb_engine *e)
+{
+    uint32_t min_len = 0;
+    for (const rb_dibf *f : e->filters) min_len = std::max<uint32_t>(min_len, (uint32_t)f->geo.kmer_size);
+    return min_len;
+}
+
+// What locate and hits fill alike in one filter's launch
+static void fill_plain_launch(const rb_engine *e, size_t fi, const PassInput &in, const uint16_t *thr, uint32_t thr_len, PlainPassLaunch *a)
+{
+    const rb_dibf *f = e->filters[fi];
+    a->f = f->dev;
+    a->f.comp_n = e->revcomp_of_n;
+    a->src = in.src;
+    a->n_items = (uint32_t)in.n_items;
+    a->col_begin = 0;
+    a->col_end = (uint32_t)f->geo.bin_width;
+    plain_geometry(e, f, in.max_len, &a->lg, &a->wpl, &a->n_slices, &a->planes, &a->nt);
+    a->thr = thr;
+    a->thr_len = thr_len;
+    a->nf = (uint32_t)e->filters.size();
+    a->fi = (uint32_t)fi;
+}
+
 // host_maxcount: optional pinned host destination for a copy of the maxcount rows, written by the decision kernel
 static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, int mode,
                                 void *d_maxcount, void *d_best_target, void *d_decision, void *d_status, void *stream,
@@ -2092,31 +2221,18 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
     const size_t n_reads = desc->n_items;
     if (n_reads >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
     if (n_reads == 0) return RB_OK;
-    const void *d_seqs = desc->d_seqs, *d_offsets = desc->d_offsets;
-    if (!d_seqs || !d_offsets || !desc->d_lens) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
-    if ((desc->d_nmask == nullptr) != (desc->d_nmask_offsets == nullptr))
-        return rb::fail(RB_ERR_INVALID_ARG, "packed input needs both the N bitmap and its offsets");
+    int rc = check_desc_buffers(desc, false);
+    if (rc != RB_OK) return rc;
     std::lock_guard<std::mutex> lock(e->mu);
-    int rc = check_device(e->device);
+    rc = check_device(e->device);
     if (rc != RB_OK) return rc;
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
     const size_t nf = e->filters.size();
-    // on-GPU chunking / read indirection: effective per-item lengths (+ the bad-chunk status) are made on the device
-    const bool chunked = desc->chunk_start != 0 || desc->chunk_length != 0 || desc->d_read_ids != nullptr;
-    const void *d_lens = desc->d_lens;
-    const uint8_t *d_pre_status = nullptr;
-    uint32_t max_len = desc->max_len;
-    if (chunked) {
-        rc = e->d_efflens.ensure(n_reads * 4);
-        if (rc == RB_OK) rc = e->d_prestatus.ensure(n_reads);
-        if (rc != RB_OK) return rc;
-        RB_HIP(launch_chunk_prep((const uint32_t *)desc->d_lens, (const uint32_t *)desc->d_read_ids, (uint32_t)n_reads,
-                                 desc->chunk_start, desc->chunk_length, (uint32_t *)e->d_efflens.p,
-                                 (uint8_t *)e->d_prestatus.p, st));
-        d_lens = e->d_efflens.p;
-        d_pre_status = (const uint8_t *)e->d_prestatus.p;
-        if (desc->chunk_length && desc->chunk_length < max_len) max_len = desc->chunk_length;
-    }
+    PassInput in;
+    if ((rc = prepare_pass_input(e, desc, st, &in)) != RB_OK) return rc;
+    const uint32_t *d_lens = in.d_lens;
+    const uint8_t *d_pre_status = in.d_pre_status;
+    const uint32_t max_len = in.max_len;
 
     uint16_t *maxcount = (uint16_t *)d_maxcount;
     if (!maxcount) {
@@ -2125,16 +2241,7 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
         maxcount = (uint16_t *)e->d_maxcount.p;
     }
     std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
-    if (e->timing && e->ev_used < ((size_t)1 << 16)) {  // bounded: a caller that never collects stops being timed
-        if (e->ev_used == e->ev_ring.size()) {
-            hipEvent_t a = nullptr, b = nullptr;
-            RB_HIP(hipEventCreate(&a));
-            RB_HIP(hipEventCreate(&b));
-            e->ev_ring.emplace_back(a, b);
-        }
-        evp = &e->ev_ring[e->ev_used++];
-        RB_HIP(hipEventRecord(evp->first, st));
-    }
+    if ((rc = begin_timed(e, st, &evp)) != RB_OK) return rc;
     // fork/join over auxiliary streams costs ~20-40 us of event traffic per call (measured): worth it for large
     // batches only; micro-batches queue their few short kernels on the one stream
     // opt-in early decision: the count kernels of the plain throughput form read the decision kernel's threshold table (made here, on the
@@ -2180,14 +2287,7 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
             }
             if (rc != RB_OK) return rc;
             CountLaunch a{};
-            a.src.seqs = (const uint8_t *)d_seqs;
-            a.src.offsets = (const uint64_t *)d_offsets;
-            a.src.lens = (const uint32_t *)d_lens;
-            a.src.nmask = (const uint8_t *)desc->d_nmask;
-            a.src.nmask_offsets = (const uint64_t *)desc->d_nmask_offsets;
-            a.src.ids = (const uint32_t *)desc->d_read_ids;
-            a.src.base_off = desc->chunk_start;
-            a.src.max_len = max_len;
+            a.src = in.src;
             a.n_reads = (uint32_t)n_reads;
             if (g->width <= 4) {
                 // a merged block of two to four words is held by ONE lane of the both-strands builds of the phased kernel: the
@@ -2230,15 +2330,6 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
             }
             a.f = g->dev;
             a.f.comp_n = e->revcomp_of_n;
-            a.src.seqs = (const uint8_t *)d_seqs;
-            a.src.offsets = (const uint64_t *)d_offsets;
-            a.src.lens = (const uint32_t *)d_lens;
-            a.src.nmask = (const uint8_t *)desc->d_nmask;
-            a.src.nmask_offsets = (const uint64_t *)desc->d_nmask_offsets;
-            a.src.ids = (const uint32_t *)desc->d_read_ids;
-            a.src.base_off = desc->chunk_start;
-            a.src.max_len = max_len;
-            a.n_reads = (uint32_t)n_reads;
             a.wpl = 1;
             a.lg = 0;
             while ((1u << a.lg) < g->width) ++a.lg;
@@ -2280,14 +2371,7 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
         CountLaunch a{};
         a.f = f->dev;
         a.f.comp_n = e->revcomp_of_n;
-        a.src.seqs = (const uint8_t *)d_seqs;
-        a.src.offsets = (const uint64_t *)d_offsets;
-        a.src.lens = (const uint32_t *)d_lens;
-        a.src.nmask = (const uint8_t *)desc->d_nmask;
-        a.src.nmask_offsets = (const uint64_t *)desc->d_nmask_offsets;
-        a.src.ids = (const uint32_t *)desc->d_read_ids;
-        a.src.base_off = desc->chunk_start;
-            a.src.max_len = max_len;
+        a.src = in.src;
         a.n_reads = (uint32_t)n_reads;
         if (!plan_geometry(e, f, n_reads, max_len, a)) {
             // this rank holds no column of this filter: its partial maxima are 0
@@ -2331,7 +2415,7 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
                     job.on = 1;
                     job.mode = mode;
                     job.maxcount = maxcount;
-                    job.lens = (const uint32_t *)d_lens;
+                    job.lens = d_lens;
                     job.pre_status = d_pre_status;
                     job.best_target = (int32_t *)d_best_target;
                     job.decision = (uint8_t *)d_decision;
@@ -2360,9 +2444,9 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
             RB_HIP(hipStreamWaitEvent(st, e->join_ev[k], 0));
         }
     }
-    if (evp) RB_HIP(hipEventRecord(evp->second, st));
+    if ((rc = end_timed(evp, st)) != RB_OK) return rc;
     if (!folded && e->shard_world == 1 && (d_best_target || d_decision || d_status)) {
-        rc = run_decide(e, maxcount, (const uint32_t *)d_lens, d_pre_status, n_reads, max_len, error_rate, significance,
+        rc = run_decide(e, maxcount, d_lens, d_pre_status, n_reads, max_len, error_rate, significance,
                         mode, (int32_t *)d_best_target, (uint8_t *)d_decision, (uint8_t *)d_status, st, host_maxcount, 1, 0, done_flag, done_seq);
         if (rc != RB_OK) return rc;
     } else if (!folded && done_flag) {
@@ -2811,6 +2895,46 @@ int rb_classify_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, c
     return RB_OK;
 }
 
+// Host form of the query passes: the caller's reads go to the engine's staging buffers, once per call.  Vets the selection, finds the
+// stretch of seqs the reads cover, uploads it with offsets and lens on `st`, and describes the batch of n work items (d_seqs: the device
+// address of the caller's seqs[0]; d_read_ids is the caller's to set, its staging layout is its own).  Without work items -- spans
+// allows that -- nothing is read and nothing copied.  The caller holds e->host_mu; after a failure that follows this call it waits for `st`.
+static int upload_reads(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *read_ids,
+                        size_t n, hipStream_t st, rb_batch_desc *desc)
+{
+    if (read_ids)
+        for (size_t i = 0; i < n; ++i)
+            if (read_ids[i] >= n_reads) return rb::fail(RB_ERR_INVALID_ARG, "read id beyond the batch");
+    uint64_t hi = 0, lo = ~0ULL;
+    uint32_t max_len = 0;
+    for (size_t i = 0; n && i < n_reads; ++i) {
+        hi = std::max<uint64_t>(hi, offsets[i] + lens[i]);
+        lo = std::min<uint64_t>(lo, offsets[i]);
+        max_len = std::max(max_len, lens[i]);
+    }
+    if (!n) lo = 0;
+    const uint64_t span = hi - lo;
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        int rc = e->d_seqs.ensure(span ? span : 1);
+        if (rc == RB_OK) rc = e->d_offsets.ensure(n_reads ? n_reads * 8 : 8);
+        if (rc == RB_OK) rc = e->d_lens.ensure(n_reads ? n_reads * 4 : 4);
+        if (rc != RB_OK) return rc;
+    }
+    if (span) RB_HIP(hipMemcpyAsync(e->d_seqs.p, seqs + lo, span, hipMemcpyHostToDevice, st));
+    if (n) {
+        RB_HIP(hipMemcpyAsync(e->d_offsets.p, offsets, n_reads * 8, hipMemcpyHostToDevice, st));
+        RB_HIP(hipMemcpyAsync(e->d_lens.p, lens, n_reads * 4, hipMemcpyHostToDevice, st));
+    }
+    std::memset(desc, 0, sizeof *desc);
+    desc->d_seqs = (const char *)e->d_seqs.p - lo;
+    desc->d_offsets = e->d_offsets.p;
+    desc->d_lens = e->d_lens.p;
+    desc->n_items = n;
+    desc->max_len = max_len;
+    return RB_OK;
+}
+
 // ---- locate: which bin and strand a read matched, and how many bins hit (no counterpart in the reference; see the boundary header).
 // Always the plain form over each filter's OWN table, counted in full: the engine's pruning / early-decision / merge / phased settings
 // do not reach it.  One launch of ibf_locate_kernel per filter plus the merge of its column slices, in sequence on the call's stream.
@@ -2820,90 +2944,32 @@ static int locate_device_impl(rb_engine *e, const rb_batch_desc *desc, double er
     if (!desc || !d_out) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor or output struct");
     if (!d_out->max_count && !d_out->best_bin && !d_out->best_strand && !d_out->hit_bins && !d_out->status)
         return rb::fail(RB_ERR_INVALID_ARG, "rb_locate_out with no output");
-    int rc = check_device(e ? e->device : 0);  // (argument shape first, then the device, then the handle: without a GPU nothing here can work)
+    int rc = check_pass_call(e, desc, 0);
     if (rc != RB_OK) return rc;
-    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
     const size_t n_items = desc->n_items;
-    if (n_items >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
     if (n_items == 0) return RB_OK;
-    if (!desc->d_seqs || !desc->d_offsets || !desc->d_lens) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
-    if ((desc->d_nmask == nullptr) != (desc->d_nmask_offsets == nullptr))
-        return rb::fail(RB_ERR_INVALID_ARG, "packed input needs both the N bitmap and its offsets");
+    if ((rc = check_desc_buffers(desc, false)) != RB_OK) return rc;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (e->shard_world != 1) return rb::fail(RB_ERR_INVALID_ARG, "locate on a column-sharded engine: a shard sees only its own bins");
+    if ((rc = refuse_sharded(e, "locate")) != RB_OK) return rc;
     const size_t nf = e->filters.size();
     if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    const bool chunked = desc->chunk_start != 0 || desc->chunk_length != 0 || desc->d_read_ids != nullptr;
-    const void *d_lens = desc->d_lens;
-    const uint8_t *d_pre_status = nullptr;
-    uint32_t max_len = desc->max_len;
-    if (chunked) {
-        rc = e->d_efflens.ensure(n_items * 4);
-        if (rc == RB_OK) rc = e->d_prestatus.ensure(n_items);
-        if (rc != RB_OK) return rc;
-        RB_HIP(launch_chunk_prep((const uint32_t *)desc->d_lens, (const uint32_t *)desc->d_read_ids, (uint32_t)n_items, desc->chunk_start,
-                                 desc->chunk_length, (uint32_t *)e->d_efflens.p, (uint8_t *)e->d_prestatus.p, st));
-        d_lens = e->d_efflens.p;
-        d_pre_status = (const uint8_t *)e->d_prestatus.p;
-        if (desc->chunk_length && desc->chunk_length < max_len) max_len = desc->chunk_length;
-    }
+    PassInput in;
+    if ((rc = prepare_pass_input(e, desc, st, &in)) != RB_OK) return rc;
     // t of hit_bins: the table the decision kernel reads, entry [len][filter][0]
     const uint16_t *thr = nullptr;
     uint32_t thr_len = 0;
-    if ((rc = ensure_thresholds(e, max_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
-    // geometry per filter as the plain kernel cuts it (whole filter: no shard), and one block of partial records for the call
+    if ((rc = ensure_thresholds(e, in.max_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
+    // geometry per filter as the plain kernel cuts it, and one block of partial records for the call
     std::vector<LocateLaunch> launches(nf);
     size_t part_records = 0;
-    uint32_t min_len = 0;  // an item shorter than some filter's k is a short read: that filter has nothing to count
     for (size_t fi = 0; fi < nf; ++fi) {
-        const rb_dibf *f = e->filters[fi];
-        LocateLaunch &a = launches[fi];
-        a = LocateLaunch{};
-        a.f = f->dev;
-        a.f.comp_n = e->revcomp_of_n;
-        a.src.seqs = (const uint8_t *)desc->d_seqs;
-        a.src.offsets = (const uint64_t *)desc->d_offsets;
-        a.src.lens = (const uint32_t *)d_lens;
-        a.src.nmask = (const uint8_t *)desc->d_nmask;
-        a.src.nmask_offsets = (const uint64_t *)desc->d_nmask_offsets;
-        a.src.ids = (const uint32_t *)desc->d_read_ids;
-        a.src.base_off = desc->chunk_start;
-        a.src.max_len = max_len;
-        a.n_items = (uint32_t)n_items;
-        const uint32_t W = (uint32_t)f->geo.bin_width;
-        a.col_begin = 0;
-        a.col_end = W;
-        if (W > 64) {
-            a.wpl = 2; a.lg = 6;
-        } else {
-            a.wpl = 1; a.lg = 0;
-            while ((1u << a.lg) < W) ++a.lg;
-        }
-        const uint32_t slice_words = (1u << a.lg) * a.wpl;
-        a.n_slices = (W + slice_words - 1) / slice_words;
-        const uint32_t kmers = max_len >= f->geo.kmer_size ? max_len - (uint32_t)f->geo.kmer_size + 1 : 0;
-        a.planes = kmers <= 1023 ? 10 : 16;
-        a.nt = f->geo.n_blocks * f->stride * 8 > e->nt_threshold_bytes;
-        a.thr = thr;
-        a.thr_len = thr_len;
-        a.nf = (uint32_t)nf;
-        a.fi = (uint32_t)fi;
-        part_records += (size_t)a.n_slices * n_items;
-        min_len = std::max<uint32_t>(min_len, (uint32_t)f->geo.kmer_size);
+        fill_plain_launch(e, fi, in, thr, thr_len, &launches[fi]);
+        part_records += (size_t)launches[fi].n_slices * n_items;
     }
     if ((rc = e->d_locate_parts.ensure(part_records * sizeof(LocatePart))) != RB_OK) return rc;
     std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
-    if (e->timing && e->ev_used < ((size_t)1 << 16)) {
-        if (e->ev_used == e->ev_ring.size()) {
-            hipEvent_t a = nullptr, b = nullptr;
-            RB_HIP(hipEventCreate(&a));
-            RB_HIP(hipEventCreate(&b));
-            e->ev_ring.emplace_back(a, b);
-        }
-        evp = &e->ev_ring[e->ev_used++];
-        RB_HIP(hipEventRecord(evp->first, st));
-    }
+    if ((rc = begin_timed(e, st, &evp)) != RB_OK) return rc;
     LocateOut out;
     out.max_count = (uint16_t *)d_out->max_count;
     out.best_bin = (int32_t *)d_out->best_bin;
@@ -2911,15 +2977,16 @@ static int locate_device_impl(rb_engine *e, const rb_batch_desc *desc, double er
     out.hit_bins = (uint32_t *)d_out->hit_bins;
     out.status = (uint8_t *)d_out->status;
     LocatePart *part = (LocatePart *)e->d_locate_parts.p;
+    const uint32_t min_len = engine_min_len(e);
     for (size_t fi = 0; fi < nf; ++fi) {
         LocateLaunch &a = launches[fi];
         a.part = part;
         RB_HIP(launch_ibf_locate(a, st));
-        RB_HIP(launch_reduce_locate_slices(part, a.n_slices, (uint32_t)n_items, (const uint32_t *)d_lens, d_pre_status, max_len, min_len, out,
+        RB_HIP(launch_reduce_locate_slices(part, a.n_slices, (uint32_t)n_items, in.d_lens, in.d_pre_status, in.max_len, min_len, out,
                                            (uint32_t)nf, (uint32_t)fi, st));
         part += (size_t)a.n_slices * n_items;
     }
-    if (evp) RB_HIP(hipEventRecord(evp->second, st));
+    if ((rc = end_timed(evp, st)) != RB_OK) return rc;
     if (!stream) RB_HIP(hipStreamSynchronize(st));
     return RB_OK;
 }
@@ -2943,41 +3010,23 @@ int rb_locate_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, con
     if (n == 0) return RB_OK;
     if (!seqs || !offsets || !lens || n_reads == 0) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
     if (n >= (1ULL << 31) || n_reads >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
-    if (read_ids)
-        for (size_t i = 0; i < n; ++i)
-            if (read_ids[i] >= n_reads) return rb::fail(RB_ERR_INVALID_ARG, "read id beyond the batch");
-    uint64_t hi = 0, lo = ~0ULL;
-    uint32_t max_len = 0;
-    for (size_t i = 0; i < n_reads; ++i) {
-        hi = std::max<uint64_t>(hi, offsets[i] + lens[i]);
-        lo = std::min<uint64_t>(lo, offsets[i]);
-        max_len = std::max(max_len, lens[i]);
-    }
     const size_t nf = e->filters.size();
-    const uint64_t span = hi - lo;
     hipStream_t st = e->stream;
     std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
+    rb_batch_desc desc;
+    if ((rc = upload_reads(e, seqs, offsets, lens, n_reads, read_ids, n, st, &desc)) != RB_OK) return rc;
     // staging: u32 ids[n] | i32 best_bin[n*nf] | u32 hit_bins[n*nf] | u16 max_count[n*nf] | u8 best_strand[n*nf] | u8 status[n]
     const size_t o_bin = 4 * n, o_hit = o_bin + 4 * n * nf, o_max = o_hit + 4 * n * nf, o_strand = o_max + 2 * n * nf, o_status = o_strand + n * nf;
     {
         std::lock_guard<std::mutex> lock(e->mu);
-        if ((rc = e->d_seqs.ensure(span ? span : 1)) != RB_OK) return rc;
-        if ((rc = e->d_offsets.ensure(n_reads * 8)) != RB_OK) return rc;
-        if ((rc = e->d_lens.ensure(n_reads * 4)) != RB_OK) return rc;
-        if ((rc = e->d_locate_io.ensure(o_status + n)) != RB_OK) return rc;
+        rc = e->d_locate_io.ensure(o_status + n);
+    }
+    if (rc != RB_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
     }
     char *io = (char *)e->d_locate_io.p;
-    if (span) RB_HIP(hipMemcpyAsync(e->d_seqs.p, seqs + lo, span, hipMemcpyHostToDevice, st));
-    RB_HIP(hipMemcpyAsync(e->d_offsets.p, offsets, n_reads * 8, hipMemcpyHostToDevice, st));
-    RB_HIP(hipMemcpyAsync(e->d_lens.p, lens, n_reads * 4, hipMemcpyHostToDevice, st));
     if (read_ids) RB_HIP(hipMemcpyAsync(io, read_ids, 4 * n, hipMemcpyHostToDevice, st));
-    rb_batch_desc desc;
-    std::memset(&desc, 0, sizeof desc);
-    desc.d_seqs = (const char *)e->d_seqs.p - lo;  // device address of the caller's seqs[0]
-    desc.d_offsets = e->d_offsets.p;
-    desc.d_lens = e->d_lens.p;
-    desc.n_items = n;
-    desc.max_len = max_len;
     desc.d_read_ids = read_ids ? io : nullptr;
     rb_locate_out d_out;
     d_out.max_count = out->max_count ? io + o_max : nullptr;
@@ -3000,7 +3049,7 @@ int rb_locate_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, con
 }
 
 // ---- hits: every (bin, strand) at or above the threshold, with its count (no counterpart in the reference; see the boundary header).
-// The locate pass's shape: per filter one launch of ibf_hits_kernel over the filter's OWN table, counted in full, plus finish_hits_kernel,
+// Per filter one launch of ibf_hits_kernel over the filter's OWN table, counted in full, plus finish_hits_kernel,
 // in sequence on the call's stream -- so one workspace, sized for the filter with the most column slices, serves every filter.
 static int hits_device_impl(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, uint16_t min_count,
                             uint32_t max_hits, const rb_hits_out *d_out, void *stream)
@@ -3008,93 +3057,39 @@ static int hits_device_impl(rb_engine *e, const rb_batch_desc *desc, double erro
     if (!desc || !d_out) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor or output struct");
     if (!d_out->hits && !d_out->n_hits && !d_out->bin_reads) return rb::fail(RB_ERR_INVALID_ARG, "rb_hits_out with no output");
     if (d_out->hits && max_hits == 0) return rb::fail(RB_ERR_INVALID_ARG, "a hits buffer with max_hits == 0");
-    int rc = check_device(e ? e->device : 0);  // (argument shape first, then the device, then the handle: without a GPU nothing here can work)
+    int rc = check_pass_call(e, desc, 0);
     if (rc != RB_OK) return rc;
-    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
     const size_t n_items = desc->n_items;
-    if (n_items >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
     if (n_items == 0) return RB_OK;
-    if (!desc->d_seqs || !desc->d_offsets || !desc->d_lens) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
-    if ((desc->d_nmask == nullptr) != (desc->d_nmask_offsets == nullptr))
-        return rb::fail(RB_ERR_INVALID_ARG, "packed input needs both the N bitmap and its offsets");
+    if ((rc = check_desc_buffers(desc, false)) != RB_OK) return rc;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (e->shard_world != 1) return rb::fail(RB_ERR_INVALID_ARG, "hits on a column-sharded engine: a shard sees only its own bins");
+    if ((rc = refuse_sharded(e, "hits")) != RB_OK) return rc;
     const size_t nf = e->filters.size();
     if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    const bool chunked = desc->chunk_start != 0 || desc->chunk_length != 0 || desc->d_read_ids != nullptr;
-    const void *d_lens = desc->d_lens;
-    const uint8_t *d_pre_status = nullptr;
-    uint32_t max_len = desc->max_len;
-    if (chunked) {
-        rc = e->d_efflens.ensure(n_items * 4);
-        if (rc == RB_OK) rc = e->d_prestatus.ensure(n_items);
-        if (rc != RB_OK) return rc;
-        RB_HIP(launch_chunk_prep((const uint32_t *)desc->d_lens, (const uint32_t *)desc->d_read_ids, (uint32_t)n_items, desc->chunk_start,
-                                 desc->chunk_length, (uint32_t *)e->d_efflens.p, (uint8_t *)e->d_prestatus.p, st));
-        d_lens = e->d_efflens.p;
-        d_pre_status = (const uint8_t *)e->d_prestatus.p;
-        if (desc->chunk_length && desc->chunk_length < max_len) max_len = desc->chunk_length;
-    }
+    PassInput in;
+    if ((rc = prepare_pass_input(e, desc, st, &in)) != RB_OK) return rc;
     // t for min_count == 0: the table the decision kernel reads, entry [len][filter][0] -- one definition of the threshold
     const uint16_t *thr = nullptr;
     uint32_t thr_len = 0;
-    if ((rc = ensure_thresholds(e, max_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
+    if ((rc = ensure_thresholds(e, in.max_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
     const uint32_t cap = d_out->hits ? max_hits : 0u;  // without a record buffer nothing is kept: the totals stay exact
     std::vector<HitsLaunch> launches(nf);
-    uint32_t min_len = 0, max_slices = 0;
+    const uint32_t min_len = engine_min_len(e);
+    uint32_t max_slices = 0;
     for (size_t fi = 0; fi < nf; ++fi) {
-        const rb_dibf *f = e->filters[fi];
         HitsLaunch &a = launches[fi];
-        a = HitsLaunch{};
-        a.f = f->dev;
-        a.f.comp_n = e->revcomp_of_n;
-        a.src.seqs = (const uint8_t *)desc->d_seqs;
-        a.src.offsets = (const uint64_t *)desc->d_offsets;
-        a.src.lens = (const uint32_t *)d_lens;
-        a.src.nmask = (const uint8_t *)desc->d_nmask;
-        a.src.nmask_offsets = (const uint64_t *)desc->d_nmask_offsets;
-        a.src.ids = (const uint32_t *)desc->d_read_ids;
-        a.src.base_off = desc->chunk_start;
-        a.src.max_len = max_len;
-        a.n_items = (uint32_t)n_items;
-        const uint32_t W = (uint32_t)f->geo.bin_width;
-        a.col_begin = 0;
-        a.col_end = W;
-        if (W > 64) {
-            a.wpl = 2; a.lg = 6;
-        } else {
-            a.wpl = 1; a.lg = 0;
-            while ((1u << a.lg) < W) ++a.lg;
-        }
-        const uint32_t slice_words = (1u << a.lg) * a.wpl;
-        a.n_slices = (W + slice_words - 1) / slice_words;
-        const uint32_t kmers = max_len >= f->geo.kmer_size ? max_len - (uint32_t)f->geo.kmer_size + 1 : 0;
-        a.planes = kmers <= 1023 ? 10 : 16;
-        a.nt = f->geo.n_blocks * f->stride * 8 > e->nt_threshold_bytes;
-        a.thr = thr;
-        a.thr_len = thr_len;
-        a.nf = (uint32_t)nf;
-        a.fi = (uint32_t)fi;
+        fill_plain_launch(e, fi, in, thr, thr_len, &a);
         a.min_count = min_count;
         a.max_hits = cap;
-        a.pre_status = d_pre_status;
+        a.min_len = min_len;
+        a.pre_status = in.d_pre_status;
         max_slices = std::max(max_slices, a.n_slices);
-        min_len = std::max<uint32_t>(min_len, (uint32_t)f->geo.kmer_size);
     }
     const size_t seg_bytes = n_items * (size_t)max_slices * 2 * (size_t)cap * 8;
     if ((rc = e->d_hits_ws.ensure(seg_bytes + n_items * (size_t)max_slices * 2 * 4)) != RB_OK) return rc;
     std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
-    if (e->timing && e->ev_used < ((size_t)1 << 16)) {
-        if (e->ev_used == e->ev_ring.size()) {
-            hipEvent_t a = nullptr, b = nullptr;
-            RB_HIP(hipEventCreate(&a));
-            RB_HIP(hipEventCreate(&b));
-            e->ev_ring.emplace_back(a, b);
-        }
-        evp = &e->ev_ring[e->ev_used++];
-        RB_HIP(hipEventRecord(evp->first, st));
-    }
+    if ((rc = begin_timed(e, st, &evp)) != RB_OK) return rc;
     HitsOut out;
     out.hits = (rb_u32x2 *)d_out->hits;
     out.n_hits = (uint32_t *)d_out->n_hits;
@@ -3102,15 +3097,14 @@ static int hits_device_impl(rb_engine *e, const rb_batch_desc *desc, double erro
     uint64_t *bin_reads = (uint64_t *)d_out->bin_reads;
     for (size_t fi = 0; fi < nf; ++fi) {
         HitsLaunch &a = launches[fi];
-        a.min_len = min_len;
         a.seg = e->d_hits_ws.p;
         a.seg_count = (uint32_t *)((char *)e->d_hits_ws.p + seg_bytes);
         a.bin_reads = bin_reads;
         RB_HIP(launch_ibf_hits(a, st));
-        RB_HIP(launch_finish_hits(a, (const uint32_t *)d_lens, out, st));
+        RB_HIP(launch_finish_hits(a, in.d_lens, out, st));
         if (bin_reads) bin_reads += e->filters[fi]->geo.n_bins;
     }
-    if (evp) RB_HIP(hipEventRecord(evp->second, st));
+    if ((rc = end_timed(evp, st)) != RB_OK) return rc;
     if (!stream) RB_HIP(hipStreamSynchronize(st));
     return RB_OK;
 }
@@ -3134,32 +3128,26 @@ int rb_hits_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const
     if (n == 0) return RB_OK;
     if (!seqs || !offsets || !lens || n_reads == 0) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
     if (n >= (1ULL << 31) || n_reads >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
-    if (read_ids)
-        for (size_t i = 0; i < n; ++i)
-            if (read_ids[i] >= n_reads) return rb::fail(RB_ERR_INVALID_ARG, "read id beyond the batch");
-    uint64_t hi = 0, lo = ~0ULL;
-    uint32_t max_len = 0;
-    for (size_t i = 0; i < n_reads; ++i) {
-        hi = std::max<uint64_t>(hi, offsets[i] + lens[i]);
-        lo = std::min<uint64_t>(lo, offsets[i]);
-        max_len = std::max(max_len, lens[i]);
-    }
-    const uint64_t span = hi - lo;
     hipStream_t st = e->stream;
     std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
+    rb_batch_desc all;
+    if ((rc = upload_reads(e, seqs, offsets, lens, n_reads, read_ids, n, st, &all)) != RB_OK) return rc;
     size_t nf = 0, total_bins = 0, max_slices = 1;
     {
         std::lock_guard<std::mutex> lock(e->mu);
         nf = e->filters.size();
-        for (const rb_dibf *f : e->filters) {
+        for (const rb_dibf *f : e->filters) {  // the column slices hits_device_impl will cut: its workspace is part of the budget below
+            int lg, wpl, planes, nt;
+            uint32_t n_slices;
+            plain_geometry(e, f, all.max_len, &lg, &wpl, &n_slices, &planes, &nt);
             total_bins += f->geo.n_bins;
-            max_slices = std::max<size_t>(max_slices, f->geo.bin_width > 64 ? (f->geo.bin_width + 127) / 128 : 1);
+            max_slices = std::max<size_t>(max_slices, n_slices);
         }
-        if ((rc = e->d_seqs.ensure(span ? span : 1)) != RB_OK) return rc;
-        if ((rc = e->d_offsets.ensure(n_reads * 8)) != RB_OK) return rc;
-        if ((rc = e->d_lens.ensure(n_reads * 4)) != RB_OK) return rc;
     }
-    if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
+    if (nf == 0) {
+        (void)hipStreamSynchronize(st);
+        return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
+    }
     // sub-batches: workspace (S x 2 x cap records and S x 2 counters per item) plus staged outputs (nf x cap records, nf counters and a
     // status byte per item) stay at or below kHitsBudget; a single item that needs more goes alone
     constexpr size_t kHitsBudget = 256ull << 20;
@@ -3170,26 +3158,26 @@ int rb_hits_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const
     const size_t o_hits = 8 * total_bins, o_n = o_hits + sub_max * nf * cap * 8, o_ids = o_n + sub_max * nf * 4, o_status = o_ids + sub_max * 4;
     {
         std::lock_guard<std::mutex> lock(e->mu);
-        if ((rc = e->d_hits_io.ensure(o_status + sub_max)) != RB_OK) return rc;
+        rc = e->d_hits_io.ensure(o_status + sub_max);
+    }
+    if (rc != RB_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
     }
     char *io = (char *)e->d_hits_io.p;
-    if (span) RB_HIP(hipMemcpyAsync(e->d_seqs.p, seqs + lo, span, hipMemcpyHostToDevice, st));
-    RB_HIP(hipMemcpyAsync(e->d_offsets.p, offsets, n_reads * 8, hipMemcpyHostToDevice, st));
-    RB_HIP(hipMemcpyAsync(e->d_lens.p, lens, n_reads * 4, hipMemcpyHostToDevice, st));
     if (out->bin_reads) RB_HIP(hipMemsetAsync(io, 0, 8 * total_bins, st));
     std::vector<uint32_t> h_n(sub_max * nf);
     std::vector<rb_hit> h_hits(cap ? sub_max * nf * cap : 0);
     for (size_t b0 = 0; b0 < n; b0 += sub_max) {
         const size_t sub = std::min(sub_max, n - b0);
         if (read_ids) RB_HIP(hipMemcpyAsync(io + o_ids, read_ids + b0, 4 * sub, hipMemcpyHostToDevice, st));
-        rb_batch_desc desc;
-        std::memset(&desc, 0, sizeof desc);
-        desc.d_seqs = (const char *)e->d_seqs.p - lo;  // device address of the caller's seqs[0]
+        rb_batch_desc desc = all;
         // work item j of the sub-batch is read read_ids[b0 + j], or read b0 + j
-        desc.d_offsets = read_ids ? e->d_offsets.p : (const void *)((const uint64_t *)e->d_offsets.p + b0);
-        desc.d_lens = read_ids ? e->d_lens.p : (const void *)((const uint32_t *)e->d_lens.p + b0);
+        if (!read_ids) {
+            desc.d_offsets = (const uint64_t *)all.d_offsets + b0;
+            desc.d_lens = (const uint32_t *)all.d_lens + b0;
+        }
         desc.n_items = sub;
-        desc.max_len = max_len;
         desc.d_read_ids = read_ids ? io + o_ids : nullptr;
         rb_hits_out d_out;
         d_out.hits = cap ? io + o_hits : nullptr;
@@ -3229,71 +3217,37 @@ static int spans_device_impl(rb_engine *e, const rb_batch_desc *desc, size_t fil
 {
     if (!desc || !d_out) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor or output struct");
     if (!d_out->spans && !d_out->mask && !d_out->n_kmers && !d_out->status) return rb::fail(RB_ERR_INVALID_ARG, "rb_spans_out with no output");
-    int rc = check_device(e ? e->device : 0);  // (argument shape first, then the device, then the handle: without a GPU nothing here can work)
+    int rc = check_pass_call(e, desc, n_queries);
     if (rc != RB_OK) return rc;
-    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
-    const size_t n_items = desc->n_items;
-    if (n_items >= (1ULL << 31) || n_queries >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
     std::lock_guard<std::mutex> lock(e->mu);
     if (filter >= e->filters.size()) return rb::fail(RB_ERR_INVALID_ARG, "filter index beyond the engine's filters");
     if (n_queries == 0) return RB_OK;
     if (!d_queries) return rb::fail(RB_ERR_INVALID_ARG, "null query buffer");
-    if (n_items && (!desc->d_seqs || !desc->d_offsets || !desc->d_lens)) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
-    if ((desc->d_nmask == nullptr) != (desc->d_nmask_offsets == nullptr))
-        return rb::fail(RB_ERR_INVALID_ARG, "packed input needs both the N bitmap and its offsets");
-    if (e->shard_world != 1) return rb::fail(RB_ERR_INVALID_ARG, "spans on a column-sharded engine: a shard sees only its own bins");
+    if ((rc = check_desc_buffers(desc, true)) != RB_OK) return rc;  // (queries against no items are answered: each is RB_ERR_INVALID_ARG)
+    if ((rc = refuse_sharded(e, "spans")) != RB_OK) return rc;
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    const bool chunked = n_items && (desc->chunk_start != 0 || desc->chunk_length != 0 || desc->d_read_ids != nullptr);
-    const void *d_lens = desc->d_lens;
-    const uint8_t *d_pre_status = nullptr;
-    uint32_t max_len = desc->max_len;
-    if (chunked) {
-        rc = e->d_efflens.ensure(n_items * 4);
-        if (rc == RB_OK) rc = e->d_prestatus.ensure(n_items);
-        if (rc != RB_OK) return rc;
-        RB_HIP(launch_chunk_prep((const uint32_t *)desc->d_lens, (const uint32_t *)desc->d_read_ids, (uint32_t)n_items, desc->chunk_start,
-                                 desc->chunk_length, (uint32_t *)e->d_efflens.p, (uint8_t *)e->d_prestatus.p, st));
-        d_lens = e->d_efflens.p;
-        d_pre_status = (const uint8_t *)e->d_prestatus.p;
-        if (desc->chunk_length && desc->chunk_length < max_len) max_len = desc->chunk_length;
-    }
+    PassInput in;
+    if ((rc = prepare_pass_input(e, desc, st, &in)) != RB_OK) return rc;
     const rb_dibf *f = e->filters[filter];
     SpansLaunch a{};
     a.f = f->dev;
     a.f.comp_n = e->revcomp_of_n;
-    a.src.seqs = (const uint8_t *)desc->d_seqs;
-    a.src.offsets = (const uint64_t *)desc->d_offsets;
-    a.src.lens = (const uint32_t *)d_lens;
-    a.src.nmask = (const uint8_t *)desc->d_nmask;
-    a.src.nmask_offsets = (const uint64_t *)desc->d_nmask_offsets;
-    a.src.ids = (const uint32_t *)desc->d_read_ids;
-    a.src.base_off = desc->chunk_start;
-    a.src.max_len = max_len;
-    a.n_items = (uint32_t)n_items;
+    a.src = in.src;
+    a.n_items = (uint32_t)in.n_items;
     a.queries = (const rb_u32x2 *)d_queries;
     a.n_queries = (uint32_t)n_queries;
     a.mask_words = d_out->mask ? mask_words : 0u;
-    a.min_len = 0;  // the item's status is the locate pass's: shorter than the k of SOME filter of the engine is a short read
-    for (const rb_dibf *g : e->filters) a.min_len = std::max<uint32_t>(a.min_len, (uint32_t)g->geo.kmer_size);
-    a.pre_status = d_pre_status;
+    a.min_len = engine_min_len(e);
+    a.pre_status = in.d_pre_status;
     a.nt = f->geo.n_blocks * f->stride * 8 > e->nt_threshold_bytes;
     a.out.spans = (uint32_t *)d_out->spans;
     a.out.mask = (uint64_t *)d_out->mask;
     a.out.n_kmers = (uint32_t *)d_out->n_kmers;
     a.out.status = (uint8_t *)d_out->status;
     std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
-    if (e->timing && e->ev_used < ((size_t)1 << 16)) {
-        if (e->ev_used == e->ev_ring.size()) {
-            hipEvent_t ea = nullptr, eb = nullptr;
-            RB_HIP(hipEventCreate(&ea));
-            RB_HIP(hipEventCreate(&eb));
-            e->ev_ring.emplace_back(ea, eb);
-        }
-        evp = &e->ev_ring[e->ev_used++];
-        RB_HIP(hipEventRecord(evp->first, st));
-    }
+    if ((rc = begin_timed(e, st, &evp)) != RB_OK) return rc;
     RB_HIP(launch_ibf_spans(a, st));
-    if (evp) RB_HIP(hipEventRecord(evp->second, st));
+    if ((rc = end_timed(evp, st)) != RB_OK) return rc;
     if (!stream) RB_HIP(hipStreamSynchronize(st));
     return RB_OK;
 }
@@ -3321,20 +3275,10 @@ int rb_spans_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, cons
     const size_t n = read_ids ? n_items : n_reads;  // without a selection the work items are the reads
     if (n && (!seqs || !offsets || !lens || n_reads == 0)) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
     if (n >= (1ULL << 31) || n_reads >= (1ULL << 31) || n_queries >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
-    if (read_ids)
-        for (size_t i = 0; i < n; ++i)
-            if (read_ids[i] >= n_reads) return rb::fail(RB_ERR_INVALID_ARG, "read id beyond the batch");
-    uint64_t hi = 0, lo = ~0ULL;
-    uint32_t max_len = 0;
-    for (size_t i = 0; n && i < n_reads; ++i) {
-        hi = std::max<uint64_t>(hi, offsets[i] + lens[i]);
-        lo = std::min<uint64_t>(lo, offsets[i]);
-        max_len = std::max(max_len, lens[i]);
-    }
-    if (!n) lo = 0;
-    const uint64_t span = hi - lo;
     hipStream_t st = e->stream;
     std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
+    rb_batch_desc desc;
+    if ((rc = upload_reads(e, seqs, offsets, lens, n_reads, read_ids, n, st, &desc)) != RB_OK) return rc;
     // sub-batches of queries: what a query stages (its masks, its two records, n_kmers, status and the query itself) stays at or below
     // kSpansBudget per call, one query at a time where a single one needs more; the reads and their ids are uploaded once
     constexpr size_t kSpansBudget = 256ull << 20;
@@ -3346,25 +3290,14 @@ int rb_spans_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, cons
                  o_status = o_ids + 4 * (read_ids ? n : 0);
     {
         std::lock_guard<std::mutex> lock(e->mu);
-        if ((rc = e->d_seqs.ensure(span ? span : 1)) != RB_OK) return rc;
-        if ((rc = e->d_offsets.ensure(n_reads ? n_reads * 8 : 8)) != RB_OK) return rc;
-        if ((rc = e->d_lens.ensure(n_reads ? n_reads * 4 : 4)) != RB_OK) return rc;
-        if ((rc = e->d_spans_io.ensure(o_status + sub_max)) != RB_OK) return rc;
+        rc = e->d_spans_io.ensure(o_status + sub_max);
+    }
+    if (rc != RB_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
     }
     char *io = (char *)e->d_spans_io.p;
-    if (span) RB_HIP(hipMemcpyAsync(e->d_seqs.p, seqs + lo, span, hipMemcpyHostToDevice, st));
-    if (n) {
-        RB_HIP(hipMemcpyAsync(e->d_offsets.p, offsets, n_reads * 8, hipMemcpyHostToDevice, st));
-        RB_HIP(hipMemcpyAsync(e->d_lens.p, lens, n_reads * 4, hipMemcpyHostToDevice, st));
-    }
     if (read_ids && n) RB_HIP(hipMemcpyAsync(io + o_ids, read_ids, 4 * n, hipMemcpyHostToDevice, st));
-    rb_batch_desc desc;
-    std::memset(&desc, 0, sizeof desc);
-    desc.d_seqs = (const char *)e->d_seqs.p - lo;  // device address of the caller's seqs[0]
-    desc.d_offsets = e->d_offsets.p;
-    desc.d_lens = e->d_lens.p;
-    desc.n_items = n;
-    desc.max_len = max_len;
     desc.d_read_ids = read_ids ? io + o_ids : nullptr;
     for (size_t b0 = 0; b0 < n_queries; b0 += sub_max) {
         const size_t sub = std::min(sub_max, n_queries - b0);

@@ -34,6 +34,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "rb_device.h"
 
@@ -504,7 +505,9 @@ __device__ __forceinline__ void phased_gather_x4(uint64_t (&x0)[N], uint64_t (&x
 constexpr uint32_t kNoBound = 0xFFFFFFFFu;
 
 // bit-sliced "some valid bin of this lane has c > t", MSB plane first (t wave-uniform: one scalar branch per plane): gt = bins already
-// above t, eq = bins equal to t's leading bits so far
+// above t, eq = bins equal to t's leading bits so far.  (Locate and hits run the same loop for their hit masks.  It is written out in all
+// three places: as a shared function the compiler holds every plane twice unless t is forced scalar inside it, and either form changes
+// the registers of these kernels -- the count builds' code with them.)
 template <int NP, int WPL>
 __device__ __forceinline__ bool bound_alive(const Planes<NP> (&pl)[WPL], const uint64_t (&valid)[WPL], uint32_t t)
 {
@@ -941,6 +944,59 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     }
 }
 
+// What the opt-in query passes (locate, hits, spans) share.
+// The status of a work item: chunk_prep's verdict first, then the declared bound, then "shorter than the k of some filter of the engine"
+// (decide_one's rules are richer and its own).
+__device__ __forceinline__ uint32_t item_status(const uint8_t *pre_status, uint32_t item, uint32_t raw_len, uint32_t max_len, uint32_t min_len)
+{
+    const uint32_t pre = pre_status ? (uint32_t)pre_status[item] : (uint32_t)RB_OK;
+    if (pre != RB_OK) return pre;
+    if (raw_len > max_len) return RB_ERR_INVALID_ARG;
+    if (raw_len < min_len) return RB_ERR_SHORT_READ;
+    return RB_OK;
+}
+
+// Locate and hits run one wave per (work item, column slice), as the plain count kernel.  SCALAR: the pair is made wave-uniform in
+// scalar registers, so that addresses made from it are scalar arithmetic and cost no vector register across the gathers (hits, for its
+// segment addresses; locate has none, and its whole-wave ten-plane build takes 23 registers more that way).
+template <bool SCALAR>
+__device__ __forceinline__ void wave_item_slice(uint32_t n_slices, int wave, uint32_t *item, uint32_t *slice)
+{
+    const uint64_t witem = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
+    const uint32_t it = (uint32_t)(witem / n_slices);
+    const uint32_t sl = (uint32_t)(witem - (uint64_t)it * n_slices);
+    *item = SCALAR ? __builtin_amdgcn_readfirstlane(it) : it;
+    *slice = SCALAR ? __builtin_amdgcn_readfirstlane(sl) : sl;
+}
+
+// ... and what such a wave sets up before it counts
+template <int WPL>
+struct PassWave {
+    LaneCols<WPL> lc;
+    BaseSrc seq;
+    uint32_t len, n;  // bases and k-mers of the item
+    uint32_t t;       // wave-uniform: the caller's threshold, or the one the decision kernel reads for this length and filter
+    uint32_t col0;    // first word column of the slice
+    bool group0;      // the lane group whose columns are reported (every group holds the same totals)
+    // word column of word w of lane `c` of group 0
+    __device__ __forceinline__ uint32_t word_col(int c, int w) const { return col0 + (uint32_t)(c * WPL + w); }
+};
+template <int LG, int WPL>
+__device__ __forceinline__ PassWave<WPL> make_pass_wave(const IbfDev &f, const ReadSrc &src, uint32_t col_begin, uint32_t col_end, uint32_t item,
+                                                            uint32_t slice, int lane, const uint16_t *thr, uint32_t thr_len, uint32_t nf, uint32_t fi,
+                                                            uint32_t min_count)
+{
+    PassWave<WPL> pw;
+    pw.lc = make_lane_cols<LG, WPL>(f, lane, col_begin, col_end, slice);
+    pw.seq = make_base_src(src, item, &pw.len);
+    pw.n = pw.len >= f.k ? pw.len - f.k + 1 : 0;
+    const uint32_t tl = pw.len < thr_len ? pw.len : thr_len - 1;
+    pw.t = min_count ? min_count : __builtin_amdgcn_readfirstlane((uint32_t)thr[((size_t)tl * nf + fi) * 2]);
+    pw.col0 = col_begin + slice * (uint32_t)((1 << LG) * WPL);
+    pw.group0 = lane < (1 << LG);
+    return pw;
+}
+
 // LOCATE: the opt-in second pass (rb_locate_batch_device) that says WHERE a read matched.  One wave per (work item, column slice) as
 // in the plain kernel above and built from the same pieces -- make_lane_cols, make_base_src, count_strand with no bound, no early
 // exit, no phasing -- so the gather schedule is the measured one; it always counts in full (bound pruning leaves stale counters in
@@ -961,20 +1017,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     __shared__ uint8_t s_stage[kWavesPerBlock][kStageBytes];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const uint64_t witem = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
-    const uint32_t item = (uint32_t)(witem / n_slices);
-    const uint32_t slice = (uint32_t)(witem - (uint64_t)item * n_slices);
+    uint32_t item, slice;
+    wave_item_slice<false>(n_slices, wave, &item, &slice);
     if (item >= n_items) return;  // wave-uniform; there are no block-level barriers below
 
-    const LaneCols<WPL> lc = make_lane_cols<LG, WPL>(f, lane, col_begin, col_end, slice);
-    uint32_t len;
-    const BaseSrc seq = make_base_src(src, item, &len);
-    const uint32_t n = len >= f.k ? len - f.k + 1 : 0;
-    // the threshold the decision kernel reads for this length and filter, at the caller's error rate
-    const uint32_t tl = len < thr_len ? len : thr_len - 1;
-    const uint32_t t = __builtin_amdgcn_readfirstlane((uint32_t)thr[((size_t)tl * nf + fi) * 2]);
-    const bool group0 = lane < (1 << LG);  // the lane group whose columns are reported (every group holds the same totals)
-    const uint32_t first_col = col_begin + slice * (uint32_t)((1 << LG) * WPL) + (uint32_t)((lane & ((1 << LG) - 1)) * WPL);
+    // t: the threshold the decision kernel reads for this length and filter, at the caller's error rate
+    const PassWave<WPL> pw = make_pass_wave<LG, WPL>(f, src, col_begin, col_end, item, slice, lane, thr, thr_len, nf, fi, 0u);
+    const LaneCols<WPL> &lc = pw.lc;
+    const uint32_t t = pw.t;
 
     uint64_t hit[WPL];
 #pragma unroll
@@ -984,7 +1034,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
         Planes<NP> pl[WPL];
 #pragma unroll
         for (int w = 0; w < WPL; ++w) pl[w].clear();
-        count_strand<LG, WPL, NP, H, NT>(pl, f, lc, seq, len, n, strand, 0u, (uint32_t)TileShape<LG>::ITEMS, 0, TileShape<LG>::STEPS / 8,
+        count_strand<LG, WPL, NP, H, NT>(pl, f, lc, pw.seq, pw.len, pw.n, strand, 0u, (uint32_t)TileShape<LG>::ITEMS, 0, TileShape<LG>::STEPS / 8,
                                          s_stage[wave], lane);
         // ---- the strand's maximum, and the bins that hold it
         uint64_t cand[WPL];
@@ -1013,11 +1063,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
             for (int w = WPL - 1; w >= 0; --w) {
                 if (cand[w] != 0ULL) {
                     has = true;
-                    mine = (first_col + (uint32_t)w) * 64u + (uint32_t)(__ffsll((unsigned long long)cand[w]) - 1);
+                    mine = pw.word_col(lane & ((1 << LG) - 1), w) * 64u + (uint32_t)(__ffsll((unsigned long long)cand[w]) - 1);
                 }
             }
             // columns rise with the lane number inside a group: the lowest lane of group 0 with a candidate holds the lowest bin
-            const uint64_t who = __ballot(has && group0);
+            const uint64_t who = __ballot(has && pw.group0);
             const uint32_t first = readlane32(mine, (int)__builtin_amdgcn_readfirstlane((uint32_t)(__ffsll((unsigned long long)who) - 1)));
             if (m > best || (m == best && first < best_bin)) {  // (strand 0 enters through m > 0 == best; an equal bin stays with strand 0)
                 best_bin = first;
@@ -1047,7 +1097,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     uint32_t hits = 0;
 #pragma unroll
     for (int w = 0; w < WPL; ++w) hits += (uint32_t)__popcll(hit[w]);
-    if (!group0) hits = 0;
+    if (!pw.group0) hits = 0;
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1) hits += shfl32(hits, lane ^ s);
     if (lane == 0) {
@@ -1069,11 +1119,7 @@ __global__ void reduce_locate_slices_kernel(const LocatePart *__restrict__ part,
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_items) return;
-    uint8_t status = RB_OK;
-    const uint32_t len = lens[i];
-    if (pre_status && pre_status[i] != RB_OK) status = pre_status[i];
-    else if (len > max_len) status = RB_ERR_INVALID_ARG;
-    else if (len < min_len) status = RB_ERR_SHORT_READ;
+    const uint8_t status = (uint8_t)item_status(pre_status, i, lens[i], max_len, min_len);
     uint32_t m = 0, bin = 0, strand = 0, hits = 0;
     if (status == RB_OK) {
         for (uint32_t s = 0; s < n_slices; ++s) {
@@ -1096,7 +1142,8 @@ __global__ void reduce_locate_slices_kernel(const LocatePart *__restrict__ part,
 }
 
 // HITS: the opt-in pass (rb_hits_batch_device) that lists EVERY (bin, strand) whose count reached the threshold, with the count --
-// the sparse form of what seqan::count returns.  The kernel is ibf_locate_kernel up to the bit-sliced c > t-1 mask of a strand; then,
+// the sparse form of what seqan::count returns.  Up to the bit-sliced c > t-1 mask of a strand it runs what ibf_locate_kernel
+// runs, behind the same wave prologue (make_pass_wave); then,
 // while that strand's planes are still live (records are per strand so that only one strand's planes ever are):
 //   * the wave walks the words that hold a hit in rising bin order (columns rise with the lane, words with w, bins with the bit): a
 //     ballot finds the lanes, the lane's mask and planes travel as scalars (readlane), and lane j of the wave handles bin j of the word;
@@ -1117,24 +1164,17 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     __shared__ uint8_t s_stage[kWavesPerBlock][kStageBytes];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const uint64_t witem = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
-    // (scalar on purpose: the segment addresses below are then scalar arithmetic and cost no vector register across the gathers)
-    const uint32_t item = __builtin_amdgcn_readfirstlane((uint32_t)(witem / n_slices));
-    const uint32_t slice = __builtin_amdgcn_readfirstlane((uint32_t)(witem - (uint64_t)(uint32_t)(witem / n_slices) * n_slices));
+    uint32_t item, slice;
+    wave_item_slice<true>(n_slices, wave, &item, &slice);
     if (item >= n_items) return;  // wave-uniform; there are no block-level barriers below
-    {  // the status rules of the locate pass (reduce_locate_slices_kernel): such an item has no hits and feeds no profile
-        const uint32_t raw = src.lens[item];
-        if ((pre_status && pre_status[item] != RB_OK) || raw > src.max_len || raw < min_len) return;  // wave-uniform
-    }
+    // an item that is not RB_OK has no hits and feeds no profile
+    if (item_status(pre_status, item, src.lens[item], src.max_len, min_len) != RB_OK) return;  // wave-uniform
 
-    const LaneCols<WPL> lc = make_lane_cols<LG, WPL>(f, lane, col_begin, col_end, slice);
-    uint32_t len;
-    const BaseSrc seq = make_base_src(src, item, &len);
-    const uint32_t n = len >= f.k ? len - f.k + 1 : 0;
-    // the caller's threshold, or the one the decision kernel reads for this length and filter at the caller's error rate
-    const uint32_t tl = len < thr_len ? len : thr_len - 1;
-    const uint32_t t = min_count ? min_count : __builtin_amdgcn_readfirstlane((uint32_t)thr[((size_t)tl * nf + fi) * 2]);
-    const bool group0 = lane < (1 << LG);  // the lane group whose columns are reported (every group holds the same totals)
+    // t: the caller's threshold, or the one the decision kernel reads for this length and filter at the caller's error rate
+    const PassWave<WPL> pw = make_pass_wave<LG, WPL>(f, src, col_begin, col_end, item, slice, lane, thr, thr_len, nf, fi, min_count);
+    const LaneCols<WPL> &lc = pw.lc;
+    const uint32_t t = pw.t;
+    const bool group0 = pw.group0;
 
     uint64_t seen[WPL];  // hit on either strand: the only per-lane state that lives across the strands
 #pragma unroll
@@ -1143,7 +1183,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
         Planes<NP> pl[WPL];
 #pragma unroll
         for (int w = 0; w < WPL; ++w) pl[w].clear();
-        count_strand<LG, WPL, NP, H, NT>(pl, f, lc, seq, len, n, strand, 0u, (uint32_t)TileShape<LG>::ITEMS, 0, TileShape<LG>::STEPS / 8,
+        count_strand<LG, WPL, NP, H, NT>(pl, f, lc, pw.seq, pw.len, pw.n, strand, 0u, (uint32_t)TileShape<LG>::ITEMS, 0, TileShape<LG>::STEPS / 8,
                                          s_stage[wave], lane);
         // ---- bins with c >= t, i.e. c > t - 1
         uint64_t hit[WPL];
@@ -1197,7 +1237,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
                     }
                     if (set && pos < max_hits) {  // pos < max_hits: inside the segment
                         rb_u32x2 rec;
-                        rec.x = (col_begin + slice * (uint32_t)((1 << LG) * WPL) + (uint32_t)(from * WPL + w)) * 64u + (uint32_t)lane;
+                        rec.x = pw.word_col(from, w) * 64u + (uint32_t)lane;
                         rec.y = c | ((uint32_t)strand << 16);
                         out[pos] = rec;
                     }
@@ -1219,14 +1259,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
             for (int w = 0; w < WPL; ++w) {
                 const uint32_t mlo = readlane32((uint32_t)seen[w], from), mhi = readlane32((uint32_t)(seen[w] >> 32), from);
                 if (((lane < 32 ? mlo : mhi) >> (lane & 31)) & 1u)
-                    atomicAdd(bin_reads + ((size_t)(col_begin + slice * (uint32_t)((1 << LG) * WPL) + (uint32_t)(from * WPL + w)) * 64u + (uint32_t)lane), 1ULL);
+                    atomicAdd(bin_reads + ((size_t)pw.word_col(from, w) * 64u + (uint32_t)lane), 1ULL);
             }
         }
     }
 }
 
 // Finish one filter of a hits call: merge the column slices of an item (slices hold rising bins) and, inside a slice, the two strands'
-// sorted runs into (bin, strand) order; apply the per-item status (the locate pass's rules); write n_hits -- exact, whatever the cap --
+// sorted runs into (bin, strand) order; apply the per-item status (item_status); write n_hits -- exact, whatever the cap --
 // and the first min(n_hits, max_hits) records.  Slots beyond those are not written.  A run longer than the cap was cut at the cap by the
 // kernel above: the first max_hits of the merge need no more than the first max_hits of either run.  One thread per work item.
 __global__ void finish_hits_kernel(const rb_u32x2 *__restrict__ seg, const uint32_t *__restrict__ seg_count, uint32_t n_slices, uint32_t n_items,
@@ -1235,11 +1275,7 @@ __global__ void finish_hits_kernel(const rb_u32x2 *__restrict__ seg, const uint3
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_items) return;
-    uint8_t status = RB_OK;
-    const uint32_t len = lens[i];
-    if (pre_status && pre_status[i] != RB_OK) status = pre_status[i];
-    else if (len > max_len) status = RB_ERR_INVALID_ARG;
-    else if (len < min_len) status = RB_ERR_SHORT_READ;
+    const uint8_t status = (uint8_t)item_status(pre_status, i, lens[i], max_len, min_len);
     const size_t o = (size_t)i * nf + fidx;
     uint32_t total = 0, written = 0;
     if (status == RB_OK) {
@@ -1276,8 +1312,8 @@ __global__ void finish_hits_kernel(const rb_u32x2 *__restrict__ seg, const uint3
 //   * a tile's result per strand is __ballot(hit) -- the mask word the caller gets, stored by one lane -- and count, first, last, the
 //     longest run (the open run is carried from word to word) and the covered bases (the word smeared by k - 1 with doubling shifts
 //     over previous word : this word) are wave-uniform integer arithmetic on those words.  No atomics, no LDS beyond the staging.
-// Every output slot of a query is written, whatever its status: a query that is not RB_OK -- the item's status by the locate pass's
-// rules, or an item / bin that does not exist, which is tested here BEFORE anything is read through it -- gets n_kmers 0, a zero
+// Every output slot of a query is written, whatever its status: a query that is not RB_OK -- the item's status by item_status,
+// or an item / bin that does not exist, which is tested here BEFORE anything is read through it -- gets n_kmers 0, a zero
 // record with 0xFFFFFFFF positions and a zero mask.  Positions at or beyond 64 mask_words are left out of the mask only.
 constexpr int kSpanTiles = 4;                                        // tiles of 64 positions per round: 2 h kSpanTiles loads in flight per lane
 constexpr int kSpanStage = 64 * kSpanTiles + rbspec::kMaxKmer;       // bases staged per round
@@ -1425,12 +1461,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     uint32_t status = RB_OK;
     if (item >= n_items || bin >= f.n_bins) {
         status = RB_ERR_INVALID_ARG;
-    } else {  // the locate pass's rules (reduce_locate_slices_kernel)
-        const uint32_t raw = src.lens[item];
-        const uint32_t pre = pre_status ? (uint32_t)pre_status[item] : (uint32_t)RB_OK;
-        if (pre != RB_OK) status = pre;
-        else if (raw > src.max_len) status = RB_ERR_INVALID_ARG;
-        else if (raw < min_len) status = RB_ERR_SHORT_READ;
+    } else {
+        status = item_status(pre_status, item, src.lens[item], src.max_len, min_len);
     }
     status = __builtin_amdgcn_readfirstlane(status);
 
@@ -3155,8 +3187,37 @@ __global__ __launch_bounds__(64 * kAsmWaves, 4) void ibf_assemble_kernel(AsmLaun
 
 // ---------------------------------------------------------------------------------------------
 // launchers
-template <int LG, int WPL, int NP, int H, bool NT>
-static hipError_t launch_count_nt(const CountLaunch &a, hipStream_t st)
+// Run-time geometry -> compile-time constants, once for every kernel family: fn(int_c<LG>, int_c<WPL>) over the blocks of 2^LG lanes with
+// one word per lane and the whole-wave block with two ...
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <typename F>
+static hipError_t dispatch_lg_wpl(int lg, int wpl, F &&fn)
+{
+    if (wpl == 2) return fn(int_c<6>{}, int_c<2>{});
+    switch (lg) {
+    case 0: return fn(int_c<0>{}, int_c<1>{});
+    case 1: return fn(int_c<1>{}, int_c<1>{});
+    case 2: return fn(int_c<2>{}, int_c<1>{});
+    case 3: return fn(int_c<3>{}, int_c<1>{});
+    case 4: return fn(int_c<4>{}, int_c<1>{});
+    case 5: return fn(int_c<5>{}, int_c<1>{});
+    default: return fn(int_c<6>{}, int_c<1>{});
+    }
+}
+// ... and on top of it the counter planes and hash count of the plain-form kernels (count, locate, hits): fn(LG, WPL, int_c<NP>, int_c<H>),
+// ten planes only with the compile-time three hash functions; H = 0 is the run-time hash count
+template <typename F>
+static hipError_t dispatch_planes_hash(uint32_t n_hash, int planes, int lg, int wpl, F &&fn)
+{
+    auto with = [&](auto np, auto h) { return dispatch_lg_wpl(lg, wpl, [&](auto LG, auto WPL) { return fn(LG, WPL, np, h); }); };
+    if (n_hash == 3) return planes <= 10 ? with(int_c<10>{}, int_c<3>{}) : with(int_c<16>{}, int_c<3>{});
+    return with(int_c<16>{}, int_c<0>{});
+}
+
+// The filters of a launch as the count kernels take them: the fused ones, or the launch's own as a set of one; for the latency form
+// (split) with each filter's geometry code, parts and shares.
+static FilterSet make_filter_set(const CountLaunch &a, bool split)
 {
     FilterSet set;
     set.n = a.n_fused > 0 ? (uint32_t)a.n_fused : 1u;
@@ -3166,13 +3227,29 @@ static hipError_t launch_count_nt(const CountLaunch &a, hipStream_t st)
             set.col_begin[i] = a.fused_col_begin[i];
             set.col_end[i] = a.fused_col_end[i];
             set.out_offset[i] = a.fused_out_offset[i];
+            if (!split) continue;
+            set.geom[i] = a.fused_geom[i];
+            set.parts[i] = a.fused_parts[i];
+            set.sub[i] = a.fused_sub[i];
         }
     } else {
         set.f[0] = a.f;
         set.col_begin[0] = a.col_begin;
         set.col_end[0] = a.col_end;
         set.out_offset[0] = 0;
+        if (split) {
+            set.geom[0] = geom_code(a.lg, a.wpl, a.nt);
+            set.parts[0] = (uint32_t)(a.split_parts > 1 ? a.split_parts : 1);
+            set.sub[0] = (uint32_t)(a.split_sub > 1 ? a.split_sub : 1);
+        }
     }
+    return set;
+}
+
+template <int LG, int WPL, int NP, int H, bool NT>
+static hipError_t launch_count_nt(const CountLaunch &a, hipStream_t st)
+{
+    const FilterSet set = make_filter_set(a, false);
     const uint64_t items = (uint64_t)a.n_reads * a.n_slices;
     dim3 grid((uint32_t)((items + kWavesPerBlock - 1) / kWavesPerBlock), set.n);
     EarlyCfg early{};
@@ -3233,46 +3310,10 @@ static hipError_t launch_split_one(const FilterSet &set, const CountLaunch &a, u
     return launch_split_kernel(ibf_count_max_split_kernel<LG, WPL, NP, 3, NT>, done, set, a, WPL, NP, grid_parts, st);
 }
 
-template <int NP, bool NT>
-static hipError_t launch_split_same(int lg, int wpl, const FilterSet &set, const CountLaunch &a, uint32_t grid_parts,
-                                    hipStream_t st)
-{
-    if (wpl == 2) return launch_split_one<6, 2, NP, NT>(set, a, grid_parts, st);
-    switch (lg) {
-    case 0: return launch_split_one<0, 1, NP, NT>(set, a, grid_parts, st);
-    case 1: return launch_split_one<1, 1, NP, NT>(set, a, grid_parts, st);
-    case 2: return launch_split_one<2, 1, NP, NT>(set, a, grid_parts, st);
-    case 3: return launch_split_one<3, 1, NP, NT>(set, a, grid_parts, st);
-    case 4: return launch_split_one<4, 1, NP, NT>(set, a, grid_parts, st);
-    case 5: return launch_split_one<5, 1, NP, NT>(set, a, grid_parts, st);
-    default: return launch_split_one<6, 1, NP, NT>(set, a, grid_parts, st);
-    }
-}
-
 template <int NP>
 static hipError_t launch_split(const CountLaunch &a, hipStream_t st)
 {
-    FilterSet set;
-    set.n = a.n_fused > 0 ? (uint32_t)a.n_fused : 1u;
-    if (a.n_fused > 0) {
-        for (uint32_t i = 0; i < set.n; ++i) {
-            set.f[i] = a.fused_f[i];
-            set.col_begin[i] = a.fused_col_begin[i];
-            set.col_end[i] = a.fused_col_end[i];
-            set.out_offset[i] = a.fused_out_offset[i];
-            set.geom[i] = a.fused_geom[i];
-            set.parts[i] = a.fused_parts[i];
-            set.sub[i] = a.fused_sub[i];
-        }
-    } else {
-        set.f[0] = a.f;
-        set.col_begin[0] = a.col_begin;
-        set.col_end[0] = a.col_end;
-        set.out_offset[0] = 0;
-        set.geom[0] = geom_code(a.lg, a.wpl, a.nt);
-        set.parts[0] = (uint32_t)(a.split_parts > 1 ? a.split_parts : 1);
-        set.sub[0] = (uint32_t)(a.split_sub > 1 ? a.split_sub : 1);
-    }
+    const FilterSet set = make_filter_set(a, true);
     const uint32_t grid_parts = a.grid_parts > 1 ? (uint32_t)a.grid_parts : 1u;
     bool same = true, wide = false;
     for (uint32_t i = 0; i < set.n; ++i) {
@@ -3286,8 +3327,10 @@ static hipError_t launch_split(const CountLaunch &a, hipStream_t st)
     const int cap = same ? split_waves_cap(wpl, NP, lg) : kSplitAnyWaves;
     if (nw < 2 || (nw & 1) || nw > cap) return hipErrorInvalidValue;
     if (same)
-        return (set.geom[0] & 16) ? launch_split_same<NP, true>(lg, wpl, set, a, grid_parts, st)
-                                  : launch_split_same<NP, false>(lg, wpl, set, a, grid_parts, st);
+        return dispatch_lg_wpl(lg, wpl, [&](auto LG, auto WPL) {
+            constexpr int L = decltype(LG)::value, W = decltype(WPL)::value;
+            return (set.geom[0] & 16) ? launch_split_one<L, W, NP, true>(set, a, grid_parts, st) : launch_split_one<L, W, NP, false>(set, a, grid_parts, st);
+        });
     static std::atomic<uint64_t> done[2];
     if (wide) return launch_split_kernel(ibf_count_max_split_any_kernel<NP, true>, done[1], set, a, 2, NP, grid_parts, st);
     return launch_split_kernel(ibf_count_max_split_any_kernel<NP, false>, done[0], set, a, 1, NP, grid_parts, st);
@@ -3359,21 +3402,6 @@ int split_parts_plan(int wpl, int planes, uint32_t max_kmers, int lg, uint32_t n
         }
     }
     return 1;
-}
-
-template <int NP, int H>
-static hipError_t dispatch_geometry(const CountLaunch &a, hipStream_t st)
-{
-    if (a.wpl == 2) return launch_count<6, 2, NP, H>(a, st);
-    switch (a.lg) {
-    case 0: return launch_count<0, 1, NP, H>(a, st);
-    case 1: return launch_count<1, 1, NP, H>(a, st);
-    case 2: return launch_count<2, 1, NP, H>(a, st);
-    case 3: return launch_count<3, 1, NP, H>(a, st);
-    case 4: return launch_count<4, 1, NP, H>(a, st);
-    case 5: return launch_count<5, 1, NP, H>(a, st);
-    default: return launch_count<6, 1, NP, H>(a, st);
-    }
 }
 
 template <int LG, int NP>
@@ -3499,11 +3527,9 @@ hipError_t launch_ibf_count_max(const CountLaunch &a, hipStream_t st)
         if (a.f.n_hash != 3) return hipErrorInvalidValue;
         return a.planes <= 10 ? launch_split<10>(a, st) : launch_split<16>(a, st);
     }
-    if (a.f.n_hash == 3) {
-        if (a.planes <= 10) return dispatch_geometry<10, 3>(a, st);
-        return dispatch_geometry<16, 3>(a, st);
-    }
-    return dispatch_geometry<16, 0>(a, st);
+    return dispatch_planes_hash(a.f.n_hash, a.planes, a.lg, a.wpl, [&](auto LG, auto WPL, auto NP, auto H) {
+        return launch_count<decltype(LG)::value, decltype(WPL)::value, decltype(NP)::value, decltype(H)::value>(a, st);
+    });
 }
 
 template <int LG, int NP>
@@ -3557,50 +3583,45 @@ hipError_t launch_invert_words(const uint64_t *src, uint64_t *dst, uint64_t n_wo
     return hipGetLastError();
 }
 
-// locate: the (LG, WPL) cases of dispatch_geometry; non-temporal builds for blocks of a whole wave only (the tables beyond the Infinity
-// Cache are the wide ones; a narrow table of that size keeps the default cache policy, which costs speed, not results)
-template <int LG, int WPL, int NP, int H>
-static hipError_t launch_locate_nt(const LocateLaunch &a, hipStream_t st)
+// locate and hits: one launch of a plain query pass.  A wave per (item, slice), the build picked as the count kernel's is; non-temporal
+// builds for blocks of a whole wave only (the tables beyond the Infinity Cache are the wide ones; a narrow table of that size keeps the
+// default cache policy, which costs speed, not results).  Pass::kernel<LG, WPL, NP, H, NT>() names the pass's kernel, `more` are its own
+// arguments behind the shared ones.
+struct LocatePass {
+    template <int LG, int WPL, int NP, int H, bool NT>
+    static constexpr auto kernel() { return &ibf_locate_kernel<LG, WPL, NP, H, NT>; }
+};
+struct HitsPass {
+    template <int LG, int WPL, int NP, int H, bool NT>
+    static constexpr auto kernel() { return &ibf_hits_kernel<LG, WPL, NP, H, NT>; }
+};
+template <typename Pass, typename... More>
+static hipError_t launch_plain_pass(const PlainPassLaunch &a, hipStream_t st, More... more)
 {
+    if (!a.thr || a.thr_len == 0 || a.n_slices == 0 || (a.wpl != 1 && a.wpl != 2) || a.lg < 0 || a.lg > 6) return hipErrorInvalidValue;
+    // every column the grid reaches lies inside the filter, every slice has its record / its segments
+    if (a.col_end > a.f.bin_width || a.col_begin > a.col_end ||
+        (uint64_t)a.n_slices * (uint64_t)((1u << a.lg) * (uint32_t)a.wpl) < (uint64_t)(a.col_end - a.col_begin))
+        return hipErrorInvalidValue;
     const uint64_t items = (uint64_t)a.n_items * a.n_slices;
-    dim3 grid((uint32_t)((items + kWavesPerBlock - 1) / kWavesPerBlock));
-    if constexpr (LG == 6) {
-        if (a.nt) {
-            hipLaunchKernelGGL((ibf_locate_kernel<LG, WPL, NP, H, true>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.col_begin, a.col_end, a.src,
-                               a.n_items, a.n_slices, a.thr, a.thr_len, a.nf, a.fi, a.part);
-            return hipGetLastError();
+    const dim3 grid((uint32_t)((items + kWavesPerBlock - 1) / kWavesPerBlock));
+    return dispatch_planes_hash(a.f.n_hash, a.planes, a.lg, a.wpl, [&](auto LG, auto WPL, auto NP, auto H) {
+        constexpr int L = decltype(LG)::value, W = decltype(WPL)::value, P = decltype(NP)::value, HH = decltype(H)::value;
+        auto kern = Pass::template kernel<L, W, P, HH, false>();
+        if constexpr (L == 6) {
+            if (a.nt) kern = Pass::template kernel<L, W, P, HH, true>();
         }
-    }
-    hipLaunchKernelGGL((ibf_locate_kernel<LG, WPL, NP, H, false>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.col_begin, a.col_end, a.src,
-                       a.n_items, a.n_slices, a.thr, a.thr_len, a.nf, a.fi, a.part);
-    return hipGetLastError();
-}
-
-template <int NP, int H>
-static hipError_t dispatch_locate(const LocateLaunch &a, hipStream_t st)
-{
-    if (a.wpl == 2) return launch_locate_nt<6, 2, NP, H>(a, st);
-    switch (a.lg) {
-    case 0: return launch_locate_nt<0, 1, NP, H>(a, st);
-    case 1: return launch_locate_nt<1, 1, NP, H>(a, st);
-    case 2: return launch_locate_nt<2, 1, NP, H>(a, st);
-    case 3: return launch_locate_nt<3, 1, NP, H>(a, st);
-    case 4: return launch_locate_nt<4, 1, NP, H>(a, st);
-    case 5: return launch_locate_nt<5, 1, NP, H>(a, st);
-    default: return launch_locate_nt<6, 1, NP, H>(a, st);
-    }
+        hipLaunchKernelGGL(kern, grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.col_begin, a.col_end, a.src, a.n_items, a.n_slices, a.thr,
+                           a.thr_len, a.nf, a.fi, more...);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_ibf_locate(const LocateLaunch &a, hipStream_t st)
 {
     if (a.n_items == 0) return hipSuccess;
-    if (!a.thr || a.thr_len == 0 || !a.part || a.n_slices == 0 || (a.wpl != 1 && a.wpl != 2) || a.lg < 0 || a.lg > 6) return hipErrorInvalidValue;
-    // every column the grid reaches lies inside the filter, every slice has a record
-    if (a.col_end > a.f.bin_width || a.col_begin > a.col_end ||
-        (uint64_t)a.n_slices * (uint64_t)((1u << a.lg) * (uint32_t)a.wpl) < (uint64_t)(a.col_end - a.col_begin))
-        return hipErrorInvalidValue;
-    if (a.f.n_hash == 3) return a.planes <= 10 ? dispatch_locate<10, 3>(a, st) : dispatch_locate<16, 3>(a, st);
-    return dispatch_locate<16, 0>(a, st);
+    if (!a.part) return hipErrorInvalidValue;
+    return launch_plain_pass<LocatePass>(a, st, a.part);
 }
 
 hipError_t launch_reduce_locate_slices(const LocatePart *part, uint32_t n_slices, uint32_t n_items, const uint32_t *lens,
@@ -3613,52 +3634,12 @@ hipError_t launch_reduce_locate_slices(const LocatePart *part, uint32_t n_slices
     return hipGetLastError();
 }
 
-// hits: the builds of the locate pass, case for case
-template <int LG, int WPL, int NP, int H>
-static hipError_t launch_hits_nt(const HitsLaunch &a, hipStream_t st)
-{
-    const uint64_t items = (uint64_t)a.n_items * a.n_slices;
-    dim3 grid((uint32_t)((items + kWavesPerBlock - 1) / kWavesPerBlock));
-    if constexpr (LG == 6) {
-        if (a.nt) {
-            hipLaunchKernelGGL((ibf_hits_kernel<LG, WPL, NP, H, true>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.col_begin, a.col_end, a.src,
-                               a.n_items, a.n_slices, a.thr, a.thr_len, a.nf, a.fi, a.min_count, a.max_hits, a.min_len, a.pre_status,
-                               (rb_u32x2 *)a.seg, a.seg_count, (unsigned long long *)a.bin_reads);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((ibf_hits_kernel<LG, WPL, NP, H, false>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.col_begin, a.col_end, a.src,
-                       a.n_items, a.n_slices, a.thr, a.thr_len, a.nf, a.fi, a.min_count, a.max_hits, a.min_len, a.pre_status,
-                       (rb_u32x2 *)a.seg, a.seg_count, (unsigned long long *)a.bin_reads);
-    return hipGetLastError();
-}
-
-template <int NP, int H>
-static hipError_t dispatch_hits(const HitsLaunch &a, hipStream_t st)
-{
-    if (a.wpl == 2) return launch_hits_nt<6, 2, NP, H>(a, st);
-    switch (a.lg) {
-    case 0: return launch_hits_nt<0, 1, NP, H>(a, st);
-    case 1: return launch_hits_nt<1, 1, NP, H>(a, st);
-    case 2: return launch_hits_nt<2, 1, NP, H>(a, st);
-    case 3: return launch_hits_nt<3, 1, NP, H>(a, st);
-    case 4: return launch_hits_nt<4, 1, NP, H>(a, st);
-    case 5: return launch_hits_nt<5, 1, NP, H>(a, st);
-    default: return launch_hits_nt<6, 1, NP, H>(a, st);
-    }
-}
-
 hipError_t launch_ibf_hits(const HitsLaunch &a, hipStream_t st)
 {
     if (a.n_items == 0) return hipSuccess;
-    if (!a.thr || a.thr_len == 0 || !a.seg_count || (a.max_hits && !a.seg) || a.n_slices == 0 || (a.wpl != 1 && a.wpl != 2) || a.lg < 0 || a.lg > 6)
-        return hipErrorInvalidValue;
-    // every column the grid reaches lies inside the filter, every slice has its segments
-    if (a.col_end > a.f.bin_width || a.col_begin > a.col_end ||
-        (uint64_t)a.n_slices * (uint64_t)((1u << a.lg) * (uint32_t)a.wpl) < (uint64_t)(a.col_end - a.col_begin))
-        return hipErrorInvalidValue;
-    if (a.f.n_hash == 3) return a.planes <= 10 ? dispatch_hits<10, 3>(a, st) : dispatch_hits<16, 3>(a, st);
-    return dispatch_hits<16, 0>(a, st);
+    if (!a.seg_count || (a.max_hits && !a.seg)) return hipErrorInvalidValue;
+    return launch_plain_pass<HitsPass>(a, st, a.min_count, a.max_hits, a.min_len, a.pre_status, (rb_u32x2 *)a.seg, a.seg_count,
+                                       (unsigned long long *)a.bin_reads);
 }
 
 hipError_t launch_finish_hits(const HitsLaunch &a, const uint32_t *lens, const HitsOut &out, hipStream_t st)

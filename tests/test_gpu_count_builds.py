@@ -20,7 +20,7 @@ from readbouncer_amd import capi
 from tests import helpers as H
 
 ORACLE_THREADS = 16
-# kernel geometries: (log2 lanes per block, words per lane), as rb_kernels.hip dispatch_geometry / launch_split_same select them
+# kernel geometries: (log2 lanes per block, words per lane), as rb_kernels.hip dispatch_lg_wpl selects them
 GEOMS = ((0, 1), (1, 1), (2, 1), (3, 1), (4, 1), (5, 1), (6, 1), (6, 2))
 
 
@@ -28,8 +28,8 @@ def _geom(lg, wpl):
     return "LG=%d,WPL=%d" % (lg, wpl)
 
 
-# every instantiation of the long-read builds the launchers can select (rb_kernels.hip: launch_ibf_count_max, dispatch_geometry,
-# launch_count_nt, launch_split / launch_split_same, the fall-through of launch_phased, launch_ibf_count_max_merged)
+# every instantiation of the long-read builds the launchers can select (rb_kernels.hip: launch_ibf_count_max, dispatch_planes_hash,
+# launch_count_nt, launch_split, the fall-through of launch_phased, launch_ibf_count_max_merged)
 EXPECTED_BUILDS = set()
 for _lg, _wpl in GEOMS:
     for _nt in (0, 1):
@@ -279,7 +279,7 @@ def build_of(p, h, form, kmers):
         return "phased<LG=%d,NP=%d,general>" % (p["lanes_per_block_log2"], np_)
     assert kernel == "ibf_count_max_kernel", p
     if h != 3:
-        return "plain<%s,NP=16,generic,NT=%d>" % (g, nt)  # (dispatch_geometry<16, 0> at any read length)
+        return "plain<%s,NP=16,generic,NT=%d>" % (g, nt)  # (dispatch_planes_hash: 16 planes, run-time hashes, at any read length)
     if form.startswith("early") and np_ == 10:
         return "early<%s,NP=10,h=3,NT=%d>" % (g, nt)
     return "plain<%s,NP=%d,h=3,NT=%d>" % (g, np_, nt)
