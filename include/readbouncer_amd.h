@@ -446,6 +446,45 @@ RB_API int rb_spans_batch(rb_engine *e, const char *seqs, const uint64_t *offset
                           const uint32_t *read_ids, size_t n_items, size_t filter, const rb_span_query *queries, size_t n_queries,
                           uint32_t mask_words, const rb_spans_out *out);
 
+/* ---- prefixes: the decision at EVERY prefix checkpoint of a read, from one pass over its k-mers -----
+ * The reference's live loop concatenates a read's chunks and runs check_unblock again on the whole grown prefix
+ * (src/main/adaptive_sampling.hpp:280-331; classify_reads does the same per chunk, src/main/classify.hpp:262-299): the decision
+ * for a read is a function of the prefix length, and not a monotone one -- the threshold grows with the length.  seqan::count adds
+ * one per k-mer, so the per-bin counters after the k-mers of a prefix are exactly the counts of that prefix, on both strands (the
+ * reverse complement of a prefix consists of the reverse complements of the prefix's own windows); one pass over the longest
+ * checkpoint, with the maximum over bins taken at each checkpoint, yields every row, where P calls of rb_classify_batch_device_ex
+ * would gather the sum of the checkpoints' worth of filter lines.
+ * prefix_lens: n_prefixes (1 to RB_PREFIX_MAX) checkpoints c_0 < c_1 < ... in bases, none 0, counted from chunk_start; a HOST array
+ * in both forms.  ROW (work item i, checkpoint p) holds exactly what rb_classify_batch_device_ex writes for work item i with the same
+ * descriptor, error rate, significance and mode, but chunk_length replaced by c_p (by min(c_p, desc->chunk_length) when the descriptor
+ * has one): decision, best target and status -- RB_ERR_SHORT_READ for a prefix shorter than k, RB_ERR_BAD_CHUNK, RB_ERR_INVALID_ARG for a
+ * row longer than max_len included -- and max_count wherever the row's status is RB_OK.  A checkpoint at or beyond the item's end
+ * repeats the whole-item row; prefix_len says so.  All three modes.
+ * Like locate an opt-in pass of its own: it always counts in full from each filter's own table, whatever the engine's pruning /
+ * early-decision / merge / phased settings are, and changes nothing any other call returns.
+ * RB_ERR_INVALID_ARG, with an rb_last_error() that names the fault: null arguments, n_prefixes of 0 or above RB_PREFIX_MAX, a
+ * checkpoint of 0, a list that is not strictly rising, an rb_prefix_out with no output, an unknown mode, a column-sharded engine. */
+#define RB_PREFIX_MAX 64
+typedef struct rb_prefix_out {   /* any member may be NULL, not all */
+    void *max_count;      /* u16 [n_items x n_prefixes x n_filters], deplete filters first */
+    void *decision;       /* u8  [n_items x n_prefixes], per rb_mode */
+    void *best_target;    /* i32 [n_items x n_prefixes] */
+    void *status;         /* u8  [n_items x n_prefixes] */
+    void *prefix_len;     /* u32 [n_items x n_prefixes]: bases the row stands for = min(c_p, bases the descriptor selects for the item) */
+    void *first_decided;  /* u32 [n_items]: lowest p with status RB_OK and decision != 0; n_prefixes when there is none */
+} rb_prefix_out;
+/* Device pointers (prefix_lens: host), asynchronous on `stream` (NULL = the engine's own stream, synchronised before returning);
+ * rb_batch_desc in full.  Workspaces are the engine's (S x n_items x n_prefixes partial maxima of 2 bytes, S = the most column
+ * slices of any filter, plus the rows the caller left out): one stream per engine, as for rb_classify_batch_device. */
+RB_API int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32_t *prefix_lens, uint32_t n_prefixes,
+                                  double error_rate, double significance, int mode, const rb_prefix_out *d_out, void *stream);
+/* Host buffers; read_ids / n_items as in rb_locate_batch.  The reads are uploaded once; large calls are processed in sub-batches
+ * so that the device workspace and the staged outputs together stay at or below 256 MiB (one work item at a time where a single
+ * item needs more). */
+RB_API int rb_prefix_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads,
+                           const uint32_t *read_ids, size_t n_items, const uint32_t *prefix_lens, uint32_t n_prefixes,
+                           double error_rate, double significance, int mode, const rb_prefix_out *out);
+
 /* bin-sharded operation: restrict the engine to word columns
  * [rank*ceil(W/world) , ...) of every block; out_maxcount then holds PARTIAL maxima that the
  * caller combines with an all-reduce(max) before rb_decide_device. world=1 restores the default. */

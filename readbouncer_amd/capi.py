@@ -30,6 +30,15 @@ class LocateOut(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class PrefixOut(C.Structure):
+    """rb_prefix_out: any member may be NULL, not all"""
+    _fields_ = [("max_count", C.c_void_p), ("decision", C.c_void_p), ("best_target", C.c_void_p), ("status", C.c_void_p),
+                ("prefix_len", C.c_void_p), ("first_decided", C.c_void_p)]
+
+
+RB_PREFIX_MAX = 64
+
+
 class Hit(C.Structure):
     """rb_hit: one (bin, strand) at or above the threshold and its count -- 8 bytes"""
     _fields_ = [("bin", C.c_uint32), ("count", C.c_uint16), ("strand", C.c_uint8), ("reserved", C.c_uint8)]
@@ -152,6 +161,8 @@ SIGNATURES = {
     "rb_classify_batch_device_ex": (_int, [_vp, C.POINTER(BatchDesc), _dbl, _dbl, _int, _vp, _vp, _vp, _vp, _vp]),
     "rb_locate_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _dbl, _dbl, C.POINTER(LocateOut), _vp]),
     "rb_locate_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _dbl, _dbl, C.POINTER(LocateOut)]),
+    "rb_prefix_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _dbl, _dbl, _int, C.POINTER(PrefixOut), _vp]),
+    "rb_prefix_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, C.c_uint32, _dbl, _dbl, _int, C.POINTER(PrefixOut)]),
     "rb_hits_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _dbl, _dbl, C.c_uint16, C.c_uint32, C.POINTER(HitsOut), _vp]),
     "rb_hits_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _dbl, _dbl, C.c_uint16, C.c_uint32, C.POINTER(HitsOut)]),
     "rb_spans_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _sz, _vp, _sz, C.c_uint32, C.POINTER(SpansOut), _vp]),
@@ -571,6 +582,36 @@ class Engine:
         out = LocateOut(d_max_count, d_best_bin, d_best_strand, d_hit_bins, d_status)
         _check(lib().rb_locate_batch_device(self.h, C.byref(desc), error_rate, significance, C.byref(out), stream),
                "rb_locate_batch_device")
+
+    def prefixes(self, seqs, offsets, lens, prefix_lens, read_ids=None, error_rate=0.1, significance=0.95, mode=RB_MODE_CHECK_UNBLOCK):
+        """the maxima and the decision of each selected read at every prefix checkpoint, from one pass over its k-mers
+        (rb_prefix_batch): host buffers in, a dict of host numpy arrays out -- max_count[n, P, nf] u16, decision[n, P] u8,
+        best_target[n, P] i32, status[n, P] u8, prefix_len[n, P] u32, first_decided[n] u32, one row per (work item, checkpoint)"""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        cps = np.ascontiguousarray(prefix_lens, dtype=np.uint32)
+        ids = None if read_ids is None else np.ascontiguousarray(read_ids, dtype=np.uint32)
+        n = len(lens) if ids is None else len(ids)
+        nf, P = self.nd + self.nt, len(cps)
+        res = {"max_count": np.zeros((n, P, nf), dtype=np.uint16), "decision": np.zeros((n, P), dtype=np.uint8),
+               "best_target": np.full((n, P), -1, dtype=np.int32), "status": np.zeros((n, P), dtype=np.uint8),
+               "prefix_len": np.zeros((n, P), dtype=np.uint32), "first_decided": np.full(n, P, dtype=np.uint32)}
+        out = PrefixOut(*[_ptr(res[k]) for k in ("max_count", "decision", "best_target", "status", "prefix_len", "first_decided")])
+        _check(lib().rb_prefix_batch(self.h, _ptr(seqs), _ptr(offsets), _ptr(lens), len(lens), None if ids is None else _ptr(ids), n,
+                                     _ptr(cps), P, error_rate, significance, mode, C.byref(out)), "rb_prefix_batch")
+        return res
+
+    def prefixes_device(self, d_seqs, d_offsets, d_lens, n_items, max_len, prefix_lens, d_nmask=None, d_nmask_offsets=None, chunk_start=0,
+                        chunk_length=0, d_read_ids=None, error_rate=0.1, significance=0.95, mode=RB_MODE_CHECK_UNBLOCK, d_max_count=None,
+                        d_decision=None, d_best_target=None, d_status=None, d_prefix_len=None, d_first_decided=None, stream=None):
+        """raw device pointers like locate_device (rb_prefix_batch_device; prefix_lens is a host sequence); any output may be None, not all"""
+        cps = np.ascontiguousarray(prefix_lens, dtype=np.uint32)
+        desc = BatchDesc(d_seqs, d_offsets, d_lens, n_items, max_len, d_nmask, d_nmask_offsets, chunk_start, chunk_length,
+                         d_read_ids)
+        out = PrefixOut(d_max_count, d_decision, d_best_target, d_status, d_prefix_len, d_first_decided)
+        _check(lib().rb_prefix_batch_device(self.h, C.byref(desc), _ptr(cps), len(cps), error_rate, significance, mode, C.byref(out), stream),
+               "rb_prefix_batch_device")
 
     def hits(self, seqs, offsets, lens, read_ids=None, error_rate=0.1, significance=0.95, min_count=0, max_hits=64, bin_reads=None,
              hits=None):

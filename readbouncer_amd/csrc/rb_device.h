@@ -252,6 +252,25 @@ hipError_t launch_reduce_locate_slices(const LocatePart *part, uint32_t n_slices
                                        const uint8_t *pre_status, uint32_t max_len, uint32_t min_len, const LocateOut &out, uint32_t nf,
                                        uint32_t fidx, hipStream_t st);
 
+// prefix pass (rb_prefix_batch_device; rb_kernels.hip, ibf_prefix_kernel): the checkpoints, strictly rising and none 0, as a by-value
+// kernel argument ...
+constexpr uint32_t kMaxPrefixes = 64;  // == RB_PREFIX_MAX: checkpoint p's maximum lives in lane p
+struct PrefixList {
+    uint32_t n;
+    uint32_t c[kMaxPrefixes];
+};
+// ... and one filter's launch
+struct PrefixLaunch : PlainPassLaunch {
+    PrefixList cps;
+    uint16_t *part;  // [n_slices][n_items][cps.n]
+};
+hipError_t launch_ibf_prefix(const PrefixLaunch &a, hipStream_t st);
+// max_count [n_items][cps.n][nf] <- the maximum over the slices; for fidx == 0 also prefix_len / row_pre [n_items][cps.n]
+hipError_t launch_finish_prefix(const PrefixLaunch &a, const uint32_t *lens, const uint8_t *pre_status, uint16_t *max_count, uint32_t *prefix_len,
+                                uint8_t *row_pre, hipStream_t st);
+hipError_t launch_first_decided(const uint8_t *decision, const uint8_t *status, uint32_t n_items, uint32_t n_prefixes, uint32_t *first_decided,
+                                hipStream_t st);
+
 // hits pass (rb_hits_batch_device; rb_kernels.hip, ibf_hits_kernel): a record as the kernels move it -- x = bin, y = count | strand << 16,
 // the eight bytes of rb_hit ...
 typedef unsigned int rb_u32x2 __attribute__((ext_vector_type(2)));

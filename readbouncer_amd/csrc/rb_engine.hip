@@ -426,6 +426,8 @@ struct rb_engine {
     DevBuf d_hits_ws;               // hits pass: the (item, slice, strand) record segments and their counters, one filter at a time
     DevBuf d_hits_io;               // rb_hits_batch: read ids in, records / n_hits / status / bin_reads back
     DevBuf d_spans_io;              // rb_spans_batch: read ids and queries in, masks / records / n_kmers / status back
+    DevBuf d_prefix_ws;             // prefix pass: partial maxima of the column slices (one filter at a time), the rows' lengths and pre-status, outputs the caller left out
+    DevBuf d_prefix_io;             // rb_prefix_batch: read ids in, the six outputs back
     PinnedBuf h_in, h_out;
     // large host batches: slice i+1 is copied on this stream while slice i is counted on `stream`
     hipStream_t copy_stream = nullptr;
@@ -1185,7 +1187,7 @@ void rb_engine_destroy(rb_engine *e)
     }
     for (void *r : e->thr_retired_dev) (void)hipFree(r);
     for (PinnedBuf &h : e->thr_retired_host) h.release();
-    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_locate_parts, &e->d_locate_io, &e->d_hits_ws, &e->d_hits_io, &e->d_spans_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
+    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_locate_parts, &e->d_locate_io, &e->d_hits_ws, &e->d_hits_io, &e->d_spans_io, &e->d_prefix_ws, &e->d_prefix_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
                       &e->d_decision, &e->d_status})
         b->release();
     e->h_in.release();
@@ -3045,6 +3047,187 @@ int rb_locate_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, con
     if (out->hit_bins) RB_HIP(hipMemcpyAsync(out->hit_bins, io + o_hit, 4 * n * nf, hipMemcpyDeviceToHost, st));
     if (out->status) RB_HIP(hipMemcpyAsync(out->status, io + o_status, n, hipMemcpyDeviceToHost, st));
     RB_HIP(hipStreamSynchronize(st));
+    return RB_OK;
+}
+
+// ---- prefixes: a work item's maxima and decision at every prefix checkpoint, from one walk over its k-mers (see the boundary header).
+// Always the plain form over each filter's OWN table, counted in full, like locate.  Per filter one launch of ibf_prefix_kernel plus the
+// merge of its column slices, in sequence on the call's stream (one block of partial maxima, sized for the filter with the most slices,
+// serves every filter); then the decision kernel itself over the n_items x P rows, with the rows' prefix lengths as its `lens`.
+static int check_prefix_args(const rb_prefix_out *out, const uint32_t *prefix_lens, uint32_t n_prefixes, int mode)
+{
+    if (!out) return rb::fail(RB_ERR_INVALID_ARG, "null output struct");
+    if (!prefix_lens) return rb::fail(RB_ERR_INVALID_ARG, "null checkpoint list");
+    if (n_prefixes == 0 || n_prefixes > RB_PREFIX_MAX) return rb::fail(RB_ERR_INVALID_ARG, "n_prefixes must be 1 to 64");
+    for (uint32_t p = 0; p < n_prefixes; ++p) {
+        if (prefix_lens[p] == 0) return rb::fail(RB_ERR_INVALID_ARG, "a checkpoint of 0 bases");
+        if (p && prefix_lens[p] <= prefix_lens[p - 1]) return rb::fail(RB_ERR_INVALID_ARG, "checkpoints must be strictly rising");
+    }
+    if (!out->max_count && !out->decision && !out->best_target && !out->status && !out->prefix_len && !out->first_decided)
+        return rb::fail(RB_ERR_INVALID_ARG, "rb_prefix_out with no output");
+    if (mode != RB_MODE_CHECK_UNBLOCK && mode != RB_MODE_CLASSIFY_CHUNK && mode != RB_MODE_CLASSIFY_ANY)
+        return rb::fail(RB_ERR_INVALID_ARG, "unknown mode");
+    return RB_OK;
+}
+
+static int prefix_device_impl(rb_engine *e, const rb_batch_desc *desc, const uint32_t *prefix_lens, uint32_t n_prefixes, double error_rate,
+                              double significance, int mode, const rb_prefix_out *d_out, void *stream)
+{
+    if (!desc) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor");
+    int rc = check_prefix_args(d_out, prefix_lens, n_prefixes, mode);
+    if (rc != RB_OK) return rc;
+    if ((rc = check_pass_call(e, desc, 0)) != RB_OK) return rc;
+    const size_t n_items = desc->n_items;
+    if (n_items == 0) return RB_OK;
+    const size_t P = n_prefixes, rows = n_items * P;
+    if (rows >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    if ((rc = check_desc_buffers(desc, false)) != RB_OK) return rc;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if ((rc = refuse_sharded(e, "prefixes")) != RB_OK) return rc;
+    const size_t nf = e->filters.size();
+    if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
+    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+    PassInput in;
+    if ((rc = prepare_pass_input(e, desc, st, &in)) != RB_OK) return rc;
+    // no row is longer than the last checkpoint: the bound of the rows (counter planes, threshold table, the decision kernel's max_len)
+    in.max_len = std::min(in.max_len, prefix_lens[P - 1]);
+    in.src.max_len = in.max_len;
+    const uint16_t *thr = nullptr;
+    uint32_t thr_len = 0;
+    if ((rc = ensure_thresholds(e, in.max_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
+    std::vector<PrefixLaunch> launches(nf);
+    uint32_t max_slices = 0;
+    for (size_t fi = 0; fi < nf; ++fi) {
+        PrefixLaunch &a = launches[fi];
+        fill_plain_launch(e, fi, in, thr, thr_len, &a);
+        a.cps.n = n_prefixes;
+        for (uint32_t p = 0; p < kMaxPrefixes; ++p) a.cps.c[p] = p < n_prefixes ? prefix_lens[p] : 0u;
+        max_slices = std::max(max_slices, a.n_slices);
+    }
+    // workspace: u16 part[max_slices][n_items][P] | u32 prefix_len[rows] | u16 max_count[rows][nf] | u8 row_pre[rows] | u8 decision[rows] |
+    // u8 status[rows] -- the outputs only where the caller left them out and a later stage reads them
+    const bool decides = d_out->decision || d_out->best_target || d_out->status || d_out->first_decided;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_len = up16((size_t)max_slices * rows * 2), o_max = o_len + up16(d_out->prefix_len ? 0 : rows * 4);
+    const size_t o_pre = o_max + up16(d_out->max_count ? 0 : rows * nf * 2), o_dec = o_pre + up16(rows);
+    const size_t o_st = o_dec + up16(d_out->first_decided && !d_out->decision ? rows : 0);
+    const size_t ws_bytes = o_st + up16(d_out->first_decided && !d_out->status ? rows : 0);
+    if ((rc = e->d_prefix_ws.ensure(ws_bytes)) != RB_OK) return rc;
+    char *ws = (char *)e->d_prefix_ws.p;
+    uint16_t *part = (uint16_t *)ws;
+    uint32_t *row_len = d_out->prefix_len ? (uint32_t *)d_out->prefix_len : (uint32_t *)(ws + o_len);
+    uint16_t *max_count = d_out->max_count ? (uint16_t *)d_out->max_count : (uint16_t *)(ws + o_max);
+    uint8_t *row_pre = (uint8_t *)(ws + o_pre);
+    uint8_t *decision = (uint8_t *)d_out->decision, *status = (uint8_t *)d_out->status;
+    if (d_out->first_decided && !decision) decision = (uint8_t *)(ws + o_dec);
+    if (d_out->first_decided && !status) status = (uint8_t *)(ws + o_st);
+    std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
+    if ((rc = begin_timed(e, st, &evp)) != RB_OK) return rc;
+    for (size_t fi = 0; fi < nf; ++fi) {
+        PrefixLaunch &a = launches[fi];
+        a.part = part;
+        RB_HIP(launch_ibf_prefix(a, st));
+        RB_HIP(launch_finish_prefix(a, in.d_lens, in.d_pre_status, max_count, row_len, row_pre, st));
+    }
+    if (decides) {
+        if ((rc = run_decide(e, max_count, row_len, row_pre, rows, in.max_len, error_rate, significance, mode, (int32_t *)d_out->best_target,
+                             decision, status, st)) != RB_OK)
+            return rc;
+        if (d_out->first_decided) RB_HIP(launch_first_decided(decision, status, (uint32_t)n_items, n_prefixes, (uint32_t *)d_out->first_decided, st));
+    }
+    if ((rc = end_timed(evp, st)) != RB_OK) return rc;
+    if (!stream) RB_HIP(hipStreamSynchronize(st));
+    return RB_OK;
+}
+
+int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32_t *prefix_lens, uint32_t n_prefixes, double error_rate,
+                           double significance, int mode, const rb_prefix_out *d_out, void *stream)
+{
+    return prefix_device_impl(e, desc, prefix_lens, n_prefixes, error_rate, significance, mode, d_out, stream);
+}
+
+int rb_prefix_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *read_ids,
+                    size_t n_items, const uint32_t *prefix_lens, uint32_t n_prefixes, double error_rate, double significance, int mode,
+                    const rb_prefix_out *out)
+{
+    int rc = check_prefix_args(out, prefix_lens, n_prefixes, mode);
+    if (rc != RB_OK) return rc;
+    if ((rc = check_device(e ? e->device : 0)) != RB_OK) return rc;
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    const size_t n = read_ids ? n_items : n_reads;  // without a selection the work items are the reads
+    if (n == 0) return RB_OK;
+    if (!seqs || !offsets || !lens || n_reads == 0) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
+    if (n >= (1ULL << 31) || n_reads >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    hipStream_t st = e->stream;
+    std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
+    rb_batch_desc all;
+    if ((rc = upload_reads(e, seqs, offsets, lens, n_reads, read_ids, n, st, &all)) != RB_OK) return rc;
+    size_t nf = 0, max_slices = 1;
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        nf = e->filters.size();
+        for (const rb_dibf *f : e->filters) {  // the column slices prefix_device_impl will cut: its workspace is part of the budget below
+            int lg, wpl, planes, nt;
+            uint32_t n_slices;
+            plain_geometry(e, f, all.max_len, &lg, &wpl, &n_slices, &planes, &nt);
+            max_slices = std::max<size_t>(max_slices, n_slices);
+        }
+    }
+    if (nf == 0) {
+        (void)hipStreamSynchronize(st);
+        return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
+    }
+    // sub-batches: workspace (S partial maxima, a length and a pre-status per row) plus staged outputs (nf maxima, a length, a target, a
+    // decision and a status per row; an id and a first_decided per item) stay at or below kPrefixBudget; a single item that needs more
+    // goes alone
+    constexpr size_t kPrefixBudget = 256ull << 20;
+    const size_t P = n_prefixes;
+    const size_t per_item = P * (max_slices * 2 + 4 + 1 + nf * 2 + 4 + 4 + 1 + 1) + 4 + 4 + 64;
+    const size_t sub_max = std::max<size_t>(1, std::min<size_t>(n, kPrefixBudget / per_item));
+    // staging: u32 ids[sub] | u32 first[sub] | u32 prefix_len[rows] | i32 best[rows] | u16 max_count[rows][nf] | u8 decision[rows] | u8 status[rows]
+    const size_t R = sub_max * P;
+    const size_t o_first = 4 * sub_max, o_len = o_first + 4 * sub_max, o_best = o_len + 4 * R, o_max = o_best + 4 * R, o_dec = o_max + 2 * R * nf,
+                 o_status = o_dec + R;
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        rc = e->d_prefix_io.ensure(o_status + R);
+    }
+    if (rc != RB_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    char *io = (char *)e->d_prefix_io.p;
+    for (size_t b0 = 0; b0 < n; b0 += sub_max) {
+        const size_t sub = std::min(sub_max, n - b0), r = sub * P;
+        if (read_ids) RB_HIP(hipMemcpyAsync(io, read_ids + b0, 4 * sub, hipMemcpyHostToDevice, st));
+        rb_batch_desc desc = all;
+        // work item j of the sub-batch is read read_ids[b0 + j], or read b0 + j
+        if (!read_ids) {
+            desc.d_offsets = (const uint64_t *)all.d_offsets + b0;
+            desc.d_lens = (const uint32_t *)all.d_lens + b0;
+        }
+        desc.n_items = sub;
+        desc.d_read_ids = read_ids ? io : nullptr;
+        rb_prefix_out d_out;
+        d_out.max_count = out->max_count ? io + o_max : nullptr;
+        d_out.decision = out->decision ? io + o_dec : nullptr;
+        d_out.best_target = out->best_target ? io + o_best : nullptr;
+        d_out.status = out->status ? io + o_status : nullptr;
+        d_out.prefix_len = out->prefix_len ? io + o_len : nullptr;
+        d_out.first_decided = out->first_decided ? io + o_first : nullptr;
+        rc = prefix_device_impl(e, &desc, prefix_lens, n_prefixes, error_rate, significance, mode, &d_out, (void *)st);
+        if (rc != RB_OK) {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+        if (out->max_count) RB_HIP(hipMemcpyAsync((uint16_t *)out->max_count + b0 * P * nf, io + o_max, 2 * r * nf, hipMemcpyDeviceToHost, st));
+        if (out->decision) RB_HIP(hipMemcpyAsync((uint8_t *)out->decision + b0 * P, io + o_dec, r, hipMemcpyDeviceToHost, st));
+        if (out->best_target) RB_HIP(hipMemcpyAsync((int32_t *)out->best_target + b0 * P, io + o_best, 4 * r, hipMemcpyDeviceToHost, st));
+        if (out->status) RB_HIP(hipMemcpyAsync((uint8_t *)out->status + b0 * P, io + o_status, r, hipMemcpyDeviceToHost, st));
+        if (out->prefix_len) RB_HIP(hipMemcpyAsync((uint32_t *)out->prefix_len + b0 * P, io + o_len, 4 * r, hipMemcpyDeviceToHost, st));
+        if (out->first_decided) RB_HIP(hipMemcpyAsync((uint32_t *)out->first_decided + b0, io + o_first, 4 * sub, hipMemcpyDeviceToHost, st));
+        RB_HIP(hipStreamSynchronize(st));
+    }
     return RB_OK;
 }
 

@@ -531,7 +531,10 @@ __device__ __forceinline__ bool bound_alive(const Planes<NP> (&pl)[WPL], const u
     return alive;
 }
 
-template <int LG, int WPL, int NP, int H, bool NT, bool PH = false, bool EARLY = false>
+// SITE: a caller that starts tiles anywhere (mt_first arbitrary: the prefix pass) names an instantiation of its own.  The body is the same; what
+// the compiler learns from the other callers' arguments before it inlines (mt_first 0 or a tile multiple) then stays theirs, and their kernels
+// compile to the code they had (profiles/isa_identity.py).
+template <int LG, int WPL, int NP, int H, bool NT, bool PH = false, bool EARLY = false, int SITE = 0>
 __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev &f, const LaneCols<WPL> &lc,
                                              const BaseSrc &seq, uint32_t len, uint32_t n, int strand,
                                              uint32_t mt_first, uint32_t mt_step, int blk_first, int blk_end,
@@ -1139,6 +1142,97 @@ __global__ void reduce_locate_slices_kernel(const LocatePart *__restrict__ part,
     if (out.best_strand) out.best_strand[o] = m > 0 ? (uint8_t)strand : (uint8_t)0;
     if (out.hit_bins) out.hit_bins[o] = hits;
     if (out.status && fidx == 0) out.status[i] = status;
+}
+
+// PREFIXES: the opt-in pass (rb_prefix_batch_device) that gives a work item's maximum at every prefix checkpoint in ONE walk over its
+// k-mers.  seqan::count adds one per k-mer, so the counters after the k-mers of a prefix ARE the counts of that prefix -- on both
+// strands: the reverse complement of a prefix consists of the reverse complements of the prefix's own windows, and count_strand counts
+// strand 1 window by window in the read's direction.  One wave per (work item, column slice) behind locate's prologue; per strand the
+// planes are cleared once and checkpoint p is one count_strand call over the k-mers [n_{p-1}, n_p) of the prefix of L_p = min(c_p, len)
+// bases, with no bound, no early exit and no phasing, followed by planes_max.  A checkpoint that adds no k-mer (below k, at or beyond
+// the item's end, n_p == n_{p-1}) gathers nothing and repeats the maximum.
+// THE BUTTERFLY RULE: count_strand ends by summing the partial counters of the NG lane groups (LG < 6), after which every group holds
+// the totals.  A second call on those planes would add totals onto totals, so before every further call the planes of the lanes
+// outside group 0 are cleared: the next butterfly then sums group 0's running totals with the other groups' new partials.
+// Checkpoint p's running maximum over the two strands lives in lane p's one register -- the only state alive across strands; lanes
+// below P of the wave write part[slice][item][0..P) coalesced.  finish_prefix_kernel merges the slices of a filter.
+template <int LG, int WPL, int NP, int H, bool NT>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(3, 8))) void ibf_prefix_kernel(
+    IbfDev f, uint32_t col_begin, uint32_t col_end, ReadSrc src, uint32_t n_items, uint32_t n_slices, const uint16_t *__restrict__ thr,
+    uint32_t thr_len, uint32_t nf, uint32_t fi, PrefixList cps, uint16_t *__restrict__ part)
+{
+    __shared__ uint8_t s_stage[kWavesPerBlock][kStageBytes];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    uint32_t item, slice;
+    wave_item_slice<false>(n_slices, wave, &item, &slice);
+    if (item >= n_items) return;  // wave-uniform; there are no block-level barriers below
+
+    // (the threshold is the decision kernel's business here: a constant min_count keeps the prologue from reading the table)
+    const PassWave<WPL> pw = make_pass_wave<LG, WPL>(f, src, col_begin, col_end, item, slice, lane, thr, thr_len, nf, fi, 1u);
+    const LaneCols<WPL> &lc = pw.lc;
+    const uint32_t len = __builtin_amdgcn_readfirstlane(pw.len);  // the checkpoint loop below is scalar
+    const uint32_t k = f.k;
+
+    uint32_t mine = 0;  // lane p: checkpoint p's maximum over the strands so far
+    for (int strand = 0; strand < 2; ++strand) {
+        Planes<NP> pl[WPL];
+#pragma unroll
+        for (int w = 0; w < WPL; ++w) pl[w].clear();
+        uint32_t n_prev = 0, m = 0;
+#pragma unroll 1
+        for (uint32_t p = 0; p < cps.n; ++p) {
+            const uint32_t L = min(cps.c[p], len);
+            const uint32_t n = L >= k ? L - k + 1 : 0;
+            if (n > n_prev) {  // wave-uniform
+                if constexpr (LG < 6) {
+                    if (!pw.group0) {  // the butterfly rule (nothing to clear before a strand's first call)
+#pragma unroll
+                        for (int w = 0; w < WPL; ++w) pl[w].clear();
+                    }
+                }
+                count_strand<LG, WPL, NP, H, NT, false, false, 1>(pl, f, lc, pw.seq, L, n, strand, n_prev, (uint32_t)TileShape<LG>::ITEMS, 0,
+                                                                  TileShape<LG>::STEPS / 8, s_stage[wave], lane);
+                m = planes_max<NP, WPL>(pl, lc.valid);
+                n_prev = n;
+            }
+            if ((uint32_t)lane == p) mine = max(mine, m);
+        }
+    }
+    if ((uint32_t)lane < cps.n) part[((size_t)slice * n_items + item) * cps.n + (uint32_t)lane] = (uint16_t)mine;
+}
+
+// Merge the column slices of one filter into max_count[item][p][filter]; the call for filter 0 also writes the bases each row stands
+// for and the row's pre-status (chunk_prep's verdict for the item, replicated), which is what the decision kernel then reads as `lens`
+// and `pre_status` over the n_items x P rows.  One thread per (item, checkpoint).
+__global__ void finish_prefix_kernel(const uint16_t *__restrict__ part, uint32_t n_slices, uint32_t n_items, PrefixList cps,
+                                     const uint32_t *__restrict__ lens, const uint8_t *__restrict__ pre_status, uint16_t *__restrict__ max_count,
+                                     uint32_t *__restrict__ prefix_len, uint8_t *__restrict__ row_pre, uint32_t nf, uint32_t fidx)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_items * cps.n) return;
+    const uint32_t i = r / cps.n, p = r - i * cps.n;
+    uint16_t m = 0;
+    for (uint32_t s = 0; s < n_slices; ++s) {
+        const uint16_t v = part[((size_t)s * n_items + i) * cps.n + p];
+        m = v > m ? v : m;
+    }
+    max_count[(size_t)r * nf + fidx] = m;
+    if (fidx == 0) {
+        prefix_len[r] = min(cps.c[p], lens[i]);
+        row_pre[r] = pre_status ? pre_status[i] : (uint8_t)RB_OK;
+    }
+}
+
+// first_decided[item] = the lowest checkpoint whose row is RB_OK with a decision other than 0; P when there is none.  One thread per item.
+__global__ void first_decided_kernel(const uint8_t *__restrict__ decision, const uint8_t *__restrict__ status, uint32_t n_items, uint32_t n_prefixes,
+                                     uint32_t *__restrict__ first_decided)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    uint32_t p = 0;
+    while (p < n_prefixes && !(status[(size_t)i * n_prefixes + p] == RB_OK && decision[(size_t)i * n_prefixes + p] != 0)) ++p;
+    first_decided[i] = p;
 }
 
 // HITS: the opt-in pass (rb_hits_batch_device) that lists EVERY (bin, strand) whose count reached the threshold, with the count --
@@ -3583,7 +3677,7 @@ hipError_t launch_invert_words(const uint64_t *src, uint64_t *dst, uint64_t n_wo
     return hipGetLastError();
 }
 
-// locate and hits: one launch of a plain query pass.  A wave per (item, slice), the build picked as the count kernel's is; non-temporal
+// locate, hits and prefixes: one launch of a plain query pass.  A wave per (item, slice), the build picked as the count kernel's is; non-temporal
 // builds for blocks of a whole wave only (the tables beyond the Infinity Cache are the wide ones; a narrow table of that size keeps the
 // default cache policy, which costs speed, not results).  Pass::kernel<LG, WPL, NP, H, NT>() names the pass's kernel, `more` are its own
 // arguments behind the shared ones.
@@ -3631,6 +3725,36 @@ hipError_t launch_reduce_locate_slices(const LocatePart *part, uint32_t n_slices
     if (n_items == 0) return hipSuccess;
     hipLaunchKernelGGL(reduce_locate_slices_kernel, dim3((n_items + 255) / 256), dim3(256), 0, st, part, n_slices, n_items, lens, pre_status,
                        max_len, min_len, out, nf, fidx);
+    return hipGetLastError();
+}
+
+struct PrefixPass {
+    template <int LG, int WPL, int NP, int H, bool NT>
+    static constexpr auto kernel() { return &ibf_prefix_kernel<LG, WPL, NP, H, NT>; }
+};
+hipError_t launch_ibf_prefix(const PrefixLaunch &a, hipStream_t st)
+{
+    if (a.n_items == 0) return hipSuccess;
+    if (!a.part || a.cps.n == 0 || a.cps.n > kMaxPrefixes) return hipErrorInvalidValue;
+    return launch_plain_pass<PrefixPass>(a, st, a.cps, a.part);
+}
+
+hipError_t launch_finish_prefix(const PrefixLaunch &a, const uint32_t *lens, const uint8_t *pre_status, uint16_t *max_count, uint32_t *prefix_len,
+                                uint8_t *row_pre, hipStream_t st)
+{
+    const uint64_t rows = (uint64_t)a.n_items * a.cps.n;
+    if (rows == 0) return hipSuccess;
+    if (rows > 0x7FFFFFFFull || !max_count || !prefix_len || !row_pre) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(finish_prefix_kernel, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, st, a.part, a.n_slices, a.n_items, a.cps, lens,
+                       pre_status, max_count, prefix_len, row_pre, a.nf, a.fi);
+    return hipGetLastError();
+}
+
+hipError_t launch_first_decided(const uint8_t *decision, const uint8_t *status, uint32_t n_items, uint32_t n_prefixes, uint32_t *first_decided,
+                                hipStream_t st)
+{
+    if (n_items == 0) return hipSuccess;
+    hipLaunchKernelGGL(first_decided_kernel, dim3((n_items + 255) / 256), dim3(256), 0, st, decision, status, n_items, n_prefixes, first_decided);
     return hipGetLastError();
 }
 

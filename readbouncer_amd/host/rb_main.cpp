@@ -508,7 +508,12 @@ struct ReadState
     std::string bin_rows;  // --report-bins: this read's lines of classified_bins.tsv
     std::string hit_rows;  // --report-hits: this read's lines of classified_hits.tsv
     std::string span_rows; // --report-spans: this read's lines of classified_spans.tsv
+    std::string prefix_row; // --report-prefixes: this read's line of classified_prefixes.tsv
 };
+
+// --report-prefixes, per checkpoint: reads that reach it, reads with decision 0 / 1 / 2 there (a row that is not RB_OK has decision 0), reads
+// first decided there, reads whose decision differs from the checkpoint before
+constexpr size_t kPrefixTallies = 6;
 
 // host pipeline knobs (command line)
 struct IngestOptions
@@ -532,6 +537,9 @@ struct IngestOptions
     bool report_bins = false;    // --report-bins: locate the reads every chunk classified (rb_locate_batch) and write classified_bins.tsv
     bool report_hits = false;    // --report-hits: list every (bin, strand) those reads hit (rb_hits_batch): classified_hits.tsv and bin_profile.tsv
     bool report_spans = false;   // --report-spans: where along those reads the best bin of every matching filter matched (rb_spans_batch): classified_spans.tsv
+    bool report_prefixes = false;  // --report-prefixes: the decision of EVERY read at every prefix checkpoint (rb_prefix_batch): classified_prefixes.tsv, prefix_summary.tsv
+    std::vector<uint32_t> prefix_lens;  // ... the checkpoints in bases, strictly rising (--prefix-lens a,b,c, or made from --prefix-step / --prefix-count)
+    uint32_t prefix_step = 0, prefix_count = 0;
     uint32_t max_hits = 64;      // --max-hits N: records kept per (read, filter); n_hits in the report stays exact
     std::vector<std::string> bin_maps;  // --bin-map FILE (may repeat): <filter name>.bins.tsv of build --write-bin-map -> a record_id column
     size_t bytes() const { return segment_bytes ? segment_bytes : (segment_mb << 20); }
@@ -599,8 +607,14 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
         // --report-spans: classified_spans.tsv, one line per (classified read, filter that matched it), in file order: where along the read the
         // locate pass's best bin matched on its best strand, positions in the read's coordinates
         std::ofstream spans_out;
-        if (opt.report_bins || opt.report_hits || opt.report_spans) {
-            if (multi) throw std::runtime_error("--report-bins, --report-hits and --report-spans work on one device");
+        // --report-prefixes: classified_prefixes.tsv, one line per read of the run in file order -- per checkpoint the bases the row stands for,
+        // the decision of the run's mode on that prefix, the best target and every filter's maximum -- and prefix_summary.tsv, per checkpoint
+        // the tallies below over the whole run
+        std::ofstream prefixes_out;
+        const size_t n_cp = opt.report_prefixes ? opt.prefix_lens.size() : 0;
+        std::vector<uint64_t> prefix_tally(n_cp * kPrefixTallies, 0);
+        if (opt.report_bins || opt.report_hits || opt.report_spans || opt.report_prefixes) {
+            if (multi) throw std::runtime_error("--report-bins, --report-hits, --report-spans and --report-prefixes work on one device");
             for (const interleave::IBFMeta& f : DepletionFilters) all_filters.push_back(&f);
             for (const interleave::IBFMeta& f : TargetFilters) all_filters.push_back(&f);
             bin_records.resize(all_filters.size());
@@ -624,6 +638,16 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
             if (!spans_out) { std::cerr << "ERROR: Unable to open the file: classified_spans.tsv" << std::endl; return; }
             spans_out << "read_id\tfilter\tbin" << (opt.bin_maps.empty() ? "" : "\trecord_id")
                       << "\tstrand\tn_kmers\tcount\tfirst\tlast\trun_start\trun_len\tcovered\n";
+        }
+        if (opt.report_prefixes) {
+            prefixes_out.open(std::filesystem::path(config.output_dir) / "classified_prefixes.tsv");
+            if (!prefixes_out) { std::cerr << "ERROR: Unable to open the file: classified_prefixes.tsv" << std::endl; return; }
+            prefixes_out << "read_id\tlength";
+            for (uint32_t c : opt.prefix_lens) {
+                prefixes_out << "\tprefix_len@" << c << "\tdecision@" << c << "\tbest_target@" << c;
+                for (const interleave::IBFMeta* f : all_filters) prefixes_out << "\tmax_" << f->name << '@' << c;
+            }
+            prefixes_out << '\n';
         }
         if (opt.report_hits) {
             hits_out.open(std::filesystem::path(config.output_dir) / "classified_hits.tsv");
@@ -718,12 +742,59 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
         // the chunk loop of one segment (classify.hpp:262-299, batch-wise): the reads go to the GPU in calls of at most
         // batch_reads; chunk 0 comes ready-made from the parser threads, later chunks are gathered here for the reads that
         // are still unclassified
-        auto classify_segment = [&](const seqio::Segment& seg, std::vector<ReadState>& state, std::vector<uint64_t>& seg_profile) {
+        auto classify_segment = [&](const seqio::Segment& seg, std::vector<ReadState>& state, std::vector<uint64_t>& seg_profile,
+                                    std::vector<uint64_t>& seg_tally) {
             const std::vector<seqio::Record>& recs = seg.batch.records;
             std::vector<char> flat;
             std::vector<uint64_t> offs;
             std::vector<uint32_t> lens;
             std::vector<size_t> idx;
+            if (opt.report_prefixes) {
+                // every read of the segment, whole, in the run's mode: one rb_prefix_batch per batch_reads reads
+                const size_t nf = all_filters.size(), P = n_cp;
+                for (size_t b0 = 0; b0 < recs.size(); b0 += opt.batch_reads) {
+                    const size_t nb = std::min(recs.size(), b0 + opt.batch_reads) - b0;
+                    flat.clear();
+                    offs.clear();
+                    lens.clear();
+                    for (size_t j = 0; j < nb; ++j) {
+                        const seqio::Record& r = recs[b0 + j];
+                        offs.push_back(flat.size());
+                        lens.push_back((uint32_t)r.seq_len);
+                        flat.insert(flat.end(), r.seq, r.seq + r.seq_len);
+                    }
+                    if (flat.empty()) flat.push_back('N');
+                    std::vector<uint16_t> mc(nb * P * nf);
+                    std::vector<uint8_t> dec(nb * P), ps(nb * P);
+                    std::vector<int32_t> bt(nb * P);
+                    std::vector<uint32_t> pl(nb * P), fd(nb);
+                    rb_prefix_out po{mc.data(), dec.data(), bt.data(), ps.data(), pl.data(), fd.data()};
+                    interleave::throw_status(rb_prefix_batch(interleave::detail::engine_for(DepletionFilters, TargetFilters), flat.data(), offs.data(),
+                                                             lens.data(), nb, nullptr, 0, opt.prefix_lens.data(), (uint32_t)P, Conf.error_rate,
+                                                             Conf.significance, RB_MODE_CLASSIFY_CHUNK, &po),
+                                             "rb_prefix_batch");
+                    for (size_t j = 0; j < nb; ++j) {
+                        const seqio::Record& r = recs[b0 + j];
+                        size_t w = 0;
+                        while (w < r.id_len && r.id[w] != ' ' && r.id[w] != '\t') ++w;
+                        std::string& row = state[b0 + j].prefix_row;
+                        row.append(r.id, w);
+                        row += '\t' + std::to_string(r.seq_len);
+                        for (size_t p = 0; p < P; ++p) {
+                            const size_t q = j * P + p;
+                            row += '\t' + std::to_string(pl[q]) + '\t' + std::to_string(dec[q]) + '\t' + std::to_string(bt[q]);
+                            for (size_t fi = 0; fi < nf; ++fi) row += '\t' + std::to_string(mc[q * nf + fi]);
+                            uint64_t* t = seg_tally.data() + p * kPrefixTallies;
+                            if (r.seq_len >= opt.prefix_lens[p]) t[0] += 1;
+                            t[1 + std::min<unsigned>(dec[q], 2u)] += 1;
+                            if (fd[j] == p) t[4] += 1;
+                            if (p > 0 && dec[q] != dec[q - 1]) t[5] += 1;
+                        }
+                        row += '\n';
+                    }
+                }
+                flat.clear();
+            }
             for (size_t b0 = 0; b0 < seg.prefix_idx.size(); b0 += opt.batch_reads) {
                 const size_t b1 = std::min(seg.prefix_idx.size(), b0 + opt.batch_reads);
                 std::vector<size_t> active(b1 - b0);
@@ -944,8 +1015,8 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                     }
                     std::vector<ReadState> state(seg->batch.records.size());
                     const auto t0 = std::chrono::steady_clock::now();
-                    std::vector<uint64_t> seg_profile(bin_profile.size(), 0);
-                    classify_segment(*seg, state, seg_profile);
+                    std::vector<uint64_t> seg_profile(bin_profile.size(), 0), seg_tally(prefix_tally.size(), 0);
+                    classify_segment(*seg, state, seg_profile, seg_tally);
                     const double secs = seconds_since(t0);
                     SegmentOutput so = size_segment(*seg, state);
                     std::vector<uint64_t> at(n_out, 0);
@@ -966,6 +1037,10 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                             for (const ReadState& rs : state) bins_out << rs.bin_rows;
                         if (opt.report_spans)
                             for (const ReadState& rs : state) spans_out << rs.span_rows;
+                        if (opt.report_prefixes) {
+                            for (const ReadState& rs : state) prefixes_out << rs.prefix_row;
+                            for (size_t b = 0; b < prefix_tally.size(); ++b) prefix_tally[b] += seg_tally[b];
+                        }
                         if (opt.report_hits) {
                             for (const ReadState& rs : state) hits_out << rs.hit_rows;
                             for (size_t b = 0; b < bin_profile.size(); ++b) bin_profile[b] += seg_profile[b];
@@ -1015,6 +1090,16 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
         for (auto& o : outputs) {
             o->close();
             if (!o->ok()) std::cerr << "ERROR: writing an output file failed: " << o->error() << std::endl;
+        }
+        if (opt.report_prefixes) {
+            std::ofstream sum(std::filesystem::path(config.output_dir) / "prefix_summary.tsv");
+            if (!sum) std::cerr << "ERROR: Unable to open the file: prefix_summary.tsv" << std::endl;
+            else sum << "prefix_len\treads_reaching\tdecision_0\tdecision_1\tdecision_2\tfirst_decided\tchanged\n";
+            for (size_t p = 0; sum && p < n_cp; ++p) {
+                sum << opt.prefix_lens[p];
+                for (size_t t = 0; t < kPrefixTallies; ++t) sum << '\t' << prefix_tally[p * kPrefixTallies + t];
+                sum << '\n';
+            }
         }
         if (opt.report_hits) {
             std::ofstream prof(std::filesystem::path(config.output_dir) / "bin_profile.tsv");
@@ -1234,6 +1319,39 @@ int main(int argc, char const* argv[])
             opt.max_hits = (uint32_t)v;
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--report-prefixes")) opt.report_prefixes = true;
+        else if (!std::strcmp(argv[i], "--prefix-lens")) {
+            // a,b,c: 1 to 64 checkpoints in bases, none 0, strictly rising
+            bool ok = i + 1 < argc && argv[i + 1][0] != '-' && argv[i + 1][0] != '\0' && opt.prefix_step == 0 && opt.prefix_count == 0 && opt.prefix_lens.empty();
+            const char* s = ok ? argv[i + 1] : "";
+            while (ok) {
+                char* end = nullptr;
+                const unsigned long long v = std::strtoull(s, &end, 10);
+                ok = end != s && v >= 1 && v <= 0xFFFFFFFFull && (opt.prefix_lens.empty() || v > opt.prefix_lens.back()) && opt.prefix_lens.size() < RB_PREFIX_MAX &&
+                     (*end == ',' || *end == '\0');
+                if (!ok) break;
+                opt.prefix_lens.push_back((uint32_t)v);
+                if (*end == '\0') break;
+                s = end + 1;
+            }
+            if (!ok) {
+                std::cerr << "ERROR: --prefix-lens a,b,c: 1 to 64 checkpoints in bases, none 0, strictly rising; not together with --prefix-step / --prefix-count" << std::endl;
+                return 1;
+            }
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--prefix-step") || !std::strcmp(argv[i], "--prefix-count")) {
+            const bool step = !std::strcmp(argv[i], "--prefix-step");
+            char* end = nullptr;
+            const unsigned long long v = i + 1 < argc ? std::strtoull(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || argv[i + 1][0] == '-' || *end != '\0' || v < 1 || v > (step ? 0xFFFFFFFFull : (unsigned long long)RB_PREFIX_MAX) || !opt.prefix_lens.empty()) {
+                std::cerr << "ERROR: " << argv[i] << (step ? " N: bases between checkpoints, 1 or more" : " M: 1 to 64 checkpoints")
+                          << "; --prefix-step / --prefix-count do not go together with --prefix-lens" << std::endl;
+                return 1;
+            }
+            (step ? opt.prefix_step : opt.prefix_count) = (uint32_t)v;
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--write-bin-map")) g_write_bin_map = true;
         else if (!std::strcmp(argv[i], "--edit-ibf") && i + 1 < argc) edit.input = argv[++i];
         else if (!std::strcmp(argv[i], "--with") && i + 1 < argc) edit.with.push_back(argv[++i]);
@@ -1296,6 +1414,11 @@ int main(int argc, char const* argv[])
                          "                                    its count, at most --max-hits per (read, filter) (n_hits stays exact); bin_profile.tsv: reads per bin\n"
                          "                  [--report-spans]  classified_spans.tsv: where along the read the best bin of every matching filter matched, on its best\n"
                          "                                    strand: n_kmers, count, first, last, run_start, run_len, covered; positions in the read's coordinates\n"
+                         "                  [--report-prefixes (--prefix-lens a,b,c | --prefix-step N [--prefix-count M])]  classified_prefixes.tsv: for EVERY read of the\n"
+                         "                                    run, at each of up to 64 prefix checkpoints (bases, strictly rising; --prefix-step: N, 2N, ... M of them, default up\n"
+                         "                                    to 1500 bases): prefix length, decision of the run's mode on that prefix, best target, every filter's maximum --\n"
+                         "                                    from one pass over the read; prefix_summary.tsv: per checkpoint reads reaching it, with decision 0 / 1 / 2, first\n"
+                         "                                    decided there, changed against the checkpoint before\n"
                          "                  [--bin-map <name>.bins.tsv ...]  adds the record id of the bin to these reports\n"
                          "                  [--filter-stats]  per-bin occupancy of every filter built: a summary and <name>.binstats.tsv (give the flag last, or\n"
                          "                                    before another flag: a bare word after it is taken as a file; a build's exit code stays 0 whatever the bins hold)\n"
@@ -1310,6 +1433,12 @@ int main(int argc, char const* argv[])
                          "                  --bin-map: also writes <out>.bins.tsv; --filter-stats: the report of the assembled table while it is in HBM (exit code 3)" << std::endl;
             return 0;
         }
+    }
+    if (opt.report_prefixes && opt.prefix_lens.empty()) {
+        if (opt.prefix_step == 0) { std::cerr << "ERROR: --report-prefixes needs --prefix-lens a,b,c or --prefix-step N [--prefix-count M]" << std::endl; return 1; }
+        // N, 2N, ...: M of them, by default as many as stay within the reference's 1500-base cut-off (at least one)
+        const uint64_t m = opt.prefix_count ? opt.prefix_count : std::min<uint64_t>(RB_PREFIX_MAX, std::max<uint64_t>(1, 1500 / opt.prefix_step));
+        for (uint64_t q = 1; q <= m && q * opt.prefix_step <= 0xFFFFFFFFull; ++q) opt.prefix_lens.push_back((uint32_t)(q * opt.prefix_step));
     }
     if (!verify_path.empty()) {
         if (verify_ref.empty()) { std::cerr << "ERROR: --verify-ibf <file.ibf> needs --reference <file.fasta> [--fragment-size N]" << std::endl; return 1; }

@@ -1,0 +1,273 @@
+"""The prefix pass (rb_prefix_batch / rb_prefix_batch_device) against the oracle, bit for bit, through the C ABI.
+
+Expected rows come from tests/prefix_rules.py alone: the oracle's counts and decisions on the ASCII prefix read[:c] of every read and
+checkpoint.  Filters and reads are those of tests/test_gpu_locate.make_case (made by the oracle on the host and uploaded); what the
+cases depend on -- a decision that is not monotone in the prefix length, reads shorter than the last checkpoint and shorter than k --
+is asserted on the oracle without a GPU in tests/test_prefix_cpu.py.  No assertion on elapsed time."""
+import functools
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as po
+from readbouncer_amd import capi
+from tests import helpers as H
+from tests import prefix_rules as PR
+from tests.test_gpu_locate import CONF, GEOMETRIES, LONG, R, make_case, upload
+
+CHECKPOINTS = (77, 140, 141, 204, 268, 360, 500, 640)
+LONG_CHECKPOINTS = (360, 720, 1080, 1440, 1500)
+# below k; exactly one k-mer; one k-mer more; the end of a 64-k-mer tile (k = 13) and the start of the next; the second tile's end;
+# beyond most reads; beyond every read
+EDGES = (5, 13, 14, 64 + 12, 64 + 13, 76 + 64, 600, 10000)
+MODES = (capi.RB_MODE_CHECK_UNBLOCK, capi.RB_MODE_CLASSIFY_CHUNK, capi.RB_MODE_CLASSIFY_ANY)
+SHORT = ["w1", "w5", "w5_h2", "w37_k15", "w128", "w129", "w485"]
+
+
+@functools.lru_cache(maxsize=None)
+def expectation(name, checkpoints, mode=capi.RB_MODE_CHECK_UNBLOCK, n_rule=3, long_reads=False):
+    """computed once per (case, list, mode, N rule) and shared; callers do not write into it"""
+    f, reads, _, _ = make_case(name, 60, True) if long_reads else make_case(name)
+    if f.n_bins > 10000:  # four slices: the oracle counts 31 000 bins per k-mer, so fewer reads -- the planted and the short ones stay
+        reads = reads[:80] + reads[-12:]
+    prev = po.set_revcomp_of_n(n_rule)
+    try:
+        exp = PR.expected_batch(reads, checkpoints, [f], [], mode, r=R, conf=CONF)
+    finally:
+        po.set_revcomp_of_n(prev)
+    return f, reads, exp
+
+
+def run_host(eng, reads, checkpoints, mode=capi.RB_MODE_CHECK_UNBLOCK, **kw):
+    buf, offs, lens = H.pack_reads(list(reads))
+    return eng.prefixes(buf, offs, lens, checkpoints, error_rate=R, significance=CONF, mode=mode, **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SHORT)
+def test_prefixes_match_oracle(name):
+    """LG = 0 (w1), the butterfly case (w5), run-time hashes (w5_h2), k = 15, a whole wave, two slices with one column in the second, four
+    slices: the non-monotone checkpoints, then the edges"""
+    assert set(SHORT) <= set(GEOMETRIES)
+    f, reads, exp = expectation(name, CHECKPOINTS)
+    eng = capi.Engine(0, [upload(f)], [])
+    PR.assert_same(run_host(eng, reads, CHECKPOINTS), exp, name)
+    _, _, exp_e = expectation(name, EDGES)
+    assert (exp_e["status"][:, 0] == capi.RB_ERR_SHORT_READ).all() and (exp_e["prefix_len"][:, -1] == [len(r) for r in reads]).all()
+    PR.assert_same(run_host(eng, reads, EDGES), exp_e, name + " edges")
+    eng.destroy()
+
+
+@pytest.mark.gpu
+def test_prefixes_of_reads_of_more_than_1023_kmers():
+    """the 16-plane builds"""
+    f, reads, exp = expectation("w5_long", LONG_CHECKPOINTS, long_reads=True)
+    assert "w5_long" in LONG and max(len(r) for r in reads) - f.kmer_size + 1 > 1023 and LONG_CHECKPOINTS[-1] - f.kmer_size + 1 > 1023
+    eng = capi.Engine(0, [upload(f)], [])
+    PR.assert_same(run_host(eng, reads, LONG_CHECKPOINTS), exp, "long reads")
+    eng.destroy()
+
+
+@pytest.mark.gpu
+def test_one_checkpoint_and_sixty_four():
+    f, reads, exp1 = expectation("w5", (300,))
+    many = tuple(13 + 10 * i for i in range(64))  # 13 .. 643: every lane of the wave holds a checkpoint
+    _, _, exp64 = expectation("w5", many)
+    eng = capi.Engine(0, [upload(f)], [])
+    PR.assert_same(run_host(eng, reads, (300,)), exp1, "P = 1")
+    PR.assert_same(run_host(eng, reads, many), exp64, "P = 64")
+    # ... and across two column slices
+    f2, reads2, exp2 = expectation("w129", many)
+    eng2 = capi.Engine(0, [upload(f2)], [])
+    PR.assert_same(run_host(eng2, reads2, many), exp2, "P = 64, two slices")
+    eng.destroy()
+    eng2.destroy()
+
+
+@pytest.mark.gpu
+def test_both_n_rules():
+    f, reads, exp3 = expectation("w5", CHECKPOINTS, n_rule=3)
+    _, _, exp4 = expectation("w5", CHECKPOINTS, n_rule=4)
+    assert any("N" in r for r in reads)
+    eng = capi.Engine(0, [upload(f)], [])
+    eng.set_revcomp_of_n(4)
+    PR.assert_same(run_host(eng, reads, CHECKPOINTS), exp4, "N stays N")
+    eng.set_revcomp_of_n(3)
+    PR.assert_same(run_host(eng, reads, CHECKPOINTS), exp3, "N -> T")
+    eng.destroy()
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_case():
+    """w5 (k = 13) and w37_k15 (k = 15) with reads of both: prefixes of 13 and 14 bases are short for one filter only"""
+    a, b = make_case("w5"), make_case("w37_k15")
+    reads = list(a[1][:110]) + list(b[1][:110]) + list(a[1][-12:])
+    return a[0], b[0], tuple(reads)
+
+
+MIXED_CHECKPOINTS = (5, 13, 14, 15, 77, 140, 141, 204, 268, 360, 500, 640)
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_expectation(kind, mode):
+    fa, fb, reads = mixed_case()
+    dep, tgt = {"deplete": ([fa], []), "target": ([], [fa]), "both": ([fa], [fb])}[kind]
+    return PR.expected_batch(reads, MIXED_CHECKPOINTS, dep, tgt, mode, r=R, conf=CONF)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["deplete", "target", "both"])
+def test_engines_and_modes(kind):
+    fa, fb, reads = mixed_case()
+    dep, tgt = {"deplete": ([fa], []), "target": ([], [fa]), "both": ([fa], [fb])}[kind]
+    eng = capi.Engine(0, [upload(f) for f in dep], [upload(f) for f in tgt])
+    seen = set()
+    for mode in MODES:
+        exp = mixed_expectation(kind, mode)
+        PR.assert_same(run_host(eng, reads, MIXED_CHECKPOINTS, mode), exp, "%s, mode %d" % (kind, mode))
+        seen |= set(exp["decision"].ravel().tolist())
+        # (the pair overload of the two-sided engine raises for no length: only classify_any has short reads there)
+        assert exp["decision"].any() and (exp["status"] != capi.RB_OK).any() == (kind != "both" or mode == capi.RB_MODE_CLASSIFY_ANY)
+    assert seen == ({0, 1, 2} if kind != "deplete" else {0, 1})
+    if kind == "both":  # the two ks: a prefix of 13 or 14 bases gives the k = 13 filter something to count and the k = 15 filter nothing
+        exp = mixed_expectation(kind, capi.RB_MODE_CHECK_UNBLOCK)
+        assert (exp["max_count"][:, 1:3, 0] > 0).any() and not exp["max_count"][:, 1:3, 1].any()
+        assert (exp["best_target"][:, 1:3] == -1).all() and (exp["best_target"][:, 4:] >= 0).any()
+    # a selection of reads, by id: repeated, none
+    for ids in ([3, 3, 7, len(reads) - 1, 0], []):
+        exp = mixed_expectation(kind, capi.RB_MODE_CHECK_UNBLOCK)
+        sel = {key: v[np.array(ids, dtype=np.int64)] for key, v in exp.items()}
+        PR.assert_same(run_host(eng, reads, MIXED_CHECKPOINTS, read_ids=np.array(ids, dtype=np.uint32)), sel, "ids %s" % ids)
+    eng.destroy()
+
+
+def device_buffers(torch, dev, n, P, nf):
+    o = {"max_count": torch.full((n, P, nf), 77, dtype=torch.int16, device=dev), "decision": torch.full((n, P), 77, dtype=torch.uint8, device=dev),
+         "best_target": torch.full((n, P), 77, dtype=torch.int32, device=dev), "status": torch.full((n, P), 77, dtype=torch.uint8, device=dev),
+         "prefix_len": torch.full((n, P), 77, dtype=torch.int32, device=dev), "first_decided": torch.full((n,), 77, dtype=torch.int32, device=dev)}
+    return o
+
+
+def to_host(o):
+    return {"max_count": o["max_count"].cpu().numpy().view(np.uint16), "decision": o["decision"].cpu().numpy(), "best_target": o["best_target"].cpu().numpy(),
+            "status": o["status"].cpu().numpy(), "prefix_len": o["prefix_len"].cpu().numpy().view(np.uint32),
+            "first_decided": o["first_decided"].cpu().numpy().view(np.uint32)}
+
+
+@pytest.mark.gpu
+def test_device_form_packed_ids_chunk_start_and_an_understated_bound():
+    torch = pytest.importorskip("torch")
+    dev = torch.device("cuda:0")
+    f, reads, _, _ = make_case("w129")
+    reads = list(reads[:60]) + list(reads[-12:])
+    eng = capi.Engine(0, [upload(f)], [])
+    buf, offs, lens = H.pack_reads(reads)
+    n = len(reads)
+    packed, p_offs, nmask, n_offs = capi.pack_reads(buf, offs, lens)
+    t_p, t_po, t_nm, t_no, t_len = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (packed, p_offs.view(np.int64), nmask, n_offs.view(np.int64),
+                                                                                            lens.view(np.int32)))
+    ids = np.array([4, 4, 0, n - 1, n - 2, 17, 33, 4, 59, 21, 8], dtype=np.uint32)
+    t_ids = torch.from_numpy(ids.view(np.int32)).to(dev)
+    start = 50
+    rest = np.array([max(0, len(reads[i]) - start) for i in ids])
+    cut = int(np.sort(rest)[len(rest) // 2])
+    cps = (13, 77, 140, 204, cut, cut + 1, 700)
+    cps = tuple(sorted(set(cps)))
+    exp = PR.expected_batch([reads[i] for i in ids], cps, [f], [], capi.RB_MODE_CHECK_UNBLOCK, r=R, conf=CONF, chunk_start=start, max_len=cut)
+    assert (exp["status"] == capi.RB_ERR_INVALID_ARG).any() and (exp["status"] == capi.RB_OK).any() and (exp["status"] == capi.RB_ERR_BAD_CHUNK).any()
+    assert exp["decision"].any()
+    o = device_buffers(torch, dev, len(ids), len(cps), 1)
+    torch.cuda.synchronize()
+    eng.prefixes_device(t_p.data_ptr(), t_po.data_ptr(), t_len.data_ptr(), len(ids), cut, cps, d_nmask=t_nm.data_ptr(), d_nmask_offsets=t_no.data_ptr(),
+                        chunk_start=start, d_read_ids=t_ids.data_ptr(), error_rate=R, significance=CONF, d_max_count=o["max_count"].data_ptr(),
+                        d_decision=o["decision"].data_ptr(), d_best_target=o["best_target"].data_ptr(), d_status=o["status"].data_ptr(),
+                        d_prefix_len=o["prefix_len"].data_ptr(), d_first_decided=o["first_decided"].data_ptr())
+    torch.cuda.synchronize()
+    PR.assert_same(to_host(o), exp, "packed, ids, chunk_start, understated max_len")
+    # a caller's stream, and one output alone (the rows it is made from live in the engine's workspace then)
+    only = torch.full((len(ids),), 77, dtype=torch.int32, device=dev)
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        eng.prefixes_device(t_p.data_ptr(), t_po.data_ptr(), t_len.data_ptr(), len(ids), cut, cps, d_nmask=t_nm.data_ptr(), d_nmask_offsets=t_no.data_ptr(),
+                            chunk_start=start, d_read_ids=t_ids.data_ptr(), error_rate=R, significance=CONF, d_first_decided=only.data_ptr(),
+                            stream=s.cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(only.cpu().numpy().view(np.uint32), exp["first_decided"])
+    with pytest.raises(capi.RBError) as ei:
+        eng.prefixes_device(t_p.data_ptr(), t_po.data_ptr(), t_len.data_ptr(), len(ids), cut, cps, d_nmask=t_nm.data_ptr(), d_nmask_offsets=t_no.data_ptr())
+    assert ei.value.status == capi.RB_ERR_INVALID_ARG
+    eng.destroy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+def test_rows_equal_the_chunked_classify_calls_they_replace(mode):
+    """the header's sentence on the product itself: row (i, p) is what rb_classify_batch_device_ex writes with chunk_length = c_p (or
+    min(c_p, the descriptor's chunk_length)), the engine at its defaults -- pruning on, the planner's forms"""
+    torch = pytest.importorskip("torch")
+    dev = torch.device("cuda:0")
+    fa, fb, reads = mixed_case()
+    reads = list(reads)
+    eng = capi.Engine(0, [upload(fa)], [upload(fb)])
+    buf, offs, lens = H.pack_reads(reads)
+    n, P, nf = len(reads), len(MIXED_CHECKPOINTS), 2
+    t_seq, t_off, t_len = (torch.from_numpy(a).to(dev) for a in (buf, offs.view(np.int64), lens.view(np.int32)))
+    max_len = int(np.sort(lens)[3 * n // 4])  # understated: the longest reads are refused once a checkpoint passes it
+    assert MIXED_CHECKPOINTS[-1] > max_len > MIXED_CHECKPOINTS[-4]
+    for start, length in ((0, 0), (50, 0), (30, 300)):
+        o = device_buffers(torch, dev, n, P, nf)
+        torch.cuda.synchronize()
+        eng.prefixes_device(t_seq.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), n, max_len, MIXED_CHECKPOINTS, chunk_start=start, chunk_length=length,
+                            error_rate=R, significance=CONF, mode=mode, d_max_count=o["max_count"].data_ptr(), d_decision=o["decision"].data_ptr(),
+                            d_best_target=o["best_target"].data_ptr(), d_status=o["status"].data_ptr(), d_prefix_len=o["prefix_len"].data_ptr(),
+                            d_first_decided=o["first_decided"].data_ptr())
+        torch.cuda.synchronize()
+        got = to_host(o)
+        want = {"max_count": np.zeros((n, P, nf), np.uint16), "decision": np.zeros((n, P), np.uint8), "best_target": np.zeros((n, P), np.int32),
+                "status": np.zeros((n, P), np.uint8)}
+        for p, c in enumerate(MIXED_CHECKPOINTS):
+            c_mc = torch.full((n, nf), 55, dtype=torch.int16, device=dev)
+            c_best = torch.full((n,), 55, dtype=torch.int32, device=dev)
+            c_dec, c_st = (torch.full((n,), 55, dtype=torch.uint8, device=dev) for _ in range(2))
+            torch.cuda.synchronize()
+            eng.classify_device_ex(t_seq.data_ptr(), t_off.data_ptr(), t_len.data_ptr(), n, max_len, chunk_start=start, chunk_length=min(c, length) if length else c,
+                                   error_rate=R, significance=CONF, mode=mode, d_maxcount=c_mc.data_ptr(), d_best=c_best.data_ptr(),
+                                   d_decision=c_dec.data_ptr(), d_status=c_st.data_ptr())
+            torch.cuda.synchronize()
+            want["max_count"][:, p], want["best_target"][:, p] = c_mc.cpu().numpy().view(np.uint16), c_best.cpu().numpy()
+            want["decision"][:, p], want["status"][:, p] = c_dec.cpu().numpy(), c_st.cpu().numpy()
+        want["ok"] = want["status"] == capi.RB_OK
+        want["first_decided"] = np.array([PR.first_decided(want["decision"][i], want["status"][i]) for i in range(n)], dtype=np.uint32)
+        rest = np.array([max(0, len(r) - start) for r in reads])
+        if length:
+            rest = np.minimum(rest, length)
+        want["prefix_len"] = np.minimum(np.array(MIXED_CHECKPOINTS)[None, :], rest[:, None]).astype(np.uint32)
+        assert want["ok"].any() and (want["status"] == capi.RB_ERR_INVALID_ARG).any() == (length == 0)
+        PR.assert_same(got, want, "mode %d, chunk %d+%d" % (mode, start, length))
+    eng.destroy()
+
+
+@pytest.mark.gpu
+def test_the_pass_changes_nothing_else_and_settings_do_not_reach_it():
+    fa, fb, reads = mixed_case()
+    exp = mixed_expectation("both", capi.RB_MODE_CHECK_UNBLOCK)
+    eng = capi.Engine(0, [upload(fa)], [upload(fb)])
+    buf, offs, lens = H.pack_reads(list(reads))
+    before = eng.classify(buf, offs, lens, error_rate=R, significance=CONF)
+    PR.assert_same(run_host(eng, reads, MIXED_CHECKPOINTS), exp, "defaults")
+    after = eng.classify(buf, offs, lens, error_rate=R, significance=CONF)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(before, after))
+    for what, change in (("early decision", lambda e: e.set_early_decision(1)), ("no pruning", lambda e: e.set_bound_pruning(0)),
+                         ("merge always", lambda e: e.set_merge(2)), ("merge never", lambda e: e.set_merge(0))):
+        change(eng)
+        eng.classify(buf, offs, lens, error_rate=R, significance=CONF)  # (lets the setting take effect on the classify path)
+        PR.assert_same(run_host(eng, reads, MIXED_CHECKPOINTS), exp, what)
+    # a column-sharded engine refuses, and says why
+    eng.set_column_shard(0, 2)
+    with pytest.raises(capi.RBError) as ei:
+        run_host(eng, reads, MIXED_CHECKPOINTS)
+    assert ei.value.status == capi.RB_ERR_INVALID_ARG and "column-sharded" in str(ei.value)
+    eng.set_column_shard(0, 1)
+    PR.assert_same(run_host(eng, reads, MIXED_CHECKPOINTS), exp, "after the shard is lifted")
+    eng.destroy()
