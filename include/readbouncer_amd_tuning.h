@@ -187,6 +187,20 @@ typedef struct rb_plan_info {
                                   * the table is cut into instead (fewer and up to 1.19 x longer; rb_phase_plan.h, phase_equal_slices) */
 } rb_plan_info;
 RB_API int rb_engine_plan(rb_engine *e, size_t filter_index, size_t n_reads, uint32_t max_len, rb_plan_info *out);
+/* The same question for the query passes of readbouncer_amd.h (locate, hits, prefixes and spans, host and device forms),
+ * which none of the settings above but rb_engine_set_nt_threshold reaches: the build a call on items of at most max_len bases takes
+ * for filter `filter_index` (prefixes: no item is longer than the last checkpoint), filled by the functions the launches themselves go
+ * through.  Host arithmetic only; for the tests, which pin every build of a pass to the oracle and need to know which one a launch
+ * took. */
+typedef struct rb_pass_plan {
+    uint32_t lanes_per_block_log2, words_per_lane, column_slices;
+    uint32_t counter_planes;     /* 10 while the k-mers of max_len bases fit them and the filter has three hash functions, else 16 */
+    uint32_t nontemporal;        /* locate, hits, prefixes: 1 = the non-temporal twin (blocks of a whole wave beyond the threshold) */
+    uint32_t hash_functions;     /* 3: the build with three compile-time hash functions; 0: the run-time hash count */
+    uint32_t spans_nontemporal;  /* spans (one wave per query, no geometry, no planes): 1 = its non-temporal twin, at any block width */
+    uint32_t reserved0;
+} rb_pass_plan;
+RB_API int rb_engine_plan_pass(rb_engine *e, size_t filter_index, uint32_t max_len, rb_pass_plan *out);
 /* Fits the window lengths of the clock-phased gathers to THIS device: the planner's table was measured on one box, and clocks,
  * firmware and compilers move the optima.  For every table the engine would serve with the phased form on batches of n_reads reads
  * of read_len bases, K1 is timed on synthetic reads with the table's window and with 0.7 / 0.85 / 1.2 / 1.45 x that (same slice

@@ -82,6 +82,13 @@ class PlanInfo(C.Structure):
                 ("phase_rule_ticks", C.c_uint32), ("reserved0", C.c_uint32), ("phase_slice_bytes", C.c_uint64)]
 
 
+class PassPlan(C.Structure):
+    """rb_pass_plan: the build the query passes take for one filter"""
+    _fields_ = [("lanes_per_block_log2", C.c_uint32), ("words_per_lane", C.c_uint32), ("column_slices", C.c_uint32),
+                ("counter_planes", C.c_uint32), ("nontemporal", C.c_uint32), ("hash_functions", C.c_uint32),
+                ("spans_nontemporal", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
 class BinRef(C.Structure):
     """rb_bin_ref: one (source filter, bin) of an assemble plan -- 8 bytes"""
     _fields_ = [("filter", C.c_uint32), ("bin", C.c_uint32)]
@@ -233,6 +240,7 @@ SIGNATURES = {
     "rb_engine_set_timing": (_int, [_vp, _int]),
     "rb_engine_kernel_time": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_u64)]),
     "rb_engine_plan": (_int, [_vp, _sz, _sz, _u32, C.POINTER(PlanInfo)]),
+    "rb_engine_plan_pass": (_int, [_vp, _sz, _u32, C.POINTER(PassPlan)]),
     "rb_engine_calibrate": (_int, [_vp, _sz, _u32, _dbl, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rb_dibf_probe_read_peak": (_int, [_vp, _u64, _u32, _int, _u32, _dbl, C.POINTER(_dbl), C.POINTER(_dbl)]),
 }
@@ -746,6 +754,12 @@ class Engine:
         d = {k: getattr(p, k) for k, _ in PlanInfo._fields_}
         d["kernel"], d["phase_shape_name"] = p.kernel.decode(), p.phase_shape_name.decode()
         return d
+
+    def plan_pass(self, filter_index, max_len):
+        """the build locate, hits, prefixes and spans take for that filter on items of at most max_len bases -> dict (rb_pass_plan)"""
+        p = PassPlan()
+        _check(lib().rb_engine_plan_pass(self.h, filter_index, max_len, C.byref(p)), "rb_engine_plan_pass")
+        return {k: getattr(p, k) for k, _ in PassPlan._fields_ if k != "reserved0"}
 
     def calibrate(self, n_reads=262144, read_len=250, max_ms=0.0):
         """fit the phased windows to this device -> (phased tables found, tables whose window changed)"""

@@ -247,6 +247,15 @@ struct PlainPassLaunch {
 struct LocateLaunch : PlainPassLaunch {
     LocatePart *part;     // [n_slices][n_items]
 };
+// Which build a plain-form launch takes, as host arithmetic: the launchers of rb_kernels.hip instantiate by these two, and
+// rb_engine_plan_pass reports them.  Ten counter planes only with the compile-time three hash functions (*h = 3); *h = 0 is the
+// run-time hash count, always on sixteen planes.  The query passes have a non-temporal twin for blocks of a whole wave only.
+inline void plain_planes_hash(uint32_t n_hash, int planes, int *np, int *h)
+{
+    *h = n_hash == 3 ? 3 : 0;
+    *np = (*h == 3 && planes <= 10) ? 10 : 16;
+}
+inline bool plain_pass_nt(int lg, int nt) { return lg == 6 && nt != 0; }
 hipError_t launch_ibf_locate(const LocateLaunch &a, hipStream_t st);
 hipError_t launch_reduce_locate_slices(const LocatePart *part, uint32_t n_slices, uint32_t n_items, const uint32_t *lens,
                                        const uint8_t *pre_status, uint32_t max_len, uint32_t min_len, const LocateOut &out, uint32_t nf,

@@ -2172,6 +2172,9 @@ static int end_timed(std::pair<hipEvent_t, hipEvent_t> *evp, hipStream_t st)
     return RB_OK;
 }
 
+// a table the query passes read with non-temporal loads (rb_engine_set_nt_threshold)
+static bool table_beyond_nt_threshold(const rb_engine *e, const rb_dibf *f) { return f->geo.n_blocks * f->stride * 8 > e->nt_threshold_bytes; }
+
 // The plain form over a WHOLE filter (no shard), as locate and hits launch it: blocks of up to 64 word columns on 2^lg lanes, wider ones
 // on a whole wave with two words per lane and as many column slices as that takes; ten counter planes while a read's k-mers fit them.
 static void plain_geometry(const rb_engine *e, const rb_dibf *f, uint32_t max_len, int *lg, int *wpl, uint32_t *n_slices, int *planes, int *nt)
@@ -2184,7 +2187,7 @@ static void plain_geometry(const rb_engine *e, const rb_dibf *f, uint32_t max_le
     *n_slices = (W + slice_words - 1) / slice_words;
     const uint32_t kmers = max_len >= f->geo.kmer_size ? max_len - (uint32_t)f->geo.kmer_size + 1 : 0;
     *planes = kmers <= 1023 ? 10 : 16;
-    *nt = f->geo.n_blocks * f->stride * 8 > e->nt_threshold_bytes;
+    *nt = table_beyond_nt_threshold(e, f);
 }
 
 // an item shorter than the k of SOME filter of the engine is a short read: that filter has nothing to count
@@ -2517,6 +2520,28 @@ extern "C" int rb_engine_plan(rb_engine *e, size_t filter_index, size_t n_reads,
             out->phase_rule_ticks = a.phase_rule_ticks;
         }
     }
+    return RB_OK;
+}
+
+// what the plain query passes would launch for filter `filter_index` on items of at most max_len bases: plain_geometry and the build
+// rules of rb_device.h, the very functions the launches go through
+extern "C" int rb_engine_plan_pass(rb_engine *e, size_t filter_index, uint32_t max_len, rb_pass_plan *out)
+{
+    if (!e || !out || filter_index >= e->filters.size()) return rb::fail(RB_ERR_INVALID_ARG, "rb_engine_plan_pass: bad argument");
+    std::lock_guard<std::mutex> lock(e->mu);
+    std::memset(out, 0, sizeof *out);
+    const rb_dibf *f = e->filters[filter_index];
+    int lg = 0, wpl = 0, planes = 0, nt = 0, np = 0, h = 0;
+    uint32_t n_slices = 0;
+    plain_geometry(e, f, max_len, &lg, &wpl, &n_slices, &planes, &nt);
+    plain_planes_hash((uint32_t)f->geo.n_hash, planes, &np, &h);
+    out->lanes_per_block_log2 = (uint32_t)lg;
+    out->words_per_lane = (uint32_t)wpl;
+    out->column_slices = n_slices;
+    out->counter_planes = (uint32_t)np;
+    out->nontemporal = plain_pass_nt(lg, nt) ? 1u : 0u;
+    out->hash_functions = (uint32_t)h;
+    out->spans_nontemporal = table_beyond_nt_threshold(e, f) ? 1u : 0u;
     return RB_OK;
 }
 
@@ -3422,7 +3447,7 @@ static int spans_device_impl(rb_engine *e, const rb_batch_desc *desc, size_t fil
     a.mask_words = d_out->mask ? mask_words : 0u;
     a.min_len = engine_min_len(e);
     a.pre_status = in.d_pre_status;
-    a.nt = f->geo.n_blocks * f->stride * 8 > e->nt_threshold_bytes;
+    a.nt = table_beyond_nt_threshold(e, f);
     a.out.spans = (uint32_t *)d_out->spans;
     a.out.mask = (uint64_t *)d_out->mask;
     a.out.n_kmers = (uint32_t *)d_out->n_kmers;

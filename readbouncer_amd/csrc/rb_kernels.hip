@@ -3305,7 +3305,9 @@ template <typename F>
 static hipError_t dispatch_planes_hash(uint32_t n_hash, int planes, int lg, int wpl, F &&fn)
 {
     auto with = [&](auto np, auto h) { return dispatch_lg_wpl(lg, wpl, [&](auto LG, auto WPL) { return fn(LG, WPL, np, h); }); };
-    if (n_hash == 3) return planes <= 10 ? with(int_c<10>{}, int_c<3>{}) : with(int_c<16>{}, int_c<3>{});
+    int np = 0, h = 0;
+    plain_planes_hash(n_hash, planes, &np, &h);
+    if (h == 3) return np == 10 ? with(int_c<10>{}, int_c<3>{}) : with(int_c<16>{}, int_c<3>{});
     return with(int_c<16>{}, int_c<0>{});
 }
 
@@ -3703,7 +3705,7 @@ static hipError_t launch_plain_pass(const PlainPassLaunch &a, hipStream_t st, Mo
         constexpr int L = decltype(LG)::value, W = decltype(WPL)::value, P = decltype(NP)::value, HH = decltype(H)::value;
         auto kern = Pass::template kernel<L, W, P, HH, false>();
         if constexpr (L == 6) {
-            if (a.nt) kern = Pass::template kernel<L, W, P, HH, true>();
+            if (plain_pass_nt(L, a.nt)) kern = Pass::template kernel<L, W, P, HH, true>();
         }
         hipLaunchKernelGGL(kern, grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.col_begin, a.col_end, a.src, a.n_items, a.n_slices, a.thr,
                            a.thr_len, a.nf, a.fi, more...);
@@ -3798,7 +3800,9 @@ hipError_t launch_ibf_spans(const SpansLaunch &a, hipStream_t st)
     if (a.f.n_bins > (uint64_t)a.f.bin_width * 64u || a.f.bin_width > a.f.stride || a.f.k == 0 || a.f.k > rbspec::kMaxKmer || a.f.n_blocks == 0 ||
         a.f.n_hash == 0 || a.f.n_hash > rbspec::kMaxHash || a.min_len < a.f.k)
         return hipErrorInvalidValue;
-    return a.f.n_hash == 3 ? launch_spans_nt<3>(a, st) : launch_spans_nt<0>(a, st);
+    int np = 0, h = 0;  // (the hash form of the plain passes; spans has no counter planes)
+    plain_planes_hash(a.f.n_hash, 16, &np, &h);
+    return h == 3 ? launch_spans_nt<3>(a, st) : launch_spans_nt<0>(a, st);
 }
 
 hipError_t launch_reduce_slices(const uint16_t *part, uint32_t n_slices, uint32_t n_reads, uint16_t *maxcount,
