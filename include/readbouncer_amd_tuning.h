@@ -256,7 +256,11 @@ RB_API int rb_engine_set_bound_pruning(rb_engine *e, int enabled);
  * k-mers are gathered for the FIRST hash only, on top of its 64-k-mer counts -- a k-mer counts for a bin only where all hashes have
  * the bit, so this is an upper bound at a third of the lines; if its maximum does not pass the first strand's maximum the strand is
  * done, otherwise it is counted in full.  Attempted where the first strand's maximum makes it promising (rb_engine_set_cert_load);
- * never in a launch that several filters share (fused micro-batches).
+ * never in a launch that several filters share (fused micro-batches).  Bit 3 (needs bits 1 and 2): the first strand is itself finished in
+ * two steps.  Its best bin after 64 k-mers lies in one 128-byte line of every block; the bins of that line are counted to the end first,
+ * alone, which gives a count that some bin truly reaches at an eighth of the lines, and all other bins of the strand are then shown not
+ * to pass it from the FIRST hash only, as for the second strand (where that is not promising, or fails, they are counted in full against
+ * it).  Attempted where the first strand's 64-k-mer maximum is large enough (rb_engine_set_lead_min).
  * 0 = the bound as rb_engine_set_bound_pruning alone gives it; ignored while bound pruning is off.  Applies to the plain count kernel's builds that take the bound (wide filters, throughput form, no early
  * decision). */
 RB_API int rb_engine_set_prune_parts(rb_engine *e, uint32_t mask);
@@ -270,9 +274,17 @@ RB_API int rb_engine_set_prune_parts(rb_engine *e, uint32_t mask);
  * goes without the certificate.  0: always attempt; >= 1: never.  The rule only picks the attempts: results never depend on it. */
 RB_API int rb_engine_set_cert_load(rb_engine *e, size_t filter_index, double load);
 
+/* When bit 3 of rb_engine_set_prune_parts is attempted for filter `filter_index`: when the first strand's maximum after 64 k-mers is at
+ * least `min_count`.  min_count < 0 (the default): the smallest count that a read without a match is not expected to reach there -- with
+ * d the load rb_engine_set_cert_load describes and h hash functions a bin counts a foreign k-mer with probability d^h, and the value is
+ * the smallest t with 2 n_bins P(Binomial(64, d^h) >= t) <= 0.01 (8 for d = 0.21, h = 3 and 8192 bins) -- so that such reads, which gain
+ * nothing, do not walk the read twice.  0: always attempt.  The value only picks the attempts: results never depend on it. */
+RB_API int rb_engine_set_lead_min(rb_engine *e, size_t filter_index, int min_count);
+
 /* Measurement and test aid, NULL by default: device memory into which every wave of the plain count kernel (throughput form) writes one
  * 8-byte record when it has finished its (read, column slice) -- bit 0: the strand finished first (0 forward, 1 reverse); bit 1: both
- * strands were probed and the lead chosen; bit 2: a certificate was attempted for the other strand; bit 3: it held; bit 15: always set; bits 16-31 and 32-47: the k-mer position at which the gathers of the
+ * strands were probed and the lead chosen; bit 2: a certificate was attempted for the other strand; bit 3: it held; bit 4: the line of the first strand's best bin was counted first;
+ * bit 5: a certificate was attempted for that strand's other bins; bit 6: it held; bit 15: always set; bits 16-31 and 32-47: the k-mer position at which the gathers of the
  * forward and of the reverse strand ended (the number of k-mers: counted to the end; less: no lane could reach the maximum any more,
  * or the strand was not continued behind its 64-k-mer probe; 0: not counted).  Records lie filter after filter in engine order,
  * within a filter [read][column slice] (rb_engine_plan names the slices); a filter that the call does not launch on its own takes NO

@@ -17,6 +17,10 @@ States: no pruning; today (checks at 64-k-mer tile boundaries, forward strand fi
   part 3  the trailing strand certified from hash 0 alone when the leader's maximum is at least
           probe maximum + ceil(d rem + z sqrt(d (1 - d) rem)), z = 4.5.  (The kernel also prunes inside that pass and leaves it at the
           first counter above the leader's maximum; the model gathers it with the lanes alive on entry, so it reads a little high there.)
+  part 4  the lead line (needs parts 2 and 3): when the leader's probe maximum is at least LEAD_MIN, the 8 lanes of the 128-byte line that
+          holds its best probe bin are counted first, alone, from k-mer 64 (3 lines per k-mer); the other 56 lanes are then certified from
+          hash 0 against the line's maximum by the rule of part 3 (pruned and left early as in the kernel), counted in full from k-mer 64
+          against it where the rule is not met, or counted again from k-mer 0 where the certificate fails.
 
   python3 profiles/prune_model.py [reads per kind, default 500] [seed, default 1]
 """
@@ -28,6 +32,7 @@ import numpy as np
 N, TILE, LANES, BPL, LPL, H = 348, 64, 64, 128, 8, 3  # k-mers, tile, lanes, bins per lane, lanes per line, hashes
 D = 55.0 / 256.0
 Z = 4.5
+LEAD_MIN = 8  # probe maxima of reads without a match stay below it
 MEASURED_TODAY = 15698.1  # TCC_EA0_RDREQ per read, profiles/bound_pruning/bench_ab.txt
 
 
@@ -51,11 +56,16 @@ def lines_of(live):
     return int(live.reshape(LANES // LPL, LPL).any(axis=1).sum())
 
 
-def run_strand(c, start, bb, sub):
-    """full pass over k-mers [start, N) with bound bb; returns (lines, held maximum).  c = per-bin cumulative counts"""
-    live = np.ones(LANES, dtype=bool)
-    held = np.zeros(LANES * BPL, dtype=np.int32)  # counters of dead lanes, frozen
+def run_strand(c, start, bb, sub, lanes=None, h=H, off=None, stop_above=None):
+    """pass over k-mers [start, N) with bound bb and h hashes; returns (lines, held maximum).  c = per-bin cumulative counts.
+    lanes: the lanes that take part (default all); the others hold `off` (default: their counts at `start`) throughout.
+    stop_above: a certificate pass, left at the first tile boundary that sees a counter above it"""
     lanes_of_bin = np.repeat(np.arange(LANES), BPL)
+    live = np.ones(LANES, dtype=bool) if lanes is None else lanes.copy()
+    held = np.zeros(LANES * BPL, dtype=np.int32)  # counters of dead lanes, frozen
+    if lanes is not None:
+        out = ~lanes[lanes_of_bin]
+        held[out] = (c[start] if off is None else off)[out]
     lines, pos, m_stale = 0, start, bb
 
     def check(q, m):
@@ -83,12 +93,14 @@ def run_strand(c, start, bb, sub):
         nxt = min(N, (pos // TILE + 1) * TILE)
         if sub:
             nxt = min(nxt, pos + 8)
-        lines += H * lines_of(live) * (nxt - pos)
+        lines += h * lines_of(live) * (nxt - pos)
         pos = nxt
         if pos >= N:
             break
         if pos % TILE == 0:
             m_stale = max(bb, held_max(pos))
+            if stop_above is not None and m_stale > stop_above:
+                break
             check(pos, m_stale)
         else:
             check(pos, m_stale)
@@ -97,6 +109,30 @@ def run_strand(c, start, bb, sub):
 
 def allowance(rem):
     return math.ceil(D * rem + Z * math.sqrt(D * (1 - D) * rem))
+
+
+def lead_line(c, c0, sub):
+    """part 4 on the leader strand (c: all hashes, c0: hash 0, cumulative): (lines behind the probe, maximum, certificate tried, held), or
+    None where the probe maximum is below LEAD_MIN"""
+    probe = c[TILE]
+    if int(probe.max()) < LEAD_MIN:
+        return None
+    line = int(np.argmax(probe)) // BPL // LPL  # (the first bin with the maximum: the lowest lane)
+    mine = np.arange(LANES) // LPL == line
+    rem = N - TILE
+    l1, m_line = run_strand(c, TILE, 0, sub, lanes=mine)
+    others = ~mine
+    theirs = int(probe[np.repeat(others, BPL)].max())
+    zeros = np.zeros(LANES * BPL, dtype=np.int32)  # (the line's lanes are finished: the bound carries their maximum)
+    if m_line >= theirs + allowance(rem):
+        ub = probe[None, :] + (c0 - c0[TILE][None, :])
+        l2, m2 = run_strand(ub, TILE, m_line, sub, lanes=others, h=1, off=zeros, stop_above=m_line)
+        if m2 <= m_line:
+            return l1 + l2, m_line, 1, 1
+        l3, m3 = run_strand(c, 0, m_line, sub, lanes=others, off=zeros)
+        return l1 + l2 + l3, max(m_line, m3), 1, 0
+    l3, m3 = run_strand(c, TILE, m_line, sub, lanes=others, off=zeros)
+    return l1 + l3, max(m_line, m3), 0, 0
 
 
 def read_lines(rng, kind):
@@ -138,6 +174,16 @@ def read_lines(rng, kind):
             tot = probe + ll + cert + (0 if held else lt)
         res["23" if not sub else "123"] = tot
         res["cert_tried"], res["cert_held"] = int(tried), int(held)
+        if sub:  # part 4 on top of 1-3: the leader by its line, the trailing strand as before against the same maximum
+            got = lead_line(cs[lead][0], cs[lead][1], sub)
+            res["line_tried"], res["line_cert"], res["line_held"] = int(got is not None), 0, 0
+            res["1234"] = tot
+            res["true_max"] = res["max_1234"] = max(m, mt)
+            if got is not None:
+                l4, m4, res["line_cert"], res["line_held"] = got
+                assert m4 == m, (m4, m)  # the leader's maximum is exact whichever way it was found
+                res["1234"] = tot - ll + l4
+                res["max_1234"] = max(m4, mt)
     return res
 
 
@@ -158,10 +204,11 @@ def main():
     pos = {k: 0.45 * (means["pos_fwd"][k] + means["pos_rev"][k]) + 0.05 * (means["near_fwd"][k] + means["near_rev"][k]) for k in means["neg"]}
     mixes = {"bench": {k: 0.5 * means["neg"][k] + 0.5 * pos[k] for k in pos}, "positive": pos, "negative": means["neg"]}
     print("\nfabric lines per read (model, %d reads per kind, seed %d)" % (per_kind, seed))
-    states = ("none", "today", "1", "2", "12", "23", "123")
-    print("%-10s" % "mix" + "".join("%10s" % ("parts " + s if s[0].isdigit() else s) for s in states) + "  cert tried/held")
+    states = ("none", "today", "1", "2", "12", "23", "123", "1234")
+    print("%-10s" % "mix" + "".join("%11s" % ("parts " + s if s[0].isdigit() else s) for s in states) + "  cert tried/held  line tried/cert/held")
     for mix, v in mixes.items():
-        print("%-10s" % mix + "".join("%10.0f" % v[s] for s in states) + "  %.3f / %.3f" % (v["cert_tried"], v["cert_held"]))
+        print("%-10s" % mix + "".join("%11.0f" % v[s] for s in states) + "  %.3f / %.3f  %.3f / %.3f / %.3f" % (
+            v["cert_tried"], v["cert_held"], v["line_tried"], v["line_cert"], v["line_held"]))
     today = mixes["bench"]["today"]
     off = today / MEASURED_TODAY - 1.0
     print("\ntoday's state on the bench mix: model %.0f, measured %.1f (%+.2f %%)" % (today, MEASURED_TODAY, 100 * off))

@@ -236,6 +236,7 @@ SIGNATURES = {
     "rb_engine_set_prune_parts": (_int, [_vp, C.c_uint32]),
     "rb_engine_set_prune_trace": (_int, [_vp, _vp]),
     "rb_engine_set_cert_load": (_int, [_vp, C.c_size_t, C.c_double]),
+    "rb_engine_set_lead_min": (_int, [_vp, C.c_size_t, C.c_int]),
     "rb_engine_set_phased": (_int, [_vp, _u64, _u64, _u32, _u32, _u32]),
     "rb_engine_set_timing": (_int, [_vp, _int]),
     "rb_engine_kernel_time": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_u64)]),
@@ -814,8 +815,14 @@ class Engine:
 
     def set_prune_parts(self, mask):
         """refinements of bound pruning: bit 0 checks after every eight k-mers, bit 1 the stronger strand first, bit 2 the other strand
-        certified from the first hash alone (default 7; results identical)"""
+        certified from the first hash alone, bit 3 the line of the leading strand's best bin counted first and its other bins certified
+        likewise (default 15; results identical)"""
         _check(lib().rb_engine_set_prune_parts(self.h, int(mask)), "rb_engine_set_prune_parts")
+
+    def set_lead_min(self, filter_index, min_count):
+        """count of the leading strand's first 64 k-mers from which bit 3 of set_prune_parts is attempted: < 0 derive from the filter's
+        load (default), 0 always attempt"""
+        _check(lib().rb_engine_set_lead_min(self.h, filter_index, int(min_count)), "rb_engine_set_lead_min")
 
     def set_cert_load(self, filter_index, load):
         """bit load (of the fullest bin) the certificate's attempt rule assumes for a filter: < 0 measure (default), 0 always attempt, >= 1 never"""

@@ -157,6 +157,7 @@ struct CountLaunch {
     int prune_parts;          // ... and its refinements, bits as in rb_engine_set_prune_parts (ignored while bound_prune is 0)
     uint64_t *prune_trace;    // ... one record per (read, slice) of this launch (prune_trace_record), or nullptr
     float cert_d, cert_c;     // ... the certificate's allowance over rem k-mers: cert_d * rem + cert_c * sqrt(rem) (see PruneCfg)
+    uint32_t lead_min;        // ... the probe maximum from which the leader's line is counted first (kPruneLeadMinShift)
 };
 
 // By-value argument of ibf_count_max_kernel: how it prunes.
@@ -164,6 +165,9 @@ constexpr uint32_t kPruneBound = 1u;    // bound pruning on
 constexpr uint32_t kPruneSubTile = 2u;  // ... checked after every eight k-mers, not only at tile boundaries
 constexpr uint32_t kPruneLead = 4u;     // ... both strands probed, the stronger finished first
 constexpr uint32_t kPruneCert = 8u;     // ... the trailing strand certified from hash 0 alone where that is promising
+constexpr uint32_t kPruneLeadLine = 16u;  // ... the 128-byte line of the leader's best probe bin counted first, its other lanes certified likewise
+constexpr uint32_t kPruneLeadMinShift = 8;  // bits 8-15 of the flags: the lead line is attempted when the leader's probe maximum is at least this
+                                            // (reads without a match stay below it; a probe counts at most 64, so 65 and more mean never)
 struct PruneCfg {
     uint32_t flags;
     float cert_d, cert_c;  // the load d of the filter's fullest bin and z * sqrt(d (1 - d)): a certificate is attempted when the leader's maximum is at
@@ -172,12 +176,15 @@ struct PruneCfg {
 };
 // The 8-byte record a wave leaves per (read, slice) when a trace is asked for (rb_engine_set_prune_trace): bit 0 = the strand that was
 // finished first (0 forward, 1 reverse), bit 1 = the strands were probed (the lead was chosen, not given), bit 2 = a certificate was
-// attempted for the trailing strand, bit 3 = it held, bit 15 = record written,
+// attempted for the trailing strand, bit 3 = it held, bit 4 = the leader's line was counted first, bit 5 = a certificate was attempted for
+// the leader's other lanes, bit 6 = it held, bit 15 = record written,
 // bits 16-31 / 32-47 = the k-mer position at which the gathers of the forward / reverse strand ended (n: counted to the end; less:
-// the whole wave was dead there, or the strand was not continued behind its probe, or -- 0 -- not counted at all).
-__host__ __device__ inline uint64_t prune_trace_record(uint32_t lead, bool probed, uint32_t cert_bits, uint32_t stop_fwd, uint32_t stop_rev)
+// the whole wave was dead there, or the strand was not continued behind its probe, or -- 0 -- not counted at all; a leader whose line
+// was counted first reports its last all-hash call: the line's where the other lanes' certificate held, the other lanes' otherwise).
+__host__ __device__ inline uint64_t prune_trace_record(uint32_t lead, bool probed, uint32_t cert_bits, uint32_t stop_fwd, uint32_t stop_rev,
+                                                         uint32_t line_bits = 0)
 {
-    return (uint64_t)(lead & 1u) | (probed ? 2ull : 0ull) | ((uint64_t)(cert_bits & 3u) << 2) | (1ull << 15) | ((uint64_t)(stop_fwd & 0xFFFFu) << 16) | ((uint64_t)(stop_rev & 0xFFFFu) << 32);
+    return (uint64_t)(lead & 1u) | (probed ? 2ull : 0ull) | ((uint64_t)(cert_bits & 3u) << 2) | ((uint64_t)(line_bits & 7u) << 4) | (1ull << 15) | ((uint64_t)(stop_fwd & 0xFFFFu) << 16) | ((uint64_t)(stop_rev & 0xFFFFu) << 32);
 }
 
 inline uint8_t geom_code(int lg, int wpl, int nt) { return (uint8_t)(lg | (wpl == 2 ? 8 : 0) | (nt ? 16 : 0)); }

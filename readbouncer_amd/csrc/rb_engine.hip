@@ -342,12 +342,15 @@ struct rb_engine {
     // finished first), and rb_engine_set_prune_trace: where the waves of the plain count kernel say which path they took (nullptr: nowhere)
     // bit 2: the trailing strand certified from hash 0 alone where the load of the filter's fullest bin says that is promising -- rb_engine_set_cert_load:
     // the load per filter index (< 0 or none: measured with the occupancy pass when the filter is first planned, and again when its bits change)
-    uint32_t prune_parts = 7;
+    // bit 3: the line of the leader's best probe bin counted first and its other lanes certified likewise -- rb_engine_set_lead_min: the probe
+    // maximum it takes (< 0: derived from the same load)
+    uint32_t prune_parts = 15;
     uint64_t *prune_trace = nullptr;
     struct CertLoad {
         double set = -1.0;       // what the caller gave (< 0: measure)
         double measured = -1.0;  // load of the filter's fullest bin at `version` (< 0: not measured yet)
         uint64_t version = 0;
+        int lead_min = -1;       // rb_engine_set_lead_min (< 0: derive)
     };
     std::vector<CertLoad> cert_loads;  // by filter index
     DevBuf d_occupancy;                // ... where the occupancy pass counts for it
@@ -1402,7 +1405,8 @@ int rb_engine_set_bound_pruning(rb_engine *e, int enabled)
 
 int rb_engine_set_prune_parts(rb_engine *e, uint32_t mask)
 {
-    if (!e || mask > 7) return rb::fail(RB_ERR_INVALID_ARG, "mask 0..7 (bit 0: sub-tile checks, bit 1: strand lead, bit 2: certificate)");
+    if (!e || mask > 15)
+        return rb::fail(RB_ERR_INVALID_ARG, "mask 0..15 (bit 0: sub-tile checks, bit 1: strand lead, bit 2: certificate, bit 3: lead line)");
     std::lock_guard<std::mutex> lock(e->mu);
     e->prune_parts = mask;
     return RB_OK;
@@ -1418,6 +1422,33 @@ int rb_engine_set_cert_load(rb_engine *e, size_t filter_index, double load)
     return RB_OK;
 }
 
+int rb_engine_set_lead_min(rb_engine *e, size_t filter_index, int min_count)
+{
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (filter_index >= e->filters.size()) return rb::fail(RB_ERR_INVALID_ARG, "no such filter");
+    if (e->cert_loads.size() < e->filters.size()) e->cert_loads.resize(e->filters.size());
+    e->cert_loads[filter_index].lead_min = min_count;
+    return RB_OK;
+}
+
+// The probe maximum from which the lead line is attempted: the smallest t that a read WITHOUT a match is not expected to reach in its
+// 64-k-mer probes.  A bin of load d counts a foreign k-mer with probability p = d^h, so its probe count is Binomial(64, p); t is the
+// smallest count with 2 strands x n_bins x P(X >= t) <= 1 %.  Such reads then never walk the read a second time for one line (d = 55/256,
+// h = 3, 8192 bins: 8).  Like the certificate's rule it picks attempts only.
+static uint32_t lead_min_for(double d, uint32_t n_hash, uint64_t n_bins)
+{
+    const double p = std::pow(std::min(std::max(d, 0.0), 1.0), (double)std::max(n_hash, 1u));
+    if (p >= 1.0) return 65;
+    double pmf = std::pow(1.0 - p, 64.0), tail = 1.0;  // P(X = 0), P(X >= 0)
+    for (uint32_t t = 0; t <= 64; ++t) {
+        if (2.0 * (double)std::max<uint64_t>(n_bins, 1) * tail <= 0.01) return std::max(t, 1u);
+        tail -= pmf;
+        pmf *= (double)(64 - t) / (double)(t + 1) * p / (1.0 - p);
+    }
+    return 65;
+}
+
 // The certificate's allowance for filter fi (kernel: cert_d * rem + cert_c * sqrt(rem)); *on = false: no attempt in this call.
 // Called only for launches that can attempt one (the plain kernel, unfused).  d is the load of the filter's FULLEST bin: the
 // certificate fails on the one bin that passes the allowance, so the allowance has to cover every bin (a filter whose bins are
@@ -1425,7 +1456,7 @@ int rb_engine_set_cert_load(rb_engine *e, size_t filter_index, double load)
 // with the occupancy pass into the engine's own buffer when the filter is first used and again after its bits have changed: about
 // a millisecond on 8 GiB plus one synchronising copy of n_bins words; never while `st` is being captured -- such a call goes
 // without the certificate until an uncaptured one has measured.
-static int cert_allowance(rb_engine *e, size_t fi, hipStream_t st, float *cert_d, float *cert_c, bool *on)
+static int cert_allowance(rb_engine *e, size_t fi, hipStream_t st, float *cert_d, float *cert_c, uint32_t *lead_min, bool *on)
 {
     constexpr double kCertZ = 4.5;  // the 8192-bin tail of the hash-0 counts sits near 3.8 sigma
     if (e->cert_loads.size() < e->filters.size()) e->cert_loads.resize(e->filters.size());
@@ -1455,6 +1486,7 @@ static int cert_allowance(rb_engine *e, size_t fi, hipStream_t st, float *cert_d
     *on = d < 1.0;
     *cert_d = (float)d;
     *cert_c = (float)(kCertZ * std::sqrt(std::max(0.0, d * (1.0 - d))));
+    *lead_min = c.lead_min >= 0 ? (uint32_t)c.lead_min : lead_min_for(d, e->filters[fi]->geo.n_hash, e->filters[fi]->geo.n_bins);
     return RB_OK;
 }
 
@@ -2392,8 +2424,8 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
         const bool fuses = a.n_slices == 1 && !fan_out && nf > 1 && n_reads <= e->split_threshold;
         if (a.bound_prune && (a.prune_parts & 4) && a.lg == 6 && a.split_waves < 2 && a.phase.n_slices == 0 && !fuses) {
             bool cert_on = false;
-            if ((rc = cert_allowance(e, fi, fs, &a.cert_d, &a.cert_c, &cert_on)) != RB_OK) return rc;
-            if (!cert_on) a.prune_parts &= ~4;
+            if ((rc = cert_allowance(e, fi, fs, &a.cert_d, &a.cert_c, &a.lead_min, &cert_on)) != RB_OK) return rc;
+            if (!cert_on) a.prune_parts &= ~(4 | 8);  // (the lead line certifies too)
         }
         if (e->prune_trace) {  // records lie filter after filter, [read][slice] within a filter
             a.prune_trace = e->prune_trace + trace_off;

@@ -487,7 +487,7 @@ __device__ __forceinline__ void phased_gather_x4(uint64_t (&x0)[N], uint64_t (&x
 // kNoBound where counters can wrap (n >= 2^NP: the 16-plane builds reproduce the reference's uint16_t wrap, and the bound is false
 // there) and where the engine switched pruning off (rb_engine_set_bound_pruning).
 //
-// Three refinements of the bound (ibf_count_max_kernel's `prune` word, rb_engine_set_prune_parts), and why the maximum stays exact:
+// Four refinements of the bound (ibf_count_max_kernel's `prune` word, rb_engine_set_prune_parts), and why the maximum stays exact:
 //   * SUB-TILE CHECKS (`sub_checks`): the same compare after every eight-step block of a tile, behind a scalar gate, with rem taken at that
 //     point and M_stale = the M of the last tile boundary.  It is the argument above with a smaller rem and an M that is never above the
 //     true one (counters never shrink): a smaller M only kills later.  For a negative read the gate opens in the last ~13 k-mers only.
@@ -501,6 +501,8 @@ __device__ __forceinline__ void phased_gather_x4(uint64_t (&x0)[N], uint64_t (&x
 //     >= true count, so if the maximum of that stays <= M (the leader's maximum) the strand's maximum is <= M and the read's result
 //     is M.  The bound prunes this pass too (an upper bound that cannot pass M any more need not be followed); the pass is left as
 //     failed the moment a counter exceeds M, and the strand is then counted in full from its probe counters.
+//   * LEAD LINE (the caller once more; `lanes`): the leader strand's passes take a subset of the lanes each -- first the line of its best probe
+//     bin, then the rest as a certificate or in full (ibf_count_max_kernel).  A lane outside `lanes` behaves as a dead one from the start.
 //   * `stop_pos` reports the k-mer position at which this call's gathers ended (n, or where the whole wave was dead).
 constexpr uint32_t kNoBound = 0xFFFFFFFFu;
 
@@ -540,7 +542,7 @@ __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev
                                              uint32_t mt_first, uint32_t mt_step, int blk_first, int blk_end,
                                              uint8_t *stage, int lane, const PhaseCfg ph = PhaseCfg{0, 0, 0, 0, 0}, uint32_t stop_at = 0xFFFFFFFFu,
                                              uint32_t bound_best = kNoBound, uint32_t mt_end = 0xFFFFFFFFu, bool sub_checks = false,
-                                             uint32_t *stop_pos = nullptr)
+                                             uint32_t *stop_pos = nullptr, uint64_t lanes = ~0ULL)
 {
     using T = TileShape<LG>;
     constexpr int NG = T::NG, SPT = T::SPT, J = T::J, ITEMS = T::ITEMS;
@@ -550,7 +552,12 @@ __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev
     const int g = lane >> LG;
     const uint32_t S = f.stride;  // words between consecutive blocks in HBM (>= bin_width, see rb_engine.hip)
     const uint32_t k = f.k;
-    bool lane_on = lc.colok;  // lane gathers (BOUND: and is not dead yet)
+    // lane gathers (BOUND: and is not dead yet).  `lanes` (wave-uniform; the lead line) names the lanes that take part at all: the others are
+    // off from the start -- they read block 0 and add 0, as dead lanes do, and keep the counters they came with
+    bool lane_on = lc.colok;
+    if constexpr (BOUND) {
+        if (lanes != ~0ULL) lane_on = lane_on && ((lanes >> lane) & 1ULL) != 0;  // (scalar branch; callers without the argument compile as they did)
+    }
     const uint32_t n_end = min(n, mt_end);  // k-mers this call counts up to
     uint32_t m_stale = bound_best;          // BOUND: the M of the last boundary check (scalar)
     uint32_t stopped = n_end;               // where the gathers ended: n_end, or the check that found the whole wave dead
@@ -812,8 +819,8 @@ struct EarlyCfg {
 // probe's counters wait in LDS meanwhile (after 64 k-mers only planes 0-6 can be set: kParkPlanes x WPL x 64 lanes x 8 bytes per
 // wave), the strand with the larger probe maximum LEADS (a tie: forward, so a read always takes the same path), and the other one
 // continues from k-mer 64 against the leader's maximum, its probe counters back from LDS -- after an attempt to CERTIFY it from hash 0
-// alone (count_strand) where the leader's maximum makes that promising.  The four passes are one loop around one count_strand call, so
-// the three-hash gather schedule exists once.
+// alone (count_strand) where the leader's maximum makes that promising.  The passes of a lead build are one loop around one count_strand
+// call per H, so the three-hash gather schedule exists once in it.
 constexpr int kParkPlanes = 7;
 constexpr bool plain_leads(int lg, int h, bool early) { return lg == 6 && h > 0 && !early; }
 
@@ -863,87 +870,175 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
     const int n_pass = leads ? 4 : 2;
     uint32_t best = 0, probe0 = 0, lead = 0, cert_bits = 0;  // (probe0: the forward probe's maximum, then the trailing strand's)
     uint32_t stops = 0;  // per strand, 16 bits each: where its gathers ended (the trace)
+    // A pass of a lead build is one to three calls (all wave-uniform), `stage` says which is next: 0 = the pass begins; 1 = the leader's
+    // line is counted, the other lanes are due; 2 = a certificate has failed, the lanes it covered are counted in full
+    const bool lead_line = cert && (prune.flags & kPruneLeadLine);
+    uint32_t stage = 0, lead_probe = 0, line_bits = 0;
+    uint64_t line = 0;  // the lanes of the leader's line
     Planes<NP> pl[WPL];
+    if constexpr (!LEADS) {
+        // (the builds without the lead keep the loop they had word for word -- `leads` is false in them -- and their code with it: any other
+        // wording of these two passes, or one loop shared with the lead builds, changed their instructions; profiles/isa_identity.py)
 #pragma unroll 1
-    for (int pass = 0; pass < n_pass; ++pass) {
-        const bool probe = leads && pass < 2;
-        const int strand = (!leads || pass < 2) ? pass : (int)(lead ^ (uint32_t)(pass & 1));
-        // a strand counts at most n per bin: once the first strand's maximum has reached n the second cannot exceed it
-        if (bound && (pass & 1) && !probe && best >= n) break;  // wave-uniform
-        if constexpr (LEADS) {
-            if (leads && pass == 1) {  // the forward probe waits in LDS
+        for (int pass = 0; pass < n_pass; ++pass) {
+            const bool probe = leads && pass < 2;
+            const int strand = (!leads || pass < 2) ? pass : (int)(lead ^ (uint32_t)(pass & 1));
+            // a strand counts at most n per bin: once the first strand's maximum has reached n the second cannot exceed it
+            if (bound && (pass & 1) && !probe && best >= n) break;  // wave-uniform
+            if (!leads || pass < 2) {
 #pragma unroll
-                for (int w = 0; w < WPL; ++w)
-#pragma unroll
-                    for (int i = 0; i < kParkPlanes; ++i) s_park[wave][w * kParkPlanes + i][lane] = pl[w].p[i];
+                for (int w = 0; w < WPL; ++w) pl[w].clear();
             }
+            uint32_t stopped = 0;
+            const bool left = count_strand<LG, WPL, NP, H, NT, false, EARLY>(pl, f, lc, seq, len, n, strand, leads && pass >= 2 ? TILE : 0u, TILE, 0,
+                                                                             TileShape<LG>::STEPS / 8, s_stage[wave], lane, PhaseCfg{0, 0, 0, 0, 0}, stop_at,
+                                                                             !bound || probe ? kNoBound : best,
+                                                                             probe ? TILE : 0xFFFFFFFFu, sub, &stopped);
+            stops = strand == 0 ? (stops & 0xFFFF0000u) | (stopped & 0xFFFFu) : (stops & 0xFFFFu) | (stopped << 16);
+            const uint32_t m = planes_max<NP, WPL>(pl, lc.valid);
+            if (!probe) best = m > best ? m : best;
+            if (EARLY && left) break;  // wave-uniform
         }
-        if (!leads || pass < 2) {
+    } else {
+#pragma unroll 1
+        for (int pass = 0; pass < n_pass;) {
+            const bool probe = leads && pass < 2;
+            const int strand = (!leads || pass < 2) ? pass : (int)(lead ^ (uint32_t)(pass & 1));
+            if (stage == 0) {
+                // a strand counts at most n per bin: once the first strand's maximum has reached n the second cannot exceed it
+                if (bound && (pass & 1) && !probe && best >= n) break;  // wave-uniform
+                if constexpr (LEADS) {
+                    if (leads && pass == 1) {  // the forward probe waits in LDS
 #pragma unroll
-            for (int w = 0; w < WPL; ++w) pl[w].clear();
-        }
-        if constexpr (LEADS) {
-            if (leads && pass == 3) {  // the other strand's probe comes back (its planes above 6 are zero)
+                        for (int w = 0; w < WPL; ++w)
 #pragma unroll
-                for (int w = 0; w < WPL; ++w) {
-                    pl[w].clear();
-#pragma unroll
-                    for (int i = 0; i < kParkPlanes; ++i) pl[w].p[i] = s_park[wave][w * kParkPlanes + i][lane];
-                }
-                // the certificate: worth a third of a strand when the leader's maximum clears the trailing probe's maximum plus the hash-0
-                // hits a bin of load d (the filter's fullest) is expected to add over the rest, z sigma up (cert_c = z sqrt(d (1 - d))).  The rule only
-                // picks the attempts; a failed one costs lines, never a result.
-                const float rem = (float)(n - TILE);
-                if (cert && (float)(best - min(best, probe0)) >= prune.cert_d * rem + prune.cert_c * __builtin_sqrtf(rem)) {
-                    cert_bits = 1u;
-                    const bool over = count_strand<LG, WPL, NP, 1, NT, false, true>(pl, f, lc, seq, len, n, strand, TILE, TILE, 0, TileShape<LG>::STEPS / 8,
-                                                                                    s_stage[wave], lane, PhaseCfg{0, 0, 0, 0, 0}, best + 1u, best,
-                                                                                    0xFFFFFFFFu, sub);
-                    if (!over && planes_max<NP, WPL>(pl, lc.valid) <= best) {  // wave-uniform
-                        cert_bits = 3u;
-                        break;
+                            for (int i = 0; i < kParkPlanes; ++i) s_park[wave][w * kParkPlanes + i][lane] = pl[w].p[i];
                     }
+                }
+                if (!leads || pass < 2) {
+#pragma unroll
+                    for (int w = 0; w < WPL; ++w) pl[w].clear();
+                }
+            }
+            uint64_t lanes = ~0ULL;                          // the lanes this call gathers for
+            uint32_t from = leads && pass >= 2 ? TILE : 0u;  // ... from this k-mer
+            bool one_hash = false;                           // ... as a certificate: hash 0 alone, left the moment a counter passes `best`
+            bool more = false;                               // ... and the pass goes on behind it
+            if constexpr (LEADS) {
+                // the certificate's rule: worth a third of the lines when the maximum in hand clears the probe maximum of the bins in question plus
+                // the hash-0 hits a bin of load d (the filter's fullest) is expected to add over the rest, z sigma up (cert_c = z sqrt(d (1 - d))).
+                // The rule only picks the attempts; a failed one costs lines, never a result.
+                const float rem = (float)(n - TILE);
+                const float allowance = prune.cert_d * rem + prune.cert_c * __builtin_sqrtf(rem);
+                if (leads && pass == 3) {  // the other strand's probe comes back (its planes above 6 are zero): at first, and after a failed certificate
 #pragma unroll
                     for (int w = 0; w < WPL; ++w) {
                         pl[w].clear();
 #pragma unroll
                         for (int i = 0; i < kParkPlanes; ++i) pl[w].p[i] = s_park[wave][w * kParkPlanes + i][lane];
                     }
+                    if (stage == 0 && cert && (float)(best - min(best, probe0)) >= allowance) {
+                        cert_bits = 1u;
+                        one_hash = true;
+                    }
                 }
-            }
-        }
-        uint32_t stopped = 0;
-        const bool left = count_strand<LG, WPL, NP, H, NT, false, EARLY>(pl, f, lc, seq, len, n, strand, leads && pass >= 2 ? TILE : 0u, TILE, 0,
-                                                                         TileShape<LG>::STEPS / 8, s_stage[wave], lane, PhaseCfg{0, 0, 0, 0, 0}, stop_at,
-                                                                         !bound || probe ? kNoBound : best,
-                                                                         probe ? TILE : 0xFFFFFFFFu, sub, &stopped);
-        stops = strand == 0 ? (stops & 0xFFFF0000u) | (stopped & 0xFFFFu) : (stops & 0xFFFFu) | (stopped << 16);
-        const uint32_t m = planes_max<NP, WPL>(pl, lc.valid);
-        if (!probe) best = m > best ? m : best;
-        if constexpr (LEADS) {
-            if (leads && pass == 0) probe0 = m;
-            if (leads && pass == 1) {
-                lead = m > probe0 ? 1u : 0u;  // a tie: forward
-                probe0 = min(m, probe0);      // the trailing strand's probe maximum
-                if (lead == 0) {  // the registers hold the reverse probe: change places with the forward one
+                // LEAD LINE (kPruneLeadLine): the leader is counted with all hashes on all lines until its own maximum has outgrown the k-mers left, and
+                // nearly all of that goes to bins that only have to be shown to stay at or below that maximum.  The maximum is one bin's count, and
+                // a bin lies in one 128-byte line of every block.  So the lanes of the line that holds the probe's best bin are counted first, alone:
+                // H lines per k-mer, after which they hold exact totals and `best` is a count some bin truly reaches.  The other lanes kept their
+                // probe counters and are then certified against it from hash 0 like a trailing strand (for every one of their bins, probe count +
+                // hash-0 hits >= true count; if none passes `best` the strand's maximum is `best`), or, where the rule does not promise that, counted
+                // in full from k-mer 64 against `best`.  After a failed certificate their counters are upper bounds: they are cleared and counted from
+                // k-mer 0.  If the strand's best bin lies in another line, that is where it is found.  `lead_min` keeps reads without a match out of
+                // the second walk over the read; like the rule it picks attempts and changes no result.
+                if (leads && pass == 2 && lead_line) {
+                    constexpr int LL = 16 / WPL;  // lanes whose columns share 128 bytes of a block
+                    uint64_t others[WPL];
 #pragma unroll
-                    for (int w = 0; w < WPL; ++w)
-#pragma unroll
-                        for (int i = 0; i < kParkPlanes; ++i) {
-                            const uint64_t t = s_park[wave][w * kParkPlanes + i][lane];
-                            s_park[wave][w * kParkPlanes + i][lane] = pl[w].p[i];
-                            pl[w].p[i] = t;
+                    for (int w = 0; w < WPL; ++w) others[w] = ((line >> lane) & 1ULL) ? 0ULL : lc.valid[w];
+                    if (stage == 0) {
+                        if (lead_probe >= ((prune.flags >> kPruneLeadMinShift) & 0xFFu)) {
+                            // lowest lane that holds the probe's maximum
+                            const bool holds = lead_probe ? bound_alive<NP, WPL>(pl, lc.valid, lead_probe - 1u) : lc.colok;
+                            const uint64_t b = __ballot(holds);
+                            if (b != 0ULL) {
+                                line = ((1ULL << LL) - 1ULL) << ((uint32_t)__builtin_ctzll(b) & ~(uint32_t)(LL - 1));
+                                lanes = line;
+                                more = true;
+                                line_bits = 1u;
+                            }
                         }
+                    } else {
+                        lanes = ~line;
+                        if (stage == 1) {
+                            const uint32_t theirs = planes_max<NP, WPL>(pl, others);
+                            if ((float)(best - min(best, theirs)) >= allowance) {
+                                line_bits |= 2u;
+                                one_hash = true;
+                            }
+                        } else {  // what the failed certificate left in the other lanes is no count
+                            from = 0u;
+#pragma unroll
+                            for (int w = 0; w < WPL; ++w)
+#pragma unroll
+                                for (int i = 0; i < NP; ++i) pl[w].p[i] = ((line >> lane) & 1ULL) ? pl[w].p[i] : 0ULL;
+                        }
+                    }
+                }
+                if (one_hash) {
+                    const bool over = count_strand<LG, WPL, NP, 1, NT, false, true>(pl, f, lc, seq, len, n, strand, TILE, TILE, 0, TileShape<LG>::STEPS / 8,
+                                                                                    s_stage[wave], lane, PhaseCfg{0, 0, 0, 0, 0}, best + 1u, best,
+                                                                                    0xFFFFFFFFu, sub, nullptr, lanes);
+                    if (!over && planes_max<NP, WPL>(pl, lc.valid) <= best) {  // wave-uniform: held
+                        if (pass == 3) {
+                            cert_bits = 3u;
+                            break;
+                        }
+                        line_bits |= 4u;
+                        pass = 3;
+                        stage = 0;
+                    } else {
+                        stage = 2;
+                    }
+                    continue;
                 }
             }
+            uint32_t stopped = 0;
+            const bool left = count_strand<LG, WPL, NP, H, NT, false, EARLY>(pl, f, lc, seq, len, n, strand, from, TILE, 0,
+                                                                             TileShape<LG>::STEPS / 8, s_stage[wave], lane, PhaseCfg{0, 0, 0, 0, 0}, stop_at,
+                                                                             !bound || probe ? kNoBound : best,
+                                                                             probe ? TILE : 0xFFFFFFFFu, sub, &stopped, lanes);
+            stops = strand == 0 ? (stops & 0xFFFF0000u) | (stopped & 0xFFFFu) : (stops & 0xFFFFu) | (stopped << 16);
+            const uint32_t m = planes_max<NP, WPL>(pl, lc.valid);
+            if (!probe) best = m > best ? m : best;
+            if constexpr (LEADS) {
+                if (leads && pass == 0) probe0 = m;
+                if (leads && pass == 1) {
+                    lead = m > probe0 ? 1u : 0u;  // a tie: forward
+                    lead_probe = max(m, probe0);  // the leader's probe maximum
+                    probe0 = min(m, probe0);      // the trailing strand's probe maximum
+                    if (lead == 0) {  // the registers hold the reverse probe: change places with the forward one
+#pragma unroll
+                        for (int w = 0; w < WPL; ++w)
+#pragma unroll
+                            for (int i = 0; i < kParkPlanes; ++i) {
+                                const uint64_t t = s_park[wave][w * kParkPlanes + i][lane];
+                                s_park[wave][w * kParkPlanes + i][lane] = pl[w].p[i];
+                                pl[w].p[i] = t;
+                            }
+                    }
+                }
+            }
+            if (EARLY && left) break;  // wave-uniform
+            stage = more ? 1u : 0u;
+            if (!more) ++pass;
         }
-        if (EARLY && left) break;  // wave-uniform
     }
     if (lane == 0) out[(size_t)read * out_read_stride + (size_t)slice * out_slice_stride] = (uint16_t)best;
     if (prune.trace) {  // (one scalar branch when there is none)
         if (lane == 0)
             prune.trace[(size_t)blockIdx.y * n_reads * n_slices + item] =
-                prune_trace_record(lead, leads, cert_bits, stops & 0xFFFFu, stops >> 16);
+                prune_trace_record(lead, leads, cert_bits, stops & 0xFFFFu, stops >> 16, line_bits);
     }
 }
 
@@ -3354,7 +3449,8 @@ static hipError_t launch_count_nt(const CountLaunch &a, hipStream_t st)
     prune.trace = a.n_fused == 0 ? a.prune_trace : nullptr;
     prune.cert_d = a.cert_d;
     prune.cert_c = a.cert_c;
-    if (a.n_fused > 0) prune.flags &= ~kPruneCert;  // (the allowance is one filter's)
+    prune.flags |= (a.lead_min < 255u ? a.lead_min : 255u) << kPruneLeadMinShift;
+    if (a.n_fused > 0) prune.flags &= ~(kPruneCert | kPruneLeadLine);  // (the allowance is one filter's)
     if constexpr (H == 3 && NP == 10) {  // (the early-decision builds exist for three hash functions and ten counter planes: what config 3 / 4 take)
         if (a.early_thr && a.n_fused == 0) {
             early.thr = a.early_thr;
