@@ -185,6 +185,8 @@ typedef struct rb_plan_info {
     uint32_t reserved0;
     uint64_t phase_slice_bytes;  /* slice length in effect: 2^phase_slice_log2, or -- four-word one-lane builds -- the equal-length slices
                                   * the table is cut into instead (fewer and up to 1.19 x longer; rb_phase_plan.h, phase_equal_slices) */
+    uint64_t row_table_bytes;    /* > 0: kernel is ibf_count_rows_kernel, the row form of the plain kernel (rb_engine_set_row_table), gathering
+                                  * from the filter's row table of that size -- the one it has, or the one the call would build */
 } rb_plan_info;
 RB_API int rb_engine_plan(rb_engine *e, size_t filter_index, size_t n_reads, uint32_t max_len, rb_plan_info *out);
 /* The same question for the query passes of readbouncer_amd.h (locate, hits, prefixes and spans, host and device forms),
@@ -294,6 +296,53 @@ RB_API int rb_engine_set_lead_min(rb_engine *e, size_t filter_index, int min_cou
  * share a launch (batches up to rb_engine_set_split_threshold on an engine with several filters): a fused launch writes no record and
  * never attempts the certificate of rb_engine_set_prune_parts. */
 RB_API int rb_engine_set_prune_trace(rb_engine *e, void *d_trace);
+
+/* ROW TABLE of a resident filter (k <= 13, blocks of a whole wave: more than 32 words).  A k-mer counts in a bin where all h of its
+ * blocks have the bit, and for a resident filter that AND depends on the k-mer alone; there are only 4^k k-mers without an N.  The table
+ * holds that AND for each of them -- row r for the k-mer whose base-4 digits are r (A C G T = 0 1 2 3, first base most significant), 4^k
+ * rows of the filter's block stride -- so that the count kernel gathers ONE block per k-mer instead of h (ibf_count_rows_kernel).  Results
+ * are identical: reads with a base outside ACGT have k-mers without a row and are counted from the filter's own table by a second
+ * launch over the same batch, the three-hash twin of the row build (a wave of either launch leaves at once when its read is the other's).  The FILTER owns the table: engines on one filter share it, rb_dibf_free frees it, and every call that changes the filter's
+ * bits (insert, add_sequence, fill_synth, rb_dibf_touch) drops it; filters made from others (resize, assemble, select, clone, open,
+ * upload) start without one.
+ *   rb_dibf_row_table_build: build it now unless a current one exists.  max_bytes = 0: no limit of the caller's; the rule that a table
+ *     takes at most half of the device memory free at that moment holds whatever max_bytes says.  A refusal is not an
+ *     error: the call returns RB_OK and rb_dibf_row_table_info says why (refused != 0) -- k above 13, narrow blocks, 4^k x stride above
+ *     max_bytes or above half of the free device memory, or the allocation failed.
+ *   rb_dibf_row_table_drop: free it.
+ *   rb_dibf_row_table_info: bytes and rows of the current table (0: none), what building it cost, why the last build was refused.
+ *   rb_dibf_row_table_download: the table's words into host memory (tests).
+ *   rb_engine_set_row_table(mode, max_bytes): RB_ROW_TABLE_OFF never uses a table; RB_ROW_TABLE_AUTO (default, max_bytes 96 GiB) uses
+ *     it -- building it inside the classify call when there is none -- for launches of the plain count kernel on whole-wave blocks with
+ *     three hash functions (no latency form, no fused micro-batch, no early-decision mode, no column shard, no trace asked for, k <= 13)
+ *     whose batch alone repays the build: items x 2 x k-mers x (h - 1) >= 4^k x (h + 1) block transfers (config 3: 193 000 reads of
+ *     360 bp); RB_ROW_TABLE_FORCE drops the batch-size rule and the trace rule.  A call whose stream is being captured neither builds
+ *     nor uses a table (a graph would keep the address of memory that the next change of the filter frees).  The row launches are
+ *     non-temporal when the ROW TABLE is beyond rb_engine_set_nt_threshold, whatever the filter's own size.
+ *     Wherever a condition fails or the build is refused the call runs the three-hash kernel as before.  max_bytes = 0 keeps the value. */
+#define RB_ROW_TABLE_OFF 0
+#define RB_ROW_TABLE_AUTO 1
+#define RB_ROW_TABLE_FORCE 2
+#define RB_ROW_REFUSED_NONE 0
+#define RB_ROW_REFUSED_K 1         /* k above 13 */
+#define RB_ROW_REFUSED_NARROW 2    /* blocks of 32 words or fewer */
+#define RB_ROW_REFUSED_MAX_BYTES 3 /* 4^k x stride above max_bytes */
+#define RB_ROW_REFUSED_FREE 4      /* ... above half of the free device memory */
+#define RB_ROW_REFUSED_ALLOC 5     /* the allocation failed */
+#define RB_ROW_REFUSED_CAPTURE 6   /* the call's stream was being captured (engine builds only) */
+typedef struct rb_row_table_info {
+    uint64_t bytes, rows;   /* of the current table; 0: none */
+    uint64_t want_bytes;    /* 4^k x stride x 8 (0: k above 13) */
+    double build_ms;        /* kernel time of the last build */
+    double alloc_s;         /* seconds its allocation took */
+    uint32_t refused;       /* RB_ROW_REFUSED_*: why the last build did not happen */
+    uint32_t builds;        /* tables built for this filter so far */
+} rb_row_table_info;
+RB_API int rb_dibf_row_table_build(rb_dibf *f, uint64_t max_bytes);
+RB_API int rb_dibf_row_table_drop(rb_dibf *f);
+RB_API int rb_dibf_row_table_info(rb_dibf *f, rb_row_table_info *out);
+RB_API int rb_dibf_row_table_download(rb_dibf *f, uint64_t *words, uint64_t n_words);
+RB_API int rb_engine_set_row_table(rb_engine *e, int mode, uint64_t max_bytes);
 
 /* How the eight XCDs walk the slices of a phased table (each has an L2 of its own, so each reloads every slice): bit 0 of `mode` -- at
  * any time every XCD works on a different slice (slice = (window + XCD number) mod slices); bit 1 -- the XCDs' windows start an eighth

@@ -79,7 +79,19 @@ class PlanInfo(C.Structure):
                 ("column_slices", C.c_uint32), ("counter_planes", C.c_uint32), ("nontemporal", C.c_uint32), ("split_waves", C.c_uint32),
                 ("phased", C.c_uint32), ("phase_shape", C.c_uint32), ("phase_shape_name", C.c_char * 64),
                 ("phase_slice_log2", C.c_uint32), ("phase_slices", C.c_uint32), ("phase_window_ticks", C.c_uint32),
-                ("phase_rule_ticks", C.c_uint32), ("reserved0", C.c_uint32), ("phase_slice_bytes", C.c_uint64)]
+                ("phase_rule_ticks", C.c_uint32), ("reserved0", C.c_uint32), ("phase_slice_bytes", C.c_uint64),
+                ("row_table_bytes", C.c_uint64)]
+
+
+class RowTableInfo(C.Structure):
+    """rb_row_table_info"""
+    _fields_ = [("bytes", C.c_uint64), ("rows", C.c_uint64), ("want_bytes", C.c_uint64), ("build_ms", C.c_double), ("alloc_s", C.c_double),
+                ("refused", C.c_uint32), ("builds", C.c_uint32)]
+
+
+RB_ROW_TABLE_OFF, RB_ROW_TABLE_AUTO, RB_ROW_TABLE_FORCE = 0, 1, 2
+(RB_ROW_REFUSED_NONE, RB_ROW_REFUSED_K, RB_ROW_REFUSED_NARROW, RB_ROW_REFUSED_MAX_BYTES, RB_ROW_REFUSED_FREE, RB_ROW_REFUSED_ALLOC,
+ RB_ROW_REFUSED_CAPTURE) = range(7)
 
 
 class PassPlan(C.Structure):
@@ -215,6 +227,11 @@ SIGNATURES = {
     "rb_engine_set_revcomp_of_n": (_int, [_vp, _u32]),
     "rb_set_default_revcomp_of_n": (_int, [_u32]),
     "rb_set_placement_tries": (_int, [_int]),
+    "rb_dibf_row_table_build": (_int, [_vp, _u64]),
+    "rb_dibf_row_table_drop": (_int, [_vp]),
+    "rb_dibf_row_table_info": (_int, [_vp, C.POINTER(RowTableInfo)]),
+    "rb_dibf_row_table_download": (_int, [_vp, _vp, _u64]),
+    "rb_engine_set_row_table": (_int, [_vp, _int, _u64]),
     "rb_dibf_placement": (_int, [_vp, C.POINTER(_u32), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "rb_dibf_placement_cost": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_u64), C.POINTER(_u32)]),
     "rb_engine_set_merge": (_int, [_vp, _int]),
@@ -416,6 +433,27 @@ class DeviceIBF:
         _check(lib().rb_dibf_probe_read_peak(self.h, table_bytes, row_bytes, int(bool(nontemporal)), loads_in_flight, target_ms,
                                              C.byref(g), C.byref(ms)), "rb_dibf_probe_read_peak")
         return g.value, ms.value
+
+    def row_table_build(self, max_bytes=0):
+        """build the row table (one row per N-free k-mer: the AND of its h blocks) unless a current one exists -> row_table_info()"""
+        _check(lib().rb_dibf_row_table_build(self.h, int(max_bytes)), "rb_dibf_row_table_build")
+        return self.row_table_info()
+
+    def row_table_drop(self):
+        _check(lib().rb_dibf_row_table_drop(self.h), "rb_dibf_row_table_drop")
+
+    def row_table_info(self):
+        """-> dict (rb_row_table_info): bytes and rows of the current table (0: none), want_bytes, build_ms, alloc_s, refused, builds"""
+        i = RowTableInfo()
+        _check(lib().rb_dibf_row_table_info(self.h, C.byref(i)), "rb_dibf_row_table_info")
+        return {k: getattr(i, k) for k, _ in RowTableInfo._fields_}
+
+    def row_table_download(self):
+        """-> np.uint64[rows, stride words]: the current row table"""
+        i = self.row_table_info()
+        out = np.zeros(i["bytes"] // 8, dtype=np.uint64)
+        _check(lib().rb_dibf_row_table_download(self.h, _ptr(out), len(out)), "rb_dibf_row_table_download")
+        return out.reshape(i["rows"], -1) if i["rows"] else out
 
     def placement(self):
         """-> (allocations probed for this table: 0 = not placed by trial, GB/s of the kept one, GB/s of the slowest one)"""
@@ -827,6 +865,11 @@ class Engine:
     def set_cert_load(self, filter_index, load):
         """bit load (of the fullest bin) the certificate's attempt rule assumes for a filter: < 0 measure (default), 0 always attempt, >= 1 never"""
         _check(lib().rb_engine_set_cert_load(self.h, filter_index, float(load)), "rb_engine_set_cert_load")
+
+    def set_row_table(self, mode, max_bytes=0):
+        """RB_ROW_TABLE_OFF / _AUTO (default) / _FORCE: whether plain whole-wave launches gather one precomputed row per k-mer from the
+        filter's row table, building it when there is none (results identical); max_bytes 0 keeps the limit (default 96 GiB)"""
+        _check(lib().rb_engine_set_row_table(self.h, int(mode), int(max_bytes)), "rb_engine_set_row_table")
 
     def set_prune_trace(self, device_ptr):
         """device memory for one 8-byte record per (filter, read, column slice) of the plain count kernel's waves, or 0 / None: none"""

@@ -158,6 +158,8 @@ struct CountLaunch {
     uint64_t *prune_trace;    // ... one record per (read, slice) of this launch (prune_trace_record), or nullptr
     float cert_d, cert_c;     // ... the certificate's allowance over rem k-mers: cert_d * rem + cert_c * sqrt(rem) (see PruneCfg)
     uint32_t lead_min;        // ... the probe maximum from which the leader's line is counted first (kPruneLeadMinShift)
+    // row form (launch_ibf_count_rows): the filter's row table -- one row of `f.stride` words per N-free k-mer -- or nullptr
+    const uint64_t *row_table;
 };
 
 // By-value argument of ibf_count_max_kernel: how it prunes.
@@ -332,6 +334,13 @@ struct SpansLaunch {
 hipError_t launch_ibf_spans(const SpansLaunch &a, hipStream_t st);
 
 hipError_t launch_ibf_count_max(const CountLaunch &a, hipStream_t st);
+// Row form of the plain whole-wave builds (rb_kernels.hip, ibf_count_rows_kernel): one gather per k-mer from a.row_table.  A filter has
+// a row table only for k <= kRowTableMaxK (4^13 rows: the block number of a row is a 32-bit rank and 4^k * stride must fit the device).
+constexpr uint32_t kRowTableMaxK = 13;
+bool row_form_serves(const CountLaunch &a);  // the launch is one the row form has a build for (geometry, form, hash count, k)
+hipError_t launch_ibf_count_rows(const CountLaunch &a, hipStream_t st);
+// rows[r * f.stride + w] <- the AND of the h blocks of the k-mer whose base-4 rank is r, for r < n_rows = 4^k
+hipError_t launch_row_table(const IbfDev &f, uint64_t *rows, uint64_t n_rows, hipStream_t st);
 hipError_t launch_ibf_count_max_merged(const CountLaunch &a, const MergeMap &map, hipStream_t st);
 // block b of a filter (width words at stride s_src, n_bins bins) -> bits [dst_bit, dst_bit + n_bins) of block b of dst (ORed in: dst starts zeroed)
 hipError_t launch_invert_words(const uint64_t *src, uint64_t *dst, uint64_t n_words, hipStream_t st);

@@ -55,7 +55,35 @@ struct rb_dibf {
     bool settle_pending = false;
     uint32_t settle_row = 0;
     std::chrono::steady_clock::time_point settle_t0{};
+    // ROW TABLE (rb_dibf_row_table_build; rb_kernels.hip, ibf_count_rows_kernel): one row per N-free k-mer, the AND of its h blocks, 4^k rows of
+    // `stride` words.  It belongs to the filter, so every engine on the filter gathers from the same one and it goes when the filter goes;
+    // it holds for the bits of `row_version` only, and whatever changes the bits drops it (dibf_changed).
+    std::mutex row_mu;
+    uint64_t *row_table = nullptr;
+    uint64_t row_version = 0, row_rows = 0, row_bytes = 0;
+    double row_build_ms = 0.0, row_alloc_s = 0.0;
+    uint32_t row_refused = 0;  // why the last build did not happen (RB_ROW_REFUSED_*)
+    uint32_t row_builds = 0;   // tables built for this filter so far
 };
+
+static void dibf_row_drop_locked(rb_dibf *f)
+{
+    if (f->row_table) {
+        (void)hipSetDevice(f->device);
+        (void)hipFree(f->row_table);  // (waits for the kernels that read it)
+    }
+    f->row_table = nullptr;
+    f->row_rows = f->row_bytes = 0;
+}
+
+// the one signal for "the bits of this filter are no longer what they were": engines measure its load again (cert_allowance), merged copies
+// go stale, and the row table is dropped
+static void dibf_changed(rb_dibf *f)
+{
+    f->version.fetch_add(1);
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    dibf_row_drop_locked(f);
+}
 
 // Tables of 1 GiB and more are PLACED BY TRIAL: the same table allocated at another moment of one process gathers 1.7-2.9 % slower or
 // faster (config 3 at the reference's sizing, 4.7 GB: 628.5 against 618.0 ms per 2 M reads; GRCh38 at the default fragment size, 4.8 GB:
@@ -346,6 +374,9 @@ struct rb_engine {
     // maximum it takes (< 0: derived from the same load)
     uint32_t prune_parts = 15;
     uint64_t *prune_trace = nullptr;
+    // rb_engine_set_row_table: whether the plain whole-wave launches gather from the filter's row table (and build it), see row_policy
+    int row_mode = RB_ROW_TABLE_AUTO;
+    uint64_t row_max_bytes = 96ull << 30;
     struct CertLoad {
         double set = -1.0;       // what the caller gave (< 0: measure)
         double measured = -1.0;  // load of the filter's fullest bin at `version` (< 0: not measured yet)
@@ -783,7 +814,7 @@ void *rb_dibf_device_words(rb_dibf *f) { return f ? f->d_words : nullptr; }
 int rb_dibf_touch(rb_dibf *f)
 {
     if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
-    f->version.fetch_add(1);
+    dibf_changed(f);
     return RB_OK;
 }
 uint64_t rb_dibf_device_stride(const rb_dibf *f) { return f ? f->stride : 0; }
@@ -796,6 +827,7 @@ void rb_dibf_free(rb_dibf *f)
         (void)hipSetDevice(f->device);
         (void)hipFree(f->d_words);
     }
+    dibf_row_drop_locked(f);  // (nobody else holds a filter that is being freed)
     delete f;
 }
 
@@ -961,11 +993,11 @@ int rb_dibf_fill_synth(rb_dibf *f, uint64_t seed)
     const uint64_t last_mask = rem ? ((1ULL << rem) - 1) : ~0ULL;
     // the version moves before the first write AND after the last one has landed: an engine that copies the table into a merged
     // group in between records the intermediate number and finds its copy stale at its next call
-    f->version.fetch_add(1);
+    dibf_changed(f);
     RB_HIP(hipMemset(f->d_words, 0, dibf_device_words(f) * 8));
     RB_HIP(launch_fill_synth(f->d_words, used, (uint32_t)f->geo.bin_width, (uint32_t)f->stride, last_mask, seed, nullptr));
     RB_HIP(hipDeviceSynchronize());
-    f->version.fetch_add(1);
+    dibf_changed(f);  // (a table another thread built in between is stale: dropped, not left holding its memory)
     return RB_OK;
 }
 
@@ -1058,7 +1090,7 @@ int rb_dibf_insert(rb_dibf *f, const char *seq, size_t len, const uint64_t *star
     const uint64_t total = prefix[n_fragments];
     if (total == 0) return RB_OK;
     if ((total + 255) / 256 >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "too many k-mers in one call");
-    f->version.fetch_add(1);
+    dibf_changed(f);
     DevBuf d_seq, d_tab;
     st = d_seq.ensure(len ? len : 1);
     if (st == RB_OK) st = d_tab.ensure((4 * n_fragments + 1) * 8);
@@ -1075,7 +1107,7 @@ int rb_dibf_insert(rb_dibf *f, const char *seq, size_t len, const uint64_t *star
     if (e == hipSuccess) e = hipDeviceSynchronize();
     d_seq.release();
     d_tab.release();
-    f->version.fetch_add(1);  // (before and after the writes, see rb_dibf_fill_synth)
+    dibf_changed(f);  // (before and after the writes, see rb_dibf_fill_synth)
     if (e != hipSuccess) return rb::fail(RB_ERR_HIP, std::string("insert: ") + hipGetErrorString(e));
     return RB_OK;
 }
@@ -1409,6 +1441,123 @@ int rb_engine_set_prune_parts(rb_engine *e, uint32_t mask)
         return rb::fail(RB_ERR_INVALID_ARG, "mask 0..15 (bit 0: sub-tile checks, bit 1: strand lead, bit 2: certificate, bit 3: lead line)");
     std::lock_guard<std::mutex> lock(e->mu);
     e->prune_parts = mask;
+    return RB_OK;
+}
+
+int rb_engine_set_row_table(rb_engine *e, int mode, uint64_t max_bytes)
+{
+    if (!e || mode < RB_ROW_TABLE_OFF || mode > RB_ROW_TABLE_FORCE) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (auto) or 2 (force)");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->row_mode = mode;
+    if (max_bytes) e->row_max_bytes = max_bytes;
+    return RB_OK;
+}
+
+// bytes of the row table of a filter (0: k too large for one)
+static uint64_t row_table_want_bytes(const rb_dibf *f)
+{
+    if (f->geo.kmer_size == 0 || f->geo.kmer_size > kRowTableMaxK) return 0;
+    return (1ull << (2 * f->geo.kmer_size)) * f->stride * 8;
+}
+
+static bool row_table_current_locked(const rb_dibf *f) { return f->row_table && f->row_version == f->version.load(); }
+
+// Builds the table unless a current one exists.  RB_OK whether it was built or refused (f->row_refused says which); an error only where the
+// runtime fails after the allocation.
+static int dibf_row_build(rb_dibf *f, uint64_t max_bytes)
+{
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (row_table_current_locked(f)) return RB_OK;
+    dibf_row_drop_locked(f);  // stale
+    const uint64_t bytes = row_table_want_bytes(f);
+    f->row_refused = RB_ROW_REFUSED_NONE;
+    if (!bytes) f->row_refused = RB_ROW_REFUSED_K;
+    else if (f->geo.bin_width <= 32) f->row_refused = RB_ROW_REFUSED_NARROW;
+    else if (max_bytes && bytes > max_bytes) f->row_refused = RB_ROW_REFUSED_MAX_BYTES;
+    if (f->row_refused) return RB_OK;
+    int st = check_device(f->device);
+    if (st != RB_OK) return st;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > (uint64_t)free_b / 2) {
+        (void)hipGetLastError();
+        f->row_refused = RB_ROW_REFUSED_FREE;
+        return RB_OK;
+    }
+    const uint64_t version = f->version.load();
+    const auto t0 = std::chrono::steady_clock::now();
+    uint64_t *rows = nullptr;
+    if (hipMalloc((void **)&rows, bytes + 64) != hipSuccess) {  // (+ a zero tail: a 16-byte lane may read one word past a row, as past a block)
+        (void)hipGetLastError();
+        f->row_refused = RB_ROW_REFUSED_ALLOC;
+        return RB_OK;
+    }
+    f->row_alloc_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const uint64_t n_rows = 1ull << (2 * f->geo.kmer_size);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float ms = 0.f;
+    hipError_t e = hipMemset((uint8_t *)rows + bytes, 0, 64);
+    if (e == hipSuccess) e = hipEventCreate(&ev0);
+    if (e == hipSuccess) e = hipEventCreate(&ev1);
+    if (e == hipSuccess) e = hipEventRecord(ev0, nullptr);
+    if (e == hipSuccess) e = launch_row_table(f->dev, rows, n_rows, nullptr);
+    if (e == hipSuccess) e = hipEventRecord(ev1, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (e != hipSuccess) {
+        (void)hipFree(rows);
+        return rb::fail(RB_ERR_HIP, std::string("row table: ") + hipGetErrorString(e));
+    }
+    f->row_table = rows;
+    f->row_rows = n_rows;
+    f->row_bytes = bytes;
+    f->row_version = version;
+    f->row_build_ms = ms;
+    f->row_builds += 1;
+    return RB_OK;
+}
+
+int rb_dibf_row_table_build(rb_dibf *f, uint64_t max_bytes)
+{
+    if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
+    return dibf_row_build(f, max_bytes);
+}
+
+int rb_dibf_row_table_drop(rb_dibf *f)
+{
+    if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    dibf_row_drop_locked(f);
+    return RB_OK;
+}
+
+int rb_dibf_row_table_info(rb_dibf *f, rb_row_table_info *out)
+{
+    if (!f || !out) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    std::memset(out, 0, sizeof *out);
+    if (row_table_current_locked(f)) {
+        out->bytes = f->row_bytes;
+        out->rows = f->row_rows;
+    }
+    out->want_bytes = row_table_want_bytes(f);
+    out->build_ms = f->row_build_ms;
+    out->alloc_s = f->row_alloc_s;
+    out->refused = f->row_refused;
+    out->builds = f->row_builds;
+    return RB_OK;
+}
+
+int rb_dibf_row_table_download(rb_dibf *f, uint64_t *words, uint64_t n_words)
+{
+    if (!f || !words) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (!row_table_current_locked(f)) return rb::fail(RB_ERR_INVALID_ARG, "the filter has no current row table");
+    if (n_words > f->row_bytes / 8) return rb::fail(RB_ERR_INVALID_ARG, "more words than the row table holds");
+    int st = check_device(f->device);
+    if (st != RB_OK) return st;
+    RB_HIP(hipMemcpy(words, f->row_table, n_words * 8, hipMemcpyDeviceToHost));
     return RB_OK;
 }
 
@@ -1798,6 +1947,64 @@ static bool plan_geometry(const rb_engine *e, const rb_dibf *f, size_t n_reads, 
         a.split_parts = split_parts_plan(a.wpl, a.planes, kmers, a.lg, (uint32_t)n_reads * a.n_slices, e->split_max_parts,
                                          e->split_max_sub, &a.split_waves, &a.split_sub);
     return true;
+}
+
+// May this launch gather from the filter's row table (rb_engine_set_row_table)?  Host arithmetic on the planned launch, shared by the call
+// and by rb_engine_plan: (a) a plain whole-wave build with three compile-time hash functions on its own -- no latency form, no phased
+// form, no fused micro-batch, no early-decision mode, no column shard, k <= 13; (b) in auto mode, a batch that repays the build alone,
+// items x 2 x k-mers x (h - 1) >= 4^k x (h + 1) block transfers, and no trace asked for (the trace describes the three-hash passes);
+// (c) a table within max_bytes.  What only the device can say -- free memory, a capturing stream -- is settled where the table is built.
+static bool row_policy(const rb_engine *e, const rb_dibf *f, const CountLaunch &a, size_t n_reads, uint32_t max_len)
+{
+    if (e->row_mode == RB_ROW_TABLE_OFF || e->early_decision || e->shard_world != 1) return false;
+    CountLaunch as_launch = a;  // (rb_engine_plan plans the geometry without the filter's descriptor)
+    as_launch.f.n_hash = (uint32_t)f->geo.n_hash;
+    as_launch.f.k = (uint32_t)f->geo.kmer_size;
+    if (!row_form_serves(as_launch) || f->geo.bin_width <= 32) return false;
+    if (a.n_slices == 1 && e->filters.size() > 1 && n_reads <= e->split_threshold) return false;  // a micro-batch that is fused with other filters
+    const uint64_t bytes = row_table_want_bytes(f);
+    if (!bytes || bytes > e->row_max_bytes) return false;
+    if (e->row_mode == RB_ROW_TABLE_AUTO) {
+        if (e->prune_trace) return false;
+        const uint64_t k = f->geo.kmer_size, h = f->geo.n_hash;
+        const uint64_t kmers = max_len >= k ? max_len - k + 1 : 0;
+        if ((uint64_t)n_reads * 2 * kmers * (h - 1) < (1ull << (2 * k)) * (h + 1)) return false;
+    }
+    return true;
+}
+
+// ... and the table itself for such a launch: the filter's current one, built now when there is none.  nullptr: the launch takes the
+// three-hash kernel.  A call whose stream is being captured never takes the row form, table or no table: the graph would keep the table's
+// address, and unlike the filter's own table, which stays where it is through every insert, the row table is freed by the next change of
+// the bits -- a replay would gather from freed memory.
+static int row_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, const uint64_t **rows, uint64_t *row_bytes)
+{
+    *rows = nullptr;
+    *row_bytes = 0;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    {
+        std::lock_guard<std::mutex> lock(f->row_mu);
+        const bool current = row_table_current_locked(f);
+        if (!current && !capturing) dibf_row_drop_locked(f);  // (a table the bits have moved away from holds its memory for nothing)
+        if (capturing) {
+            if (!current) f->row_refused = RB_ROW_REFUSED_CAPTURE;
+            return RB_OK;
+        }
+        if (current) {
+            *rows = f->row_table;
+            *row_bytes = f->row_bytes;
+            return RB_OK;
+        }
+    }
+    int rc = dibf_row_build(f, e->row_max_bytes);
+    if (rc != RB_OK) return rc;
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (row_table_current_locked(f)) {
+        *rows = f->row_table;
+        *row_bytes = f->row_bytes;
+    }
+    return RB_OK;
 }
 
 static int ensure_split_ws(rb_engine *e, CountLaunch &a, size_t n_filters, hipStream_t st);
@@ -2422,7 +2629,14 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
         // (only where the launch can attempt a certificate: the plain kernel on its own -- not the latency form, not the phased forms,
         // not a micro-batch that is fused with other filters below)
         const bool fuses = a.n_slices == 1 && !fan_out && nf > 1 && n_reads <= e->split_threshold;
-        if (a.bound_prune && (a.prune_parts & 4) && a.lg == 6 && a.split_waves < 2 && a.phase.n_slices == 0 && !fuses) {
+        // the row form first: it has nothing to certify, so the filter's load is not measured for it, and its gathers go to the row table,
+        // whose size -- not the filter's -- says whether they are non-temporal
+        if (row_policy(e, f, a, n_reads, max_len)) {
+            uint64_t row_bytes = 0;
+            if ((rc = row_table_for(e, e->filters[fi], fs, &a.row_table, &row_bytes)) != RB_OK) return rc;
+            if (a.row_table) a.nt = row_bytes > e->nt_threshold_bytes;
+        }
+        if (!a.row_table && a.bound_prune && (a.prune_parts & 4) && a.lg == 6 && a.split_waves < 2 && a.phase.n_slices == 0 && !fuses) {
             bool cert_on = false;
             if ((rc = cert_allowance(e, fi, fs, &a.cert_d, &a.cert_c, &a.lead_min, &cert_on)) != RB_OK) return rc;
             if (!cert_on) a.prune_parts &= ~(4 | 8);  // (the lead line certifies too)
@@ -2439,6 +2653,7 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
             a.early_nf = (uint32_t)nf;
             a.early_fi = (uint32_t)fi;
         }
+        auto launch_count = [](const CountLaunch &l, hipStream_t s) { return l.row_table ? launch_ibf_count_rows(l, s) : launch_ibf_count_max(l, s); };
         if (a.n_slices == 1) {
             a.out = maxcount + fi;
             a.out_read_stride = (uint32_t)nf;
@@ -2461,7 +2676,7 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
                     folded = true;
                 }
                 if ((rc = ensure_split_ws(e, a, 1, fs)) != RB_OK) return rc;
-                RB_HIP(launch_ibf_count_max(a, fs));
+                RB_HIP(launch_count(a, fs));
             }
         } else {
             rc = e->d_parts[fi].ensure((size_t)a.n_slices * n_reads * 2);
@@ -2470,7 +2685,7 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
             a.out_read_stride = 1;
             a.out_slice_stride = (uint32_t)n_reads;
             if ((rc = ensure_split_ws(e, a, 1, fs)) != RB_OK) return rc;
-            RB_HIP(launch_ibf_count_max(a, fs));
+            RB_HIP(launch_count(a, fs));
             RB_HIP(launch_reduce_slices(a.out, a.n_slices, (uint32_t)n_reads, maxcount, (uint32_t)nf, (uint32_t)fi, fs));
         }
     }
@@ -2538,6 +2753,18 @@ extern "C" int rb_engine_plan(rb_engine *e, size_t filter_index, size_t n_reads,
     if (a.split_waves >= 2) form = "ibf_count_max_split_kernel";
     else if (merged_plain) form = "ibf_count_max_merged_kernel";
     else if (a.phase.n_slices) form = a.multi_reads ? "ibf_count_max_phased_multi_kernel" : "ibf_count_max_phased_kernel";
+    if (!g && row_policy(e, f, a, n_reads, max_len)) {
+        // the row form, when the filter has its table or the call could build it (a build that was refused for want of memory stays refused
+        // in this answer until something is built or dropped)
+        rb_dibf *fm = e->filters[filter_index];
+        std::lock_guard<std::mutex> rows_lock(fm->row_mu);
+        const bool current = row_table_current_locked(fm);
+        if (current || (fm->row_refused != RB_ROW_REFUSED_FREE && fm->row_refused != RB_ROW_REFUSED_ALLOC)) {
+            form = "ibf_count_rows_kernel";
+            out->row_table_bytes = row_table_want_bytes(fm);
+            out->nontemporal = out->row_table_bytes > e->nt_threshold_bytes ? 1u : 0u;  // (the table the gathers go to)
+        }
+    }
     std::snprintf(out->kernel, sizeof out->kernel, "%s", form);
     out->reserved0 = (uint32_t)a.multi_reads;  // reads per wave of the multi build (0: the one-read build)
     if (!merged_plain && a.split_waves < 2 && a.phase.n_slices) {

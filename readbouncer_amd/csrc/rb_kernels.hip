@@ -536,7 +536,10 @@ __device__ __forceinline__ bool bound_alive(const Planes<NP> (&pl)[WPL], const u
 // SITE: a caller that starts tiles anywhere (mt_first arbitrary: the prefix pass) names an instantiation of its own.  The body is the same; what
 // the compiler learns from the other callers' arguments before it inlines (mt_first 0 or a tile multiple) then stays theirs, and their kernels
 // compile to the code they had (profiles/isa_identity.py).
-template <int LG, int WPL, int NP, int H, bool NT, bool PH = false, bool EARLY = false, int SITE = 0>
+// ROWS (H == 1; ibf_count_rows_kernel): `f.words` is the filter's ROW TABLE -- one row per N-free k-mer, the AND of its h blocks -- and the
+// block number of a k-mer is its base-4 rank (first base most significant).  The caller hands over N-free reads only; a digit is masked to
+// two bits all the same, so no rank leaves the table.
+template <int LG, int WPL, int NP, int H, bool NT, bool PH = false, bool EARLY = false, int SITE = 0, bool ROWS = false>
 __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev &f, const LaneCols<WPL> &lc,
                                              const BaseSrc &seq, uint32_t len, uint32_t n, int strand,
                                              uint32_t mt_first, uint32_t mt_step, int blk_first, int blk_end,
@@ -601,7 +604,19 @@ __device__ __forceinline__ bool count_strand(Planes<NP> (&pl)[WPL], const IbfDev
                 }
             }
             kv[j] = v;
-            if constexpr (H > 0) {
+            if constexpr (ROWS) {
+                static_assert(H == 1 && !PH, "a row holds the AND of all hash functions");
+                uint32_t r = 0;
+                if (p < n) {
+                    const uint8_t *b = stage + (p - mt);
+                    if (strand == 0) {
+                        for (uint32_t i = 0; i < k; ++i) r = (r << 2) | (b[i] & 3u);
+                    } else {
+                        for (uint32_t i = 0; i < k; ++i) r = (r << 2) | (rbspec::dna5_comp(b[k - 1 - i], f.comp_n) & 3u);
+                    }
+                }
+                idx[j][0] = r;
+            } else if constexpr (H > 0) {
 #pragma unroll
                 for (int h = 0; h < H; ++h)
                     idx[j][h] = rbspec::block_index(v, f.precalc[h], f.n_blocks, f.magic, f.pow2_mask);
@@ -1039,6 +1054,133 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_pe
         if (lane == 0)
             prune.trace[(size_t)blockIdx.y * n_reads * n_slices + item] =
                 prune_trace_record(lead, leads, cert_bits, stops & 0xFFFFu, stops >> 16, line_bits);
+    }
+}
+
+// ROW FORM of the kernel above (rb_dibf_row_table_build, rb_engine_set_row_table): for a resident filter the AND of a k-mer's h blocks is a
+// function of the k-mer alone, and at k <= 13 there are at most 4^13 k-mers without an N.  `rows` holds that AND for each of them (row =
+// base-4 rank), so a strand costs one gather per k-mer instead of h, and hash 0 alone being the whole count, nothing is left to certify:
+// the bound, the sub-tile checks, the strand lead and the parked probe stay, the certificate and the lead line fall away.  A k-mer with an
+// N hashes to real blocks and can count, but has no row: a read with any base outside ACGT takes the same passes with the three-hash
+// gathers on the filter's own table.  The two kinds of read have a build each, ROWS and !ROWS, launched one behind the other over the
+// whole batch: a wave looks over its read's bases first and leaves at once when the read is the other build's (wave-uniform), so every
+// item is written by exactly one of them, no item list is made, and the row build carries neither the three-hash gather schedule nor its
+// registers (one build with a branch between the two spilt at sixteen planes).  Every form of pruning is exact, so either way the result
+// is the maximum the kernel above writes.  Blocks of a whole wave, three compile-time hash functions.
+template <int WPL, int NP, bool NT, bool ROWS>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(3, 8))) void ibf_count_rows_kernel(
+    IbfDev f, const uint64_t *__restrict__ rows, uint32_t col_begin, uint32_t col_end, ReadSrc src, uint32_t n_reads, uint32_t n_slices,
+    uint16_t *__restrict__ out, uint32_t out_read_stride, uint32_t out_slice_stride, PruneCfg prune)
+{
+    constexpr int LG = 6;
+    constexpr uint32_t TILE = (uint32_t)TileShape<LG>::ITEMS;
+    __shared__ uint8_t s_stage[kWavesPerBlock][kStageBytes];
+    __shared__ uint64_t s_park[kWavesPerBlock][kParkPlanes * WPL][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t item = (uint64_t)blockIdx.x * kWavesPerBlock + wave;
+    const uint32_t read = (uint32_t)(item / n_slices);
+    const uint32_t slice = (uint32_t)(item - (uint64_t)read * n_slices);
+    if (read >= n_reads) return;  // wave-uniform; there are no block-level barriers below
+
+    uint32_t len;
+    const BaseSrc seq = make_base_src(src, read, &len);
+    const uint32_t n = len >= f.k ? len - f.k + 1 : 0;
+    bool outside = false;
+    for (uint32_t i = lane; i < len; i += 64) outside |= seq.ord(i) > 3u;
+    if ((__ballot(outside) != 0ULL) == ROWS) return;  // wave-uniform: the other build's read
+
+    LaneCols<WPL> lc = make_lane_cols<LG, WPL>(f, lane, col_begin, col_end, slice);
+    if constexpr (ROWS) {  // the same columns of the row table
+        lc.lane_base = rows + (lc.lane_base - f.words);
+        lc.safe_base = rows + (lc.safe_base - f.words);
+    }
+
+    const bool bound = (prune.flags & kPruneBound) && n < (1u << NP);
+    const bool sub = bound && (prune.flags & kPruneSubTile);
+    const bool leads = bound && (prune.flags & kPruneLead) && n > TILE;
+    // passes (all wave-uniform), as in the kernel above: without the lead 0 = forward, 1 = reverse, each whole; with it 0 / 1 = the probes,
+    // 2 = the leader from k-mer 64, 3 = the other strand from k-mer 64
+    const int n_pass = leads ? 4 : 2;
+    uint32_t best = 0, probe0 = 0, lead = 0, stops = 0;
+    Planes<NP> pl[WPL];
+#pragma unroll 1
+    for (int pass = 0; pass < n_pass; ++pass) {
+        const bool probe = leads && pass < 2;
+        const int strand = (!leads || pass < 2) ? pass : (int)(lead ^ (uint32_t)(pass & 1));
+        if (bound && (pass & 1) && !probe && best >= n) break;  // wave-uniform
+        if (leads && pass == 1) {  // the forward probe waits in LDS
+#pragma unroll
+            for (int w = 0; w < WPL; ++w)
+#pragma unroll
+                for (int i = 0; i < kParkPlanes; ++i) s_park[wave][w * kParkPlanes + i][lane] = pl[w].p[i];
+        }
+        if (!leads || pass < 2 || pass == 3) {
+#pragma unroll
+            for (int w = 0; w < WPL; ++w) pl[w].clear();
+        }
+        if (leads && pass == 3) {  // the other strand's probe comes back (its planes above 6 are zero)
+#pragma unroll
+            for (int w = 0; w < WPL; ++w)
+#pragma unroll
+                for (int i = 0; i < kParkPlanes; ++i) pl[w].p[i] = s_park[wave][w * kParkPlanes + i][lane];
+        }
+        const uint32_t from = leads && pass >= 2 ? TILE : 0u;
+        const uint32_t against = !bound || probe ? kNoBound : best;
+        const uint32_t upto = probe ? TILE : 0xFFFFFFFFu;
+        uint32_t stopped = 0;
+        if constexpr (!ROWS)
+            count_strand<LG, WPL, NP, 3, NT>(pl, f, lc, seq, len, n, strand, from, TILE, 0, TileShape<LG>::STEPS / 8, s_stage[wave], lane,
+                                             PhaseCfg{0, 0, 0, 0, 0}, 0xFFFFFFFFu, against, upto, sub, &stopped);
+        else
+            count_strand<LG, WPL, NP, 1, NT, false, false, 0, true>(pl, f, lc, seq, len, n, strand, from, TILE, 0, TileShape<LG>::STEPS / 8,
+                                                                    s_stage[wave], lane, PhaseCfg{0, 0, 0, 0, 0}, 0xFFFFFFFFu, against, upto, sub,
+                                                                    &stopped);
+        stops = strand == 0 ? (stops & 0xFFFF0000u) | (stopped & 0xFFFFu) : (stops & 0xFFFFu) | (stopped << 16);
+        const uint32_t m = planes_max<NP, WPL>(pl, lc.valid);
+        if (!probe) best = m > best ? m : best;
+        if (leads && pass == 0) probe0 = m;
+        if (leads && pass == 1) {
+            lead = m > probe0 ? 1u : 0u;  // a tie: forward
+            if (lead == 0) {  // the registers hold the reverse probe: change places with the forward one
+#pragma unroll
+                for (int w = 0; w < WPL; ++w)
+#pragma unroll
+                    for (int i = 0; i < kParkPlanes; ++i) {
+                        const uint64_t t = s_park[wave][w * kParkPlanes + i][lane];
+                        s_park[wave][w * kParkPlanes + i][lane] = pl[w].p[i];
+                        pl[w].p[i] = t;
+                    }
+            }
+        }
+    }
+    if (lane == 0) out[(size_t)read * out_read_stride + (size_t)slice * out_slice_stride] = (uint16_t)best;
+    if (prune.trace) {  // (one scalar branch when there is none)
+        if (lane == 0) prune.trace[item] = prune_trace_record(lead, leads, 0u, stops & 0xFFFFu, stops >> 16, 0u);
+    }
+}
+
+// The row table of a filter: one wave per row.  Row r belongs to the k-mer whose base-4 digits are r (A, C, G, T as Dna5 ordinals 0-3,
+// the first base most significant); its base-5 value is formed as count_strand's phase A forms it, its block numbers are the filter's own,
+// and the row is the AND of those blocks over the padded stride (pad words are zero in every block, so they are zero in every row).
+__global__ __launch_bounds__(256) void ibf_row_table_kernel(IbfDev f, uint64_t *__restrict__ rows, uint64_t n_rows)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const uint64_t S = f.stride;
+    const uint32_t nh = f.n_hash < rbspec::kMaxHash ? f.n_hash : rbspec::kMaxHash;
+    // (a grid of one wave per row would pass 2^32 threads at k = 13: the waves stride over the rows)
+    for (uint64_t r = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < n_rows; r += waves) {  // wave-uniform
+        uint64_t v = 0;
+        for (uint32_t i = 0; i < f.k; ++i) v = v * 5u + ((r >> (2u * (f.k - 1u - i))) & 3u);
+        for (uint64_t w = (uint64_t)lane; w < S; w += 64) {
+            uint64_t acc = ~0ULL;
+            for (uint32_t h = 0; h < nh; ++h) {
+                const uint32_t b = rbspec::block_index(v, f.precalc[h], f.n_blocks, f.magic, f.pow2_mask);
+                acc &= f.words[(uint64_t)b * S + w];
+            }
+            rows[r * S + w] = acc;
+        }
     }
 }
 
@@ -3722,6 +3864,53 @@ hipError_t launch_ibf_count_max(const CountLaunch &a, hipStream_t st)
     return dispatch_planes_hash(a.f.n_hash, a.planes, a.lg, a.wpl, [&](auto LG, auto WPL, auto NP, auto H) {
         return launch_count<decltype(LG)::value, decltype(WPL)::value, decltype(NP)::value, decltype(H)::value>(a, st);
     });
+}
+
+// the row form (ibf_count_rows_kernel): the engine plans it for the plain whole-wave builds with three compile-time hash functions only
+template <int WPL, int NP, bool NT>
+static hipError_t launch_rows_nt(const CountLaunch &a, hipStream_t st)
+{
+    const uint64_t items = (uint64_t)a.n_reads * a.n_slices;
+    dim3 grid((uint32_t)((items + kWavesPerBlock - 1) / kWavesPerBlock));
+    PruneCfg prune{};
+    prune.flags = a.bound_prune ? (kPruneBound | (((uint32_t)a.prune_parts & 3u) << 1)) : 0u;  // (no certificate, no lead line: nothing to certify)
+    prune.trace = a.prune_trace;
+    // the N-free reads from the row table, then the others from the filter's own: every item is one build's
+    hipLaunchKernelGGL((ibf_count_rows_kernel<WPL, NP, NT, true>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.row_table, a.col_begin, a.col_end,
+                       a.src, a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, prune);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ibf_count_rows_kernel<WPL, NP, NT, false>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.row_table, a.col_begin, a.col_end,
+                       a.src, a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, prune);
+    return hipGetLastError();
+}
+
+bool row_form_serves(const CountLaunch &a)
+{
+    int np = 0, h = 0;
+    plain_planes_hash(a.f.n_hash, a.planes, &np, &h);
+    return a.lg == 6 && h == 3 && a.split_waves < 2 && a.phase.n_slices == 0 && a.n_fused == 0 && !a.early_thr && a.f.k <= kRowTableMaxK;
+}
+
+hipError_t launch_ibf_count_rows(const CountLaunch &a, hipStream_t st)
+{
+    if (a.n_reads == 0) return hipSuccess;
+    if (!a.row_table || !row_form_serves(a)) return hipErrorInvalidValue;
+    const bool p10 = a.planes <= 10, nt = a.nt != 0;
+    if (a.wpl == 2) {
+        if (p10) return nt ? launch_rows_nt<2, 10, true>(a, st) : launch_rows_nt<2, 10, false>(a, st);
+        return nt ? launch_rows_nt<2, 16, true>(a, st) : launch_rows_nt<2, 16, false>(a, st);
+    }
+    if (p10) return nt ? launch_rows_nt<1, 10, true>(a, st) : launch_rows_nt<1, 10, false>(a, st);
+    return nt ? launch_rows_nt<1, 16, true>(a, st) : launch_rows_nt<1, 16, false>(a, st);
+}
+
+hipError_t launch_row_table(const IbfDev &f, uint64_t *rows, uint64_t n_rows, hipStream_t st)
+{
+    if (n_rows == 0 || n_rows > (1ull << (2 * kRowTableMaxK)) || f.k == 0 || f.k > kRowTableMaxK) return hipErrorInvalidValue;
+    const uint64_t blocks = std::min<uint64_t>((n_rows + 3) / 4, 1ull << 20);  // four waves each; beyond 2^22 waves they stride
+    hipLaunchKernelGGL(ibf_row_table_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, f, rows, n_rows);
+    return hipGetLastError();
 }
 
 template <int LG, int NP>
