@@ -485,6 +485,65 @@ RB_API int rb_prefix_batch(rb_engine *e, const char *seqs, const uint64_t *offse
                            const uint32_t *read_ids, size_t n_items, const uint32_t *prefix_lens, uint32_t n_prefixes,
                            double error_rate, double significance, int mode, const rb_prefix_out *out);
 
+/* ---- resume: a read's counts stay in HBM between chunks, a call counts the NEW k-mers only ----------
+ * Reads arrive from the sequencer a chunk at a time and every decision is taken on the prefix grown so far.  The reference
+ * concatenates a read's undecided chunks and runs check_unblock on the whole prefix again (src/main/adaptive_sampling.hpp:280-331), so
+ * a read that needs four chunks gathers 1 + 2 + 3 + 4 chunks' worth of filter lines.  The prefix pass above needs all bases at once.
+ * This is the state between the calls: seqan::count adds one per k-mer, on both strands window by window, so the per-bin counters of a
+ * prefix are the counters of the shorter prefix plus one per new window, and the new windows are exactly the k-mers of "the last k - 1
+ * bases seen so far + the new chunk".  A set of SLOTS in HBM each holds one read's per-bin uint16_t counters (they wrap at 65 536 as
+ * seqan::count's do), both strands, for every filter of the engine, plus the read's last k - 1 bases and its length so far; a call
+ * takes new chunks only and counts only their k-mers onto the slots.
+ * CONTRACT.  The row of item i is what rb_classify_batch_device_ex writes for ONE read that is the concatenation of every chunk
+ * committed to slot d_slots[i] since its last RB_RESUME_FIRST, followed by this chunk, with max_len = max_total_len and the same error
+ * rate, significance and mode -- all three modes; max_count is valid wherever the status is RB_OK, and total_len is that read's length.
+ * A chunk of zero bases is allowed and repeats the slot's row; while the total is below k the status is RB_ERR_SHORT_READ and the bases
+ * are kept.  Error rate and significance may differ from call to call: the state holds counts, not decisions.  The counts follow the
+ * engine's N rule (rb_engine_set_revcomp_of_n) as it stood when each chunk was fed.
+ * Like locate and prefixes an opt-in pass of its own: it always counts in full from each filter's own table, whatever the engine's
+ * pruning / early-decision / merge / phased / row-table settings are, and changes nothing any other call returns.
+ * PER ITEM, vetted on the device before any address is formed from it, the slot left exactly as it was, status, decision 0,
+ * best_target -1 and total_len 0 in the row, the other items of the batch unaffected:
+ *   RB_ERR_INVALID_ARG  slot >= n_slots; a chunk longer than max_chunk_len; a total that would exceed max_total_len
+ *   RB_ERR_BAD_CHUNK    chunk_start beyond the end of the read (as in every descriptor call)
+ * REFUSED WHOLE with RB_ERR_INVALID_ARG and an rb_last_error() that names the fault: null arguments, an rb_resume_out with no member,
+ * an unknown mode, a column-sharded engine, an engine whose filters do not all share one k, a filter of the engine whose bits changed
+ * since rb_resume_create (the counters are stale: create a new set); rb_resume_create with 0 slots, or with max_chunk_len 0 or above
+ * max_total_len.  HBM that cannot be had is RB_ERR_NOMEM.
+ * A SLOT AT MOST ONCE PER CALL.  The host form finds a slot named twice and refuses the call; in the device form it is the caller's
+ * precondition.  Breaking it leaves that slot's counts undefined until its next RB_RESUME_FIRST; it harms no other slot and reads or
+ * writes nothing outside the slot.
+ * The slots cost rb_resume_bytes(): per slot, for every filter 2 strands x 16 planes x 8 bytes x the filter's padded word columns
+ * (bin_width rounded up to the next power of two up to 64; beyond 64 to a multiple of 128), plus 40 bytes.  A set belongs to its
+ * engine and is destroyed before it. */
+typedef struct rb_resume rb_resume;
+#define RB_RESUME_FIRST 1u   /* this chunk starts a new read in the slot: what it held is dropped */
+#define RB_RESUME_PEEK  2u   /* answer as if the chunk were appended; leave the slot exactly as it was */
+typedef struct rb_resume_out {   /* any member may be NULL, not all */
+    void *max_count;   /* u16 [n_items x n_filters], deplete filters first */
+    void *decision;    /* u8  [n_items], per rb_mode */
+    void *best_target; /* i32 [n_items] */
+    void *status;      /* u8  [n_items] */
+    void *total_len;   /* u32 [n_items]: bases the row stands for */
+} rb_resume_out;
+RB_API int rb_resume_create(rb_engine *e, uint32_t n_slots, uint32_t max_chunk_len, uint32_t max_total_len, rb_resume **out);
+RB_API void rb_resume_destroy(rb_resume *r);
+RB_API uint64_t rb_resume_bytes(const rb_resume *r);   /* HBM held by the slots */
+/* Device pointers, asynchronous on `stream` (NULL = the engine's own stream, synchronised before returning).  rb_batch_desc selects
+ * each item's CHUNK as in every descriptor call: packed reads, chunk_start / chunk_length, d_read_ids; desc->max_len is not looked at
+ * (max_chunk_len bounds a chunk).  d_slots: u32 per item; d_flags: u8 per item of RB_RESUME_* bits, NULL = 0.  Workspaces are the
+ * engine's (n_items x (max_chunk_len + 31) bytes of stitched bases and the partial maxima): one stream per engine, as for
+ * rb_classify_batch_device. */
+RB_API int rb_resume_batch_device(rb_resume *r, const rb_batch_desc *desc, const void *d_slots, const void *d_flags,
+                                  double error_rate, double significance, int mode, const rb_resume_out *d_out, void *stream);
+/* Host buffers: read i is the new chunk of slot slots[i] (flags may be NULL). */
+RB_API int rb_resume_batch(rb_resume *r, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads,
+                           const uint32_t *slots, const uint8_t *flags, double error_rate, double significance, int mode,
+                           const rb_resume_out *out);
+/* One slot's counters of one filter as the two count vectors of seqan::count (forward, then reverse complement), and the slot's total
+ * length; either output may be NULL, not both.  Synchronous, on the engine's own stream. */
+RB_API int rb_resume_counts(rb_resume *r, uint32_t slot, size_t filter, uint16_t *out_counts /* [2][n_bins] */, uint32_t *out_total_len);
+
 /* bin-sharded operation: restrict the engine to word columns
  * [rank*ceil(W/world) , ...) of every block; out_maxcount then holds PARTIAL maxima that the
  * caller combines with an all-reduce(max) before rb_decide_device. world=1 restores the default. */

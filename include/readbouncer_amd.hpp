@@ -529,6 +529,90 @@ public:
     }
 };
 
+// ---- resumable counts: a read's counters stay in HBM between chunks (rb_resume) ------------------
+// One slot per read in flight (per channel of a flow cell); feed() takes the NEW chunks only and returns, per item, what classify_batch
+// returns for the concatenation of everything the slot was fed since its last RB_RESUME_FIRST.  Owns an engine of its own over the
+// borrowed filters -- the slots die with it, never before.
+struct ResumeResult : BatchResult
+{
+    std::vector<uint32_t> total_len;  // bases each row stands for
+};
+
+class ResumableCounts
+{
+    rb_engine* engine_ = nullptr;
+    rb_resume* slots_ = nullptr;
+    size_t nf_ = 0;
+    std::vector<uint64_t> bins_;
+public:
+    ResumableCounts(const std::vector<IBFMeta>& DepletionFilters, const std::vector<IBFMeta>& TargetFilters, uint32_t n_slots,
+                    uint32_t max_chunk_len, uint32_t max_total_len)
+    {
+        if (DepletionFilters.empty() && TargetFilters.empty()) throw NullFilterException("No IBF provided to classify the read!");
+        std::vector<rb_dibf*> d, t;
+        for (const IBFMeta& m : DepletionFilters) d.push_back(m.filter.handle());
+        for (const IBFMeta& m : TargetFilters) t.push_back(m.filter.handle());
+        for (const std::vector<rb_dibf*>* set : {&d, &t})
+            for (rb_dibf* f : *set) {
+                rb_ibf_info g{};
+                if (f) rb_dibf_get_info(f, &g);
+                bins_.push_back(g.n_bins);
+            }
+        nf_ = d.size() + t.size();
+        const int dev = !d.empty() ? rb_dibf_device(d[0]) : rb_dibf_device(t[0]);
+        throw_status(rb_engine_create(dev, d.data(), d.size(), t.data(), t.size(), &engine_), "engine");
+        const int st = rb_resume_create(engine_, n_slots, max_chunk_len, max_total_len, &slots_);
+        if (st != RB_OK) {
+            rb_engine_destroy(engine_);
+            engine_ = nullptr;
+            throw_status(st, "rb_resume_create");
+        }
+    }
+    ~ResumableCounts()
+    {
+        rb_resume_destroy(slots_);
+        rb_engine_destroy(engine_);
+    }
+    ResumableCounts(const ResumableCounts&) = delete;
+    ResumableCounts& operator=(const ResumableCounts&) = delete;
+
+    uint64_t bytes() const { return rb_resume_bytes(slots_); }
+
+    // read i = seqs[offsets[i] .. offsets[i] + lens[i]) is the new chunk of slot slots[i]; flags (RB_RESUME_* per item) may be null
+    ResumeResult feed_flat(const ClassifyConfig& conf, const char* seqs, const uint64_t* offsets, const uint32_t* lens, size_t n,
+                           const uint32_t* slots, const uint8_t* flags, int mode)
+    {
+        ResumeResult r;
+        r.maxcount.resize(n * nf_);
+        r.best_target.resize(n);
+        r.decision.resize(n);
+        r.status.resize(n);
+        r.total_len.resize(n);
+        const rb_resume_out out = {r.maxcount.data(), r.decision.data(), r.best_target.data(), r.status.data(), r.total_len.data()};
+        throw_status(rb_resume_batch(slots_, seqs, offsets, lens, n, slots, flags, conf.error_rate, conf.significance, mode, &out),
+                     "rb_resume_batch");
+        return r;
+    }
+
+    // device pointers, asynchronous on `stream`: rb_resume_batch_device as it is
+    void feed_device(const ClassifyConfig& conf, const rb_batch_desc& desc, const void* d_slots, const void* d_flags, int mode,
+                     const rb_resume_out& d_out, void* stream)
+    {
+        throw_status(rb_resume_batch_device(slots_, &desc, d_slots, d_flags, conf.error_rate, conf.significance, mode, &d_out, stream),
+                     "rb_resume_batch_device");
+    }
+
+    // the two count vectors of one slot and filter (forward, then reverse complement: 2 x n_bins entries) and the slot's length
+    std::vector<uint16_t> counts(uint32_t slot, size_t filter, uint32_t* total_len = nullptr)
+    {
+        std::vector<uint16_t> c(filter < bins_.size() ? 2 * bins_[filter] : 0);
+        uint32_t total = 0;
+        throw_status(rb_resume_counts(slots_, slot, filter, c.empty() ? nullptr : c.data(), &total), "rb_resume_counts");
+        if (total_len) *total_len = total;
+        return c;
+    }
+};
+
 // ---- Read (src/IBF/IBF.hpp:169-226) -------------------------------------------------------------
 class Read
 {

@@ -39,6 +39,15 @@ class PrefixOut(C.Structure):
 RB_PREFIX_MAX = 64
 
 
+class ResumeOut(C.Structure):
+    """rb_resume_out: any member may be NULL, not all"""
+    _fields_ = [("max_count", C.c_void_p), ("decision", C.c_void_p), ("best_target", C.c_void_p), ("status", C.c_void_p),
+                ("total_len", C.c_void_p)]
+
+
+RB_RESUME_FIRST, RB_RESUME_PEEK = 1, 2
+
+
 class Hit(C.Structure):
     """rb_hit: one (bin, strand) at or above the threshold and its count -- 8 bytes"""
     _fields_ = [("bin", C.c_uint32), ("count", C.c_uint16), ("strand", C.c_uint8), ("reserved", C.c_uint8)]
@@ -182,6 +191,12 @@ SIGNATURES = {
     "rb_locate_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _dbl, _dbl, C.POINTER(LocateOut)]),
     "rb_prefix_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _dbl, _dbl, _int, C.POINTER(PrefixOut), _vp]),
     "rb_prefix_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, C.c_uint32, _dbl, _dbl, _int, C.POINTER(PrefixOut)]),
+    "rb_resume_create": (_int, [_vp, _u32, _u32, _u32, _pp]),
+    "rb_resume_destroy": (None, [_vp]),
+    "rb_resume_bytes": (_u64, [_vp]),
+    "rb_resume_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _vp, _vp, _dbl, _dbl, _int, C.POINTER(ResumeOut), _vp]),
+    "rb_resume_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _dbl, _dbl, _int, C.POINTER(ResumeOut)]),
+    "rb_resume_counts": (_int, [_vp, _u32, _sz, _vp, _vp]),
     "rb_hits_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _dbl, _dbl, C.c_uint16, C.c_uint32, C.POINTER(HitsOut), _vp]),
     "rb_hits_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _dbl, _dbl, C.c_uint16, C.c_uint32, C.POINTER(HitsOut)]),
     "rb_spans_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _sz, _vp, _sz, C.c_uint32, C.POINTER(SpansOut), _vp]),
@@ -660,6 +675,10 @@ class Engine:
         _check(lib().rb_prefix_batch_device(self.h, C.byref(desc), _ptr(cps), len(cps), error_rate, significance, mode, C.byref(out), stream),
                "rb_prefix_batch_device")
 
+    def resume(self, n_slots, max_chunk_len, max_total_len):
+        """a set of slots that keep a read's counts in HBM between chunks (rb_resume_create) -> Resume"""
+        return Resume(self, n_slots, max_chunk_len, max_total_len)
+
     def hits(self, seqs, offsets, lens, read_ids=None, error_rate=0.1, significance=0.95, min_count=0, max_hits=64, bin_reads=None,
              hits=None):
         """every (bin, strand) of each selected read at or above the threshold, with its count (rb_hits_batch): host buffers in, a dict
@@ -894,6 +913,72 @@ class Engine:
     def destroy(self):
         if self.h:
             lib().rb_engine_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class Resume:
+    """rb_resume: slots in HBM that each hold one read's per-bin counts, both strands, for every filter of an engine, plus its last
+    k - 1 bases and its length; a feed counts only the k-mers of the new chunks.  Destroyed before its engine."""
+
+    def __init__(self, engine, n_slots, max_chunk_len, max_total_len):
+        self.h = None
+        self.engine = engine  # (keeps the engine alive as long as the slots)
+        h = C.c_void_p()
+        _check(lib().rb_resume_create(engine.h, n_slots, max_chunk_len, max_total_len, C.byref(h)), "rb_resume_create")
+        self.h = h
+        self.n_slots, self.max_chunk_len, self.max_total_len = n_slots, max_chunk_len, max_total_len
+
+    @property
+    def bytes(self):
+        return int(lib().rb_resume_bytes(self.h))
+
+    def feed(self, seqs, offsets, lens, slots, flags=None, error_rate=0.1, significance=0.95, mode=RB_MODE_CHECK_UNBLOCK):
+        """read i is the new chunk of slot slots[i] (rb_resume_batch): host buffers in, a dict of host numpy arrays out --
+        max_count[n, nf] u16, decision[n] u8, best_target[n] i32, status[n] u8, total_len[n] u32"""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        n, nf = len(lens), self.engine.nd + self.engine.nt
+        assert len(slots) == n and (fl is None or len(fl) == n)
+        if len(seqs) == 0:
+            seqs = np.zeros(1, dtype=np.uint8)  # (a batch of empty chunks still names a buffer)
+        res = {"max_count": np.zeros((n, nf), dtype=np.uint16), "decision": np.zeros(n, dtype=np.uint8),
+               "best_target": np.full(n, -1, dtype=np.int32), "status": np.zeros(n, dtype=np.uint8),
+               "total_len": np.zeros(n, dtype=np.uint32)}
+        out = ResumeOut(*[_ptr(res[k]) for k in ("max_count", "decision", "best_target", "status", "total_len")])
+        _check(lib().rb_resume_batch(self.h, _ptr(seqs), _ptr(offsets), _ptr(lens), n, _ptr(slots), None if fl is None else _ptr(fl),
+                                     error_rate, significance, mode, C.byref(out)), "rb_resume_batch")
+        return res
+
+    def feed_device(self, d_seqs, d_offsets, d_lens, n_items, d_slots, d_flags=None, d_nmask=None, d_nmask_offsets=None, chunk_start=0,
+                    chunk_length=0, d_read_ids=None, error_rate=0.1, significance=0.95, mode=RB_MODE_CHECK_UNBLOCK, d_max_count=None,
+                    d_decision=None, d_best_target=None, d_status=None, d_total_len=None, stream=None):
+        """raw device pointers like locate_device (rb_resume_batch_device); any output may be None, not all"""
+        desc = BatchDesc(d_seqs, d_offsets, d_lens, n_items, 0, d_nmask, d_nmask_offsets, chunk_start, chunk_length, d_read_ids)
+        out = ResumeOut(d_max_count, d_decision, d_best_target, d_status, d_total_len)
+        _check(lib().rb_resume_batch_device(self.h, C.byref(desc), d_slots, d_flags, error_rate, significance, mode, C.byref(out), stream),
+               "rb_resume_batch_device")
+
+    def counts(self, slot, filter):
+        """(counts u16 [2, n_bins]: forward and reverse complement, total_len) of one slot and filter (rb_resume_counts)"""
+        filters = self.engine._keep[0] + self.engine._keep[1]
+        n_bins = filters[filter].info["n_bins"] if 0 <= filter < len(filters) else 1  # (a filter the set does not have: the call says so)
+        counts = np.zeros((2, n_bins), dtype=np.uint16)
+        total = C.c_uint32(0)
+        _check(lib().rb_resume_counts(self.h, slot, filter, _ptr(counts), C.addressof(total)), "rb_resume_counts")
+        return counts, int(total.value)
+
+    def destroy(self):
+        if self.h:
+            lib().rb_resume_destroy(self.h)
             self.h = None
 
     def __del__(self):

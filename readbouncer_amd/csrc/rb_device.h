@@ -289,6 +289,56 @@ hipError_t launch_finish_prefix(const PrefixLaunch &a, const uint32_t *lens, con
 hipError_t launch_first_decided(const uint8_t *decision, const uint8_t *status, uint32_t n_items, uint32_t n_prefixes, uint32_t *first_decided,
                                 hipStream_t st);
 
+// resume pass (rb_resume_batch_device; rb_kernels.hip, ibf_resume_kernel): a slot's bookkeeping beside its counter planes ...
+constexpr uint32_t kResumePlanes = 16;   // counters wrap at 2^16 as the reference's uint16_t counts do
+constexpr uint32_t kResumeMaxTail = 31;  // k - 1 at the largest k
+struct ResumeMeta {
+    uint32_t total;                // bases committed to the slot since its last FIRST
+    uint32_t tail_len;             // min(total, k - 1)
+    uint8_t tail[kResumeMaxTail + 1];  // the last tail_len bases as Dna5 ordinals
+};
+// ... what the prep kernel makes of an item for the pass (bits 0 and 1 are the caller's RB_RESUME_FIRST / RB_RESUME_PEEK) ...
+constexpr uint32_t kResumeFirst = 1u;  // start from zero, load nothing
+constexpr uint32_t kResumePeek = 2u;   // store nothing
+constexpr uint32_t kResumeSkip = 4u;   // refused: the slot is neither read nor written (its number may not even exist)
+// ... the slots as the pass kernel sees them (by-value kernel argument; the planes of slot s and this filter are
+// state[s * slot_words + filter_off + (strand * 16 + plane) * pad_cols + column]) ...
+struct ResumeSlots {
+    uint64_t *state;
+    const uint32_t *slot;  // per item; vetted by the prep kernel wherever ctl has no kResumeSkip
+    const uint8_t *ctl;    // per item: kResume* bits
+    uint64_t slot_words;   // words of one slot, all filters
+    uint64_t filter_off;   // words before this filter's planes inside a slot
+    uint32_t pad_cols;     // n_slices * 2^lg * wpl >= bin_width
+};
+// ... one filter's launch (src: the stitched items "tail + chunk" in the workspace) ...
+struct ResumeLaunch : PlainPassLaunch {
+    ResumeSlots slots;
+    uint16_t *part;  // [n_slices][n_items]
+};
+hipError_t launch_ibf_resume(const ResumeLaunch &a, hipStream_t st);
+// ... and the small kernels around the pass.  Prep: vets item i (slot number, chunk length, total), writes its stitched string as ASCII at
+// stitched + i * stitch_stride, its length, the bytes offset, the total the row stands for, its pre-status and its ctl bits.
+struct ResumePrep {
+    ReadSrc src;               // the caller's reads (src.lens: FULL read lengths; src.base_off: chunk_start)
+    uint32_t chunk_length;     // rb_batch_desc's (0: to the end of the read)
+    const uint32_t *slot;
+    const uint8_t *flags;      // or nullptr
+    const ResumeMeta *meta;
+    uint32_t n_items, n_slots, max_chunk_len, max_total_len, k;
+    uint8_t *stitched;
+    uint32_t stitch_stride;
+    uint64_t *st_offsets;
+    uint32_t *st_lens, *total_lens;
+    uint8_t *pre_status, *ctl;
+    uint32_t *out_total_len;   // the caller's, or nullptr
+};
+hipError_t launch_resume_prep(const ResumePrep &a, hipStream_t st);
+hipError_t launch_resume_commit(ResumeMeta *meta, const uint32_t *slot, const uint8_t *ctl, const uint8_t *stitched, uint32_t stitch_stride,
+                                const uint32_t *st_lens, const uint32_t *total_lens, uint32_t n_items, uint32_t k, hipStream_t st);
+// counts [2][n_bins] u16 <- the planes of one slot and filter (planes: state + slot * slot_words + filter_off)
+hipError_t launch_resume_counts(const uint64_t *planes, uint32_t pad_cols, uint32_t n_bins, uint16_t *counts, hipStream_t st);
+
 // hits pass (rb_hits_batch_device; rb_kernels.hip, ibf_hits_kernel): a record as the kernels move it -- x = bin, y = count | strand << 16,
 // the eight bytes of rb_hit ...
 typedef unsigned int rb_u32x2 __attribute__((ext_vector_type(2)));

@@ -462,6 +462,8 @@ struct rb_engine {
     DevBuf d_spans_io;              // rb_spans_batch: read ids and queries in, masks / records / n_kmers / status back
     DevBuf d_prefix_ws;             // prefix pass: partial maxima of the column slices (one filter at a time), the rows' lengths and pre-status, outputs the caller left out
     DevBuf d_prefix_io;             // rb_prefix_batch: read ids in, the six outputs back
+    DevBuf d_resume_ws;             // resume pass: the stitched items, their lengths and totals, pre-status and ctl bits, partial maxima (one filter at a time), maxima the caller left out
+    DevBuf d_resume_io;             // rb_resume_batch: slots and flags in, the five outputs back; rb_resume_counts: the two count vectors
     PinnedBuf h_in, h_out;
     // large host batches: slice i+1 is copied on this stream while slice i is counted on `stream`
     hipStream_t copy_stream = nullptr;
@@ -1222,7 +1224,7 @@ void rb_engine_destroy(rb_engine *e)
     }
     for (void *r : e->thr_retired_dev) (void)hipFree(r);
     for (PinnedBuf &h : e->thr_retired_host) h.release();
-    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_locate_parts, &e->d_locate_io, &e->d_hits_ws, &e->d_hits_io, &e->d_spans_io, &e->d_prefix_ws, &e->d_prefix_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
+    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_locate_parts, &e->d_locate_io, &e->d_hits_ws, &e->d_hits_io, &e->d_spans_io, &e->d_prefix_ws, &e->d_prefix_io, &e->d_resume_ws, &e->d_resume_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
                       &e->d_decision, &e->d_status})
         b->release();
     e->h_in.release();
@@ -3512,6 +3514,303 @@ int rb_prefix_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, con
         if (out->first_decided) RB_HIP(hipMemcpyAsync((uint32_t *)out->first_decided + b0, io + o_first, 4 * sub, hipMemcpyDeviceToHost, st));
         RB_HIP(hipStreamSynchronize(st));
     }
+    return RB_OK;
+}
+
+// ---- resume: a read's per-bin counters stay in HBM between chunks, a call counts the new k-mers only (see the boundary header).
+// A set of slots belongs to one engine; each slot holds, for every filter of the engine, both strands' sixteen counter planes over the
+// filter's padded columns, plus the read's total length and its last k - 1 bases (ResumeMeta).  A call is: resume_prep_kernel (vets the
+// items, stitches "tail + chunk" into the engine's workspace), per filter one launch of ibf_resume_kernel over the filter's OWN table
+// plus the ordinary slice reduction, the decision kernel with the slots' total lengths as its `lens`, and resume_commit_kernel.
+struct rb_resume {
+    rb_engine *e = nullptr;
+    int device = 0;
+    uint32_t n_slots = 0, max_chunk_len = 0, max_total_len = 0, k = 0;
+    struct PerFilter {
+        int lg = 0, wpl = 1;
+        uint32_t n_slices = 1, pad_cols = 0;
+        uint64_t off = 0;      // words before this filter's planes inside a slot
+        uint64_t version = 0;  // the filter's bits at rb_resume_create
+    };
+    std::vector<PerFilter> per;
+    uint64_t slot_words = 0;
+    uint64_t *d_state = nullptr;
+    ResumeMeta *d_meta = nullptr;
+};
+
+static int check_resume_args(const rb_resume_out *out, int mode)
+{
+    if (!out) return rb::fail(RB_ERR_INVALID_ARG, "null output struct");
+    if (!out->max_count && !out->decision && !out->best_target && !out->status && !out->total_len)
+        return rb::fail(RB_ERR_INVALID_ARG, "rb_resume_out with no output");
+    if (mode != RB_MODE_CHECK_UNBLOCK && mode != RB_MODE_CLASSIFY_CHUNK && mode != RB_MODE_CLASSIFY_ANY)
+        return rb::fail(RB_ERR_INVALID_ARG, "unknown mode");
+    return RB_OK;
+}
+
+// the handle, after the device (without a GPU nothing here can work: check_pass_call's order)
+static int check_resume_handle(const rb_resume *r)
+{
+    const int rc = check_device(r ? r->device : 0);
+    if (rc != RB_OK) return rc;
+    if (!r) return rb::fail(RB_ERR_INVALID_ARG, "null resume handle");
+    return RB_OK;
+}
+
+// the counters of a slot are counts of the filters' bits at rb_resume_create
+static int check_resume_fresh(const rb_resume *r)
+{
+    for (size_t fi = 0; fi < r->per.size(); ++fi)
+        if (r->e->filters[fi]->version.load() != r->per[fi].version)
+            return rb::fail(RB_ERR_INVALID_ARG, "filter " + std::to_string(fi) + " changed since rb_resume_create: the slots' counters are stale");
+    return RB_OK;
+}
+
+static int resume_device_impl(rb_resume *r, const rb_batch_desc *desc, const void *d_slots, const void *d_flags, double error_rate,
+                              double significance, int mode, const rb_resume_out *d_out, void *stream)
+{
+    if (!desc) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor");
+    int rc = check_resume_args(d_out, mode);
+    if (rc != RB_OK) return rc;
+    if ((rc = check_resume_handle(r)) != RB_OK) return rc;
+    const size_t n = desc->n_items;
+    if (n >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    if (n == 0) return RB_OK;
+    if (!d_slots) return rb::fail(RB_ERR_INVALID_ARG, "null slot array");
+    if ((rc = check_desc_buffers(desc, false)) != RB_OK) return rc;
+    rb_engine *e = r->e;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if ((rc = refuse_sharded(e, "resume")) != RB_OK) return rc;
+    if ((rc = check_resume_fresh(r)) != RB_OK) return rc;
+    const size_t nf = e->filters.size();
+    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+    const uint16_t *thr = nullptr;
+    uint32_t thr_len = 0;
+    if ((rc = ensure_thresholds(e, r->max_total_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
+    // workspace: u64 st_offsets[n] | u32 st_lens[n] | u32 total_lens[n] | u16 part[max_slices][n] | u16 max_count[n][nf] (where the caller
+    // left it out) | u8 pre_status[n] | u8 ctl[n] | u8 stitched[n][stride]
+    uint32_t max_slices = 1;
+    for (const rb_resume::PerFilter &p : r->per) max_slices = std::max(max_slices, p.n_slices);
+    const uint32_t stride = (r->max_chunk_len + kResumeMaxTail + 15u) & ~15u;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_slen = up16(n * 8), o_tot = o_slen + up16(n * 4), o_part = o_tot + up16(n * 4), o_max = o_part + up16((size_t)max_slices * n * 2);
+    const size_t o_pre = o_max + up16(d_out->max_count ? 0 : n * nf * 2), o_ctl = o_pre + up16(n), o_seq = o_ctl + up16(n);
+    if ((rc = e->d_resume_ws.ensure(o_seq + n * (size_t)stride)) != RB_OK) return rc;
+    char *ws = (char *)e->d_resume_ws.p;
+    uint16_t *part = (uint16_t *)(ws + o_part);
+    uint16_t *max_count = d_out->max_count ? (uint16_t *)d_out->max_count : (uint16_t *)(ws + o_max);
+    ResumePrep prep{};
+    prep.src.seqs = (const uint8_t *)desc->d_seqs;
+    prep.src.offsets = (const uint64_t *)desc->d_offsets;
+    prep.src.lens = (const uint32_t *)desc->d_lens;
+    prep.src.nmask = (const uint8_t *)desc->d_nmask;
+    prep.src.nmask_offsets = (const uint64_t *)desc->d_nmask_offsets;
+    prep.src.ids = (const uint32_t *)desc->d_read_ids;
+    prep.src.base_off = desc->chunk_start;
+    prep.chunk_length = desc->chunk_length;
+    prep.slot = (const uint32_t *)d_slots;
+    prep.flags = (const uint8_t *)d_flags;
+    prep.meta = r->d_meta;
+    prep.n_items = (uint32_t)n;
+    prep.n_slots = r->n_slots;
+    prep.max_chunk_len = r->max_chunk_len;
+    prep.max_total_len = r->max_total_len;
+    prep.k = r->k;
+    prep.stitched = (uint8_t *)(ws + o_seq);
+    prep.stitch_stride = stride;
+    prep.st_offsets = (uint64_t *)ws;
+    prep.st_lens = (uint32_t *)(ws + o_slen);
+    prep.total_lens = (uint32_t *)(ws + o_tot);
+    prep.pre_status = (uint8_t *)(ws + o_pre);
+    prep.ctl = (uint8_t *)(ws + o_ctl);
+    prep.out_total_len = (uint32_t *)d_out->total_len;
+    std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
+    if ((rc = begin_timed(e, st, &evp)) != RB_OK) return rc;
+    RB_HIP(launch_resume_prep(prep, st));
+    // what the pass reads: the stitched items, ASCII, one per work item
+    PassInput in{};
+    in.src.seqs = prep.stitched;
+    in.src.offsets = prep.st_offsets;
+    in.src.lens = prep.st_lens;
+    in.src.max_len = r->max_chunk_len + kResumeMaxTail;
+    in.d_lens = prep.st_lens;
+    in.max_len = in.src.max_len;
+    in.n_items = n;
+    for (size_t fi = 0; fi < nf; ++fi) {
+        const rb_resume::PerFilter &p = r->per[fi];
+        ResumeLaunch a{};
+        fill_plain_launch(e, fi, in, thr, thr_len, &a);
+        if (a.lg != p.lg || a.wpl != p.wpl || a.n_slices != p.n_slices) return rb::fail(RB_ERR_INVALID_ARG, "filter geometry moved under the slots");
+        a.planes = (int)kResumePlanes;
+        a.slots.state = r->d_state;
+        a.slots.slot = prep.slot;
+        a.slots.ctl = prep.ctl;
+        a.slots.slot_words = r->slot_words;
+        a.slots.filter_off = p.off;
+        a.slots.pad_cols = p.pad_cols;
+        a.part = part;
+        RB_HIP(launch_ibf_resume(a, st));
+        RB_HIP(launch_reduce_slices(part, a.n_slices, (uint32_t)n, max_count, (uint32_t)nf, (uint32_t)fi, st));
+    }
+    if (d_out->decision || d_out->best_target || d_out->status) {
+        if ((rc = run_decide(e, max_count, prep.total_lens, prep.pre_status, n, r->max_total_len, error_rate, significance, mode,
+                             (int32_t *)d_out->best_target, (uint8_t *)d_out->decision, (uint8_t *)d_out->status, st)) != RB_OK)
+            return rc;
+    }
+    RB_HIP(launch_resume_commit(r->d_meta, prep.slot, prep.ctl, prep.stitched, stride, prep.st_lens, prep.total_lens, (uint32_t)n, r->k, st));
+    if ((rc = end_timed(evp, st)) != RB_OK) return rc;
+    if (!stream) RB_HIP(hipStreamSynchronize(st));
+    return RB_OK;
+}
+
+int rb_resume_create(rb_engine *e, uint32_t n_slots, uint32_t max_chunk_len, uint32_t max_total_len, rb_resume **out)
+{
+    if (!out) return rb::fail(RB_ERR_INVALID_ARG, "null out");
+    *out = nullptr;
+    if (n_slots == 0) return rb::fail(RB_ERR_INVALID_ARG, "a resume set needs at least one slot");
+    if (max_chunk_len == 0 || max_chunk_len > max_total_len) return rb::fail(RB_ERR_INVALID_ARG, "max_chunk_len must be 1 to max_total_len");
+    if (max_total_len >= (1u << 30)) return rb::fail(RB_ERR_INVALID_ARG, "max_total_len must be below 2^30");
+    int rc = check_device(e ? e->device : 0);
+    if (rc != RB_OK) return rc;
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    std::unique_ptr<rb_resume> r(new (std::nothrow) rb_resume());
+    if (!r) return rb::fail(RB_ERR_NOMEM, "alloc");
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        if ((rc = refuse_sharded(e, "resume")) != RB_OK) return rc;
+        if (e->filters.empty()) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
+        r->e = e;
+        r->device = e->device;
+        r->n_slots = n_slots;
+        r->max_chunk_len = max_chunk_len;
+        r->max_total_len = max_total_len;
+        r->k = (uint32_t)e->filters[0]->geo.kmer_size;
+        for (const rb_dibf *f : e->filters) {
+            if (f->geo.kmer_size != r->k)
+                return rb::fail(RB_ERR_INVALID_ARG, "resume needs one k for all filters of the engine: each k would need stitched items of its own");
+            rb_resume::PerFilter p;
+            int planes, nt;
+            plain_geometry(e, f, max_total_len, &p.lg, &p.wpl, &p.n_slices, &planes, &nt);
+            p.pad_cols = p.n_slices * (1u << p.lg) * (uint32_t)p.wpl;
+            p.off = r->slot_words;
+            p.version = f->version.load();
+            r->slot_words += 2ull * kResumePlanes * p.pad_cols;
+            r->per.push_back(p);
+        }
+        if (r->k == 0 || r->k - 1 > kResumeMaxTail) return rb::fail(RB_ERR_UNSUPPORTED, "k-mer size above 32");
+    }
+    const uint64_t state_bytes = (uint64_t)n_slots * r->slot_words * 8, meta_bytes = (uint64_t)n_slots * sizeof(ResumeMeta);
+    hipError_t he = hipMalloc((void **)&r->d_state, state_bytes);
+    if (he == hipSuccess) he = hipMalloc((void **)&r->d_meta, meta_bytes);
+    // a slot that was never given FIRST continues from an empty read
+    if (he == hipSuccess) he = hipMemset(r->d_state, 0, state_bytes);
+    if (he == hipSuccess) he = hipMemset(r->d_meta, 0, meta_bytes);
+    if (he != hipSuccess) {
+        (void)hipGetLastError();
+        rb_resume_destroy(r.release());
+        if (he == hipErrorOutOfMemory || he == hipErrorMemoryAllocation)
+            return rb::fail(RB_ERR_NOMEM, "rb_resume_create: " + std::to_string(state_bytes + meta_bytes) + " bytes of HBM refused");
+        return rb::fail(RB_ERR_HIP, std::string("rb_resume_create: ") + hipGetErrorString(he));
+    }
+    *out = r.release();
+    return RB_OK;
+}
+
+void rb_resume_destroy(rb_resume *r)
+{
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    if (r->d_state) (void)hipFree(r->d_state);  // (waits for the kernels that use it)
+    if (r->d_meta) (void)hipFree(r->d_meta);
+    delete r;
+}
+
+uint64_t rb_resume_bytes(const rb_resume *r) { return r ? (uint64_t)r->n_slots * (r->slot_words * 8 + sizeof(ResumeMeta)) : 0; }
+
+int rb_resume_batch_device(rb_resume *r, const rb_batch_desc *desc, const void *d_slots, const void *d_flags, double error_rate,
+                           double significance, int mode, const rb_resume_out *d_out, void *stream)
+{
+    return resume_device_impl(r, desc, d_slots, d_flags, error_rate, significance, mode, d_out, stream);
+}
+
+int rb_resume_batch(rb_resume *r, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *slots,
+                    const uint8_t *flags, double error_rate, double significance, int mode, const rb_resume_out *out)
+{
+    int rc = check_resume_args(out, mode);
+    if (rc != RB_OK) return rc;
+    if ((rc = check_resume_handle(r)) != RB_OK) return rc;
+    const size_t n = n_reads;
+    if (n == 0) return RB_OK;
+    if (!seqs || !offsets || !lens || !slots) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
+    if (n >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    {   // each slot at most once per call: two items of one slot would race for its counters
+        std::vector<uint32_t> sorted(slots, slots + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) return rb::fail(RB_ERR_INVALID_ARG, "slot " + std::to_string(*dup) + " named twice in one call");
+    }
+    rb_engine *e = r->e;
+    const size_t nf = e->filters.size();
+    hipStream_t st = e->stream;
+    std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
+    rb_batch_desc desc;
+    if ((rc = upload_reads(e, seqs, offsets, lens, n_reads, nullptr, n, st, &desc)) != RB_OK) return rc;
+    // staging: u32 slots[n] | u32 total_len[n] | i32 best[n] | u16 max_count[n][nf] | u8 flags[n] | u8 decision[n] | u8 status[n]
+    const size_t o_tot = 4 * n, o_best = o_tot + 4 * n, o_max = o_best + 4 * n, o_flags = o_max + 2 * n * nf, o_dec = o_flags + n, o_status = o_dec + n;
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        rc = e->d_resume_io.ensure(o_status + n);
+    }
+    if (rc != RB_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    char *io = (char *)e->d_resume_io.p;
+    RB_HIP(hipMemcpyAsync(io, slots, 4 * n, hipMemcpyHostToDevice, st));
+    if (flags) RB_HIP(hipMemcpyAsync(io + o_flags, flags, n, hipMemcpyHostToDevice, st));
+    rb_resume_out d_out;
+    d_out.max_count = out->max_count ? io + o_max : nullptr;
+    d_out.decision = out->decision ? io + o_dec : nullptr;
+    d_out.best_target = out->best_target ? io + o_best : nullptr;
+    d_out.status = out->status ? io + o_status : nullptr;
+    d_out.total_len = out->total_len ? io + o_tot : nullptr;
+    rc = resume_device_impl(r, &desc, io, flags ? io + o_flags : nullptr, error_rate, significance, mode, &d_out, (void *)st);
+    if (rc != RB_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if (out->max_count) RB_HIP(hipMemcpyAsync(out->max_count, io + o_max, 2 * n * nf, hipMemcpyDeviceToHost, st));
+    if (out->decision) RB_HIP(hipMemcpyAsync(out->decision, io + o_dec, n, hipMemcpyDeviceToHost, st));
+    if (out->best_target) RB_HIP(hipMemcpyAsync(out->best_target, io + o_best, 4 * n, hipMemcpyDeviceToHost, st));
+    if (out->status) RB_HIP(hipMemcpyAsync(out->status, io + o_status, n, hipMemcpyDeviceToHost, st));
+    if (out->total_len) RB_HIP(hipMemcpyAsync(out->total_len, io + o_tot, 4 * n, hipMemcpyDeviceToHost, st));
+    RB_HIP(hipStreamSynchronize(st));
+    return RB_OK;
+}
+
+int rb_resume_counts(rb_resume *r, uint32_t slot, size_t filter, uint16_t *out_counts, uint32_t *out_total_len)
+{
+    int rc = check_resume_handle(r);
+    if (rc != RB_OK) return rc;
+    if (!out_counts && !out_total_len) return rb::fail(RB_ERR_INVALID_ARG, "null outputs");
+    if (slot >= r->n_slots) return rb::fail(RB_ERR_INVALID_ARG, "slot beyond the set");
+    if (filter >= r->per.size()) return rb::fail(RB_ERR_INVALID_ARG, "filter index beyond the engine's filters");
+    rb_engine *e = r->e;
+    hipStream_t st = e->stream;
+    std::lock_guard<std::mutex> host_lock(e->host_mu);
+    const uint32_t n_bins = (uint32_t)e->filters[filter]->geo.n_bins;
+    if (out_counts) {
+        {
+            std::lock_guard<std::mutex> lock(e->mu);
+            rc = e->d_resume_io.ensure((size_t)n_bins * 4);
+        }
+        if (rc != RB_OK) return rc;
+        const rb_resume::PerFilter &p = r->per[filter];
+        RB_HIP(launch_resume_counts(r->d_state + (uint64_t)slot * r->slot_words + p.off, p.pad_cols, n_bins, (uint16_t *)e->d_resume_io.p, st));
+        RB_HIP(hipMemcpyAsync(out_counts, e->d_resume_io.p, (size_t)n_bins * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (out_total_len) RB_HIP(hipMemcpyAsync(out_total_len, &r->d_meta[slot].total, 4, hipMemcpyDeviceToHost, st));
+    RB_HIP(hipStreamSynchronize(st));
     return RB_OK;
 }
 

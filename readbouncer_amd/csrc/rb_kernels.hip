@@ -1472,6 +1472,169 @@ __global__ void first_decided_kernel(const uint8_t *__restrict__ decision, const
     first_decided[i] = p;
 }
 
+// RESUME: the opt-in pass (rb_resume_batch_device) that counts only the NEW k-mers of a read onto per-bin counters kept in HBM between
+// calls.  seqan::count adds one per k-mer, on both strands window by window (the prefix pass's argument above), so the counters of a
+// grown prefix are the counters of the shorter one plus one per new window, and the new windows are the k-mers of "the last k - 1 bases
+// seen so far + the new chunk" -- the stitched item resume_prep_kernel wrote.  One wave per (work item, column slice) behind locate's
+// prologue; per strand group 0's lanes load the slot's sixteen planes of their columns (a FIRST item: nothing), the other lane groups
+// start from cleared planes -- THE BUTTERFLY RULE of the prefix pass: count_strand's closing butterfly sums the groups, and totals must
+// never be added onto totals --, count_strand runs over the stitched item with no bound, no early exit and no phasing, planes_max gives
+// the slice's maximum, and group 0 stores the planes back (a PEEK item: nothing).  Sixteen planes only: the counters wrap at 2^16 as the
+// reference's do, whatever the read's length.  The state is streamed -- read once and written once per call, non-temporal both ways.
+// A plane of a slice is one contiguous run of the state (ResumeSlots), every (item, slice) wave touches its own columns only: no
+// atomics, no cross-wave order.  A refused item (kResumeSkip) touches no slot at all.
+template <int LG, int WPL, int NP, int H, bool NT>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(3, 8))) void ibf_resume_kernel(
+    IbfDev f, uint32_t col_begin, uint32_t col_end, ReadSrc src, uint32_t n_items, uint32_t n_slices, const uint16_t *__restrict__ thr,
+    uint32_t thr_len, uint32_t nf, uint32_t fi, ResumeSlots rs, uint16_t *__restrict__ part)
+{
+    static_assert(NP == (int)kResumePlanes, "the state holds sixteen planes");
+    __shared__ uint8_t s_stage[kWavesPerBlock][kStageBytes];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    uint32_t item, slice;
+    wave_item_slice<false>(n_slices, wave, &item, &slice);
+    if (item >= n_items) return;  // wave-uniform; there are no block-level barriers below
+
+    const uint32_t ctl = __builtin_amdgcn_readfirstlane((uint32_t)rs.ctl[item]);
+    if (ctl & kResumeSkip) {  // wave-uniform: the slot number was never vetted, no address is formed from it
+        if (lane == 0) part[(size_t)slice * n_items + item] = 0;
+        return;
+    }
+    // (the threshold is the decision kernel's business: a constant min_count keeps the prologue from reading the table)
+    const PassWave<WPL> pw = make_pass_wave<LG, WPL>(f, src, col_begin, col_end, item, slice, lane, thr, thr_len, nf, fi, 1u);
+    const LaneCols<WPL> &lc = pw.lc;
+    // This lane's columns of the slot and strand: group 0's lanes cover the slice's 2^LG * WPL padded columns side by side.  The address
+    // is formed where it is used, from an opaque copy of the lane number: kept across count_strand it costs the two registers that
+    // separate the h = 3 build for blocks of eight lanes from locate's four waves per SIMD.
+    // (by value: `lane` captured by reference would reach the prologue through memory, and what the compiler knows about the lane
+    // number in make_lane_cols is shared with every kernel that calls it -- profiles/isa_identity.py)
+    const uint32_t slot = __builtin_amdgcn_readfirstlane(rs.slot[item]);
+    auto strand_planes = [rs, slot, slice, lane](int strand) -> uint64_t * {
+        uint32_t l = (uint32_t)lane;
+        asm volatile("" : "+v"(l));
+        return rs.state + (uint64_t)slot * rs.slot_words + rs.filter_off + (uint64_t)(strand * NP) * rs.pad_cols +
+               (uint64_t)slice * (uint32_t)((1 << LG) * WPL) + (l & (uint32_t)((1 << LG) - 1)) * (uint32_t)WPL;
+    };
+    const bool loads = pw.group0 && !(ctl & kResumeFirst), stores = pw.group0 && !(ctl & kResumePeek);
+
+    uint32_t best = 0;
+    for (int strand = 0; strand < 2; ++strand) {
+        Planes<NP> pl[WPL];
+#pragma unroll
+        for (int w = 0; w < WPL; ++w) pl[w].clear();
+        if (loads) {
+            const uint64_t *sp = strand_planes(strand);
+#pragma unroll
+            for (int i = 0; i < NP; ++i)
+#pragma unroll
+                for (int w = 0; w < WPL; ++w) pl[w].p[i] = __builtin_nontemporal_load(sp + (uint64_t)i * rs.pad_cols + w);
+        }
+        count_strand<LG, WPL, NP, H, NT, false, false, 2>(pl, f, lc, pw.seq, pw.len, pw.n, strand, 0u, (uint32_t)TileShape<LG>::ITEMS, 0,
+                                                          TileShape<LG>::STEPS / 8, s_stage[wave], lane);
+        const uint32_t m = planes_max<NP, WPL>(pl, lc.valid);
+        best = m > best ? m : best;
+        if (stores) {
+            uint64_t *sp = strand_planes(strand);
+#pragma unroll
+            for (int i = 0; i < NP; ++i)
+#pragma unroll
+                for (int w = 0; w < WPL; ++w) __builtin_nontemporal_store(pl[w].p[i], sp + (uint64_t)i * rs.pad_cols + w);
+        }
+    }
+    if (lane == 0) part[(size_t)slice * n_items + item] = (uint16_t)best;
+}
+
+// Before the pass: one wave per item.  Vets the item ON THE DEVICE -- no slot number forms an address before it is checked --, applies
+// the descriptor's chunking as chunk_prep_kernel does, and writes the stitched string "tail + chunk" as ASCII where the pass reads it
+// through the ordinary ReadSrc.  The chunk is read through BaseSrc::ord, so ASCII and packed input, chunk_start / chunk_length and
+// d_read_ids work as in every descriptor call.  A refused item (slot >= n_slots, chunk longer than max_chunk_len, total beyond
+// max_total_len: RB_ERR_INVALID_ARG; chunk_start beyond the read: RB_ERR_BAD_CHUNK) is an empty string with kResumeSkip.
+// (a Dna5 ordinal as the ASCII letter dna5_ord reads back as that ordinal; arithmetic, not a string constant of the module)
+__device__ __forceinline__ uint8_t dna5_ascii(uint32_t o)
+{
+    constexpr uint32_t kAcgt = (uint32_t)'A' | ((uint32_t)'C' << 8) | ((uint32_t)'G' << 16) | ((uint32_t)'T' << 24);
+    return o < 4u ? (uint8_t)((kAcgt >> (8u * o)) & 0xFFu) : (uint8_t)'N';
+}
+__global__ __launch_bounds__(64 * kWavesPerBlock) void resume_prep_kernel(ResumePrep a)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t i = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (i >= a.n_items) return;
+    const uint32_t rid = a.src.ids ? a.src.ids[i] : i;
+    const uint32_t len = a.src.lens[rid];
+    const bool bad_chunk = a.src.base_off > len;
+    const uint32_t rest = bad_chunk ? 0u : len - a.src.base_off;
+    const uint32_t chunk = (a.chunk_length && a.chunk_length < rest) ? a.chunk_length : rest;
+    const uint32_t slot = a.slot[i];
+    const uint32_t flags = a.flags ? (uint32_t)a.flags[i] : 0u;
+    uint32_t status = bad_chunk ? (uint32_t)RB_ERR_BAD_CHUNK : (uint32_t)RB_OK;
+    uint32_t old_total = 0, tail_len = 0;
+    const bool slot_ok = slot < a.n_slots;
+    if (status == RB_OK && (!slot_ok || chunk > a.max_chunk_len)) status = RB_ERR_INVALID_ARG;
+    if (status == RB_OK && !(flags & kResumeFirst)) {
+        old_total = a.meta[slot].total;
+        tail_len = min(a.meta[slot].tail_len, min(a.k - 1u, kResumeMaxTail));
+    }
+    if (status == RB_OK && (uint64_t)old_total + chunk > (uint64_t)a.max_total_len) status = RB_ERR_INVALID_ARG;
+    const bool ok = status == RB_OK;
+    uint8_t *dst = a.stitched + (uint64_t)i * a.stitch_stride;
+    if (ok) {
+        if ((uint32_t)lane < tail_len) dst[lane] = dna5_ascii(a.meta[slot].tail[lane]);
+        BaseSrc b;
+        if (a.src.nmask) {
+            b.bytes = a.src.seqs + a.src.offsets[rid];
+            b.nm = a.src.nmask + a.src.nmask_offsets[rid];
+            b.first = a.src.base_off;
+        } else {
+            b.bytes = a.src.seqs + a.src.offsets[rid] + a.src.base_off;
+            b.nm = nullptr;
+            b.first = 0;
+        }
+        for (uint32_t p = (uint32_t)lane; p < chunk; p += 64) dst[tail_len + p] = dna5_ascii(b.ord(p));
+    }
+    if (lane == 0) {
+        a.st_offsets[i] = (uint64_t)i * a.stitch_stride;
+        a.st_lens[i] = ok ? tail_len + chunk : 0u;
+        a.total_lens[i] = ok ? old_total + chunk : 0u;
+        a.pre_status[i] = (uint8_t)status;
+        a.ctl[i] = ok ? (uint8_t)(flags & (kResumeFirst | kResumePeek)) : (uint8_t)kResumeSkip;
+        if (a.out_total_len) a.out_total_len[i] = ok ? old_total + chunk : 0u;
+    }
+}
+
+// After the last filter's pass: the slot's new total and tail -- the last min(total, k - 1) bases of the stitched string, which is
+// "everything so far" while the total is below k.  Not for a PEEK or a refused item.  One thread per item.
+__global__ void resume_commit_kernel(ResumeMeta *__restrict__ meta, const uint32_t *__restrict__ slot, const uint8_t *__restrict__ ctl,
+                                     const uint8_t *__restrict__ stitched, uint32_t stitch_stride, const uint32_t *__restrict__ st_lens,
+                                     const uint32_t *__restrict__ total_lens, uint32_t n_items, uint32_t k)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    if (ctl[i] & (kResumeSkip | kResumePeek)) return;
+    const uint32_t sl = st_lens[i];
+    const uint32_t tl = min(sl, min(k - 1u, kResumeMaxTail));
+    const uint8_t *src = stitched + (uint64_t)i * stitch_stride + (sl - tl);
+    ResumeMeta m;
+    m.total = total_lens[i];
+    m.tail_len = tl;
+    for (uint32_t j = 0; j <= kResumeMaxTail; ++j) m.tail[j] = j < tl ? (uint8_t)rbspec::dna5_ord(src[j]) : (uint8_t)0;
+    meta[slot[i]] = m;
+}
+
+// rb_resume_counts: the bit-sliced planes of one slot and filter as the two uint16_t count vectors of seqan::count.  One thread per
+// (strand, bin).
+__global__ void resume_counts_kernel(const uint64_t *__restrict__ planes, uint32_t pad_cols, uint32_t n_bins, uint16_t *__restrict__ counts)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2u * n_bins) return;
+    const uint32_t strand = t / n_bins, bin = t - strand * n_bins;
+    const uint64_t *p = planes + (uint64_t)(strand * kResumePlanes) * pad_cols + (bin >> 6);
+    uint32_t c = 0;
+    for (uint32_t i = 0; i < kResumePlanes; ++i) c |= (uint32_t)((p[(uint64_t)i * pad_cols] >> (bin & 63u)) & 1ULL) << i;
+    counts[t] = (uint16_t)c;
+}
+
 // HITS: the opt-in pass (rb_hits_batch_device) that lists EVERY (bin, strand) whose count reached the threshold, with the count --
 // the sparse form of what seqan::count returns.  Up to the bit-sliced c > t-1 mask of a strand it runs what ibf_locate_kernel
 // runs, behind the same wave prologue (make_pass_wave); then,
@@ -4042,6 +4205,49 @@ hipError_t launch_first_decided(const uint8_t *decision, const uint8_t *status, 
 {
     if (n_items == 0) return hipSuccess;
     hipLaunchKernelGGL(first_decided_kernel, dim3((n_items + 255) / 256), dim3(256), 0, st, decision, status, n_items, n_prefixes, first_decided);
+    return hipGetLastError();
+}
+
+// (sixteen planes whatever the launch says: the state holds no other kind, and no ten-plane build of this kernel exists)
+struct ResumePass {
+    template <int LG, int WPL, int NP, int H, bool NT>
+    static constexpr auto kernel() { return &ibf_resume_kernel<LG, WPL, (int)kResumePlanes, H, NT>; }
+};
+hipError_t launch_ibf_resume(const ResumeLaunch &a, hipStream_t st)
+{
+    if (a.n_items == 0) return hipSuccess;
+    if (!a.part || !a.slots.state || !a.slots.slot || !a.slots.ctl || a.planes != (int)kResumePlanes) return hipErrorInvalidValue;
+    // every column a wave of the grid loads or stores lies inside the filter's share of a slot
+    if ((uint64_t)a.n_slices * (uint64_t)((1u << a.lg) * (uint32_t)a.wpl) != (uint64_t)a.slots.pad_cols || a.col_begin != 0 ||
+        a.slots.filter_off + 2ull * kResumePlanes * a.slots.pad_cols > a.slots.slot_words)
+        return hipErrorInvalidValue;
+    return launch_plain_pass<ResumePass>(a, st, a.slots, a.part);
+}
+
+hipError_t launch_resume_prep(const ResumePrep &a, hipStream_t st)
+{
+    if (a.n_items == 0) return hipSuccess;
+    if (!a.slot || !a.meta || !a.stitched || !a.st_offsets || !a.st_lens || !a.total_lens || !a.pre_status || !a.ctl || a.k == 0 ||
+        a.k > rbspec::kMaxKmer || (uint64_t)a.stitch_stride < (uint64_t)a.max_chunk_len + kResumeMaxTail)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(resume_prep_kernel, dim3((a.n_items + kWavesPerBlock - 1) / kWavesPerBlock), dim3(64 * kWavesPerBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_resume_commit(ResumeMeta *meta, const uint32_t *slot, const uint8_t *ctl, const uint8_t *stitched, uint32_t stitch_stride,
+                                const uint32_t *st_lens, const uint32_t *total_lens, uint32_t n_items, uint32_t k, hipStream_t st)
+{
+    if (n_items == 0) return hipSuccess;
+    hipLaunchKernelGGL(resume_commit_kernel, dim3((n_items + 255) / 256), dim3(256), 0, st, meta, slot, ctl, stitched, stitch_stride, st_lens,
+                       total_lens, n_items, k);
+    return hipGetLastError();
+}
+
+hipError_t launch_resume_counts(const uint64_t *planes, uint32_t pad_cols, uint32_t n_bins, uint16_t *counts, hipStream_t st)
+{
+    if (n_bins == 0) return hipSuccess;
+    if ((uint64_t)pad_cols * 64u < n_bins || n_bins >= (1u << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(resume_counts_kernel, dim3((2u * n_bins + 255) / 256), dim3(256), 0, st, planes, pad_cols, n_bins, counts);
     return hipGetLastError();
 }
 
