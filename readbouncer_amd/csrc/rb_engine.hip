@@ -21,6 +21,7 @@
 #include "rb_device.h"
 #include "rb_io.h"
 #include "rb_phase_plan.h"
+#include "rb_stage.h"
 
 using namespace rb;
 using namespace rbplan;
@@ -455,15 +456,13 @@ struct rb_engine {
     // staging for the host-pointer API
     DevBuf d_seqs, d_offsets, d_lens, d_best, d_decision, d_status;
     DevBuf d_efflens, d_prestatus;  // on-GPU chunking: effective lengths and the bad-chunk status per item
-    DevBuf d_locate_parts;          // locate pass: partial records of the column slices, all filters of a call
-    DevBuf d_locate_io;             // rb_locate_batch: read ids in, the five outputs back
-    DevBuf d_hits_ws;               // hits pass: the (item, slice, strand) record segments and their counters, one filter at a time
-    DevBuf d_hits_io;               // rb_hits_batch: read ids in, records / n_hits / status / bin_reads back
-    DevBuf d_spans_io;              // rb_spans_batch: read ids and queries in, masks / records / n_kmers / status back
-    DevBuf d_prefix_ws;             // prefix pass: partial maxima of the column slices (one filter at a time), the rows' lengths and pre-status, outputs the caller left out
-    DevBuf d_prefix_io;             // rb_prefix_batch: read ids in, the six outputs back
-    DevBuf d_resume_ws;             // resume pass: the stitched items, their lengths and totals, pre-status and ctl bits, partial maxima (one filter at a time), maxima the caller left out
-    DevBuf d_resume_io;             // rb_resume_batch: slots and flags in, the five outputs back; rb_resume_counts: the two count vectors
+    // The query passes (locate, hits, spans, prefixes, resume) share two blocks, each cut by an rb::StageLayout per call.  What allows it is
+    // the contract of rb_classify_batch_device: "An engine's workspaces ... are per engine: calls on one engine may come from several
+    // threads, but their GPU work must be ordered -- use one stream per engine, or order the streams with events" -- d_efflens and
+    // d_prestatus above are shared on it already, and host forms are serialised by host_mu.  Two and not one: a host form holds its
+    // staged arrays in d_pass_io while the device form it calls cuts d_pass_ws.
+    DevBuf d_pass_ws;  // device forms: partial records of the column slices, rows and outputs the caller left out, resume's stitched items
+    DevBuf d_pass_io;  // host forms: ids / slots / flags / queries in, the outputs back; rb_resume_counts: the two count vectors
     PinnedBuf h_in, h_out;
     // large host batches: slice i+1 is copied on this stream while slice i is counted on `stream`
     hipStream_t copy_stream = nullptr;
@@ -1224,7 +1223,7 @@ void rb_engine_destroy(rb_engine *e)
     }
     for (void *r : e->thr_retired_dev) (void)hipFree(r);
     for (PinnedBuf &h : e->thr_retired_host) h.release();
-    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_locate_parts, &e->d_locate_io, &e->d_hits_ws, &e->d_hits_io, &e->d_spans_io, &e->d_prefix_ws, &e->d_prefix_io, &e->d_resume_ws, &e->d_resume_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
+    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_pass_ws, &e->d_pass_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
                       &e->d_decision, &e->d_status})
         b->release();
     e->h_in.release();
@@ -2413,6 +2412,46 @@ static int end_timed(std::pair<hipEvent_t, hipEvent_t> *evp, hipStream_t st)
     return RB_OK;
 }
 
+// The frame of a device-form query pass, after its argument checks: holds e->mu for the rest of the call, knows the call's stream and
+// carries what the steps make -- input, thresholds, the timing pair.  A pass composes the steps it has: begin() is what locate, hits
+// and prefixes do alike, spans and resume vet an engine of their own kind and make their input themselves.
+struct PassCall {
+    rb_engine *e;
+    std::unique_lock<std::mutex> lock;
+    hipStream_t st;
+    bool own_stream;  // the engine's own stream: end() waits for it
+    size_t nf;
+    PassInput in{};
+    const uint16_t *thr = nullptr;
+    uint32_t thr_len = 0;
+    std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
+    PassCall(rb_engine *e_, void *stream) : e(e_), lock(e_->mu), st(stream ? (hipStream_t)stream : e_->stream), own_stream(!stream), nf(e_->filters.size()) {}
+    // a whole engine with filters, then the input
+    int begin(const rb_batch_desc *desc, const char *pass)
+    {
+        const int rc = refuse_sharded(e, pass);
+        if (rc != RB_OK) return rc;
+        if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
+        return prepare_pass_input(e, desc, st, &in);
+    }
+    // the table the decision kernel reads, entry [len][filter][0] -- one definition of the threshold
+    int thresholds(uint32_t max_len, double r, double conf) { return ensure_thresholds(e, max_len, r, conf, st, &thr, &thr_len); }
+    // the call's workspace, ws(), then the timing pair: one per device-form call
+    int start(size_t ws_bytes = 0)
+    {
+        const int rc = e->d_pass_ws.ensure(ws_bytes);
+        return rc != RB_OK ? rc : begin_timed(e, st, &evp);
+    }
+    char *ws() const { return (char *)e->d_pass_ws.p; }
+    int end()
+    {
+        const int rc = end_timed(evp, st);
+        if (rc != RB_OK) return rc;
+        if (own_stream) RB_HIP(hipStreamSynchronize(st));
+        return RB_OK;
+    }
+};
+
 // a table the query passes read with non-temporal loads (rb_engine_set_nt_threshold)
 static bool table_beyond_nt_threshold(const rb_engine *e, const rb_dibf *f) { return f->geo.n_blocks * f->stride * 8 > e->nt_threshold_bytes; }
 
@@ -3183,10 +3222,30 @@ int rb_classify_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, c
     return RB_OK;
 }
 
-// Host form of the query passes: the caller's reads go to the engine's staging buffers, once per call.  Vets the selection, finds the
-// stretch of seqs the reads cover, uploads it with offsets and lens on `st`, and describes the batch of n work items (d_seqs: the device
-// address of the caller's seqs[0]; d_read_ids is the caller's to set, its staging layout is its own).  Without work items -- spans
-// allows that -- nothing is read and nothing copied.  The caller holds e->host_mu; after a failure that follows this call it waits for `st`.
+// ---- what the host forms of the query passes share.  A host form is: its own argument-shape checks, check_host_engine, the work items
+// n (an empty call is RB_OK before the buffers are looked at), check_host_reads, upload_reads under e->host_mu and a DrainUnlessDone
+// from there on, one rb::StageLayout for what it stages in e->d_pass_io, then per sub-batch the device form and the copy-back.
+// The device, then the handle: without a GPU nothing here can work (check_pass_call's order).
+static int check_host_engine(const rb_engine *e)
+{
+    const int rc = check_device(e ? e->device : 0);
+    if (rc != RB_OK) return rc;
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    return RB_OK;
+}
+
+// n work items out of n_reads reads (n_extra: the queries of spans)
+static int check_host_reads(const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, size_t n, size_t n_extra)
+{
+    if (n && (!seqs || !offsets || !lens || n_reads == 0)) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
+    if (n >= (1ULL << 31) || n_reads >= (1ULL << 31) || n_extra >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    return RB_OK;
+}
+
+// The caller's reads go to the engine's staging buffers, once per call.  Vets the selection, finds the stretch of seqs the reads cover,
+// uploads it with offsets and lens on `st`, and describes the batch of n work items (d_seqs: the device address of the caller's seqs[0];
+// d_read_ids is the caller's to set).  Without work items -- spans allows that -- nothing is read and nothing copied.  The caller holds
+// e->host_mu and, once this has succeeded, a DrainUnlessDone on `st`.
 static int upload_reads(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *read_ids,
                         size_t n, hipStream_t st, rb_batch_desc *desc)
 {
@@ -3223,11 +3282,66 @@ static int upload_reads(rb_engine *e, const char *seqs, const uint64_t *offsets,
     return RB_OK;
 }
 
+// After upload_reads the stream may still be reading the caller's seqs: a host form that leaves by anything but done() waits for it.
+struct DrainUnlessDone {
+    hipStream_t st;
+    bool ok = false;
+    ~DrainUnlessDone() { if (!ok) (void)hipStreamSynchronize(st); }
+    int done() { return ok = true, RB_OK; }
+};
+
+// the host forms' staging block (grown under e->mu like every buffer of the engine), and the staged outputs' places in it
+static int stage_block(rb_engine *e, size_t bytes, char **io, const rb::StagedOuts *outs = nullptr)
+{
+    std::lock_guard<std::mutex> lock(e->mu);
+    const int rc = e->d_pass_io.ensure(bytes);
+    *io = (char *)e->d_pass_io.p;
+    if (rc == RB_OK && outs) outs->bind(*io);
+    return rc;
+}
+
+static int copy_back(const rb::StagedOuts &outs, const char *io, size_t b0, size_t sub, hipStream_t st)
+{
+    return outs.copy_back(io, b0, sub, [st](void *dst, const void *src, size_t bytes) -> int {
+        RB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+        return RB_OK;
+    });
+}
+
+// Work item j of a sub-batch is read read_ids[b0 + j] (d_read_ids: where the caller staged read_ids + b0), or read b0 + j
+static rb_batch_desc sub_batch_desc(const rb_batch_desc &all, size_t b0, size_t sub, const void *d_read_ids)
+{
+    rb_batch_desc desc = all;
+    if (!d_read_ids) {
+        desc.d_offsets = (const uint64_t *)all.d_offsets + b0;
+        desc.d_lens = (const uint32_t *)all.d_lens + b0;
+    }
+    desc.n_items = sub;
+    desc.d_read_ids = d_read_ids;
+    return desc;
+}
+
+// What prefixes and hits size their sub-batches by: the filters, their bins, and the most column slices the device form will cut
+static void host_pass_geometry(rb_engine *e, uint32_t max_len, size_t *nf, size_t *total_bins, size_t *max_slices)
+{
+    std::lock_guard<std::mutex> lock(e->mu);
+    *nf = e->filters.size();
+    *total_bins = 0;
+    *max_slices = 1;
+    for (const rb_dibf *f : e->filters) {
+        int lg, wpl, planes, nt;
+        uint32_t n_slices;
+        plain_geometry(e, f, max_len, &lg, &wpl, &n_slices, &planes, &nt);
+        *total_bins += f->geo.n_bins;
+        *max_slices = std::max<size_t>(*max_slices, n_slices);
+    }
+}
+
 // ---- locate: which bin and strand a read matched, and how many bins hit (no counterpart in the reference; see the boundary header).
 // Always the plain form over each filter's OWN table, counted in full: the engine's pruning / early-decision / merge / phased settings
 // do not reach it.  One launch of ibf_locate_kernel per filter plus the merge of its column slices, in sequence on the call's stream.
-static int locate_device_impl(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, const rb_locate_out *d_out,
-                              void *stream)
+int rb_locate_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, const rb_locate_out *d_out,
+                           void *stream)
 {
     if (!desc || !d_out) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor or output struct");
     if (!d_out->max_count && !d_out->best_bin && !d_out->best_strand && !d_out->hit_bins && !d_out->status)
@@ -3237,52 +3351,34 @@ static int locate_device_impl(rb_engine *e, const rb_batch_desc *desc, double er
     const size_t n_items = desc->n_items;
     if (n_items == 0) return RB_OK;
     if ((rc = check_desc_buffers(desc, false)) != RB_OK) return rc;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if ((rc = refuse_sharded(e, "locate")) != RB_OK) return rc;
-    const size_t nf = e->filters.size();
-    if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    PassInput in;
-    if ((rc = prepare_pass_input(e, desc, st, &in)) != RB_OK) return rc;
-    // t of hit_bins: the table the decision kernel reads, entry [len][filter][0]
-    const uint16_t *thr = nullptr;
-    uint32_t thr_len = 0;
-    if ((rc = ensure_thresholds(e, in.max_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
+    PassCall c(e, stream);
+    if ((rc = c.begin(desc, "locate")) != RB_OK) return rc;
+    if ((rc = c.thresholds(c.in.max_len, error_rate, significance)) != RB_OK) return rc;  // t of hit_bins
     // geometry per filter as the plain kernel cuts it, and one block of partial records for the call
+    const size_t nf = c.nf;
     std::vector<LocateLaunch> launches(nf);
-    size_t part_records = 0;
+    std::vector<size_t> o_part(nf);
+    rb::StageLayout lay;
     for (size_t fi = 0; fi < nf; ++fi) {
-        fill_plain_launch(e, fi, in, thr, thr_len, &launches[fi]);
-        part_records += (size_t)launches[fi].n_slices * n_items;
+        fill_plain_launch(e, fi, c.in, c.thr, c.thr_len, &launches[fi]);
+        o_part[fi] = lay.take((size_t)launches[fi].n_slices * n_items * sizeof(LocatePart));
     }
-    if ((rc = e->d_locate_parts.ensure(part_records * sizeof(LocatePart))) != RB_OK) return rc;
-    std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
-    if ((rc = begin_timed(e, st, &evp)) != RB_OK) return rc;
+    if ((rc = c.start(lay.bytes())) != RB_OK) return rc;
     LocateOut out;
     out.max_count = (uint16_t *)d_out->max_count;
     out.best_bin = (int32_t *)d_out->best_bin;
     out.best_strand = (uint8_t *)d_out->best_strand;
     out.hit_bins = (uint32_t *)d_out->hit_bins;
     out.status = (uint8_t *)d_out->status;
-    LocatePart *part = (LocatePart *)e->d_locate_parts.p;
     const uint32_t min_len = engine_min_len(e);
     for (size_t fi = 0; fi < nf; ++fi) {
         LocateLaunch &a = launches[fi];
-        a.part = part;
-        RB_HIP(launch_ibf_locate(a, st));
-        RB_HIP(launch_reduce_locate_slices(part, a.n_slices, (uint32_t)n_items, in.d_lens, in.d_pre_status, in.max_len, min_len, out,
-                                           (uint32_t)nf, (uint32_t)fi, st));
-        part += (size_t)a.n_slices * n_items;
+        a.part = (LocatePart *)(c.ws() + o_part[fi]);
+        RB_HIP(launch_ibf_locate(a, c.st));
+        RB_HIP(launch_reduce_locate_slices(a.part, a.n_slices, (uint32_t)n_items, c.in.d_lens, c.in.d_pre_status, c.in.max_len, min_len, out,
+                                           (uint32_t)nf, (uint32_t)fi, c.st));
     }
-    if ((rc = end_timed(evp, st)) != RB_OK) return rc;
-    if (!stream) RB_HIP(hipStreamSynchronize(st));
-    return RB_OK;
-}
-
-int rb_locate_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, const rb_locate_out *d_out,
-                           void *stream)
-{
-    return locate_device_impl(e, desc, error_rate, significance, d_out, stream);
+    return c.end();
 }
 
 int rb_locate_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *read_ids,
@@ -3291,49 +3387,34 @@ int rb_locate_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, con
     if (!out) return rb::fail(RB_ERR_INVALID_ARG, "null output struct");
     if (!out->max_count && !out->best_bin && !out->best_strand && !out->hit_bins && !out->status)
         return rb::fail(RB_ERR_INVALID_ARG, "rb_locate_out with no output");
-    int rc = check_device(e ? e->device : 0);
+    int rc = check_host_engine(e);
     if (rc != RB_OK) return rc;
-    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
     const size_t n = read_ids ? n_items : n_reads;  // without a selection the work items are the reads
     if (n == 0) return RB_OK;
-    if (!seqs || !offsets || !lens || n_reads == 0) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
-    if (n >= (1ULL << 31) || n_reads >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    if ((rc = check_host_reads(seqs, offsets, lens, n_reads, n, 0)) != RB_OK) return rc;
     const size_t nf = e->filters.size();
     hipStream_t st = e->stream;
     std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
     rb_batch_desc desc;
     if ((rc = upload_reads(e, seqs, offsets, lens, n_reads, read_ids, n, st, &desc)) != RB_OK) return rc;
-    // staging: u32 ids[n] | i32 best_bin[n*nf] | u32 hit_bins[n*nf] | u16 max_count[n*nf] | u8 best_strand[n*nf] | u8 status[n]
-    const size_t o_bin = 4 * n, o_hit = o_bin + 4 * n * nf, o_max = o_hit + 4 * n * nf, o_strand = o_max + 2 * n * nf, o_status = o_strand + n * nf;
-    {
-        std::lock_guard<std::mutex> lock(e->mu);
-        rc = e->d_locate_io.ensure(o_status + n);
-    }
-    if (rc != RB_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    char *io = (char *)e->d_locate_io.p;
-    if (read_ids) RB_HIP(hipMemcpyAsync(io, read_ids, 4 * n, hipMemcpyHostToDevice, st));
-    desc.d_read_ids = read_ids ? io : nullptr;
+    DrainUnlessDone drain{st};
+    rb::StageLayout lay;
+    rb::StagedOuts outs;
     rb_locate_out d_out;
-    d_out.max_count = out->max_count ? io + o_max : nullptr;
-    d_out.best_bin = out->best_bin ? io + o_bin : nullptr;
-    d_out.best_strand = out->best_strand ? io + o_strand : nullptr;
-    d_out.hit_bins = out->hit_bins ? io + o_hit : nullptr;
-    d_out.status = out->status ? io + o_status : nullptr;
-    rc = locate_device_impl(e, &desc, error_rate, significance, &d_out, (void *)st);
-    if (rc != RB_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    if (out->max_count) RB_HIP(hipMemcpyAsync(out->max_count, io + o_max, 2 * n * nf, hipMemcpyDeviceToHost, st));
-    if (out->best_bin) RB_HIP(hipMemcpyAsync(out->best_bin, io + o_bin, 4 * n * nf, hipMemcpyDeviceToHost, st));
-    if (out->best_strand) RB_HIP(hipMemcpyAsync(out->best_strand, io + o_strand, n * nf, hipMemcpyDeviceToHost, st));
-    if (out->hit_bins) RB_HIP(hipMemcpyAsync(out->hit_bins, io + o_hit, 4 * n * nf, hipMemcpyDeviceToHost, st));
-    if (out->status) RB_HIP(hipMemcpyAsync(out->status, io + o_status, n, hipMemcpyDeviceToHost, st));
+    const size_t o_ids = lay.take(read_ids ? 4 * n : 0);
+    outs.add(lay, out->max_count, &d_out.max_count, 2 * nf, n);
+    outs.add(lay, out->best_bin, &d_out.best_bin, 4 * nf, n);
+    outs.add(lay, out->best_strand, &d_out.best_strand, nf, n);
+    outs.add(lay, out->hit_bins, &d_out.hit_bins, 4 * nf, n);
+    outs.add(lay, out->status, &d_out.status, 1, n);
+    char *io;
+    if ((rc = stage_block(e, lay.bytes(), &io, &outs)) != RB_OK) return rc;
+    if (read_ids) RB_HIP(hipMemcpyAsync(io + o_ids, read_ids, 4 * n, hipMemcpyHostToDevice, st));
+    desc.d_read_ids = read_ids ? io + o_ids : nullptr;
+    if ((rc = rb_locate_batch_device(e, &desc, error_rate, significance, &d_out, (void *)st)) != RB_OK) return rc;
+    if ((rc = copy_back(outs, io, 0, n, st)) != RB_OK) return rc;
     RB_HIP(hipStreamSynchronize(st));
-    return RB_OK;
+    return drain.done();
 }
 
 // ---- prefixes: a work item's maxima and decision at every prefix checkpoint, from one walk over its k-mers (see the boundary header).
@@ -3356,8 +3437,8 @@ static int check_prefix_args(const rb_prefix_out *out, const uint32_t *prefix_le
     return RB_OK;
 }
 
-static int prefix_device_impl(rb_engine *e, const rb_batch_desc *desc, const uint32_t *prefix_lens, uint32_t n_prefixes, double error_rate,
-                              double significance, int mode, const rb_prefix_out *d_out, void *stream)
+int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32_t *prefix_lens, uint32_t n_prefixes, double error_rate,
+                           double significance, int mode, const rb_prefix_out *d_out, void *stream)
 {
     if (!desc) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor");
     int rc = check_prefix_args(d_out, prefix_lens, n_prefixes, mode);
@@ -3368,68 +3449,52 @@ static int prefix_device_impl(rb_engine *e, const rb_batch_desc *desc, const uin
     const size_t P = n_prefixes, rows = n_items * P;
     if (rows >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
     if ((rc = check_desc_buffers(desc, false)) != RB_OK) return rc;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if ((rc = refuse_sharded(e, "prefixes")) != RB_OK) return rc;
-    const size_t nf = e->filters.size();
-    if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    PassInput in;
-    if ((rc = prepare_pass_input(e, desc, st, &in)) != RB_OK) return rc;
+    PassCall c(e, stream);
+    if ((rc = c.begin(desc, "prefixes")) != RB_OK) return rc;
     // no row is longer than the last checkpoint: the bound of the rows (counter planes, threshold table, the decision kernel's max_len)
-    in.max_len = std::min(in.max_len, prefix_lens[P - 1]);
-    in.src.max_len = in.max_len;
-    const uint16_t *thr = nullptr;
-    uint32_t thr_len = 0;
-    if ((rc = ensure_thresholds(e, in.max_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
+    c.in.max_len = std::min(c.in.max_len, prefix_lens[P - 1]);
+    c.in.src.max_len = c.in.max_len;
+    if ((rc = c.thresholds(c.in.max_len, error_rate, significance)) != RB_OK) return rc;
+    const size_t nf = c.nf;
     std::vector<PrefixLaunch> launches(nf);
     uint32_t max_slices = 0;
     for (size_t fi = 0; fi < nf; ++fi) {
         PrefixLaunch &a = launches[fi];
-        fill_plain_launch(e, fi, in, thr, thr_len, &a);
+        fill_plain_launch(e, fi, c.in, c.thr, c.thr_len, &a);
         a.cps.n = n_prefixes;
         for (uint32_t p = 0; p < kMaxPrefixes; ++p) a.cps.c[p] = p < n_prefixes ? prefix_lens[p] : 0u;
         max_slices = std::max(max_slices, a.n_slices);
     }
-    // workspace: u16 part[max_slices][n_items][P] | u32 prefix_len[rows] | u16 max_count[rows][nf] | u8 row_pre[rows] | u8 decision[rows] |
-    // u8 status[rows] -- the outputs only where the caller left them out and a later stage reads them
+    // workspace: the partial maxima u16[max_slices][n_items][P] and the rows' pre-status, and the outputs a later stage reads where the
+    // caller left them out
     const bool decides = d_out->decision || d_out->best_target || d_out->status || d_out->first_decided;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_len = up16((size_t)max_slices * rows * 2), o_max = o_len + up16(d_out->prefix_len ? 0 : rows * 4);
-    const size_t o_pre = o_max + up16(d_out->max_count ? 0 : rows * nf * 2), o_dec = o_pre + up16(rows);
-    const size_t o_st = o_dec + up16(d_out->first_decided && !d_out->decision ? rows : 0);
-    const size_t ws_bytes = o_st + up16(d_out->first_decided && !d_out->status ? rows : 0);
-    if ((rc = e->d_prefix_ws.ensure(ws_bytes)) != RB_OK) return rc;
-    char *ws = (char *)e->d_prefix_ws.p;
-    uint16_t *part = (uint16_t *)ws;
+    rb::StageLayout lay;
+    const size_t o_part = lay.take((size_t)max_slices * rows * 2), o_pre = lay.take(rows);
+    const size_t o_len = lay.take(d_out->prefix_len ? 0 : rows * 4), o_max = lay.take(d_out->max_count ? 0 : rows * nf * 2);
+    const size_t o_dec = lay.take(d_out->first_decided && !d_out->decision ? rows : 0);
+    const size_t o_st = lay.take(d_out->first_decided && !d_out->status ? rows : 0);
+    if ((rc = c.start(lay.bytes())) != RB_OK) return rc;
+    char *ws = c.ws();
+    uint16_t *part = (uint16_t *)(ws + o_part);
     uint32_t *row_len = d_out->prefix_len ? (uint32_t *)d_out->prefix_len : (uint32_t *)(ws + o_len);
     uint16_t *max_count = d_out->max_count ? (uint16_t *)d_out->max_count : (uint16_t *)(ws + o_max);
     uint8_t *row_pre = (uint8_t *)(ws + o_pre);
     uint8_t *decision = (uint8_t *)d_out->decision, *status = (uint8_t *)d_out->status;
     if (d_out->first_decided && !decision) decision = (uint8_t *)(ws + o_dec);
     if (d_out->first_decided && !status) status = (uint8_t *)(ws + o_st);
-    std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
-    if ((rc = begin_timed(e, st, &evp)) != RB_OK) return rc;
     for (size_t fi = 0; fi < nf; ++fi) {
         PrefixLaunch &a = launches[fi];
         a.part = part;
-        RB_HIP(launch_ibf_prefix(a, st));
-        RB_HIP(launch_finish_prefix(a, in.d_lens, in.d_pre_status, max_count, row_len, row_pre, st));
+        RB_HIP(launch_ibf_prefix(a, c.st));
+        RB_HIP(launch_finish_prefix(a, c.in.d_lens, c.in.d_pre_status, max_count, row_len, row_pre, c.st));
     }
     if (decides) {
-        if ((rc = run_decide(e, max_count, row_len, row_pre, rows, in.max_len, error_rate, significance, mode, (int32_t *)d_out->best_target,
-                             decision, status, st)) != RB_OK)
+        if ((rc = run_decide(e, max_count, row_len, row_pre, rows, c.in.max_len, error_rate, significance, mode, (int32_t *)d_out->best_target,
+                             decision, status, c.st)) != RB_OK)
             return rc;
-        if (d_out->first_decided) RB_HIP(launch_first_decided(decision, status, (uint32_t)n_items, n_prefixes, (uint32_t *)d_out->first_decided, st));
+        if (d_out->first_decided) RB_HIP(launch_first_decided(decision, status, (uint32_t)n_items, n_prefixes, (uint32_t *)d_out->first_decided, c.st));
     }
-    if ((rc = end_timed(evp, st)) != RB_OK) return rc;
-    if (!stream) RB_HIP(hipStreamSynchronize(st));
-    return RB_OK;
-}
-
-int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32_t *prefix_lens, uint32_t n_prefixes, double error_rate,
-                           double significance, int mode, const rb_prefix_out *d_out, void *stream)
-{
-    return prefix_device_impl(e, desc, prefix_lens, n_prefixes, error_rate, significance, mode, d_out, stream);
+    return c.end();
 }
 
 int rb_prefix_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *read_ids,
@@ -3438,31 +3503,18 @@ int rb_prefix_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, con
 {
     int rc = check_prefix_args(out, prefix_lens, n_prefixes, mode);
     if (rc != RB_OK) return rc;
-    if ((rc = check_device(e ? e->device : 0)) != RB_OK) return rc;
-    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    if ((rc = check_host_engine(e)) != RB_OK) return rc;
     const size_t n = read_ids ? n_items : n_reads;  // without a selection the work items are the reads
     if (n == 0) return RB_OK;
-    if (!seqs || !offsets || !lens || n_reads == 0) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
-    if (n >= (1ULL << 31) || n_reads >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    if ((rc = check_host_reads(seqs, offsets, lens, n_reads, n, 0)) != RB_OK) return rc;
     hipStream_t st = e->stream;
     std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
     rb_batch_desc all;
     if ((rc = upload_reads(e, seqs, offsets, lens, n_reads, read_ids, n, st, &all)) != RB_OK) return rc;
-    size_t nf = 0, max_slices = 1;
-    {
-        std::lock_guard<std::mutex> lock(e->mu);
-        nf = e->filters.size();
-        for (const rb_dibf *f : e->filters) {  // the column slices prefix_device_impl will cut: its workspace is part of the budget below
-            int lg, wpl, planes, nt;
-            uint32_t n_slices;
-            plain_geometry(e, f, all.max_len, &lg, &wpl, &n_slices, &planes, &nt);
-            max_slices = std::max<size_t>(max_slices, n_slices);
-        }
-    }
-    if (nf == 0) {
-        (void)hipStreamSynchronize(st);
-        return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
-    }
+    DrainUnlessDone drain{st};
+    size_t nf, total_bins, max_slices;
+    host_pass_geometry(e, all.max_len, &nf, &total_bins, &max_slices);
+    if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
     // sub-batches: workspace (S partial maxima, a length and a pre-status per row) plus staged outputs (nf maxima, a length, a target, a
     // decision and a status per row; an id and a first_decided per item) stay at or below kPrefixBudget; a single item that needs more
     // goes alone
@@ -3470,51 +3522,27 @@ int rb_prefix_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, con
     const size_t P = n_prefixes;
     const size_t per_item = P * (max_slices * 2 + 4 + 1 + nf * 2 + 4 + 4 + 1 + 1) + 4 + 4 + 64;
     const size_t sub_max = std::max<size_t>(1, std::min<size_t>(n, kPrefixBudget / per_item));
-    // staging: u32 ids[sub] | u32 first[sub] | u32 prefix_len[rows] | i32 best[rows] | u16 max_count[rows][nf] | u8 decision[rows] | u8 status[rows]
-    const size_t R = sub_max * P;
-    const size_t o_first = 4 * sub_max, o_len = o_first + 4 * sub_max, o_best = o_len + 4 * R, o_max = o_best + 4 * R, o_dec = o_max + 2 * R * nf,
-                 o_status = o_dec + R;
-    {
-        std::lock_guard<std::mutex> lock(e->mu);
-        rc = e->d_prefix_io.ensure(o_status + R);
-    }
-    if (rc != RB_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    char *io = (char *)e->d_prefix_io.p;
+    rb::StageLayout lay;
+    rb::StagedOuts outs;
+    rb_prefix_out d_out;
+    const size_t o_ids = lay.take(read_ids ? 4 * sub_max : 0);
+    outs.add(lay, out->max_count, &d_out.max_count, 2 * P * nf, sub_max);
+    outs.add(lay, out->decision, &d_out.decision, P, sub_max);
+    outs.add(lay, out->best_target, &d_out.best_target, 4 * P, sub_max);
+    outs.add(lay, out->status, &d_out.status, P, sub_max);
+    outs.add(lay, out->prefix_len, &d_out.prefix_len, 4 * P, sub_max);
+    outs.add(lay, out->first_decided, &d_out.first_decided, 4, sub_max);
+    char *io;
+    if ((rc = stage_block(e, lay.bytes(), &io, &outs)) != RB_OK) return rc;
     for (size_t b0 = 0; b0 < n; b0 += sub_max) {
-        const size_t sub = std::min(sub_max, n - b0), r = sub * P;
-        if (read_ids) RB_HIP(hipMemcpyAsync(io, read_ids + b0, 4 * sub, hipMemcpyHostToDevice, st));
-        rb_batch_desc desc = all;
-        // work item j of the sub-batch is read read_ids[b0 + j], or read b0 + j
-        if (!read_ids) {
-            desc.d_offsets = (const uint64_t *)all.d_offsets + b0;
-            desc.d_lens = (const uint32_t *)all.d_lens + b0;
-        }
-        desc.n_items = sub;
-        desc.d_read_ids = read_ids ? io : nullptr;
-        rb_prefix_out d_out;
-        d_out.max_count = out->max_count ? io + o_max : nullptr;
-        d_out.decision = out->decision ? io + o_dec : nullptr;
-        d_out.best_target = out->best_target ? io + o_best : nullptr;
-        d_out.status = out->status ? io + o_status : nullptr;
-        d_out.prefix_len = out->prefix_len ? io + o_len : nullptr;
-        d_out.first_decided = out->first_decided ? io + o_first : nullptr;
-        rc = prefix_device_impl(e, &desc, prefix_lens, n_prefixes, error_rate, significance, mode, &d_out, (void *)st);
-        if (rc != RB_OK) {
-            (void)hipStreamSynchronize(st);
-            return rc;
-        }
-        if (out->max_count) RB_HIP(hipMemcpyAsync((uint16_t *)out->max_count + b0 * P * nf, io + o_max, 2 * r * nf, hipMemcpyDeviceToHost, st));
-        if (out->decision) RB_HIP(hipMemcpyAsync((uint8_t *)out->decision + b0 * P, io + o_dec, r, hipMemcpyDeviceToHost, st));
-        if (out->best_target) RB_HIP(hipMemcpyAsync((int32_t *)out->best_target + b0 * P, io + o_best, 4 * r, hipMemcpyDeviceToHost, st));
-        if (out->status) RB_HIP(hipMemcpyAsync((uint8_t *)out->status + b0 * P, io + o_status, r, hipMemcpyDeviceToHost, st));
-        if (out->prefix_len) RB_HIP(hipMemcpyAsync((uint32_t *)out->prefix_len + b0 * P, io + o_len, 4 * r, hipMemcpyDeviceToHost, st));
-        if (out->first_decided) RB_HIP(hipMemcpyAsync((uint32_t *)out->first_decided + b0, io + o_first, 4 * sub, hipMemcpyDeviceToHost, st));
+        const size_t sub = std::min(sub_max, n - b0);
+        if (read_ids) RB_HIP(hipMemcpyAsync(io + o_ids, read_ids + b0, 4 * sub, hipMemcpyHostToDevice, st));
+        const rb_batch_desc desc = sub_batch_desc(all, b0, sub, read_ids ? io + o_ids : nullptr);
+        if ((rc = rb_prefix_batch_device(e, &desc, prefix_lens, n_prefixes, error_rate, significance, mode, &d_out, (void *)st)) != RB_OK) return rc;
+        if ((rc = copy_back(outs, io, b0, sub, st)) != RB_OK) return rc;
         RB_HIP(hipStreamSynchronize(st));
     }
-    return RB_OK;
+    return drain.done();
 }
 
 // ---- resume: a read's per-bin counters stay in HBM between chunks, a call counts the new k-mers only (see the boundary header).
@@ -3566,8 +3594,8 @@ static int check_resume_fresh(const rb_resume *r)
     return RB_OK;
 }
 
-static int resume_device_impl(rb_resume *r, const rb_batch_desc *desc, const void *d_slots, const void *d_flags, double error_rate,
-                              double significance, int mode, const rb_resume_out *d_out, void *stream)
+int rb_resume_batch_device(rb_resume *r, const rb_batch_desc *desc, const void *d_slots, const void *d_flags, double error_rate,
+                           double significance, int mode, const rb_resume_out *d_out, void *stream)
 {
     if (!desc) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor");
     int rc = check_resume_args(d_out, mode);
@@ -3579,24 +3607,22 @@ static int resume_device_impl(rb_resume *r, const rb_batch_desc *desc, const voi
     if (!d_slots) return rb::fail(RB_ERR_INVALID_ARG, "null slot array");
     if ((rc = check_desc_buffers(desc, false)) != RB_OK) return rc;
     rb_engine *e = r->e;
-    std::lock_guard<std::mutex> lock(e->mu);
+    PassCall c(e, stream);
     if ((rc = refuse_sharded(e, "resume")) != RB_OK) return rc;
     if ((rc = check_resume_fresh(r)) != RB_OK) return rc;
-    const size_t nf = e->filters.size();
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    const uint16_t *thr = nullptr;
-    uint32_t thr_len = 0;
-    if ((rc = ensure_thresholds(e, r->max_total_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
-    // workspace: u64 st_offsets[n] | u32 st_lens[n] | u32 total_lens[n] | u16 part[max_slices][n] | u16 max_count[n][nf] (where the caller
-    // left it out) | u8 pre_status[n] | u8 ctl[n] | u8 stitched[n][stride]
+    const size_t nf = c.nf;
+    if ((rc = c.thresholds(r->max_total_len, error_rate, significance)) != RB_OK) return rc;
+    // workspace: what resume_prep_kernel makes of the items (offsets, lengths and totals, pre-status, ctl bits, the stitched bases at
+    // `stride` per item), the partial maxima u16[max_slices][n], and the maxima where the caller left them out
     uint32_t max_slices = 1;
     for (const rb_resume::PerFilter &p : r->per) max_slices = std::max(max_slices, p.n_slices);
     const uint32_t stride = (r->max_chunk_len + kResumeMaxTail + 15u) & ~15u;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_slen = up16(n * 8), o_tot = o_slen + up16(n * 4), o_part = o_tot + up16(n * 4), o_max = o_part + up16((size_t)max_slices * n * 2);
-    const size_t o_pre = o_max + up16(d_out->max_count ? 0 : n * nf * 2), o_ctl = o_pre + up16(n), o_seq = o_ctl + up16(n);
-    if ((rc = e->d_resume_ws.ensure(o_seq + n * (size_t)stride)) != RB_OK) return rc;
-    char *ws = (char *)e->d_resume_ws.p;
+    rb::StageLayout lay;
+    const size_t o_soff = lay.take(n * 8), o_slen = lay.take(n * 4), o_tot = lay.take(n * 4), o_pre = lay.take(n), o_ctl = lay.take(n);
+    const size_t o_seq = lay.take(n * (size_t)stride), o_part = lay.take((size_t)max_slices * n * 2);
+    const size_t o_max = lay.take(d_out->max_count ? 0 : n * nf * 2);
+    if ((rc = c.start(lay.bytes())) != RB_OK) return rc;
+    char *ws = c.ws();
     uint16_t *part = (uint16_t *)(ws + o_part);
     uint16_t *max_count = d_out->max_count ? (uint16_t *)d_out->max_count : (uint16_t *)(ws + o_max);
     ResumePrep prep{};
@@ -3618,28 +3644,25 @@ static int resume_device_impl(rb_resume *r, const rb_batch_desc *desc, const voi
     prep.k = r->k;
     prep.stitched = (uint8_t *)(ws + o_seq);
     prep.stitch_stride = stride;
-    prep.st_offsets = (uint64_t *)ws;
+    prep.st_offsets = (uint64_t *)(ws + o_soff);
     prep.st_lens = (uint32_t *)(ws + o_slen);
     prep.total_lens = (uint32_t *)(ws + o_tot);
     prep.pre_status = (uint8_t *)(ws + o_pre);
     prep.ctl = (uint8_t *)(ws + o_ctl);
     prep.out_total_len = (uint32_t *)d_out->total_len;
-    std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
-    if ((rc = begin_timed(e, st, &evp)) != RB_OK) return rc;
-    RB_HIP(launch_resume_prep(prep, st));
+    RB_HIP(launch_resume_prep(prep, c.st));
     // what the pass reads: the stitched items, ASCII, one per work item
-    PassInput in{};
-    in.src.seqs = prep.stitched;
-    in.src.offsets = prep.st_offsets;
-    in.src.lens = prep.st_lens;
-    in.src.max_len = r->max_chunk_len + kResumeMaxTail;
-    in.d_lens = prep.st_lens;
-    in.max_len = in.src.max_len;
-    in.n_items = n;
+    c.in.src.seqs = prep.stitched;
+    c.in.src.offsets = prep.st_offsets;
+    c.in.src.lens = prep.st_lens;
+    c.in.src.max_len = r->max_chunk_len + kResumeMaxTail;
+    c.in.d_lens = prep.st_lens;
+    c.in.max_len = c.in.src.max_len;
+    c.in.n_items = n;
     for (size_t fi = 0; fi < nf; ++fi) {
         const rb_resume::PerFilter &p = r->per[fi];
         ResumeLaunch a{};
-        fill_plain_launch(e, fi, in, thr, thr_len, &a);
+        fill_plain_launch(e, fi, c.in, c.thr, c.thr_len, &a);
         if (a.lg != p.lg || a.wpl != p.wpl || a.n_slices != p.n_slices) return rb::fail(RB_ERR_INVALID_ARG, "filter geometry moved under the slots");
         a.planes = (int)kResumePlanes;
         a.slots.state = r->d_state;
@@ -3649,18 +3672,16 @@ static int resume_device_impl(rb_resume *r, const rb_batch_desc *desc, const voi
         a.slots.filter_off = p.off;
         a.slots.pad_cols = p.pad_cols;
         a.part = part;
-        RB_HIP(launch_ibf_resume(a, st));
-        RB_HIP(launch_reduce_slices(part, a.n_slices, (uint32_t)n, max_count, (uint32_t)nf, (uint32_t)fi, st));
+        RB_HIP(launch_ibf_resume(a, c.st));
+        RB_HIP(launch_reduce_slices(part, a.n_slices, (uint32_t)n, max_count, (uint32_t)nf, (uint32_t)fi, c.st));
     }
     if (d_out->decision || d_out->best_target || d_out->status) {
         if ((rc = run_decide(e, max_count, prep.total_lens, prep.pre_status, n, r->max_total_len, error_rate, significance, mode,
-                             (int32_t *)d_out->best_target, (uint8_t *)d_out->decision, (uint8_t *)d_out->status, st)) != RB_OK)
+                             (int32_t *)d_out->best_target, (uint8_t *)d_out->decision, (uint8_t *)d_out->status, c.st)) != RB_OK)
             return rc;
     }
-    RB_HIP(launch_resume_commit(r->d_meta, prep.slot, prep.ctl, prep.stitched, stride, prep.st_lens, prep.total_lens, (uint32_t)n, r->k, st));
-    if ((rc = end_timed(evp, st)) != RB_OK) return rc;
-    if (!stream) RB_HIP(hipStreamSynchronize(st));
-    return RB_OK;
+    RB_HIP(launch_resume_commit(r->d_meta, prep.slot, prep.ctl, prep.stitched, stride, prep.st_lens, prep.total_lens, (uint32_t)n, r->k, c.st));
+    return c.end();
 }
 
 int rb_resume_create(rb_engine *e, uint32_t n_slots, uint32_t max_chunk_len, uint32_t max_total_len, rb_resume **out)
@@ -3705,6 +3726,9 @@ int rb_resume_create(rb_engine *e, uint32_t n_slots, uint32_t max_chunk_len, uin
     // a slot that was never given FIRST continues from an empty read
     if (he == hipSuccess) he = hipMemset(r->d_state, 0, state_bytes);
     if (he == hipSuccess) he = hipMemset(r->d_meta, 0, meta_bytes);
+    // (a fill of device memory may return before it has run, and the engine's stream is not ordered behind the null stream: without
+    // the wait a first call's commit can land before the fill and be wiped by it)
+    if (he == hipSuccess) he = hipStreamSynchronize(nullptr);
     if (he != hipSuccess) {
         (void)hipGetLastError();
         rb_resume_destroy(r.release());
@@ -3726,12 +3750,6 @@ void rb_resume_destroy(rb_resume *r)
 }
 
 uint64_t rb_resume_bytes(const rb_resume *r) { return r ? (uint64_t)r->n_slots * (r->slot_words * 8 + sizeof(ResumeMeta)) : 0; }
-
-int rb_resume_batch_device(rb_resume *r, const rb_batch_desc *desc, const void *d_slots, const void *d_flags, double error_rate,
-                           double significance, int mode, const rb_resume_out *d_out, void *stream)
-{
-    return resume_device_impl(r, desc, d_slots, d_flags, error_rate, significance, mode, d_out, stream);
-}
 
 int rb_resume_batch(rb_resume *r, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *slots,
                     const uint8_t *flags, double error_rate, double significance, int mode, const rb_resume_out *out)
@@ -3755,37 +3773,25 @@ int rb_resume_batch(rb_resume *r, const char *seqs, const uint64_t *offsets, con
     std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
     rb_batch_desc desc;
     if ((rc = upload_reads(e, seqs, offsets, lens, n_reads, nullptr, n, st, &desc)) != RB_OK) return rc;
-    // staging: u32 slots[n] | u32 total_len[n] | i32 best[n] | u16 max_count[n][nf] | u8 flags[n] | u8 decision[n] | u8 status[n]
-    const size_t o_tot = 4 * n, o_best = o_tot + 4 * n, o_max = o_best + 4 * n, o_flags = o_max + 2 * n * nf, o_dec = o_flags + n, o_status = o_dec + n;
-    {
-        std::lock_guard<std::mutex> lock(e->mu);
-        rc = e->d_resume_io.ensure(o_status + n);
-    }
-    if (rc != RB_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    char *io = (char *)e->d_resume_io.p;
-    RB_HIP(hipMemcpyAsync(io, slots, 4 * n, hipMemcpyHostToDevice, st));
-    if (flags) RB_HIP(hipMemcpyAsync(io + o_flags, flags, n, hipMemcpyHostToDevice, st));
+    DrainUnlessDone drain{st};
+    rb::StageLayout lay;
+    rb::StagedOuts outs;
     rb_resume_out d_out;
-    d_out.max_count = out->max_count ? io + o_max : nullptr;
-    d_out.decision = out->decision ? io + o_dec : nullptr;
-    d_out.best_target = out->best_target ? io + o_best : nullptr;
-    d_out.status = out->status ? io + o_status : nullptr;
-    d_out.total_len = out->total_len ? io + o_tot : nullptr;
-    rc = resume_device_impl(r, &desc, io, flags ? io + o_flags : nullptr, error_rate, significance, mode, &d_out, (void *)st);
-    if (rc != RB_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    if (out->max_count) RB_HIP(hipMemcpyAsync(out->max_count, io + o_max, 2 * n * nf, hipMemcpyDeviceToHost, st));
-    if (out->decision) RB_HIP(hipMemcpyAsync(out->decision, io + o_dec, n, hipMemcpyDeviceToHost, st));
-    if (out->best_target) RB_HIP(hipMemcpyAsync(out->best_target, io + o_best, 4 * n, hipMemcpyDeviceToHost, st));
-    if (out->status) RB_HIP(hipMemcpyAsync(out->status, io + o_status, n, hipMemcpyDeviceToHost, st));
-    if (out->total_len) RB_HIP(hipMemcpyAsync(out->total_len, io + o_tot, 4 * n, hipMemcpyDeviceToHost, st));
+    const size_t o_slots = lay.take(4 * n), o_flags = lay.take(flags ? n : 0);
+    outs.add(lay, out->max_count, &d_out.max_count, 2 * nf, n);
+    outs.add(lay, out->decision, &d_out.decision, 1, n);
+    outs.add(lay, out->best_target, &d_out.best_target, 4, n);
+    outs.add(lay, out->status, &d_out.status, 1, n);
+    outs.add(lay, out->total_len, &d_out.total_len, 4, n);
+    char *io;
+    if ((rc = stage_block(e, lay.bytes(), &io, &outs)) != RB_OK) return rc;
+    RB_HIP(hipMemcpyAsync(io + o_slots, slots, 4 * n, hipMemcpyHostToDevice, st));
+    if (flags) RB_HIP(hipMemcpyAsync(io + o_flags, flags, n, hipMemcpyHostToDevice, st));
+    rc = rb_resume_batch_device(r, &desc, io + o_slots, flags ? io + o_flags : nullptr, error_rate, significance, mode, &d_out, (void *)st);
+    if (rc != RB_OK) return rc;
+    if ((rc = copy_back(outs, io, 0, n, st)) != RB_OK) return rc;
     RB_HIP(hipStreamSynchronize(st));
-    return RB_OK;
+    return drain.done();
 }
 
 int rb_resume_counts(rb_resume *r, uint32_t slot, size_t filter, uint16_t *out_counts, uint32_t *out_total_len)
@@ -3800,14 +3806,11 @@ int rb_resume_counts(rb_resume *r, uint32_t slot, size_t filter, uint16_t *out_c
     std::lock_guard<std::mutex> host_lock(e->host_mu);
     const uint32_t n_bins = (uint32_t)e->filters[filter]->geo.n_bins;
     if (out_counts) {
-        {
-            std::lock_guard<std::mutex> lock(e->mu);
-            rc = e->d_resume_io.ensure((size_t)n_bins * 4);
-        }
-        if (rc != RB_OK) return rc;
+        char *io;
+        if ((rc = stage_block(e, (size_t)n_bins * 4, &io)) != RB_OK) return rc;
         const rb_resume::PerFilter &p = r->per[filter];
-        RB_HIP(launch_resume_counts(r->d_state + (uint64_t)slot * r->slot_words + p.off, p.pad_cols, n_bins, (uint16_t *)e->d_resume_io.p, st));
-        RB_HIP(hipMemcpyAsync(out_counts, e->d_resume_io.p, (size_t)n_bins * 4, hipMemcpyDeviceToHost, st));
+        RB_HIP(launch_resume_counts(r->d_state + (uint64_t)slot * r->slot_words + p.off, p.pad_cols, n_bins, (uint16_t *)io, st));
+        RB_HIP(hipMemcpyAsync(out_counts, io, (size_t)n_bins * 4, hipMemcpyDeviceToHost, st));
     }
     if (out_total_len) RB_HIP(hipMemcpyAsync(out_total_len, &r->d_meta[slot].total, 4, hipMemcpyDeviceToHost, st));
     RB_HIP(hipStreamSynchronize(st));
@@ -3817,8 +3820,8 @@ int rb_resume_counts(rb_resume *r, uint32_t slot, size_t filter, uint16_t *out_c
 // ---- hits: every (bin, strand) at or above the threshold, with its count (no counterpart in the reference; see the boundary header).
 // Per filter one launch of ibf_hits_kernel over the filter's OWN table, counted in full, plus finish_hits_kernel,
 // in sequence on the call's stream -- so one workspace, sized for the filter with the most column slices, serves every filter.
-static int hits_device_impl(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, uint16_t min_count,
-                            uint32_t max_hits, const rb_hits_out *d_out, void *stream)
+int rb_hits_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, uint16_t min_count, uint32_t max_hits,
+                         const rb_hits_out *d_out, void *stream)
 {
     if (!desc || !d_out) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor or output struct");
     if (!d_out->hits && !d_out->n_hits && !d_out->bin_reads) return rb::fail(RB_ERR_INVALID_ARG, "rb_hits_out with no output");
@@ -3828,34 +3831,27 @@ static int hits_device_impl(rb_engine *e, const rb_batch_desc *desc, double erro
     const size_t n_items = desc->n_items;
     if (n_items == 0) return RB_OK;
     if ((rc = check_desc_buffers(desc, false)) != RB_OK) return rc;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if ((rc = refuse_sharded(e, "hits")) != RB_OK) return rc;
-    const size_t nf = e->filters.size();
-    if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    PassInput in;
-    if ((rc = prepare_pass_input(e, desc, st, &in)) != RB_OK) return rc;
-    // t for min_count == 0: the table the decision kernel reads, entry [len][filter][0] -- one definition of the threshold
-    const uint16_t *thr = nullptr;
-    uint32_t thr_len = 0;
-    if ((rc = ensure_thresholds(e, in.max_len, error_rate, significance, st, &thr, &thr_len)) != RB_OK) return rc;
+    PassCall c(e, stream);
+    if ((rc = c.begin(desc, "hits")) != RB_OK) return rc;
+    if ((rc = c.thresholds(c.in.max_len, error_rate, significance)) != RB_OK) return rc;  // t for min_count == 0
+    const size_t nf = c.nf;
     const uint32_t cap = d_out->hits ? max_hits : 0u;  // without a record buffer nothing is kept: the totals stay exact
     std::vector<HitsLaunch> launches(nf);
     const uint32_t min_len = engine_min_len(e);
     uint32_t max_slices = 0;
     for (size_t fi = 0; fi < nf; ++fi) {
         HitsLaunch &a = launches[fi];
-        fill_plain_launch(e, fi, in, thr, thr_len, &a);
+        fill_plain_launch(e, fi, c.in, c.thr, c.thr_len, &a);
         a.min_count = min_count;
         a.max_hits = cap;
         a.min_len = min_len;
-        a.pre_status = in.d_pre_status;
+        a.pre_status = c.in.d_pre_status;
         max_slices = std::max(max_slices, a.n_slices);
     }
-    const size_t seg_bytes = n_items * (size_t)max_slices * 2 * (size_t)cap * 8;
-    if ((rc = e->d_hits_ws.ensure(seg_bytes + n_items * (size_t)max_slices * 2 * 4)) != RB_OK) return rc;
-    std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
-    if ((rc = begin_timed(e, st, &evp)) != RB_OK) return rc;
+    // workspace: per (item, slice, strand) a segment of cap records, and its counter
+    rb::StageLayout lay;
+    const size_t o_seg = lay.take(n_items * (size_t)max_slices * 2 * (size_t)cap * 8), o_count = lay.take(n_items * (size_t)max_slices * 2 * 4);
+    if ((rc = c.start(lay.bytes())) != RB_OK) return rc;
     HitsOut out;
     out.hits = (rb_u32x2 *)d_out->hits;
     out.n_hits = (uint32_t *)d_out->n_hits;
@@ -3863,22 +3859,14 @@ static int hits_device_impl(rb_engine *e, const rb_batch_desc *desc, double erro
     uint64_t *bin_reads = (uint64_t *)d_out->bin_reads;
     for (size_t fi = 0; fi < nf; ++fi) {
         HitsLaunch &a = launches[fi];
-        a.seg = e->d_hits_ws.p;
-        a.seg_count = (uint32_t *)((char *)e->d_hits_ws.p + seg_bytes);
+        a.seg = c.ws() + o_seg;
+        a.seg_count = (uint32_t *)(c.ws() + o_count);
         a.bin_reads = bin_reads;
-        RB_HIP(launch_ibf_hits(a, st));
-        RB_HIP(launch_finish_hits(a, in.d_lens, out, st));
+        RB_HIP(launch_ibf_hits(a, c.st));
+        RB_HIP(launch_finish_hits(a, c.in.d_lens, out, c.st));
         if (bin_reads) bin_reads += e->filters[fi]->geo.n_bins;
     }
-    if ((rc = end_timed(evp, st)) != RB_OK) return rc;
-    if (!stream) RB_HIP(hipStreamSynchronize(st));
-    return RB_OK;
-}
-
-int rb_hits_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, uint16_t min_count, uint32_t max_hits,
-                         const rb_hits_out *d_out, void *stream)
-{
-    return hits_device_impl(e, desc, error_rate, significance, min_count, max_hits, d_out, stream);
+    return c.end();
 }
 
 int rb_hits_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *read_ids,
@@ -3887,77 +3875,49 @@ int rb_hits_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const
     if (!out) return rb::fail(RB_ERR_INVALID_ARG, "null output struct");
     if (!out->hits && !out->n_hits && !out->bin_reads) return rb::fail(RB_ERR_INVALID_ARG, "rb_hits_out with no output");
     if (out->hits && max_hits == 0) return rb::fail(RB_ERR_INVALID_ARG, "a hits buffer with max_hits == 0");
-    int rc = check_device(e ? e->device : 0);
+    int rc = check_host_engine(e);
     if (rc != RB_OK) return rc;
-    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
     const size_t n = read_ids ? n_items : n_reads;  // without a selection the work items are the reads
     if (n == 0) return RB_OK;
-    if (!seqs || !offsets || !lens || n_reads == 0) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
-    if (n >= (1ULL << 31) || n_reads >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    if ((rc = check_host_reads(seqs, offsets, lens, n_reads, n, 0)) != RB_OK) return rc;
     hipStream_t st = e->stream;
     std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
     rb_batch_desc all;
     if ((rc = upload_reads(e, seqs, offsets, lens, n_reads, read_ids, n, st, &all)) != RB_OK) return rc;
-    size_t nf = 0, total_bins = 0, max_slices = 1;
-    {
-        std::lock_guard<std::mutex> lock(e->mu);
-        nf = e->filters.size();
-        for (const rb_dibf *f : e->filters) {  // the column slices hits_device_impl will cut: its workspace is part of the budget below
-            int lg, wpl, planes, nt;
-            uint32_t n_slices;
-            plain_geometry(e, f, all.max_len, &lg, &wpl, &n_slices, &planes, &nt);
-            total_bins += f->geo.n_bins;
-            max_slices = std::max<size_t>(max_slices, n_slices);
-        }
-    }
-    if (nf == 0) {
-        (void)hipStreamSynchronize(st);
-        return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
-    }
+    DrainUnlessDone drain{st};
+    size_t nf, total_bins, max_slices;
+    host_pass_geometry(e, all.max_len, &nf, &total_bins, &max_slices);
+    if (nf == 0) return rb::fail(RB_ERR_NULL_FILTER, "engine without filters");
     // sub-batches: workspace (S x 2 x cap records and S x 2 counters per item) plus staged outputs (nf x cap records, nf counters and a
     // status byte per item) stay at or below kHitsBudget; a single item that needs more goes alone
     constexpr size_t kHitsBudget = 256ull << 20;
     const size_t cap = out->hits ? max_hits : 0;
     const size_t per_item = max_slices * 2 * (cap * 8 + 4) + nf * (cap * 8 + 4) + 1 + 4;
     const size_t sub_max = std::max<size_t>(1, std::min<size_t>(n, kHitsBudget / per_item));
-    // staging: u64 bin_reads[total_bins] | rb_hit hits[sub x nf x cap] | u32 n_hits[sub x nf] | u32 ids[sub] | u8 status[sub]
-    const size_t o_hits = 8 * total_bins, o_n = o_hits + sub_max * nf * cap * 8, o_ids = o_n + sub_max * nf * 4, o_status = o_ids + sub_max * 4;
-    {
-        std::lock_guard<std::mutex> lock(e->mu);
-        rc = e->d_hits_io.ensure(o_status + sub_max);
-    }
-    if (rc != RB_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    char *io = (char *)e->d_hits_io.p;
-    if (out->bin_reads) RB_HIP(hipMemsetAsync(io, 0, 8 * total_bins, st));
+    // staged: the profile of the whole call, and per sub-batch the ids, the records, their counters (always: the copy below keeps to the
+    // records that were written) and the status
+    rb::StageLayout lay;
+    rb::StagedOuts outs;
+    rb_hits_out d_out;
+    const size_t o_bins = lay.take(out->bin_reads ? 8 * total_bins : 0), o_ids = lay.take(read_ids ? 4 * sub_max : 0);
+    const size_t o_hits = lay.take(sub_max * nf * cap * 8), o_n = lay.take(sub_max * nf * 4);
+    outs.add(lay, out->status, &d_out.status, 1, sub_max);
+    char *io;
+    if ((rc = stage_block(e, lay.bytes(), &io, &outs)) != RB_OK) return rc;
+    d_out.hits = cap ? io + o_hits : nullptr;
+    d_out.n_hits = io + o_n;
+    d_out.bin_reads = out->bin_reads ? io + o_bins : nullptr;
+    if (out->bin_reads) RB_HIP(hipMemsetAsync(io + o_bins, 0, 8 * total_bins, st));
     std::vector<uint32_t> h_n(sub_max * nf);
     std::vector<rb_hit> h_hits(cap ? sub_max * nf * cap : 0);
     for (size_t b0 = 0; b0 < n; b0 += sub_max) {
         const size_t sub = std::min(sub_max, n - b0);
         if (read_ids) RB_HIP(hipMemcpyAsync(io + o_ids, read_ids + b0, 4 * sub, hipMemcpyHostToDevice, st));
-        rb_batch_desc desc = all;
-        // work item j of the sub-batch is read read_ids[b0 + j], or read b0 + j
-        if (!read_ids) {
-            desc.d_offsets = (const uint64_t *)all.d_offsets + b0;
-            desc.d_lens = (const uint32_t *)all.d_lens + b0;
-        }
-        desc.n_items = sub;
-        desc.d_read_ids = read_ids ? io + o_ids : nullptr;
-        rb_hits_out d_out;
-        d_out.hits = cap ? io + o_hits : nullptr;
-        d_out.n_hits = io + o_n;  // (always: the copy below keeps to the records that were written)
-        d_out.status = out->status ? io + o_status : nullptr;
-        d_out.bin_reads = out->bin_reads ? io : nullptr;
-        rc = hits_device_impl(e, &desc, error_rate, significance, min_count, max_hits, &d_out, (void *)st);
-        if (rc != RB_OK) {
-            (void)hipStreamSynchronize(st);
-            return rc;
-        }
+        const rb_batch_desc desc = sub_batch_desc(all, b0, sub, read_ids ? io + o_ids : nullptr);
+        if ((rc = rb_hits_batch_device(e, &desc, error_rate, significance, min_count, max_hits, &d_out, (void *)st)) != RB_OK) return rc;
         RB_HIP(hipMemcpyAsync(h_n.data(), io + o_n, 4 * sub * nf, hipMemcpyDeviceToHost, st));
         if (cap) RB_HIP(hipMemcpyAsync(h_hits.data(), io + o_hits, 8 * sub * nf * cap, hipMemcpyDeviceToHost, st));
-        if (out->status) RB_HIP(hipMemcpyAsync((uint8_t *)out->status + b0, io + o_status, sub, hipMemcpyDeviceToHost, st));
+        if ((rc = copy_back(outs, io, b0, sub, st)) != RB_OK) return rc;
         RB_HIP(hipStreamSynchronize(st));
         if (out->n_hits) std::memcpy((uint32_t *)out->n_hits + b0 * nf, h_n.data(), 4 * sub * nf);
         if (cap)  // only what was written: the caller's slots beyond a list stay as they are
@@ -3968,60 +3928,49 @@ int rb_hits_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const
     }
     if (out->bin_reads) {  // ADD: the caller's profile accumulates over calls
         std::vector<uint64_t> h_bins(total_bins);
-        RB_HIP(hipMemcpy(h_bins.data(), io, 8 * total_bins, hipMemcpyDeviceToHost));
+        RB_HIP(hipMemcpy(h_bins.data(), io + o_bins, 8 * total_bins, hipMemcpyDeviceToHost));
         uint64_t *dst = (uint64_t *)out->bin_reads;
         for (size_t b = 0; b < total_bins; ++b) dst[b] += h_bins[b];
     }
-    return RB_OK;
+    return drain.done();
 }
 
 // ---- spans: where along a read a bin matched (no counterpart in the reference; see the boundary header).  One launch of ibf_spans_kernel
 // over the named filter's OWN table, one wave per query: no threshold, no workspace, and none of the engine's pruning / early-decision /
 // merge / phased settings reaches it.  Items and bins are vetted by the kernel: queries may be another kernel's output.
-static int spans_device_impl(rb_engine *e, const rb_batch_desc *desc, size_t filter, const void *d_queries, size_t n_queries, uint32_t mask_words,
-                             const rb_spans_out *d_out, void *stream)
+int rb_spans_batch_device(rb_engine *e, const rb_batch_desc *desc, size_t filter, const void *d_queries, size_t n_queries, uint32_t mask_words,
+                          const rb_spans_out *d_out, void *stream)
 {
     if (!desc || !d_out) return rb::fail(RB_ERR_INVALID_ARG, "null descriptor or output struct");
     if (!d_out->spans && !d_out->mask && !d_out->n_kmers && !d_out->status) return rb::fail(RB_ERR_INVALID_ARG, "rb_spans_out with no output");
     int rc = check_pass_call(e, desc, n_queries);
     if (rc != RB_OK) return rc;
-    std::lock_guard<std::mutex> lock(e->mu);
-    if (filter >= e->filters.size()) return rb::fail(RB_ERR_INVALID_ARG, "filter index beyond the engine's filters");
+    PassCall c(e, stream);
+    if (filter >= c.nf) return rb::fail(RB_ERR_INVALID_ARG, "filter index beyond the engine's filters");
     if (n_queries == 0) return RB_OK;
     if (!d_queries) return rb::fail(RB_ERR_INVALID_ARG, "null query buffer");
     if ((rc = check_desc_buffers(desc, true)) != RB_OK) return rc;  // (queries against no items are answered: each is RB_ERR_INVALID_ARG)
     if ((rc = refuse_sharded(e, "spans")) != RB_OK) return rc;
-    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    PassInput in;
-    if ((rc = prepare_pass_input(e, desc, st, &in)) != RB_OK) return rc;
+    if ((rc = prepare_pass_input(e, desc, c.st, &c.in)) != RB_OK) return rc;
     const rb_dibf *f = e->filters[filter];
     SpansLaunch a{};
     a.f = f->dev;
     a.f.comp_n = e->revcomp_of_n;
-    a.src = in.src;
-    a.n_items = (uint32_t)in.n_items;
+    a.src = c.in.src;
+    a.n_items = (uint32_t)c.in.n_items;
     a.queries = (const rb_u32x2 *)d_queries;
     a.n_queries = (uint32_t)n_queries;
     a.mask_words = d_out->mask ? mask_words : 0u;
     a.min_len = engine_min_len(e);
-    a.pre_status = in.d_pre_status;
+    a.pre_status = c.in.d_pre_status;
     a.nt = table_beyond_nt_threshold(e, f);
     a.out.spans = (uint32_t *)d_out->spans;
     a.out.mask = (uint64_t *)d_out->mask;
     a.out.n_kmers = (uint32_t *)d_out->n_kmers;
     a.out.status = (uint8_t *)d_out->status;
-    std::pair<hipEvent_t, hipEvent_t> *evp = nullptr;
-    if ((rc = begin_timed(e, st, &evp)) != RB_OK) return rc;
-    RB_HIP(launch_ibf_spans(a, st));
-    if ((rc = end_timed(evp, st)) != RB_OK) return rc;
-    if (!stream) RB_HIP(hipStreamSynchronize(st));
-    return RB_OK;
-}
-
-int rb_spans_batch_device(rb_engine *e, const rb_batch_desc *desc, size_t filter, const void *d_queries, size_t n_queries, uint32_t mask_words,
-                          const rb_spans_out *d_out, void *stream)
-{
-    return spans_device_impl(e, desc, filter, d_queries, n_queries, mask_words, d_out, stream);
+    if ((rc = c.start()) != RB_OK) return rc;
+    RB_HIP(launch_ibf_spans(a, c.st));
+    return c.end();
 }
 
 int rb_spans_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, const uint32_t *lens, size_t n_reads, const uint32_t *read_ids,
@@ -4029,9 +3978,8 @@ int rb_spans_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, cons
 {
     if (!out) return rb::fail(RB_ERR_INVALID_ARG, "null output struct");
     if (!out->spans && !out->mask && !out->n_kmers && !out->status) return rb::fail(RB_ERR_INVALID_ARG, "rb_spans_out with no output");
-    int rc = check_device(e ? e->device : 0);
+    int rc = check_host_engine(e);
     if (rc != RB_OK) return rc;
-    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
     {
         std::lock_guard<std::mutex> lock(e->mu);
         if (filter >= e->filters.size()) return rb::fail(RB_ERR_INVALID_ARG, "filter index beyond the engine's filters");
@@ -4039,52 +3987,38 @@ int rb_spans_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, cons
     if (n_queries == 0) return RB_OK;
     if (!queries) return rb::fail(RB_ERR_INVALID_ARG, "null query buffer");
     const size_t n = read_ids ? n_items : n_reads;  // without a selection the work items are the reads
-    if (n && (!seqs || !offsets || !lens || n_reads == 0)) return rb::fail(RB_ERR_INVALID_ARG, "null input buffer");
-    if (n >= (1ULL << 31) || n_reads >= (1ULL << 31) || n_queries >= (1ULL << 31)) return rb::fail(RB_ERR_INVALID_ARG, "batch too large");
+    if ((rc = check_host_reads(seqs, offsets, lens, n_reads, n, n_queries)) != RB_OK) return rc;
     hipStream_t st = e->stream;
     std::lock_guard<std::mutex> host_lock(e->host_mu);  // the staging buffers below are per engine
     rb_batch_desc desc;
     if ((rc = upload_reads(e, seqs, offsets, lens, n_reads, read_ids, n, st, &desc)) != RB_OK) return rc;
+    DrainUnlessDone drain{st};
     // sub-batches of queries: what a query stages (its masks, its two records, n_kmers, status and the query itself) stays at or below
     // kSpansBudget per call, one query at a time where a single one needs more; the reads and their ids are uploaded once
     constexpr size_t kSpansBudget = 256ull << 20;
     const size_t mw = out->mask ? mask_words : 0;
     const size_t per_query = 16 * mw + sizeof(rb_span_query) + 2 * sizeof(rb_span) + 4 + 1;
     const size_t sub_max = std::max<size_t>(1, std::min<size_t>(n_queries, kSpansBudget / per_query));
-    // staging: u64 mask[sub x 2 x mw] | rb_span_query q[sub] | rb_span spans[sub x 2] | u32 n_kmers[sub] | u32 ids[n] | u8 status[sub]
-    const size_t o_q = 16 * mw * sub_max, o_spans = o_q + 8 * sub_max, o_nk = o_spans + 48 * sub_max, o_ids = o_nk + 4 * sub_max,
-                 o_status = o_ids + 4 * (read_ids ? n : 0);
-    {
-        std::lock_guard<std::mutex> lock(e->mu);
-        rc = e->d_spans_io.ensure(o_status + sub_max);
-    }
-    if (rc != RB_OK) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    char *io = (char *)e->d_spans_io.p;
+    rb::StageLayout lay;
+    rb::StagedOuts outs;
+    rb_spans_out d_out;
+    const size_t o_ids = lay.take(read_ids ? 4 * n : 0), o_q = lay.take(sizeof(rb_span_query) * sub_max);
+    outs.add(lay, out->spans, &d_out.spans, 2 * sizeof(rb_span), sub_max);
+    outs.add(lay, out->mask, &d_out.mask, 16 * mw, sub_max);
+    outs.add(lay, out->n_kmers, &d_out.n_kmers, 4, sub_max);
+    outs.add(lay, out->status, &d_out.status, 1, sub_max);
+    char *io;
+    if ((rc = stage_block(e, lay.bytes(), &io, &outs)) != RB_OK) return rc;
     if (read_ids && n) RB_HIP(hipMemcpyAsync(io + o_ids, read_ids, 4 * n, hipMemcpyHostToDevice, st));
     desc.d_read_ids = read_ids ? io + o_ids : nullptr;
     for (size_t b0 = 0; b0 < n_queries; b0 += sub_max) {
         const size_t sub = std::min(sub_max, n_queries - b0);
         RB_HIP(hipMemcpyAsync(io + o_q, queries + b0, sizeof(rb_span_query) * sub, hipMemcpyHostToDevice, st));
-        rb_spans_out d_out;
-        d_out.spans = out->spans ? io + o_spans : nullptr;
-        d_out.mask = out->mask ? io : nullptr;
-        d_out.n_kmers = out->n_kmers ? io + o_nk : nullptr;
-        d_out.status = out->status ? io + o_status : nullptr;
-        rc = spans_device_impl(e, &desc, filter, io + o_q, sub, mask_words, &d_out, (void *)st);
-        if (rc != RB_OK) {
-            (void)hipStreamSynchronize(st);
-            return rc;
-        }
-        if (out->spans) RB_HIP(hipMemcpyAsync((rb_span *)out->spans + 2 * b0, io + o_spans, 48 * sub, hipMemcpyDeviceToHost, st));
-        if (out->mask && mw) RB_HIP(hipMemcpyAsync((uint64_t *)out->mask + 2 * mw * b0, io, 16 * mw * sub, hipMemcpyDeviceToHost, st));
-        if (out->n_kmers) RB_HIP(hipMemcpyAsync((uint32_t *)out->n_kmers + b0, io + o_nk, 4 * sub, hipMemcpyDeviceToHost, st));
-        if (out->status) RB_HIP(hipMemcpyAsync((uint8_t *)out->status + b0, io + o_status, sub, hipMemcpyDeviceToHost, st));
+        if ((rc = rb_spans_batch_device(e, &desc, filter, io + o_q, sub, mask_words, &d_out, (void *)st)) != RB_OK) return rc;
+        if ((rc = copy_back(outs, io, b0, sub, st)) != RB_OK) return rc;
         RB_HIP(hipStreamSynchronize(st));
     }
-    return RB_OK;
+    return drain.done();
 }
 
 // pointer-array form: read i = seq_ptrs[i][0 .. lens[i]) -- what a basecaller hands over (one buffer per read)

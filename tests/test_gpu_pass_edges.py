@@ -209,7 +209,7 @@ def test_prefixes_at_the_counter_edges(name):
                 reads, cps, exp = PE.prefix_expectation(name, case, mode)
                 for nt in (False, True):
                     rig.nontemporal(nt)
-                    p = rig.plan(min(max_len_of(reads), cps[-1]), nt)  # (no row is longer than the last checkpoint: rb_engine.hip, prefix_device_impl)
+                    p = rig.plan(min(max_len_of(reads), cps[-1]), nt)  # (no row is longer than the last checkpoint: rb_engine.hip, rb_prefix_batch_device)
                     PR.assert_same(run_prefixes(rig, reads, cps, mode), exp, "%s %s mode %d nt %d" % (name, case, mode, nt))
                     reached(build_label("prefix", p), case)
                 rig.nontemporal(False)

@@ -4,6 +4,7 @@ Expected rows come from tests/prefix_rules.py alone: the oracle's counts and dec
 checkpoint.  Filters and reads are those of tests/test_gpu_locate.make_case (made by the oracle on the host and uploaded); what the
 cases depend on -- a decision that is not monotone in the prefix length, reads shorter than the last checkpoint and shorter than k --
 is asserted on the oracle without a GPU in tests/test_prefix_cpu.py.  No assertion on elapsed time."""
+import ctypes as C
 import functools
 
 import numpy as np
@@ -270,4 +271,81 @@ def test_the_pass_changes_nothing_else_and_settings_do_not_reach_it():
     assert ei.value.status == capi.RB_ERR_INVALID_ARG and "column-sharded" in str(ei.value)
     eng.set_column_shard(0, 1)
     PR.assert_same(run_host(eng, reads, MIXED_CHECKPOINTS), exp, "after the shard is lifted")
+    eng.destroy()
+
+
+WIDE = (64 * 8192, 61, 3, 13)  # n_bins, n_blocks, n_hash, k: 8 192 word columns = 64 column slices of a whole wave, two words per lane
+WIDE_CHECKPOINTS = tuple(range(1, 65))  # the first twelve below k; the last beyond every read
+
+
+def sub_batch_items(n_bins, P):
+    """work items per sub-batch of rb_prefix_batch, from the budget its comment states: workspace (S partial maxima, a length and a
+    pre-status per row, S = the most column slices of any filter) plus staged outputs (nf maxima, a length, a target, a decision and a
+    status per row; an id and a first_decided per item, 64 bytes of slack) at or below 256 MiB, one item at a time where one needs more"""
+    W = max((b + 63) // 64 for b in n_bins)
+    S = (W + 127) // 128 if W > 64 else 1
+    per_item = P * (S * 2 + 4 + 1 + len(n_bins) * 2 + 4 + 4 + 1 + 1) + 4 + 4 + 64
+    return max(1, (256 << 20) // per_item)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case():
+    """a filter of 64 column slices and few blocks, eighteen reads of up to 30 bases (the oracle counts 524 288 bins per k-mer) and
+    three shorter than k, and the oracle's rows for them"""
+    n_bins, n_blocks, h, k = WIDE
+    rng = np.random.default_rng(64)
+    f = po.OracleIBF(n_bins, h, k, n_bins * n_blocks)
+    # fragments of eighteen k-mers in bins of the first and the last slice and of slices in between: half of a bin's rows set
+    bins = [0, 8191, 8192, n_bins - 1] + sorted(rng.choice(n_bins, size=14, replace=False).tolist())
+    frags = [H.random_dna(rng, 30) for _ in bins]
+    for b, s in zip(bins, frags):
+        f.insert(po.encode(s), b)
+    reads = []
+    for i in range(18):
+        L = int(rng.integers(14, 31))
+        reads.append(frags[i][:L] if i % 3 == 0 else revcomp_of(frags[i][30 - L:]) if i % 3 == 1 else H.random_dna(rng, L))
+    reads += ["ACGT", "A" * (k - 1), ""]
+    exp = PR.expected_batch(reads, WIDE_CHECKPOINTS, [f], [], capi.RB_MODE_CHECK_UNBLOCK, r=R, conf=CONF)
+    return f, tuple(reads), exp
+
+
+def revcomp_of(s):
+    return s[::-1].translate(str.maketrans("ACGT", "TGCA"))
+
+
+def run_host_over_sentinels(eng, reads, checkpoints, ids=None):
+    """Engine.prefixes with every output buffer filled with 0xA5 before the call"""
+    buf, offs, lens = H.pack_reads(list(reads))
+    cps = np.ascontiguousarray(checkpoints, dtype=np.uint32)
+    n, P, nf = len(lens) if ids is None else len(ids), len(cps), eng.nd + eng.nt
+    res = {"max_count": np.full((n, P, nf), 0xA5A5, np.uint16), "decision": np.full((n, P), 0xA5, np.uint8),
+           "best_target": np.full((n, P), 0x25A5A5A5, np.int32), "status": np.full((n, P), 0xA5, np.uint8),
+           "prefix_len": np.full((n, P), 0xA5A5A5A5, np.uint32), "first_decided": np.full(n, 0xA5A5A5A5, np.uint32)}
+    out = capi.PrefixOut(*[capi._ptr(res[key]) for key in ("max_count", "decision", "best_target", "status", "prefix_len", "first_decided")])
+    capi._check(capi.lib().rb_prefix_batch(eng.h, capi._ptr(buf), capi._ptr(offs), capi._ptr(lens), len(lens), None if ids is None else capi._ptr(ids),
+                                           n, capi._ptr(cps), P, R, CONF, capi.RB_MODE_CHECK_UNBLOCK, C.byref(out)), "rb_prefix_batch")
+    return res
+
+
+@pytest.mark.gpu
+def test_host_call_in_several_sub_batches():
+    """64 column slices and 64 checkpoints make an item cost 9 352 bytes of the host form's 256 MiB: 60 011 items go in three sub-batches,
+    the last one short.  Every row of item j equals the row of its read from one call over the distinct reads alone (a single
+    sub-batch, itself checked against the oracle) -- selected through read ids, then with the reads themselves replicated"""
+    f, reads, exp = wide_case()
+    P = len(WIDE_CHECKPOINTS)
+    per = sub_batch_items([f.n_bins], P)
+    assert P == 64 and P * (2 * 64 + 2 + 15) + 72 == 9352 and per == (256 << 20) // 9352 == 28703
+    assert 0 < exp["decision"].sum() < exp["ok"].sum() and (exp["status"] == capi.RB_ERR_SHORT_READ).any() and len(reads) < per
+    eng = capi.Engine(0, [upload(f)], [])
+    small = run_host(eng, reads, WIDE_CHECKPOINTS)
+    PR.assert_same(small, exp, "the distinct reads, one sub-batch")
+    n = 60011
+    ids = np.random.default_rng(9).integers(0, len(reads), size=n).astype(np.uint32)
+    assert n > 2 * per and n % per != 0 and len(set(ids[:per].tolist())) == len(reads)
+    sel = ids.astype(np.int64)
+    want = {key: v[sel] for key, v in small.items()}
+    want["ok"] = want["status"] == capi.RB_OK
+    PR.assert_same(run_host_over_sentinels(eng, reads, WIDE_CHECKPOINTS, ids), want, "sub-batches, read ids")
+    PR.assert_same(run_host_over_sentinels(eng, [reads[i] for i in sel], WIDE_CHECKPOINTS), want, "sub-batches, replicated reads")
     eng.destroy()
