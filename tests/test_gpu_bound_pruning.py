@@ -34,8 +34,9 @@ def rc(s):
 class Plant:
     """reads + the sequences inserted for them (sequence -> bin) + the maximum each read was built for"""
 
-    def __init__(self, n_bins, seed):
+    def __init__(self, n_bins, seed, k=K):
         self.n_bins = n_bins
+        self.k = k
         self.rng = np.random.default_rng(seed)
         self.used = set()
         self.items, self.bins = [], []
@@ -86,23 +87,23 @@ class Plant:
 
     def split(self, n, a_kmers, where, reverse, lo=0):
         """first a_kmers k-mers of R into A, the rest into B; the engine sees R (forward best) or rc(R) (reverse best)"""
-        R = H.random_dna(self.rng, n + K - 1)
+        R = H.random_dna(self.rng, n + self.k - 1)
         A, B = self.pair(where, lo)
-        self.put(R[:a_kmers + K - 1], A)
+        self.put(R[:a_kmers + self.k - 1], A)
         self.put(R[a_kmers:], B)
         self.read(rc(R) if reverse else R, max(a_kmers, n - a_kmers))
 
     def strands(self, n, x, y, where):
         """x k-mers of the forward strand's start into A, y k-mers of the reverse strand's END into B: max(x, y)"""
-        R = H.random_dna(self.rng, n + K - 1)
+        R = H.random_dna(self.rng, n + self.k - 1)
         A, B = self.pair(where)
-        self.put(R[:x + K - 1], A)
+        self.put(R[:x + self.k - 1], A)
         Q = rc(R)
-        self.put(Q[len(Q) - (y + K - 1):], B)
+        self.put(Q[len(Q) - (y + self.k - 1):], B)
         self.read(R, max(x, y))
 
     def whole(self, n, reverse):
-        R = H.random_dna(self.rng, n + K - 1)
+        R = H.random_dna(self.rng, n + self.k - 1)
         self.put(R, self.fresh())
         self.read(rc(R) if reverse else R, n)
 
@@ -112,8 +113,8 @@ class Plant:
         d.insert("".join(self.items), starts, ends, np.array(self.bins, dtype=np.uint64))
 
 
-def tight_plant(n_bins, seed, kmers=KMERS, lo=0):
-    p = Plant(n_bins, seed)
+def tight_plant(n_bins, seed, kmers=KMERS, lo=0, k=K):
+    p = Plant(n_bins, seed, k)
     for n in kmers:
         for where in ("lane", "line", "lines"):
             for reverse in (False, True):
@@ -127,9 +128,9 @@ def tight_plant(n_bins, seed, kmers=KMERS, lo=0):
     return p
 
 
-def make_filter(bins, n_blocks=N_BLOCKS, fill_seed=None):
+def make_filter(bins, n_blocks=N_BLOCKS, fill_seed=None, k=K):
     W = (bins + 63) // 64
-    d = capi.DeviceIBF.create(0, bins, 3, K, W * 64 * n_blocks)
+    d = capi.DeviceIBF.create(0, bins, 3, k, W * 64 * n_blocks)
     if fill_seed is not None:
         d.fill_synth(fill_seed)
     return d

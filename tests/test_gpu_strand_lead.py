@@ -89,21 +89,21 @@ def check(eng, reads_or_batch, deplete, target, label, masks=ALL_MASKS, repeats=
 class WindowPlant(BP.Plant):
     """reads planted by window ranges per strand; `lead` = the strand the kernel must finish first (None: no probe, or not said)"""
 
-    def __init__(self, n_bins, seed):
-        super().__init__(n_bins, seed)
+    def __init__(self, n_bins, seed, k=K):
+        super().__init__(n_bins, seed, k)
         self.lead = []
 
     def windows(self, n, fwd, rev, lead, where="lines", want=None):
         """fwd / rev: lists of (first window, windows) put into bin A / B; the read's maximum is `want` (default: the larger total)"""
-        R = H.random_dna(self.rng, n + K - 1)
+        R = H.random_dna(self.rng, n + self.k - 1)
         A, B = self.pair(where)
         Q = BP.rc(R)
         for s, c in fwd:
             assert 0 <= s and s + c <= n and c > 0
-            self.put(R[s:s + c + K - 1], A)
+            self.put(R[s:s + c + self.k - 1], A)
         for s, c in rev:
             assert 0 <= s and s + c <= n and c > 0
-            self.put(Q[n - s - c:n - s + K - 1], B)
+            self.put(Q[n - s - c:n - s + self.k - 1], B)
         self.read(R, max(sum(c for _, c in fwd), sum(c for _, c in rev)) if want is None else want)
         self.lead.append(lead)
         return A, B
@@ -117,10 +117,10 @@ class WindowPlant(BP.Plant):
         self.lead.append(None if n <= TILE else int(reverse))
 
 
-def sub_tile_plant(seed):
+def sub_tile_plant(seed, k=K):
     """B ends one above A (and the mirror) with the crossover at every 8-k-mer offset of the first two tiles and one k-mer either
     side of each; A and B in one lane, two lanes of a line, different lines; the best strand forward and reverse"""
-    p = WindowPlant(8192, seed)
+    p = WindowPlant(8192, seed, k)
     for tile in (0, 1):
         for j in range(1, 9):
             for d in (-1, 0, 1):
@@ -193,8 +193,8 @@ def test_sub_tile_tightness():
         tr.close()
 
 
-def lead_plant(seed):
-    p = WindowPlant(8192, seed)
+def lead_plant(seed, k=K):
+    p = WindowPlant(8192, seed, k)
     p.windows(65, [(0, 5)], [(62, 3)], lead=0)  # one k-mer behind the probe: the end of a strand lies inside the other's probe windows
     p.windows(65, [(62, 3)], [(0, 5)], lead=1)
     for n in (65, 128, 348, 401):
