@@ -6,7 +6,6 @@ and both builds of ibf_assemble_kernel compile for gfx950 without scratch at the
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 
 from readbouncer_amd import capi
 from tests import assemble_rules as R
+from tests.kernel_build import builds, resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("rb_dibf_assemble", "rb_dibf_select_bins")
@@ -191,35 +191,10 @@ def test_cli_names_the_flags():
         assert p.returncode == 1 and "--edit-ibf" in p.stderr, flags
 
 
-def _resources(stderr):
-    found, cur = {}, None
-    for line in stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            b = re.search(r"\d+ibf_assemble_kernelI((?:L[ib]\d+E)+)E", m.group(1))
-            cur = tuple(int(x) for x in re.findall(r"L[ib](\d+)E", b.group(1))) if b else None
-            if cur:
-                found[cur] = {}
-            continue
-        if cur:
-            for key, pat in (("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgpr", r" VGPRs: (\d+)")):
-                m = re.search(pat, line)
-                if m:
-                    found[cur][key] = int(m.group(1))
-    return found
-
-
-def test_assemble_builds_compile_without_scratch_at_the_stated_waves(tmp_path):
+def test_assemble_builds_compile_without_scratch_at_the_stated_waves():
     """compiled like test_kernel_resources.py does: both ibf_assemble_kernel builds have no scratch, and their waves per SIMD, from the
     compiler's own remarks, are what DESIGN 4.9 states"""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("no hipcc on this box: the occupancy classes are pinned where the library is built")
-    p = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=off", "--offload-arch=gfx950",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "readbouncer_amd", "csrc", "rb_kernels.hip"),
-                        "-o", str(tmp_path / "k.o")], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    found = _resources(p.stderr)
+    found = builds(resources("rb_kernels.hip"), "ibf_assemble_kernel")
     assert set(found) == set(DESIGN_WAVES), sorted(found)
     design = open(os.path.join(ROOT, "DESIGN.md")).read().split("### 4.9")[1]
     for a, v in sorted(found.items()):

@@ -7,7 +7,6 @@ three orders of margin and still catches a wrong formula."""
 import math
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -16,6 +15,7 @@ import pytest
 from oracle import pyoracle as po
 from readbouncer_amd import capi
 from tests import helpers as H
+from tests.kernel_build import resources
 from tests.occupancy_rules import bin_occupancy, summary
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -167,28 +167,8 @@ def test_cli_names_the_flags_and_needs_a_device(tmp_path):
 OCCUPANCY_EXPECT = {"<1,0>": 4, "<1,1>": 4, "<2,0>": 4, "<2,1>": 4}
 
 
-def test_occupancy_kernel_builds_keep_their_waves_and_do_not_spill(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("no hipcc on this box: the occupancy classes are pinned where the library is built")
-    p = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=off", "--offload-arch=gfx950",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "readbouncer_amd", "csrc", "rb_kernels.hip"),
-                        "-o", str(tmp_path / "k.o")], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    found, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            k = re.search(r"ibf_bin_occupancy_kernelILi(\d+)ELb(\d+)EE", m.group(1))
-            cur = "<%s,%s>" % k.groups() if k else None
-            if cur:
-                found[cur] = {}
-            continue
-        if cur:
-            for key, pat in (("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgpr", r" VGPRs: (\d+)")):
-                m = re.search(pat, line)
-                if m:
-                    found[cur][key] = int(m.group(1))
+def test_occupancy_kernel_builds_keep_their_waves_and_do_not_spill():
+    found = {k[len("ibf_bin_occupancy_kernel"):]: v for k, v in resources("rb_kernels.hip").items() if k.startswith("ibf_bin_occupancy_kernel<")}
     assert sorted(found) == sorted(OCCUPANCY_EXPECT), sorted(found)
     for k, waves in OCCUPANCY_EXPECT.items():
         assert found[k]["occ"] >= waves and found[k]["scratch"] == 0 and found[k]["vgpr"] <= 128, (k, found[k])

@@ -3,15 +3,9 @@ The narrow-filter kernels live on the lookups a CU holds in registers: their bui
 (`amdgpu_waves_per_eu`, rb_kernels.hip) and ONE register more can drop a build from seven to six waves per SIMD -- round 4 lost
 16 % on two-word tables that way (73 instead of 72 VGPRs after an innocent change at the END of the kernel) and only a benchmark
 noticed.  This pins waves per SIMD and "no scratch" for the builds the planner's window lengths were fitted with."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "readbouncer_amd", "csrc")
+from tests.kernel_build import resources
 
 # kernel<template arguments> -> least waves per SIMD
 EXPECT = {
@@ -41,35 +35,8 @@ EXPECT = {
 }
 
 
-def _demangle_args(mangled):
-    """template arguments of _ZN2rb..._kernelI...EEv... as '<a,b,c>' (integers and bools only)"""
-    m = re.search(r"_kernelI((?:L[ib]\d+E)+)E", mangled)
-    return "<" + ",".join(re.findall(r"L[ib](\d+)E", m.group(1))) + ">" if m else ""
-
-
-def test_occupancy_classes_and_no_scratch(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("no hipcc on this box: the occupancy classes are pinned where the library is built")
-    p = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=off", "--offload-arch=gfx950",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "rb_kernels.hip"), "-o", str(tmp_path / "k.o")],
-                       capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    found, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            base = re.search(r"\d+(ibf_count_max\w*_kernel)I", name)
-            cur = (base.group(1) + _demangle_args(name)) if base else None
-            if cur:
-                found[cur] = {}
-            continue
-        if cur:
-            for key, pat in (("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgpr", r" VGPRs: (\d+)")):
-                m = re.search(pat, line)
-                if m:
-                    found[cur][key] = int(m.group(1))
+def test_occupancy_classes_and_no_scratch():
+    found = {k: v for k, v in resources("rb_kernels.hip").items() if re.match(r"ibf_count_max\w*_kernel<", k)}
     assert len(found) > 40, sorted(found)[:5]
     for k, waves in EXPECT.items():
         assert k in found, (k, sorted(x for x in found if x.startswith(k.split("<")[0]))[:20])

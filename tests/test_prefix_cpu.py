@@ -6,7 +6,6 @@ the same template arguments."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 
 from readbouncer_amd import capi
 from tests import prefix_rules as PR
+from tests.kernel_build import builds, resources
 from tests.test_gpu_locate import make_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -193,37 +193,11 @@ def test_case_conditions_hold_on_the_oracle(name):
     assert (exp["first_decided"] == 1).sum() == decided[1] and (exp["first_decided"] == 0).sum() == 0
 
 
-def _resources(stderr):
-    found, cur = {}, None
-    for line in stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            b = re.search(r"\d+(ibf_(?:prefix|locate)_kernel)I((?:L[ib]\d+E)+)E", m.group(1))
-            cur = (b.group(1), tuple(int(x) for x in re.findall(r"L[ib](\d+)E", b.group(2)))) if b else None
-            if cur:
-                found[cur] = {}
-            continue
-        if cur:
-            for key, pat in (("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
-                m = re.search(pat, line)
-                if m:
-                    found[cur][key] = int(m.group(1))
-    return found
-
-
-def test_prefix_builds_keep_the_locate_builds_register_class(tmp_path):
+def test_prefix_builds_keep_the_locate_builds_register_class():
     """compiled like tests/test_hits_cpu.py does: every ibf_prefix_kernel build has no scratch, and its waves per SIMD are no lower than
     those of the ibf_locate_kernel build of the same template arguments, read from the same compile"""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("no hipcc on this box: the occupancy classes are pinned where the library is built")
-    p = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=off", "--offload-arch=gfx950",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "readbouncer_amd", "csrc", "rb_kernels.hip"),
-                        "-o", str(tmp_path / "k.o")], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    found = _resources(p.stderr)
-    prefix = {a: v for (k, a), v in found.items() if k == "ibf_prefix_kernel"}
-    locate = {a: v for (k, a), v in found.items() if k == "ibf_locate_kernel"}
+    found = resources("rb_kernels.hip")
+    prefix, locate = builds(found, "ibf_prefix_kernel"), builds(found, "ibf_locate_kernel")
     # the (LG, WPL) x {10 planes, 16 planes, 16 planes with run-time hashes} cases, non-temporal twins where locate has them
     assert set(prefix) == set(locate) and len(prefix) == 8 * 3 + 2 * 3, (sorted(prefix), sorted(locate))
     for a, v in sorted(prefix.items()):

@@ -6,7 +6,6 @@ ibf_locate_kernel build of the same template arguments."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 from oracle import pyoracle as po
 from readbouncer_amd import capi
 from tests import helpers as H
+from tests.kernel_build import builds, resources
 from tests import resume_rules as RR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -193,37 +193,12 @@ def test_rules_model_commits_what_the_header_says():
 
 
 
-def _resources(stderr):
-    found, cur = {}, None
-    for line in stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            b = re.search(r"\d+(ibf_(?:resume|locate)_kernel)I((?:L[ib]\d+E)+)E", m.group(1))
-            cur = (b.group(1), tuple(int(x) for x in re.findall(r"L[ib](\d+)E", b.group(2)))) if b else None
-            if cur:
-                found[cur] = {}
-            continue
-        if cur:
-            for key, pat in (("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
-                m = re.search(pat, line)
-                if m:
-                    found[cur][key] = int(m.group(1))
-    return found
-
-
-def test_resume_builds_keep_the_locate_builds_register_class(tmp_path):
+def test_resume_builds_keep_the_locate_builds_register_class():
     """compiled like tests/test_hits_cpu.py does, once: every ibf_resume_kernel build has no scratch, its waves per SIMD are no lower
     than those of the ibf_locate_kernel build of the same template arguments, and the set of builds is locate's sixteen-plane set"""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("no hipcc on this box: the occupancy classes are pinned where the library is built")
-    p = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=off", "--offload-arch=gfx950",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "readbouncer_amd", "csrc", "rb_kernels.hip"),
-                        "-o", str(tmp_path / "k.o")], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    found = _resources(p.stderr)
-    resume = {a: v for (k, a), v in found.items() if k == "ibf_resume_kernel"}
-    locate = {a: v for (k, a), v in found.items() if k == "ibf_locate_kernel" and a[2] == 16}
+    found = resources("rb_kernels.hip")
+    resume = builds(found, "ibf_resume_kernel")
+    locate = {a: v for a, v in builds(found, "ibf_locate_kernel").items() if a[2] == 16}
     # the (LG, WPL) x {h = 3, run-time hashes} cases on sixteen planes, non-temporal twins where locate has them
     assert set(resume) == set(locate) and len(resume) == 8 * 2 + 2 * 2, (sorted(resume), sorted(locate))
     assert all(a[2] == 16 for a in resume)

@@ -6,7 +6,6 @@ waves per SIMD than DESIGN 4.8 states."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 from oracle import pyoracle as po
 from readbouncer_amd import capi
 from tests import helpers as H
+from tests.kernel_build import builds, resources
 from tests.spans_rules import NONE, QUERY, SPAN, as_queries, expected_arrays, mask_words, position_hits, record
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -225,35 +225,10 @@ def test_expected_arrays_apply_the_status_rules():
         assert tuple(spans[i, 0]) == tuple(spans[i, 1]) == (0, NONE, NONE, NONE, 0, 0) and not mask[i].any()
 
 
-def _resources(stderr):
-    found, cur = {}, None
-    for line in stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            b = re.search(r"\d+ibf_spans_kernelI((?:L[ib]\d+E)+)E", m.group(1))
-            cur = tuple(int(x) for x in re.findall(r"L[ib](\d+)E", b.group(1))) if b else None
-            if cur:
-                found[cur] = {}
-            continue
-        if cur:
-            for key, pat in (("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgpr", r" VGPRs: (\d+)")):
-                m = re.search(pat, line)
-                if m:
-                    found[cur][key] = int(m.group(1))
-    return found
-
-
-def test_spans_builds_compile_without_scratch_at_the_stated_waves(tmp_path):
+def test_spans_builds_compile_without_scratch_at_the_stated_waves():
     """compiled like test_kernel_resources.py does: every ibf_spans_kernel build has no scratch, and its waves per SIMD, from the
     compiler's own remarks, are no lower than the figure DESIGN 4.8 states"""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("no hipcc on this box: the occupancy classes are pinned where the library is built")
-    p = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=off", "--offload-arch=gfx950",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "readbouncer_amd", "csrc", "rb_kernels.hip"),
-                        "-o", str(tmp_path / "k.o")], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    found = _resources(p.stderr)
+    found = builds(resources("rb_kernels.hip"), "ibf_spans_kernel")
     assert set(found) == set(DESIGN_WAVES), sorted(found)
     design = open(os.path.join(ROOT, "DESIGN.md")).read().split("### 4.8")[1]
     for a, v in sorted(found.items()):
