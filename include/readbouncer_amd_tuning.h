@@ -344,6 +344,60 @@ RB_API int rb_dibf_row_table_info(rb_dibf *f, rb_row_table_info *out);
 RB_API int rb_dibf_row_table_download(rb_dibf *f, uint64_t *words, uint64_t n_words);
 RB_API int rb_engine_set_row_table(rb_engine *e, int mode, uint64_t max_bytes);
 
+/* LIST TABLE of a resident filter: the row table's content as sparse lists.  A row has d^h of its bits set (a filter sized for a
+ * false-positive rate of 0.01: about 1 %), so per N-free k-mer the table holds the BIN NUMBERS of its row, ascending, as 16-bit entries in
+ * one slot of 1, 2 or 4 lines of 128 bytes, the rest of the slot 0xFFFF; the count kernel (ibf_count_lists_kernel) gathers that slot
+ * instead of the row's 8 lines and counts each listed bin with one LDS add into per-read 16-bit counters.  The slot size is the smallest
+ * that at most one in 1024 of up to 65 536 sampled rows overflows; a row that does overflow keeps its dense row in a side table that its
+ * slot names (first entry 0xFFFE, then the row's index in two entries).  Serves what the row table serves with, in addition, one column
+ * slice of at most 128 words (8192 bins) and reads of fewer than 65 536 k-mers; results are identical.  Owned, dropped and freed like
+ * the row table; reads with a base outside ACGT go to the three-hash twin as there.
+ *   rb_dibf_list_table_build: build it now unless a current one exists; max_bytes as for the row table.  A refusal is not an error
+ *     (RB_LIST_REFUSED_*): besides the row table's reasons, a filter of more than 8192 bins or 128 words, a filter too dense for
+ *     every slot size (DENSITY), or more overflowing rows than the side table holds (SIDE_FULL: 4^k / 512 + 64 rows, or what
+ *     rb_set_list_side_capacity says).
+ *   rb_dibf_list_table_info / _drop / _download (entries: rows x lines x 64 of uint16_t; side: side_rows x stride words; either may be
+ *     null with a count of 0).
+ *   rb_engine_set_row_table(RB_ROW_TABLE_LISTS): the list form wherever the geometry serves, else as RB_ROW_TABLE_FORCE.
+ *   RB_ROW_TABLE_AUTO prefers the list form when (a) the DENSE row table would lie beyond rb_engine_set_list_min_dense_bytes (default
+ *     512 MiB, 2 x the Infinity Cache: below it the dense table is cache-served and lines do not limit it), (b) the launch is one
+ *     the row table's rule (a) admits, (c) the batch alone repays the build in 128-byte lines -- items x 2 x k-mers x (L x h - 4) >=
+ *     4^k x (L x h + 4), L = lines per block (config 3: 135 000 reads of 360 bp) -- (d) the table fits max_bytes and half of the free
+ *     device memory, (e) the stream is not being captured.  Where the list build is refused, AUTO goes on to the row table's rule, and an
+ *     engine does not ask again (nor does rb_engine_plan report the list form) for the same bits and max_bytes until
+ *     rb_dibf_list_table_build or _drop is called. */
+#define RB_ROW_TABLE_LISTS 3
+#define RB_LIST_REFUSED_NONE 0
+#define RB_LIST_REFUSED_K 1          /* k above 13 */
+#define RB_LIST_REFUSED_GEOMETRY 2   /* blocks of 32 words or fewer, of more than 128 words, or more than 8192 bins */
+#define RB_LIST_REFUSED_MAX_BYTES 3  /* the table and its side table above max_bytes */
+#define RB_LIST_REFUSED_FREE 4       /* the table above half of the free device memory */
+#define RB_LIST_REFUSED_ALLOC 5      /* the allocation failed */
+#define RB_LIST_REFUSED_CAPTURE 6    /* the call's stream was being captured (engine builds only) */
+#define RB_LIST_REFUSED_DENSITY 7    /* more than one sampled row in 1024 overflows even a four-line slot */
+#define RB_LIST_REFUSED_SIDE_FULL 8  /* more overflowing rows than the side table holds */
+typedef struct rb_list_table_info {
+    uint64_t bytes, rows;    /* of the current table's slots; 0: none */
+    uint64_t side_bytes;     /* of its side table */
+    uint32_t lines;          /* 128-byte lines per slot: 1, 2 or 4 */
+    uint32_t side_rows;      /* overflow rows in use */
+    uint32_t side_capacity;  /* ... and how many the side table holds */
+    uint32_t refused;        /* RB_LIST_REFUSED_*: why the last build did not happen */
+    uint32_t builds;         /* tables built for this filter so far */
+    uint32_t stride_words;   /* words per row of the side table (the filter's block stride) */
+    uint64_t census_rows, census_over[3]; /* rows the last census looked at, and how many of them had more than 64, 128, 256 bits set */
+    double build_ms;         /* kernel time of the last build, census included */
+    double alloc_s;          /* seconds its allocations took */
+} rb_list_table_info;
+RB_API int rb_dibf_list_table_build(rb_dibf *f, uint64_t max_bytes);
+RB_API int rb_dibf_list_table_drop(rb_dibf *f);
+RB_API int rb_dibf_list_table_info(rb_dibf *f, rb_list_table_info *out);
+RB_API int rb_dibf_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n_entries, uint64_t *side_words, uint64_t n_side_words);
+/* the dense-table size from which RB_ROW_TABLE_AUTO prefers the list form (0: always, where the other rules hold) */
+RB_API int rb_engine_set_list_min_dense_bytes(rb_engine *e, uint64_t bytes);
+/* rows of the side table of list tables built from now on (process-wide; 0: the default, 4^k / 512 + 64) */
+RB_API void rb_set_list_side_capacity(uint32_t rows);
+
 /* How the eight XCDs walk the slices of a phased table (each has an L2 of its own, so each reloads every slice): bit 0 of `mode` -- at
  * any time every XCD works on a different slice (slice = (window + XCD number) mod slices); bit 1 -- the XCDs' windows start an eighth
  * of a window apart, so that they refill their L2s one after the other instead of all in the same instant.  0 (default): one clock, one

@@ -25,6 +25,12 @@ States: no pruning; today (checks at 64-k-mer tile boundaries, forward strand fi
   rows    the row form (ibf_count_rows_kernel): one gather per k-mer from the filter's row table, whose row is the AND of the k-mer's three
           blocks -- the counts are the full counts, every step costs one line per live line instead of three -- under parts 1 and 2;
           hash 0 alone being the whole count, parts 3 and 4 have nothing to certify.
+  lists   the list form (ibf_count_lists_kernel): one slot of LIST_LINES lines per k-mer from the filter's list table, a counter per bin
+          in LDS.  No lane dies (a slot is fetched whole or not at all): the forward strand is counted to its end, the reverse strand is
+          skipped when the forward one reached N and stops at the first tile boundary where its maximum so far plus the k-mers to come
+          cannot pass the forward maximum.
+  lists_lead  the lists state with the strand lead on top (a model only: it needs a second counter array or a recount of the loser's
+          probe): both strands probed for 64 k-mers, the stronger finished first, the other continued against its maximum.
 
   python3 profiles/prune_model.py [reads per kind, default 500] [seed, default 1]
   python3 profiles/prune_model.py --calibrate [reads per kind, default 4000] [seed, default 1]
@@ -40,6 +46,7 @@ import numpy as np
 N, TILE, LANES, BPL, LPL, H = 348, 64, 64, 128, 8, 3  # k-mers, tile, lanes, bins per lane, lanes per line, hashes
 D = 55.0 / 256.0
 Z = 4.5
+LIST_LINES = 2  # lines per slot of the list table at this load: 81 of 8192 bins per row, 128 entries
 LEAD_MIN = 8  # probe maxima of reads without a match stay below it
 MEASURED_TODAY = 15698.1  # TCC_EA0_RDREQ per read, profiles/bound_pruning/bench_ab.txt
 
@@ -140,6 +147,14 @@ def run_strand(c, start, bb, sub, lanes=None, h=H, off=None, stop_above=None):
     return lines, held_max(min(pos, N))
 
 
+def list_strand_rows(c, start, best):
+    """slots gathered by the list kernel over k-mers [start, N) of a strand with cumulative counts c, against `best` (0: no bound)"""
+    for q in range((start // TILE) * TILE, N, TILE):
+        if q >= start and q > 0 and best and int(c[q].max()) + (N - q) <= best:
+            return q - start
+    return N - start
+
+
 def allowance(rem):
     return math.ceil(D * rem + Z * math.sqrt(D * (1 - D) * rem))
 
@@ -213,6 +228,11 @@ def read_lines(rng, kind, only_today=False):
                 assert max(m_line, m3) == m
                 lt2, mt2 = (0, 0) if m >= N else run_strand(cs[trail][0], TILE, m, sub, h=1)
                 res["rows_line"] = probe // H + l1 + l3 + lt2
+            # the list form: whole slots, the forward strand first and unbounded
+            f_max, r_max = int(cs[0][0][N].max()), int(cs[1][0][N].max())
+            res["lists"] = LIST_LINES * (N + (0 if f_max >= N else list_strand_rows(cs[1][0], 0, f_max)))
+            lead_max = int(cs[lead][0][N].max())
+            res["lists_lead"] = LIST_LINES * (2 * TILE + (N - TILE) + (0 if lead_max >= N else list_strand_rows(cs[trail][0], TILE, lead_max)))
         assert max(m, mt) == max(int(cs[0][0][N].max()), int(cs[1][0][N].max()))
         # part 3: hash 0 alone over [TILE, N) on top of the trailing probe's counters
         rem = N - TILE
@@ -286,7 +306,7 @@ def main():
     pos = {k: 0.45 * (means["pos_fwd"][k] + means["pos_rev"][k]) + 0.05 * (means["near_fwd"][k] + means["near_rev"][k]) for k in means["neg"]}
     mixes = {"bench": {k: 0.5 * means["neg"][k] + 0.5 * pos[k] for k in pos}, "positive": pos, "negative": means["neg"]}
     print("\nfabric lines per read (model, %d reads per kind, seed %d)" % (per_kind, seed))
-    states = ("none", "today", "1", "2", "12", "23", "123", "1234", "rows", "rows_line")
+    states = ("none", "today", "1", "2", "12", "23", "123", "1234", "rows", "rows_line", "lists", "lists_lead")
     print("%-10s" % "mix" + "".join("%11s" % ("parts " + s if s[0].isdigit() else s) for s in states) + "  cert tried/held  line tried/cert/held")
     for mix, v in mixes.items():
         print("%-10s" % mix + "".join("%11.0f" % v[s] for s in states) + "  %.3f / %.3f  %.3f / %.3f / %.3f" % (

@@ -1,0 +1,180 @@
+// row_list_probe.hip -- step 0 of the sparse bin lists: before any kernel work, what would a count kernel
+// deliver that gathers one 256-byte LIST of bin numbers per k-mer (two 128-byte lines) instead of the 1 KiB bit row (eight), and
+// counts each listed bin with one returning LDS add?  No hashing, no reads, no pruning: the gather and the adds alone.
+//   table  : 4^13 = 2^26 rows of 256 bytes = 16 GiB.  A row is a sorted list of distinct bin numbers < 8192 as uint16_t, 72-91 of
+//            its 128 entries used (mean 81.5 = 63.7 %, the d^3 = (55/256)^3 of config 3 at design load), the rest 0xFFFF
+//   wave   : one wave per "read", one 64-thread workgroup each, 16 KiB of LDS (8192 uint16_t counters, two per dword): ten waves
+//            per CU is what the LDS allows.  A read is 704 rows (config 3 has 696 k-mers on two strands); the counters are
+//            cleared once per read
+//   tile   : R rows in flight per wave (32 or 64; a row costs ONE VGPR: one dword per lane).  Lane u of the tile draws the row
+//            number of row u, as a lane of the count kernel ranks its own k-mer; the numbers travel by v_readlane; the R gathers
+//            are issued back to back (sched_barrier), non-temporal or temporal
+//   count  : per row and lane two returning adds (ds_add_rtn_u32 of 1 << 16·(bin & 1) at dword bin >> 1) for the entries below
+//            8192, and a running maximum of "old half + 1", as the kernel would keep it
+//   nolds  : the same loop with the LDS part replaced by an XOR
+// Prints rows/s and lines/s (2 per row) per setting, best of 3 runs after one warm-up, and the gate of the issue: today's row
+// kernel completes 6.16 G rows/s at 0.946 of its own probe, so the list form can only win above 6.5 G rows/s.
+// build+run on the GPU box:  hipcc -O3 --offload-arch=gfx950 profiles/row_list_probe.hip -o /tmp/row_list_probe && /tmp/row_list_probe
+//   optional arguments: [log2 rows, default 26] [reads per wave, default 48]
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+
+#define CHECK(x)                                                                                        \
+    do {                                                                                                \
+        hipError_t e_ = (x);                                                                            \
+        if (e_ != hipSuccess) {                                                                         \
+            printf("%s failed: %s (line %d)\n", #x, hipGetErrorString(e_), __LINE__);                   \
+            return 1;                                                                                   \
+        }                                                                                               \
+    } while (0)
+
+constexpr uint32_t kBins = 8192;
+constexpr uint32_t kRowDwords = 64;     // 256 bytes
+constexpr uint32_t kRowsPerRead = 704;  // 11 tiles of 64, 22 of 32
+
+__host__ __device__ __forceinline__ uint64_t mix(uint64_t z)
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+// entry j of row r: the j-th of n_r sorted distinct bins, one in every stride of 8192 / n_r; 0xFFFF from n_r on
+__device__ __forceinline__ uint32_t entry(uint64_t r, uint32_t j, uint32_t n_r, uint32_t stride)
+{
+    if (j >= n_r) return 0xFFFFu;
+    return j * stride + (uint32_t)(mix(r * 128 + j) % stride);  // <= n_r * stride - 1 <= 8191
+}
+
+__global__ __launch_bounds__(256) void fill_rows(uint32_t *__restrict__ table, uint64_t n_rows)
+{
+    const uint64_t n = n_rows * kRowDwords;
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        const uint64_t r = i / kRowDwords;
+        const uint32_t l = (uint32_t)(i % kRowDwords);
+        const uint32_t n_r = 72 + (uint32_t)(mix(~r) % 20);
+        const uint32_t stride = kBins / n_r;
+        table[i] = entry(r, 2 * l, n_r, stride) | (entry(r, 2 * l + 1, n_r, stride) << 16);
+    }
+}
+
+template <int R, bool NT, bool LDS>
+__global__ __launch_bounds__(64) void list_probe(const uint32_t *__restrict__ table, uint32_t lg_rows, uint32_t reads, uint32_t *out)
+{
+    extern __shared__ uint32_t cnt[];  // kBins / 2 dwords, given at the launch so that the build without the adds keeps the occupancy
+    const uint32_t lane = threadIdx.x;
+    uint32_t best = 0, acc = 0;
+    uint64_t s = mix((uint64_t)blockIdx.x + 1);
+    for (uint32_t rd = 0; rd < reads; ++rd) {
+        if constexpr (LDS) {
+            uint4 *c4 = reinterpret_cast<uint4 *>(cnt);
+#pragma unroll
+            for (uint32_t i = 0; i < kBins / 2 / 4 / 64; ++i) c4[i * 64 + lane] = make_uint4(0, 0, 0, 0);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+        }
+        uint32_t m = 0;
+#pragma unroll 1
+        for (uint32_t t = 0; t < kRowsPerRead / R; ++t) {
+            s += 0x9E3779B97F4A7C15ULL;
+            const uint32_t mine = (uint32_t)(mix(s + lane) >> (64 - lg_rows));  // this lane's row number, < 2^lg_rows
+            uint32_t v[R];
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)mine, u % 64);
+                const uint32_t *p = table + (size_t)row * kRowDwords + lane;
+                if constexpr (NT) v[u] = __builtin_nontemporal_load(p);
+                else v[u] = *p;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                if constexpr (LDS) {
+                    const uint32_t b0 = v[u] & 0xFFFFu, b1 = v[u] >> 16;
+                    if (b0 < kBins) {  // also the bound of the LDS index: bin >> 1 < 4096
+                        const uint32_t sh = (b0 & 1u) * 16u;
+                        const uint32_t old = __hip_atomic_fetch_add(&cnt[b0 >> 1], 1u << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        m = max(m, ((old >> sh) & 0xFFFFu) + 1u);
+                    }
+                    if (b1 < kBins) {
+                        const uint32_t sh = (b1 & 1u) * 16u;
+                        const uint32_t old = __hip_atomic_fetch_add(&cnt[b1 >> 1], 1u << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        m = max(m, ((old >> sh) & 0xFFFFu) + 1u);
+                    }
+                } else {
+                    acc ^= v[u];
+                }
+            }
+        }
+        best = max(best, m);
+    }
+    if ((best ^ acc) == 0x12345678u) out[0] = best;
+}
+
+template <int R, bool NT, bool LDS>
+static int run(const uint32_t *table, uint32_t lg_rows, uint32_t reads, uint32_t *out, double *rows_per_s)
+{
+    const int blocks = 256 * 10 * 8;  // ten waves per CU, eight rounds
+    hipEvent_t a, b;
+    CHECK(hipEventCreate(&a));
+    CHECK(hipEventCreate(&b));
+    float best = 1e30f;
+    for (int rep = 0; rep < 4; ++rep) {
+        CHECK(hipEventRecord(a));
+        hipLaunchKernelGGL((list_probe<R, NT, LDS>), dim3(blocks), dim3(64), kBins * 2, 0, table, lg_rows, reads, out);
+        CHECK(hipGetLastError());
+        CHECK(hipEventRecord(b));
+        CHECK(hipEventSynchronize(b));
+        float ms = 0;
+        CHECK(hipEventElapsedTime(&ms, a, b));
+        if (rep && ms < best) best = ms;
+    }
+    const double rows = (double)blocks * reads * kRowsPerRead;
+    *rows_per_s = rows / best / 1e6;  // G rows/s
+    printf("rows in flight %2d  %-8s  %-8s : %7.2f G rows/s  %7.2f G lines/s  (%.1f ms)\n", R, NT ? "nt" : "temporal",
+           LDS ? "lds adds" : "no lds", *rows_per_s, 2.0 * *rows_per_s, best);
+    fflush(stdout);
+    CHECK(hipEventDestroy(a));
+    CHECK(hipEventDestroy(b));
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    const uint32_t lg_rows = argc > 1 ? (uint32_t)atoi(argv[1]) : 26;
+    const uint32_t reads = argc > 2 ? (uint32_t)atoi(argv[2]) : 48;
+    if (lg_rows < 10 || lg_rows > 26 || reads < 1 || reads > 4096) {
+        printf("usage: row_list_probe [log2 rows 10..26] [reads per wave 1..4096]\n");
+        return 2;
+    }
+    const uint64_t n_rows = 1ULL << lg_rows;
+    const size_t bytes = (size_t)n_rows * kRowDwords * 4;
+    uint32_t *table = nullptr, *out = nullptr;
+    CHECK(hipMalloc(&table, bytes));
+    CHECK(hipMalloc(&out, 4));
+    hipLaunchKernelGGL(fill_rows, dim3(256 * 32), dim3(256), 0, 0, table, n_rows);
+    CHECK(hipGetLastError());
+    CHECK(hipDeviceSynchronize());
+    printf("table: 2^%u rows of 256 bytes = %.2f GiB, 72-91 of 128 entries per row; %u reads of %u rows per wave, 10 waves per CU\n", lg_rows,
+           bytes / 1073741824.0, reads, kRowsPerRead);
+    double g[8];
+    int i = 0;
+    if (run<32, true, true>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<64, true, true>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<32, false, true>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<64, false, true>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<32, true, false>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<64, true, false>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<32, false, false>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<64, false, false>(table, lg_rows, reads, out, &g[i++])) return 1;
+    double best = 0;
+    for (int k = 0; k < 4; ++k) best = g[k] > best ? g[k] : best;
+    printf("best with the LDS adds: %.2f G rows/s; gate 6.50 G rows/s (6.16 / 0.946): %s\n", best, best > 6.5 ? "go on" : "stop");
+    CHECK(hipFree(table));
+    CHECK(hipFree(out));
+    return 0;
+}

@@ -98,7 +98,17 @@ class RowTableInfo(C.Structure):
                 ("refused", C.c_uint32), ("builds", C.c_uint32)]
 
 
-RB_ROW_TABLE_OFF, RB_ROW_TABLE_AUTO, RB_ROW_TABLE_FORCE = 0, 1, 2
+class ListTableInfo(C.Structure):
+    """rb_list_table_info"""
+    _fields_ = [("bytes", C.c_uint64), ("rows", C.c_uint64), ("side_bytes", C.c_uint64), ("lines", C.c_uint32), ("side_rows", C.c_uint32),
+                ("side_capacity", C.c_uint32), ("refused", C.c_uint32), ("builds", C.c_uint32), ("stride_words", C.c_uint32),
+                ("census_rows", C.c_uint64), ("census_over", C.c_uint64 * 3), ("build_ms", C.c_double), ("alloc_s", C.c_double)]
+
+
+RB_ROW_TABLE_OFF, RB_ROW_TABLE_AUTO, RB_ROW_TABLE_FORCE, RB_ROW_TABLE_LISTS = 0, 1, 2, 3
+(RB_LIST_REFUSED_NONE, RB_LIST_REFUSED_K, RB_LIST_REFUSED_GEOMETRY, RB_LIST_REFUSED_MAX_BYTES, RB_LIST_REFUSED_FREE, RB_LIST_REFUSED_ALLOC,
+ RB_LIST_REFUSED_CAPTURE, RB_LIST_REFUSED_DENSITY, RB_LIST_REFUSED_SIDE_FULL) = range(9)
+LIST_SENTINEL, LIST_OVERFLOW_MARK = 0xFFFF, 0xFFFE  # rb_lists.h
 (RB_ROW_REFUSED_NONE, RB_ROW_REFUSED_K, RB_ROW_REFUSED_NARROW, RB_ROW_REFUSED_MAX_BYTES, RB_ROW_REFUSED_FREE, RB_ROW_REFUSED_ALLOC,
  RB_ROW_REFUSED_CAPTURE) = range(7)
 
@@ -247,6 +257,12 @@ SIGNATURES = {
     "rb_dibf_row_table_info": (_int, [_vp, C.POINTER(RowTableInfo)]),
     "rb_dibf_row_table_download": (_int, [_vp, _vp, _u64]),
     "rb_engine_set_row_table": (_int, [_vp, _int, _u64]),
+    "rb_dibf_list_table_build": (_int, [_vp, _u64]),
+    "rb_dibf_list_table_drop": (_int, [_vp]),
+    "rb_dibf_list_table_info": (_int, [_vp, C.POINTER(ListTableInfo)]),
+    "rb_dibf_list_table_download": (_int, [_vp, _vp, _u64, _vp, _u64]),
+    "rb_engine_set_list_min_dense_bytes": (_int, [_vp, _u64]),
+    "rb_set_list_side_capacity": (None, [C.c_uint32]),
     "rb_dibf_placement": (_int, [_vp, C.POINTER(_u32), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "rb_dibf_placement_cost": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_u64), C.POINTER(_u32)]),
     "rb_engine_set_merge": (_int, [_vp, _int]),
@@ -469,6 +485,32 @@ class DeviceIBF:
         out = np.zeros(i["bytes"] // 8, dtype=np.uint64)
         _check(lib().rb_dibf_row_table_download(self.h, _ptr(out), len(out)), "rb_dibf_row_table_download")
         return out.reshape(i["rows"], -1) if i["rows"] else out
+
+    def list_table_build(self, max_bytes=0):
+        """build the list table (per N-free k-mer the sorted bin numbers of its row, in slots of 1, 2 or 4 lines) unless a current one
+        exists -> list_table_info()"""
+        _check(lib().rb_dibf_list_table_build(self.h, int(max_bytes)), "rb_dibf_list_table_build")
+        return self.list_table_info()
+
+    def list_table_drop(self):
+        _check(lib().rb_dibf_list_table_drop(self.h), "rb_dibf_list_table_drop")
+
+    def list_table_info(self):
+        """-> dict (rb_list_table_info)"""
+        i = ListTableInfo()
+        _check(lib().rb_dibf_list_table_info(self.h, C.byref(i)), "rb_dibf_list_table_info")
+        d = {k: getattr(i, k) for k, _ in ListTableInfo._fields_}
+        d["census_over"] = list(i.census_over)
+        return d
+
+    def list_table_download(self):
+        """-> (np.uint16[rows, 64 x lines]: the slots, np.uint64[side rows in use, stride words]: the dense rows overflow slots name)"""
+        i = self.list_table_info()
+        slots = np.zeros(i["bytes"] // 2, dtype=np.uint16)
+        side = np.zeros(i["side_rows"] * i["stride_words"], dtype=np.uint64)
+        _check(lib().rb_dibf_list_table_download(self.h, _ptr(slots) if len(slots) else None, len(slots), _ptr(side) if len(side) else None,
+                                                 len(side)), "rb_dibf_list_table_download")
+        return (slots.reshape(i["rows"], -1) if i["rows"] else slots), side.reshape(i["side_rows"], i["stride_words"])  # (a table none of whose rows overflow has no side rows)
 
     def placement(self):
         """-> (allocations probed for this table: 0 = not placed by trial, GB/s of the kept one, GB/s of the slowest one)"""
@@ -886,9 +928,13 @@ class Engine:
         _check(lib().rb_engine_set_cert_load(self.h, filter_index, float(load)), "rb_engine_set_cert_load")
 
     def set_row_table(self, mode, max_bytes=0):
-        """RB_ROW_TABLE_OFF / _AUTO (default) / _FORCE: whether plain whole-wave launches gather one precomputed row per k-mer from the
+        """RB_ROW_TABLE_OFF / _AUTO (default) / _FORCE / _LISTS (the list table wherever it serves): whether plain whole-wave launches gather one precomputed row per k-mer from the
         filter's row table, building it when there is none (results identical); max_bytes 0 keeps the limit (default 96 GiB)"""
         _check(lib().rb_engine_set_row_table(self.h, int(mode), int(max_bytes)), "rb_engine_set_row_table")
+
+    def set_list_min_dense_bytes(self, n_bytes):
+        """size of the dense row table from which RB_ROW_TABLE_AUTO prefers the list table (default 512 MiB; 0: always)"""
+        _check(lib().rb_engine_set_list_min_dense_bytes(self.h, int(n_bytes)), "rb_engine_set_list_min_dense_bytes")
 
     def set_prune_trace(self, device_ptr):
         """device memory for one 8-byte record per (filter, read, column slice) of the plain count kernel's waves, or 0 / None: none"""
@@ -1235,6 +1281,11 @@ def nt_threshold_default():
 def set_placement_tries(tries):
     """process-wide: candidates a table of >= 1 GiB is allocated and probed as (default 5; 0 / 1 = off)"""
     _check(lib().rb_set_placement_tries(int(tries)), "rb_set_placement_tries")
+
+
+def set_list_side_capacity(rows):
+    """process-wide: rows of the side table of list tables built from now on (0: the default, 4^k / 512 + 64)"""
+    lib().rb_set_list_side_capacity(int(rows))
 
 
 def pack_reads(seqs, offsets, lens):

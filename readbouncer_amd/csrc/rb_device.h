@@ -160,6 +160,11 @@ struct CountLaunch {
     uint32_t lead_min;        // ... the probe maximum from which the leader's line is counted first (kPruneLeadMinShift)
     // row form (launch_ibf_count_rows): the filter's row table -- one row of `f.stride` words per N-free k-mer -- or nullptr
     const uint64_t *row_table;
+    // list form (launch_ibf_count_lists, rb_lists.hip): the filter's list table -- one slot of list_lines lines per N-free k-mer (rb_lists.h) --
+    // and its side table of list_side_rows dense rows for the slots that overflowed, or nullptr
+    const uint16_t *list_table;
+    const uint64_t *list_side;
+    uint32_t list_side_rows, list_lines;
 };
 
 // By-value argument of ibf_count_max_kernel: how it prunes.
@@ -391,6 +396,17 @@ bool row_form_serves(const CountLaunch &a);  // the launch is one the row form h
 hipError_t launch_ibf_count_rows(const CountLaunch &a, hipStream_t st);
 // rows[r * f.stride + w] <- the AND of the h blocks of the k-mer whose base-4 rank is r, for r < n_rows = 4^k
 hipError_t launch_row_table(const IbfDev &f, uint64_t *rows, uint64_t n_rows, hipStream_t st);
+// ... the three-hash build of the row form alone (the reads with a base outside ACGT): what the list form launches behind its own kernel
+hipError_t launch_ibf_count_rows_twin(const CountLaunch &a, hipStream_t st);
+// List form (rb_lists.hip, ibf_count_lists_kernel): one gather of a.list_lines lines per k-mer from a.list_table, a returning LDS add per listed bin.
+bool list_form_serves(const CountLaunch &a);  // the row form's launches with one column slice, at most 8192 bins and strands below 65 536 k-mers
+hipError_t launch_ibf_count_lists(const CountLaunch &a, hipStream_t st);
+// counters[1 + i] += rows among 0, step, 2 step, ... < n_rows with more than 64 << i set bits (i = 0, 1, 2); counters start zeroed
+hipError_t launch_list_census(const IbfDev &f, uint32_t *counters, uint64_t n_rows, uint64_t step, hipStream_t st);
+// slots <- the list table at `lines` lines per slot, side <- the dense rows of the slots that overflow (at most side_cap are written),
+// counters[0] += such slots; counters start zeroed
+hipError_t launch_list_table(const IbfDev &f, uint16_t *slots, uint64_t *side, uint32_t *counters, uint64_t n_rows, uint32_t lines, uint32_t side_cap,
+                             hipStream_t st);
 hipError_t launch_ibf_count_max_merged(const CountLaunch &a, const MergeMap &map, hipStream_t st);
 // block b of a filter (width words at stride s_src, n_bins bins) -> bits [dst_bit, dst_bit + n_bins) of block b of dst (ORed in: dst starts zeroed)
 hipError_t launch_invert_words(const uint64_t *src, uint64_t *dst, uint64_t n_words, hipStream_t st);

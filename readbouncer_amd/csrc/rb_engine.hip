@@ -21,6 +21,7 @@
 #include "rb_device.h"
 #include "rb_io.h"
 #include "rb_phase_plan.h"
+#include "rb_lists.h"
 #include "rb_stage.h"
 
 using namespace rb;
@@ -65,6 +66,18 @@ struct rb_dibf {
     double row_build_ms = 0.0, row_alloc_s = 0.0;
     uint32_t row_refused = 0;  // why the last build did not happen (RB_ROW_REFUSED_*)
     uint32_t row_builds = 0;   // tables built for this filter so far
+    // LIST TABLE (rb_dibf_list_table_build; rb_lists.h, rb_lists.hip): the same rows as sorted lists of bin numbers, one slot of list_lines
+    // lines per N-free k-mer, and the dense rows of the slots that overflow in list_side.  Owned, guarded (row_mu) and dropped as the row table.
+    uint16_t *list_table = nullptr;
+    uint64_t *list_side = nullptr;
+    uint64_t list_version = 0, list_rows = 0, list_bytes = 0, list_side_bytes = 0;
+    uint32_t list_lines = 0, list_side_rows = 0, list_side_cap = 0;
+    uint64_t list_census_rows = 0, list_census_over[3] = {0, 0, 0};
+    double list_build_ms = 0.0, list_alloc_s = 0.0;
+    uint32_t list_refused = 0;          // why the last build did not happen (RB_LIST_REFUSED_*)
+    uint64_t list_refused_version = 0;  // ... and the bits it was refused for: an engine does not ask again until they change
+    uint64_t list_refused_max_bytes = 0;  // ... and the max_bytes of that build (list_refusal_stands_locked)
+    uint32_t list_builds = 0;
 };
 
 static void dibf_row_drop_locked(rb_dibf *f)
@@ -77,6 +90,19 @@ static void dibf_row_drop_locked(rb_dibf *f)
     f->row_rows = f->row_bytes = 0;
 }
 
+static void dibf_list_drop_locked(rb_dibf *f)
+{
+    if (f->list_table || f->list_side) {
+        (void)hipSetDevice(f->device);
+        if (f->list_table) (void)hipFree(f->list_table);  // (waits for the kernels that read it)
+        if (f->list_side) (void)hipFree(f->list_side);
+    }
+    f->list_table = nullptr;
+    f->list_side = nullptr;
+    f->list_rows = f->list_bytes = f->list_side_bytes = 0;
+    f->list_lines = f->list_side_rows = f->list_side_cap = 0;
+}
+
 // the one signal for "the bits of this filter are no longer what they were": engines measure its load again (cert_allowance), merged copies
 // go stale, and the row table is dropped
 static void dibf_changed(rb_dibf *f)
@@ -84,6 +110,7 @@ static void dibf_changed(rb_dibf *f)
     f->version.fetch_add(1);
     std::lock_guard<std::mutex> lock(f->row_mu);
     dibf_row_drop_locked(f);
+    dibf_list_drop_locked(f);
 }
 
 // Tables of 1 GiB and more are PLACED BY TRIAL: the same table allocated at another moment of one process gathers 1.7-2.9 % slower or
@@ -378,6 +405,9 @@ struct rb_engine {
     // rb_engine_set_row_table: whether the plain whole-wave launches gather from the filter's row table (and build it), see row_policy
     int row_mode = RB_ROW_TABLE_AUTO;
     uint64_t row_max_bytes = 96ull << 30;
+    // ... and from which size of the DENSE row table auto prefers the list table (rb_engine_set_list_min_dense_bytes): a constant of its
+    // own, not nt_threshold_bytes -- below it the dense table is served from the Infinity Cache and lines are not what limits it
+    uint64_t list_min_dense_bytes = 512ull << 20;
     struct CertLoad {
         double set = -1.0;       // what the caller gave (< 0: measure)
         double measured = -1.0;  // load of the filter's fullest bin at `version` (< 0: not measured yet)
@@ -829,6 +859,7 @@ void rb_dibf_free(rb_dibf *f)
         (void)hipFree(f->d_words);
     }
     dibf_row_drop_locked(f);  // (nobody else holds a filter that is being freed)
+    dibf_list_drop_locked(f);
     delete f;
 }
 
@@ -1447,7 +1478,7 @@ int rb_engine_set_prune_parts(rb_engine *e, uint32_t mask)
 
 int rb_engine_set_row_table(rb_engine *e, int mode, uint64_t max_bytes)
 {
-    if (!e || mode < RB_ROW_TABLE_OFF || mode > RB_ROW_TABLE_FORCE) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (auto) or 2 (force)");
+    if (!e || mode < RB_ROW_TABLE_OFF || mode > RB_ROW_TABLE_LISTS) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (auto), 2 (force) or 3 (lists)");
     std::lock_guard<std::mutex> lock(e->mu);
     e->row_mode = mode;
     if (max_bytes) e->row_max_bytes = max_bytes;
@@ -1559,6 +1590,178 @@ int rb_dibf_row_table_download(rb_dibf *f, uint64_t *words, uint64_t n_words)
     int st = check_device(f->device);
     if (st != RB_OK) return st;
     RB_HIP(hipMemcpy(words, f->row_table, n_words * 8, hipMemcpyDeviceToHost));
+    return RB_OK;
+}
+
+// ---- the list table (rb_lists.h): census, slot size, build
+static std::atomic<uint32_t> g_list_side_capacity{0};
+
+void rb_set_list_side_capacity(uint32_t rows) { g_list_side_capacity.store(rows); }
+
+int rb_engine_set_list_min_dense_bytes(rb_engine *e, uint64_t bytes)
+{
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->list_min_dense_bytes = bytes;
+    return RB_OK;
+}
+
+static bool list_table_current_locked(const rb_dibf *f) { return f->list_table && f->list_version == f->version.load(); }
+
+// Does the last refusal still stand for a call that allows the table `max_bytes`?  Every refusal but the one of a capturing stream is
+// remembered for the version of the bits it was given for, so that neither a call nor rb_engine_plan takes the census again only to be
+// refused again: density and a full side table are properties of the bits; a table beyond max_bytes stays beyond it until the caller
+// allows more; want of memory stands until the bits change or rb_dibf_list_table_build / _drop is called (what the row table does).
+static bool list_refusal_stands_locked(const rb_dibf *f, uint64_t max_bytes)
+{
+    if (f->list_refused == RB_LIST_REFUSED_NONE || f->list_refused == RB_LIST_REFUSED_CAPTURE) return false;
+    if (f->list_refused_version != f->version.load()) return false;
+    return f->list_refused != RB_LIST_REFUSED_MAX_BYTES || max_bytes == f->list_refused_max_bytes;
+}
+
+// why a filter can have no list table whatever its bits (RB_LIST_REFUSED_NONE: it can)
+static uint32_t list_table_geometry_refusal(const rb_dibf *f)
+{
+    if (f->geo.kmer_size == 0 || f->geo.kmer_size > kRowTableMaxK) return RB_LIST_REFUSED_K;
+    if (f->geo.bin_width <= 32 || f->geo.bin_width > 128 || f->geo.n_bins > rblist::kMaxBins) return RB_LIST_REFUSED_GEOMETRY;
+    return RB_LIST_REFUSED_NONE;
+}
+
+// Builds the table unless a current one exists.  RB_OK whether it was built or refused (f->list_refused says which); an error only where
+// the runtime fails.
+static int dibf_list_build(rb_dibf *f, uint64_t max_bytes)
+{
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (list_table_current_locked(f)) return RB_OK;
+    dibf_list_drop_locked(f);  // stale
+    const uint64_t version = f->version.load();
+    f->list_refused_version = version;
+    f->list_refused_max_bytes = max_bytes;
+    f->list_refused = list_table_geometry_refusal(f);
+    if (f->list_refused) return RB_OK;
+    int st = check_device(f->device);
+    if (st != RB_OK) return st;
+    const uint64_t n_rows = 1ull << (2 * f->geo.kmer_size);
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t *d_counters = nullptr;
+    uint32_t counters[4] = {0, 0, 0, 0};
+    RB_HIP(hipMalloc((void **)&d_counters, sizeof counters));
+    auto fail_hip = [&](hipError_t e, uint16_t *slots, uint64_t *side) {
+        (void)hipFree(d_counters);
+        if (slots) (void)hipFree(slots);
+        if (side) (void)hipFree(side);
+        return rb::fail(RB_ERR_HIP, std::string("list table: ") + hipGetErrorString(e));
+    };
+    // the census: how many of up to 2^16 rows, evenly spaced, overflow each slot size
+    const uint64_t step = std::max<uint64_t>(1, n_rows / rblist::kCensusRows);
+    hipError_t e = hipMemset(d_counters, 0, sizeof counters);
+    if (e == hipSuccess) e = launch_list_census(f->dev, d_counters, n_rows, step, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip(e, nullptr, nullptr);
+    f->list_census_rows = (n_rows + step - 1) / step;
+    for (int i = 0; i < 3; ++i) f->list_census_over[i] = counters[1 + i];
+    const uint32_t lines = rblist::choose_lines(f->list_census_over, f->list_census_rows);
+    if (!lines) {
+        (void)hipFree(d_counters);
+        f->list_refused = RB_LIST_REFUSED_DENSITY;
+        return RB_OK;
+    }
+    const uint32_t cap_set = g_list_side_capacity.load();
+    const uint64_t side_cap = cap_set ? cap_set : rblist::side_capacity(n_rows);
+    const uint64_t bytes = n_rows * rblist::slot_bytes(lines), side_bytes = side_cap * f->stride * 8;
+    size_t free_b = 0, total_b = 0;
+    if (max_bytes && bytes + side_bytes > max_bytes) f->list_refused = RB_LIST_REFUSED_MAX_BYTES;
+    else if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + side_bytes > (uint64_t)free_b / 2) f->list_refused = RB_LIST_REFUSED_FREE;
+    if (f->list_refused) {
+        (void)hipGetLastError();
+        (void)hipFree(d_counters);
+        return RB_OK;
+    }
+    const auto t_alloc = std::chrono::steady_clock::now();
+    uint16_t *slots = nullptr;
+    uint64_t *side = nullptr;
+    if (hipMalloc((void **)&slots, bytes) != hipSuccess || hipMalloc((void **)&side, side_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        if (slots) (void)hipFree(slots);
+        (void)hipFree(d_counters);
+        f->list_refused = RB_LIST_REFUSED_ALLOC;
+        return RB_OK;
+    }
+    f->list_alloc_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc).count();
+    e = hipMemset(d_counters, 0, sizeof counters);
+    if (e == hipSuccess) e = launch_list_table(f->dev, slots, side, d_counters, n_rows, lines, (uint32_t)side_cap, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip(e, slots, side);
+    (void)hipFree(d_counters);
+    f->list_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - f->list_alloc_s * 1e3;
+    if (counters[0] > side_cap) {  // rows were left unwritten: nothing is ever counted from such a table
+        (void)hipFree(slots);
+        (void)hipFree(side);
+        f->list_refused = RB_LIST_REFUSED_SIDE_FULL;
+        return RB_OK;
+    }
+    f->list_table = slots;
+    f->list_side = side;
+    f->list_rows = n_rows;
+    f->list_bytes = bytes;
+    f->list_side_bytes = side_bytes;
+    f->list_lines = lines;
+    f->list_side_rows = counters[0];
+    f->list_side_cap = (uint32_t)side_cap;
+    f->list_version = version;
+    f->list_builds += 1;
+    return RB_OK;
+}
+
+int rb_dibf_list_table_build(rb_dibf *f, uint64_t max_bytes)
+{
+    if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
+    return dibf_list_build(f, max_bytes);
+}
+
+int rb_dibf_list_table_drop(rb_dibf *f)
+{
+    if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    dibf_list_drop_locked(f);
+    f->list_refused = RB_LIST_REFUSED_NONE;  // the next call may ask again
+    return RB_OK;
+}
+
+int rb_dibf_list_table_info(rb_dibf *f, rb_list_table_info *out)
+{
+    if (!f || !out) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    std::memset(out, 0, sizeof *out);
+    if (list_table_current_locked(f)) {
+        out->bytes = f->list_bytes;
+        out->rows = f->list_rows;
+        out->side_bytes = f->list_side_bytes;
+        out->lines = f->list_lines;
+        out->side_rows = f->list_side_rows;
+        out->side_capacity = f->list_side_cap;
+    }
+    out->refused = f->list_refused;
+    out->builds = f->list_builds;
+    out->stride_words = (uint32_t)f->stride;
+    out->census_rows = f->list_census_rows;
+    for (int i = 0; i < 3; ++i) out->census_over[i] = f->list_census_over[i];
+    out->build_ms = f->list_build_ms;
+    out->alloc_s = f->list_alloc_s;
+    return RB_OK;
+}
+
+int rb_dibf_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n_entries, uint64_t *side_words, uint64_t n_side_words)
+{
+    if (!f || (!entries && n_entries) || (!side_words && n_side_words)) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (!list_table_current_locked(f)) return rb::fail(RB_ERR_INVALID_ARG, "the filter has no current list table");
+    if (n_entries > f->list_bytes / 2) return rb::fail(RB_ERR_INVALID_ARG, "more entries than the list table holds");
+    if (n_side_words > (uint64_t)f->list_side_rows * f->stride) return rb::fail(RB_ERR_INVALID_ARG, "more words than the side table's rows in use hold");
+    int st = check_device(f->device);
+    if (st != RB_OK) return st;
+    if (n_entries) RB_HIP(hipMemcpy(entries, f->list_table, n_entries * 2, hipMemcpyDeviceToHost));
+    if (n_side_words) RB_HIP(hipMemcpy(side_words, f->list_side, n_side_words * 8, hipMemcpyDeviceToHost));
     return RB_OK;
 }
 
@@ -2005,6 +2208,75 @@ static int row_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, const uint64_
         *rows = f->row_table;
         *row_bytes = f->row_bytes;
     }
+    return RB_OK;
+}
+
+// May this launch count from the filter's LIST table?  Mode lists: wherever the geometry serves -- the row form's launches with one
+// column slice of at most 128 words and strands below 65 536 k-mers.  Mode auto, in addition: (a) the DENSE row table would lie beyond
+// list_min_dense_bytes; (c) the batch alone repays the build, in 128-byte lines: a k-mer costs L x h lines today (L lines per block; L
+// where the dense row table stands) and at most 4 from a slot, the build reads 4^k x L x h lines and writes at most 4^k x 4 -- a current
+// list table has nothing left to repay; no trace asked for.  Size (d) and capture (e) are settled where the table is built.
+static bool list_policy(const rb_engine *e, rb_dibf *f, const CountLaunch &a, size_t n_reads, uint32_t max_len)
+{
+    if (e->row_mode != RB_ROW_TABLE_LISTS && e->row_mode != RB_ROW_TABLE_AUTO) return false;
+    if (e->early_decision || e->shard_world != 1) return false;
+    CountLaunch as_launch = a;  // (rb_engine_plan plans the geometry without the filter's descriptor)
+    as_launch.f.n_hash = (uint32_t)f->geo.n_hash;
+    as_launch.f.k = (uint32_t)f->geo.kmer_size;
+    as_launch.f.n_bins = (uint32_t)f->geo.n_bins;
+    as_launch.f.bin_width = (uint32_t)f->geo.bin_width;
+    as_launch.src.max_len = max_len;
+    if (!list_form_serves(as_launch) || list_table_geometry_refusal(f)) return false;
+    if (e->filters.size() > 1 && n_reads <= e->split_threshold) return false;  // a micro-batch that is fused with other filters
+    const uint64_t n_rows = 1ull << (2 * f->geo.kmer_size);
+    if (n_rows * rblist::slot_bytes(1) > e->row_max_bytes) return false;
+    if (e->row_mode == RB_ROW_TABLE_AUTO) {
+        if (e->prune_trace) return false;
+        if (row_table_want_bytes(f) <= e->list_min_dense_bytes) return false;
+        std::lock_guard<std::mutex> lock(f->row_mu);
+        if (list_table_current_locked(f)) return true;
+        const uint64_t k = f->geo.kmer_size, h = f->geo.n_hash, L = (f->stride * 8 + rblist::kLineBytes - 1) / rblist::kLineBytes;
+        const uint64_t kmers = max_len >= k ? max_len - k + 1 : 0;
+        const uint64_t per_kmer = row_table_current_locked(f) ? L : L * h;
+        if (per_kmer <= rblist::kMaxLines) return false;
+        if ((uint64_t)n_reads * 2 * kmers * (per_kmer - rblist::kMaxLines) < n_rows * (L * h + rblist::kMaxLines)) return false;
+    }
+    return true;
+}
+
+// ... and the table for such a launch: the filter's current one, built now when there is none and this version of the bits has not been
+// refused one already.  a.list_table stays null where there is none: the call goes on to the row table's rule.  Never under capture, as
+// the row table.
+static int list_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, CountLaunch &a, uint64_t *list_bytes)
+{
+    *list_bytes = 0;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    auto take = [&]() {
+        a.list_table = f->list_table;
+        a.list_side = f->list_side;
+        a.list_side_rows = f->list_side_rows;
+        a.list_lines = f->list_lines;
+        *list_bytes = f->list_bytes;
+    };
+    {
+        std::lock_guard<std::mutex> lock(f->row_mu);
+        const bool current = list_table_current_locked(f);
+        if (!current && !capturing) dibf_list_drop_locked(f);
+        if (capturing) {
+            if (!current) f->list_refused = RB_LIST_REFUSED_CAPTURE;
+            return RB_OK;
+        }
+        if (current) {
+            take();
+            return RB_OK;
+        }
+        if (list_refusal_stands_locked(f, e->row_max_bytes)) return RB_OK;
+    }
+    int rc = dibf_list_build(f, e->row_max_bytes);
+    if (rc != RB_OK) return rc;
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (list_table_current_locked(f)) take();
     return RB_OK;
 }
 
@@ -2672,12 +2944,17 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
         const bool fuses = a.n_slices == 1 && !fan_out && nf > 1 && n_reads <= e->split_threshold;
         // the row form first: it has nothing to certify, so the filter's load is not measured for it, and its gathers go to the row table,
         // whose size -- not the filter's -- says whether they are non-temporal
-        if (row_policy(e, f, a, n_reads, max_len)) {
+        if (list_policy(e, e->filters[fi], a, n_reads, max_len)) {  // the list table before the dense one; refused: on to the row rule
+            uint64_t list_bytes = 0;
+            if ((rc = list_table_for(e, e->filters[fi], fs, a, &list_bytes)) != RB_OK) return rc;
+            if (a.list_table) a.nt = list_bytes > e->nt_threshold_bytes;
+        }
+        if (!a.list_table && row_policy(e, f, a, n_reads, max_len)) {
             uint64_t row_bytes = 0;
             if ((rc = row_table_for(e, e->filters[fi], fs, &a.row_table, &row_bytes)) != RB_OK) return rc;
             if (a.row_table) a.nt = row_bytes > e->nt_threshold_bytes;
         }
-        if (!a.row_table && a.bound_prune && (a.prune_parts & 4) && a.lg == 6 && a.split_waves < 2 && a.phase.n_slices == 0 && !fuses) {
+        if (!a.list_table && !a.row_table && a.bound_prune && (a.prune_parts & 4) && a.lg == 6 && a.split_waves < 2 && a.phase.n_slices == 0 && !fuses) {
             bool cert_on = false;
             if ((rc = cert_allowance(e, fi, fs, &a.cert_d, &a.cert_c, &a.lead_min, &cert_on)) != RB_OK) return rc;
             if (!cert_on) a.prune_parts &= ~(4 | 8);  // (the lead line certifies too)
@@ -2694,7 +2971,9 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
             a.early_nf = (uint32_t)nf;
             a.early_fi = (uint32_t)fi;
         }
-        auto launch_count = [](const CountLaunch &l, hipStream_t s) { return l.row_table ? launch_ibf_count_rows(l, s) : launch_ibf_count_max(l, s); };
+        auto launch_count = [](const CountLaunch &l, hipStream_t s) {
+            return l.list_table ? launch_ibf_count_lists(l, s) : l.row_table ? launch_ibf_count_rows(l, s) : launch_ibf_count_max(l, s);
+        };
         if (a.n_slices == 1) {
             a.out = maxcount + fi;
             a.out_read_stride = (uint32_t)nf;
@@ -2794,7 +3073,21 @@ extern "C" int rb_engine_plan(rb_engine *e, size_t filter_index, size_t n_reads,
     if (a.split_waves >= 2) form = "ibf_count_max_split_kernel";
     else if (merged_plain) form = "ibf_count_max_merged_kernel";
     else if (a.phase.n_slices) form = a.multi_reads ? "ibf_count_max_phased_multi_kernel" : "ibf_count_max_phased_kernel";
-    if (!g && row_policy(e, f, a, n_reads, max_len)) {
+    bool lists_planned = false;
+    if (!g && list_policy(e, e->filters[filter_index], a, n_reads, max_len)) {
+        // the list form, when the filter has its table or the call could build it: not where this version of the bits was refused one
+        rb_dibf *fm = e->filters[filter_index];
+        std::lock_guard<std::mutex> rows_lock(fm->row_mu);
+        const bool current = list_table_current_locked(fm);
+        if (current || !list_refusal_stands_locked(fm, e->row_max_bytes)) {  // (what list_table_for asks before it builds)
+            lists_planned = true;
+            form = "ibf_count_lists_kernel";
+            // (before the census: two lines per slot, what a filter at its design load gets)
+            out->row_table_bytes = current ? fm->list_bytes : (1ull << (2 * fm->geo.kmer_size)) * rblist::slot_bytes(2);
+            out->nontemporal = out->row_table_bytes > e->nt_threshold_bytes ? 1u : 0u;
+        }
+    }
+    if (!g && !lists_planned && row_policy(e, f, a, n_reads, max_len)) {
         // the row form, when the filter has its table or the call could build it (a build that was refused for want of memory stays refused
         // in this answer until something is built or dropped)
         rb_dibf *fm = e->filters[filter_index];

@@ -4031,18 +4031,21 @@ hipError_t launch_ibf_count_max(const CountLaunch &a, hipStream_t st)
 
 // the row form (ibf_count_rows_kernel): the engine plans it for the plain whole-wave builds with three compile-time hash functions only
 template <int WPL, int NP, bool NT>
-static hipError_t launch_rows_nt(const CountLaunch &a, hipStream_t st)
+static hipError_t launch_rows_nt(const CountLaunch &a, hipStream_t st, bool twin_only = false)
 {
     const uint64_t items = (uint64_t)a.n_reads * a.n_slices;
     dim3 grid((uint32_t)((items + kWavesPerBlock - 1) / kWavesPerBlock));
     PruneCfg prune{};
     prune.flags = a.bound_prune ? (kPruneBound | (((uint32_t)a.prune_parts & 3u) << 1)) : 0u;  // (no certificate, no lead line: nothing to certify)
     prune.trace = a.prune_trace;
-    // the N-free reads from the row table, then the others from the filter's own: every item is one build's
-    hipLaunchKernelGGL((ibf_count_rows_kernel<WPL, NP, NT, true>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.row_table, a.col_begin, a.col_end,
-                       a.src, a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, prune);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    // the N-free reads from the row table, then the others from the filter's own: every item is one build's (twin_only: the list form's
+    // kernel has written the N-free reads)
+    if (!twin_only) {
+        hipLaunchKernelGGL((ibf_count_rows_kernel<WPL, NP, NT, true>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.row_table, a.col_begin, a.col_end,
+                           a.src, a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, prune);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL((ibf_count_rows_kernel<WPL, NP, NT, false>), grid, dim3(64 * kWavesPerBlock), 0, st, a.f, a.row_table, a.col_begin, a.col_end,
                        a.src, a.n_reads, a.n_slices, a.out, a.out_read_stride, a.out_slice_stride, prune);
     return hipGetLastError();
@@ -4055,17 +4058,29 @@ bool row_form_serves(const CountLaunch &a)
     return a.lg == 6 && h == 3 && a.split_waves < 2 && a.phase.n_slices == 0 && a.n_fused == 0 && !a.early_thr && a.f.k <= kRowTableMaxK;
 }
 
+static hipError_t launch_rows_builds(const CountLaunch &a, hipStream_t st, bool twin_only)
+{
+    const bool p10 = a.planes <= 10, nt = a.nt != 0;
+    if (a.wpl == 2) {
+        if (p10) return nt ? launch_rows_nt<2, 10, true>(a, st, twin_only) : launch_rows_nt<2, 10, false>(a, st, twin_only);
+        return nt ? launch_rows_nt<2, 16, true>(a, st, twin_only) : launch_rows_nt<2, 16, false>(a, st, twin_only);
+    }
+    if (p10) return nt ? launch_rows_nt<1, 10, true>(a, st, twin_only) : launch_rows_nt<1, 10, false>(a, st, twin_only);
+    return nt ? launch_rows_nt<1, 16, true>(a, st, twin_only) : launch_rows_nt<1, 16, false>(a, st, twin_only);
+}
+
 hipError_t launch_ibf_count_rows(const CountLaunch &a, hipStream_t st)
 {
     if (a.n_reads == 0) return hipSuccess;
     if (!a.row_table || !row_form_serves(a)) return hipErrorInvalidValue;
-    const bool p10 = a.planes <= 10, nt = a.nt != 0;
-    if (a.wpl == 2) {
-        if (p10) return nt ? launch_rows_nt<2, 10, true>(a, st) : launch_rows_nt<2, 10, false>(a, st);
-        return nt ? launch_rows_nt<2, 16, true>(a, st) : launch_rows_nt<2, 16, false>(a, st);
-    }
-    if (p10) return nt ? launch_rows_nt<1, 10, true>(a, st) : launch_rows_nt<1, 10, false>(a, st);
-    return nt ? launch_rows_nt<1, 16, true>(a, st) : launch_rows_nt<1, 16, false>(a, st);
+    return launch_rows_builds(a, st, false);
+}
+
+hipError_t launch_ibf_count_rows_twin(const CountLaunch &a, hipStream_t st)
+{
+    if (a.n_reads == 0) return hipSuccess;
+    if (!row_form_serves(a)) return hipErrorInvalidValue;
+    return launch_rows_builds(a, st, true);
 }
 
 hipError_t launch_row_table(const IbfDev &f, uint64_t *rows, uint64_t n_rows, hipStream_t st)

@@ -1,0 +1,103 @@
+// rb_lists.h -- the slot layout of a filter's LIST TABLE (rb_dibf_list_table_build; rb_lists.hip, ibf_count_lists_kernel), shared by the
+// kernels, the engine and the tests.  No HIP in here: tests/cpp/test_lists.cpp compiles it alone, plain and with sanitizers.
+//
+// The row of an N-free k-mer -- the AND of its h blocks -- has d^h of its bits set (config 3 at design load: about 81 of 8192), so the bin
+// numbers of the set bits take far fewer 128-byte lines than the bits.  The list table has one SLOT per such k-mer (the rank of the row
+// table: base-4 digits, first base most significant).  A slot is `lines` lines of 128 bytes, lines in {1, 2, 4}, the same for every slot
+// of a table, and holds up to 64 x lines entries of 16 bits: the row's bin numbers in ascending order, then kSentinel to the end.
+// A row with more set bits than a slot holds is an OVERFLOW slot: entry 0 is kOverflowMark, entries 1 and 2 are the low and the high half
+// of the index of its dense row (`stride` 64-bit words, as in the row table) in the table's side table, the rest is kSentinel.
+// Bin numbers are below kMaxBins, so neither mark is a bin.
+#pragma once
+#include <cstdint>
+
+namespace rblist {
+
+constexpr uint32_t kLineBytes = 128;
+constexpr uint32_t kEntriesPerLine = kLineBytes / 2;
+constexpr uint32_t kMaxLines = 4;
+constexpr uint16_t kSentinel = 0xFFFFu;
+constexpr uint16_t kOverflowMark = 0xFFFEu;
+constexpr uint32_t kMaxBins = 8192;      // one column slice of two words per lane: what the count kernel holds counters for
+constexpr uint32_t kMaxKmers = 65535;    // per strand: a bin's count fits its 16-bit counter
+// the census: a slot size serves a filter when at most one sampled row in 2^kOverflowShift overflows it
+constexpr uint32_t kOverflowShift = 10;
+constexpr uint64_t kCensusRows = 1ull << 16;
+
+constexpr uint32_t slot_entries(uint32_t lines) { return lines * kEntriesPerLine; }
+constexpr uint64_t slot_bytes(uint32_t lines) { return (uint64_t)lines * kLineBytes; }
+constexpr bool lines_valid(uint32_t lines) { return lines == 1 || lines == 2 || lines == 4; }
+
+// rows the side table holds for a table of n_rows slots: twice what the census allows to overflow, and never fewer than 64
+constexpr uint64_t side_capacity(uint64_t n_rows) { return (n_rows >> (kOverflowShift - 1)) + 64; }
+
+// What one wave of ibf_count_lists_kernel keeps in LDS, and what launch_lists_nt asks for: a 16-bit counter for every bin, two per dword,
+// rounded up to 1 KiB; one spare dword per lane behind them (where an entry that is no bin adds 0); the bases of one 64-k-mer tile as
+// Dna5 ordinals (64 + k - 1 <= 76 at k <= 13).
+constexpr uint32_t kCountSpareDwords = 64;
+constexpr uint32_t kCountStageBytes = 128;
+constexpr uint32_t kLdsPerCuBytes = 160 * 1024;
+constexpr uint32_t count_cnt_dwords(uint32_t n_bins) { return ((n_bins + 1u) / 2u + 255u) & ~255u; }
+constexpr uint32_t count_lds_bytes(uint32_t n_bins) { return (count_cnt_dwords(n_bins) + kCountSpareDwords) * 4u + kCountStageBytes; }
+// one wave per workgroup: the workgroups of a CU that the LDS leaves room for
+constexpr uint32_t count_resident_workgroups(uint32_t n_bins) { return kLdsPerCuBytes / count_lds_bytes(n_bins); }
+
+// The census's verdict. over[i] = sampled rows with more than 64 << i set bits (i = 0, 1, 2), of `sampled` rows.
+// -> lines of the smallest slot that at most sampled >> kOverflowShift rows overflow, or 0: no slot size serves (the filter is too dense)
+inline uint32_t choose_lines(const uint64_t over[3], uint64_t sampled)
+{
+    const uint64_t allowed = sampled >> kOverflowShift;
+    for (uint32_t i = 0; i < 3; ++i)
+        if (over[i] <= allowed) return 1u << i;
+    return 0;
+}
+
+// What one slot says.  n >= 0: a list of n bins (ascending, written to bins[0..n)); -1: an overflow slot, *side_index names its dense
+// row; -2: not a slot the builder writes (an entry out of order, a bin behind a sentinel, a mark in the wrong place).
+inline int decode_slot(const uint16_t *slot, uint32_t lines, uint16_t *bins, uint32_t *side_index)
+{
+    const uint32_t cap = slot_entries(lines);
+    if (slot[0] == kOverflowMark) {
+        for (uint32_t i = 3; i < cap; ++i)
+            if (slot[i] != kSentinel) return -2;
+        *side_index = (uint32_t)slot[1] | ((uint32_t)slot[2] << 16);
+        return -1;
+    }
+    uint32_t n = 0;
+    while (n < cap && slot[n] != kSentinel) {
+        if (slot[n] >= kMaxBins || (n && slot[n] <= slot[n - 1])) return -2;
+        bins[n] = slot[n];
+        ++n;
+    }
+    for (uint32_t i = n; i < cap; ++i)
+        if (slot[i] != kSentinel) return -2;
+    return (int)n;
+}
+
+// ... and the other way round, as the builder does it: the set bits of a dense row of `n_words` words (bins below n_bins) into a slot.
+// -> false: the row overflows the slot, which then names side_index
+inline bool encode_slot(const uint64_t *row, uint32_t n_words, uint32_t n_bins, uint32_t lines, uint32_t side_index, uint16_t *slot)
+{
+    const uint32_t cap = slot_entries(lines);
+    uint32_t n = 0;
+    bool fits = true;
+    for (uint32_t i = 0; i < cap; ++i) slot[i] = kSentinel;
+    for (uint32_t w = 0; w < n_words && fits; ++w)
+        for (uint32_t b = 0; b < 64; ++b) {
+            const uint32_t bin = w * 64 + b;
+            if (bin >= n_bins || !((row[w] >> b) & 1ull)) continue;
+            if (n == cap) {
+                fits = false;
+                break;
+            }
+            slot[n++] = (uint16_t)bin;
+        }
+    if (fits) return true;
+    for (uint32_t i = 0; i < cap; ++i) slot[i] = kSentinel;
+    slot[0] = kOverflowMark;
+    slot[1] = (uint16_t)(side_index & 0xFFFFu);
+    slot[2] = (uint16_t)(side_index >> 16);
+    return false;
+}
+
+}  // namespace rblist

@@ -1,0 +1,401 @@
+// rb_lists.hip -- the LIST FORM of the plain count kernel: a filter's list table (rb_lists.h: per N-free k-mer the bin numbers of its
+// row, the AND of its h blocks, in one slot of 1, 2 or 4 lines) and the kernel that counts from it.  A translation unit of its own: what
+// it needs of rb_kernels.hip -- how a read's bases are found and turned into Dna5 ordinals -- is the few lines below, written again.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "rb_device.h"
+#include "rb_lists.h"
+
+namespace rb {
+
+// (BaseSrc and make_base_src of rb_kernels.hip)
+struct ListBaseSrc {
+    const uint8_t *bytes;
+    const uint8_t *nm;
+    uint32_t first;
+    __device__ __forceinline__ uint32_t ord(uint32_t i) const
+    {
+        if (nm == nullptr) return rbspec::dna5_ord(bytes[i]);
+        const uint32_t b = first + i;
+        const uint32_t code = (bytes[b >> 2] >> ((b & 3u) << 1)) & 3u;
+        return ((nm[b >> 3] >> (b & 7u)) & 1u) ? 4u : code;
+    }
+};
+
+__device__ __forceinline__ ListBaseSrc make_list_base_src(const ReadSrc &r, uint32_t item, uint32_t *len_out)
+{
+    const uint32_t rid = r.ids ? r.ids[item] : item;
+    const uint32_t len = r.lens[item];
+    *len_out = (r.max_len && len > r.max_len) ? r.max_len : len;  // never beyond the declared bound
+    ListBaseSrc b;
+    if (r.nmask) {
+        b.bytes = r.seqs + r.offsets[rid];
+        b.nm = r.nmask + r.nmask_offsets[rid];
+        b.first = r.base_off;
+    } else {
+        b.bytes = r.seqs + r.offsets[rid] + r.base_off;
+        b.nm = nullptr;
+        b.first = 0;
+    }
+    return b;
+}
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, 64));
+    return v;
+}
+
+// one listed bin: a returning add into its half of the counter dword, and the lane's running maximum of "what the bin now counts".
+// nb is the lane's bound on bin numbers (n_bins, or 0 for a lane whose dword is no part of the slot): sentinel, overflow mark and every
+// number the counters have no room for fall outside it.  (The overflow rows' form; the lists take list_add / list_seen below.)
+__device__ __forceinline__ void count_bin(uint32_t *cnt, uint32_t bin, uint32_t nb, uint32_t &m)
+{
+    if (bin < nb) {
+        const uint32_t sh = (bin & 1u) << 4;
+        const uint32_t old = __hip_atomic_fetch_add(&cnt[bin >> 1], 1u << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        m = max(m, ((old >> sh) & 0xFFFFu) + 1u);
+    }
+}
+
+// The same without control flow, in two halves, so that a group of rows issues its adds back to back and looks at what came back
+// afterwards (a branch around every add made the wave wait for each one: 128 LDS round trips per tile, one after the other).  An entry
+// that is no bin adds 0 to the lane's own spare dword behind the counters (zero, and it stays zero), so it sees 0 and adds 0 to the maximum.
+__device__ __forceinline__ uint32_t list_add(uint32_t *cnt, uint32_t bin, uint32_t nb, uint32_t spare)
+{
+    const bool valid = bin < nb;
+    const uint32_t sh = (bin & 1u) << 4;
+    return __hip_atomic_fetch_add(&cnt[valid ? bin >> 1 : spare], (valid ? 1u : 0u) << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void list_seen(uint32_t old, uint32_t bin, uint32_t nb, uint32_t &m)
+{
+    m = max(m, ((old >> ((bin & 1u) << 4)) & 0xFFFFu) + (bin < nb ? 1u : 0u));
+}
+
+typedef unsigned int list_u32x2 __attribute__((ext_vector_type(2)));
+constexpr uint32_t kListSpareDwords = rblist::kCountSpareDwords;  // one per lane, behind the counters
+
+// One wave, one workgroup, one read; N-free reads only (a wave whose read has a base outside ACGT leaves at once: the three-hash twin
+// ibf_count_rows_kernel<.., false>, launched behind this kernel, writes those).  Per strand the wave keeps a 16-bit counter for every bin
+// in LDS, two per dword, cleared first; per tile of 64 k-mers every lane ranks its own k-mer (base 4, first base most significant; the
+// reverse strand: the rank of the reverse complement), the tile's slots are gathered back to back -- lane l takes dword l of a two-line
+// slot, dwords 2l and 2l + 1 of a four-line slot (two halves of 32 slots then), dword l & 31 of a one-line slot, where lanes 32-63 count
+// nothing -- and every entry below n_bins is one count_bin.  Bins within a slot are distinct, so within one instruction a counter half is
+// touched by one lane only, and the strand's maximum is the wave maximum of the lanes' running maxima: the counters are never scanned.
+// An overflow slot (rb_lists.h) names a dense row of the side table; its set bits are counted one by one after the tile's lists.
+// Pruning (flags & kPruneBound): the second strand is skipped when the first reached n, and it stops at the tile boundary where its
+// maximum so far plus the k-mers still to come cannot pass the first strand's maximum.  Exact: the output is the maximum over both.
+template <int LINES, bool NT>
+__global__ __launch_bounds__(64) void ibf_count_lists_kernel(IbfDev f, const uint32_t *__restrict__ slots, const uint64_t *__restrict__ side,
+                                                             uint32_t side_rows, ReadSrc src, uint32_t n_reads, uint16_t *__restrict__ out,
+                                                             uint32_t out_read_stride, uint32_t flags, uint64_t *__restrict__ trace,
+                                                             uint32_t cnt_dwords)
+{
+    static_assert(LINES == 1 || LINES == 2 || LINES == 4, "slot sizes of rb_lists.h");
+    constexpr int DW = LINES == 4 ? 2 : 1;  // dwords per lane and slot
+    constexpr int R = 64 / DW;              // slots gathered back to back: 64 registers of a lane either way
+    constexpr uint32_t SLOT_DWORDS = LINES * 32;
+    extern __shared__ uint32_t s_lds[];
+    uint32_t *cnt = s_lds;                                                                   // cnt_dwords counters (a multiple of 256), kListSpareDwords spares
+    uint8_t *stage = reinterpret_cast<uint8_t *>(s_lds + cnt_dwords + kListSpareDwords);    // rblist::kCountStageBytes
+    const uint32_t lane = threadIdx.x;
+    const uint32_t read = blockIdx.x;
+    if (read >= n_reads) return;
+
+    uint32_t len;
+    const ListBaseSrc seq = make_list_base_src(src, read, &len);
+    const uint32_t k = f.k;
+    const uint32_t n = len >= k ? len - k + 1 : 0;
+    bool outside = false;
+    for (uint32_t i = lane; i < len; i += 64) outside |= seq.ord(i) > 3u;
+    if (__ballot(outside) != 0ULL) return;  // wave-uniform: the twin's read
+
+    const bool bound = (flags & kPruneBound) != 0;
+    const uint32_t nb = (LINES == 1 && lane >= 32) ? 0u : f.n_bins;
+    const uint32_t lane_dword = LINES == 1 ? (lane & 31u) : lane * DW;
+    const uint32_t spare = cnt_dwords + lane;
+    uint32_t best = 0, stops = 0;
+#pragma unroll 1
+    for (int strand = 0; strand < 2; ++strand) {
+        if (bound && strand == 1 && best >= n) break;  // wave-uniform
+        __builtin_amdgcn_wave_barrier();
+        {
+            uint4 *c4 = reinterpret_cast<uint4 *>(cnt);
+            for (uint32_t i = lane; i < (cnt_dwords + kListSpareDwords) / 4; i += 64) c4[i] = make_uint4(0, 0, 0, 0);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        uint32_t m = 0, stopped = n;
+#pragma unroll 1
+        for (uint32_t mt = 0; mt < n; mt += 64) {
+            if (bound && strand == 1) {  // a bin counts at most once per k-mer: nothing to come can pass `best`
+                const uint32_t so_far = __builtin_amdgcn_readfirstlane(wave_max_u32(m));
+                if (so_far + (n - mt) <= best) {
+                    stopped = mt;
+                    break;
+                }
+            }
+            // ---- the tile's bases as Dna5 ordinals, and one rank per lane
+            const uint32_t wlen = min(64u + k - 1u, len - mt);
+            __builtin_amdgcn_wave_barrier();
+            for (uint32_t i = lane; i < wlen; i += 64) stage[i] = (uint8_t)seq.ord(mt + i);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            const uint32_t p = mt + lane;
+            uint32_t rank = 0;
+            if (p < n) {
+                const uint8_t *b = stage + lane;
+                if (strand == 0) {
+                    for (uint32_t i = 0; i < k; ++i) rank = (rank << 2) | (b[i] & 3u);
+                } else {
+                    for (uint32_t i = 0; i < k; ++i) rank = (rank << 2) | (rbspec::dna5_comp(b[k - 1 - i], f.comp_n) & 3u);
+                }
+            }
+            const uint32_t in_tile = __builtin_amdgcn_readfirstlane(min(64u, n - mt));
+#pragma unroll 1
+            for (uint32_t first = 0; first < in_tile; first += R) {
+                // ---- the gathers, back to back; a slot past the end of the strand stays a row of sentinels
+                uint32_t v[R][DW];
+#pragma unroll
+                for (int u = 0; u < R; ++u) {
+#pragma unroll
+                    for (int d = 0; d < DW; ++d) v[u][d] = 0xFFFFFFFFu;
+                    if (first + (uint32_t)u < in_tile) {  // wave-uniform
+                        const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)rank, (int)((R == 64 ? 0 : first) + u));
+                        const uint32_t *ptr = slots + (size_t)slot * SLOT_DWORDS + lane_dword;  // slot < 4^k: masked digits
+                        if constexpr (DW == 2) {
+                            const list_u32x2 *p2 = reinterpret_cast<const list_u32x2 *>(ptr);
+                            const list_u32x2 q = NT ? __builtin_nontemporal_load(p2) : *p2;
+                            v[u][0] = q.x;
+                            v[u][1] = q.y;
+                        } else {
+                            v[u][0] = NT ? __builtin_nontemporal_load(ptr) : *ptr;
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                // ---- overflow slots are set aside (lane u keeps the side index of slot u) and list nothing
+                uint64_t overflow = 0;
+                uint32_t side_index = 0;
+#pragma unroll
+                for (int u = 0; u < R; ++u) {
+                    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)v[u][0], 0);
+                    if ((d0 & 0xFFFFu) == rblist::kOverflowMark) {  // wave-uniform
+                        const uint32_t d1 = DW == 2 ? (uint32_t)__builtin_amdgcn_readlane((int)v[u][1], 0) : (uint32_t)__builtin_amdgcn_readlane((int)v[u][0], 1);
+                        overflow |= 1ull << u;
+                        if (lane == (uint32_t)u) side_index = (d0 >> 16) | ((d1 & 0xFFFFu) << 16);
+#pragma unroll
+                        for (int d = 0; d < DW; ++d) v[u][d] = 0xFFFFFFFFu;
+                    }
+                }
+                // ---- count: eight slots' adds back to back, then what they returned
+                constexpr int G = 8;
+                if (LINES != 1 || lane < 32)  // a one-line slot is 32 dwords: the upper half of the wave sits the adds out, all of them at once
+#pragma unroll
+                for (int g = 0; g < R / G; ++g) {
+                    uint32_t old[G][DW][2];
+#pragma unroll
+                    for (int u = 0; u < G; ++u)
+#pragma unroll
+                        for (int d = 0; d < DW; ++d) {
+                            old[u][d][0] = list_add(cnt, v[g * G + u][d] & 0xFFFFu, nb, spare);
+                            old[u][d][1] = list_add(cnt, v[g * G + u][d] >> 16, nb, spare);
+                        }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int u = 0; u < G; ++u)
+#pragma unroll
+                        for (int d = 0; d < DW; ++d) {
+                            list_seen(old[u][d][0], v[g * G + u][d] & 0xFFFFu, nb, m);
+                            list_seen(old[u][d][1], v[g * G + u][d] >> 16, nb, m);
+                        }
+                }
+                while (overflow) {  // wave-uniform, rare: the dense row's set bits one by one
+                    const int u = __builtin_ctzll(overflow);
+                    overflow &= overflow - 1;
+                    const uint32_t idx = (uint32_t)__builtin_amdgcn_readlane((int)side_index, u);
+                    if (idx >= side_rows) continue;  // (the builder never names a row it did not write)
+                    const uint64_t *row = side + (size_t)idx * f.stride;
+                    for (uint32_t w = lane; w < f.bin_width; w += 64) {
+                        uint64_t word = row[w];
+                        while (word) {
+                            const uint32_t bit = (uint32_t)__builtin_ctzll(word);
+                            word &= word - 1;
+                            count_bin(cnt, w * 64u + bit, f.n_bins, m);
+                        }
+                    }
+                }
+            }
+        }
+        best = max(best, (uint32_t)__builtin_amdgcn_readfirstlane(wave_max_u32(m)));
+        stops = strand == 0 ? (stopped & 0xFFFFu) : (stops | (stopped << 16));
+    }
+    if (lane == 0) out[(size_t)read * out_read_stride] = (uint16_t)best;
+    if (trace) {
+        if (lane == 0) trace[read] = prune_trace_record(0u, false, 0u, stops & 0xFFFFu, stops >> 16, 0u);
+    }
+}
+
+// The list table of a filter, one wave per slot (the waves stride over the slots, as ibf_row_table_kernel's over its rows): the AND of
+// the k-mer's h blocks, word `lane` and word `lane + 64` of it per lane (a block of at most 128 words), a wave prefix sum of the popcounts,
+// and every lane writes the bin numbers of its set bits at its offset -- into the slot's image in LDS, which starts as all sentinels and
+// leaves as whole dwords.  Pad words and the bits behind n_bins list nothing.  A row with more set bits than the slot holds takes the next
+// row of the side table (an atomic counter; the order may vary from build to build, the rows may not) and leaves an overflow slot; past
+// `side_cap` it writes no row, and the host, which reads the counter, refuses the table.
+// lines == 0 is the CENSUS: nothing is written but counters[1 + i] += 1 for a row with more than 64 << i set bits (i = 0, 1, 2); `step`
+// is the distance between the rows it looks at.
+__global__ __launch_bounds__(256) void ibf_list_table_kernel(IbfDev f, uint32_t *__restrict__ slots, uint64_t *__restrict__ side,
+                                                             uint32_t *__restrict__ counters, uint64_t n_rows, uint64_t step, uint32_t lines,
+                                                             uint32_t side_cap)
+{
+    __shared__ uint16_t s_slot[4][rblist::kMaxLines * rblist::kEntriesPerLine];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const uint64_t S = f.stride;
+    const uint32_t W = f.bin_width;
+    const uint32_t nh = f.n_hash < rbspec::kMaxHash ? f.n_hash : rbspec::kMaxHash;
+    const uint32_t rem = f.n_bins & 63u;
+    uint16_t *img = s_slot[wave];
+    for (uint64_t r = (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * step; r < n_rows; r += waves * step) {  // wave-uniform
+        uint64_t v = 0;
+        for (uint32_t i = 0; i < f.k; ++i) v = v * 5u + ((r >> (2u * (f.k - 1u - i))) & 3u);
+        uint64_t word[2];
+        uint32_t c[2], incl[2], total[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const uint32_t w = lane + 64u * j;
+            uint64_t acc = 0;
+            if (w < W) {
+                acc = ~0ULL;
+                for (uint32_t h = 0; h < nh; ++h) {
+                    const uint32_t b = rbspec::block_index(v, f.precalc[h], f.n_blocks, f.magic, f.pow2_mask);
+                    acc &= f.words[(uint64_t)b * S + w];
+                }
+                if (w == W - 1 && rem) acc &= (1ULL << rem) - 1;
+            }
+            word[j] = acc;
+            c[j] = (uint32_t)__popcll(acc);
+            uint32_t s = c[j];
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t o = (uint32_t)__shfl_up((int)s, d, 64);
+                if (lane >= (uint32_t)d) s += o;
+            }
+            incl[j] = s;
+            total[j] = (uint32_t)__builtin_amdgcn_readlane((int)s, 63);
+        }
+        const uint32_t set = total[0] + total[1];
+        if (lines == 0) {
+            if (lane == 0)
+                for (uint32_t i = 0; i < 3; ++i)
+                    if (set > (64u << i)) atomicAdd(&counters[1 + i], 1u);
+            continue;
+        }
+        const uint32_t cap = lines * rblist::kEntriesPerLine;
+        __builtin_amdgcn_wave_barrier();
+        reinterpret_cast<uint2 *>(img)[lane] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);  // 4 entries per lane: all kMaxLines lines
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        if (set <= cap) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                uint32_t at = (j ? total[0] : 0u) + incl[j] - c[j];
+                uint64_t bits = word[j];
+                while (bits) {
+                    const uint32_t bit = (uint32_t)__builtin_ctzll(bits);
+                    bits &= bits - 1;
+                    img[at++] = (uint16_t)((lane + 64u * j) * 64u + bit);  // at < set <= cap
+                }
+            }
+        } else {
+            uint32_t idx = 0;
+            if (lane == 0) idx = atomicAdd(&counters[0], 1u);
+            idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)idx);
+            if (lane == 0) {
+                img[0] = rblist::kOverflowMark;
+                img[1] = (uint16_t)(idx & 0xFFFFu);
+                img[2] = (uint16_t)(idx >> 16);
+            }
+            if (idx < side_cap) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const uint32_t w = lane + 64u * j;
+                    if (w < S) side[(uint64_t)idx * S + w] = word[j];
+                }
+                for (uint32_t w = lane + 128u; w < S; w += 64) side[(uint64_t)idx * S + w] = 0;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t slot_dwords = lines * 32u;
+        for (uint32_t d = lane; d < slot_dwords; d += 64) slots[r * slot_dwords + d] = reinterpret_cast<const uint32_t *>(img)[d];
+    }
+}
+
+static hipError_t list_builder_args_ok(const IbfDev &f, uint64_t n_rows)
+{
+    if (n_rows == 0 || n_rows > (1ull << (2 * kRowTableMaxK)) || f.k == 0 || f.k > kRowTableMaxK) return hipErrorInvalidValue;
+    if (f.bin_width == 0 || f.bin_width > 128 || f.n_bins > rblist::kMaxBins || f.stride < f.bin_width) return hipErrorInvalidValue;
+    return hipSuccess;
+}
+
+hipError_t launch_list_census(const IbfDev &f, uint32_t *counters, uint64_t n_rows, uint64_t step, hipStream_t st)
+{
+    hipError_t e = list_builder_args_ok(f, n_rows);
+    if (e != hipSuccess || step == 0) return hipErrorInvalidValue;
+    const uint64_t looked_at = (n_rows + step - 1) / step;
+    const uint64_t blocks = std::min<uint64_t>((looked_at + 3) / 4, 1ull << 20);
+    hipLaunchKernelGGL(ibf_list_table_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, f, (uint32_t *)nullptr, (uint64_t *)nullptr, counters, n_rows,
+                       step, 0u, 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_list_table(const IbfDev &f, uint16_t *slots, uint64_t *side, uint32_t *counters, uint64_t n_rows, uint32_t lines,
+                             uint32_t side_cap, hipStream_t st)
+{
+    hipError_t e = list_builder_args_ok(f, n_rows);
+    if (e != hipSuccess || !rblist::lines_valid(lines) || !slots || !side || !counters) return hipErrorInvalidValue;
+    const uint64_t blocks = std::min<uint64_t>((n_rows + 3) / 4, 1ull << 20);
+    hipLaunchKernelGGL(ibf_list_table_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, f, reinterpret_cast<uint32_t *>(slots), side, counters, n_rows,
+                       (uint64_t)1, lines, side_cap);
+    return hipGetLastError();
+}
+
+// the list form serves what the row form serves, with one column slice of at most 128 words and strands of at most 65 535 k-mers (the
+// engine checks the latter against the declared max_len: make_list_base_src never looks beyond it)
+bool list_form_serves(const CountLaunch &a)
+{
+    return row_form_serves(a) && a.n_slices == 1 && a.f.n_bins <= rblist::kMaxBins && a.f.bin_width <= 128 && a.src.max_len != 0 &&
+           a.src.max_len < a.f.k + rblist::kMaxKmers;
+}
+
+template <int LINES>
+static hipError_t launch_lists_nt(const CountLaunch &a, hipStream_t st)
+{
+    const uint32_t cnt_dwords = rblist::count_cnt_dwords(a.f.n_bins);
+    const size_t lds = rblist::count_lds_bytes(a.f.n_bins);
+    const uint32_t flags = a.bound_prune ? kPruneBound : 0u;
+    const uint32_t *slots = reinterpret_cast<const uint32_t *>(a.list_table);
+    if (a.nt)
+        hipLaunchKernelGGL((ibf_count_lists_kernel<LINES, true>), dim3(a.n_reads), dim3(64), lds, st, a.f, slots, a.list_side, a.list_side_rows, a.src,
+                           a.n_reads, a.out, a.out_read_stride, flags, a.prune_trace, cnt_dwords);
+    else
+        hipLaunchKernelGGL((ibf_count_lists_kernel<LINES, false>), dim3(a.n_reads), dim3(64), lds, st, a.f, slots, a.list_side, a.list_side_rows, a.src,
+                           a.n_reads, a.out, a.out_read_stride, flags, a.prune_trace, cnt_dwords);
+    return hipGetLastError();
+}
+
+// the N-free reads from the list table, then the others from the filter's own table (launch_ibf_count_rows_twin, rb_kernels.hip)
+hipError_t launch_ibf_count_lists(const CountLaunch &a, hipStream_t st)
+{
+    if (a.n_reads == 0) return hipSuccess;
+    if (!a.list_table || !a.list_side || !list_form_serves(a)) return hipErrorInvalidValue;
+    hipError_t e = a.list_lines == 1 ? launch_lists_nt<1>(a, st) : a.list_lines == 2 ? launch_lists_nt<2>(a, st) : a.list_lines == 4 ? launch_lists_nt<4>(a, st) : hipErrorInvalidValue;
+    if (e != hipSuccess) return e;
+    return launch_ibf_count_rows_twin(a, st);
+}
+
+}  // namespace rb
