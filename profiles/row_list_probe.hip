@@ -12,6 +12,11 @@
 //   count  : per row and lane two returning adds (ds_add_rtn_u32 of 1 << 16·(bin & 1) at dword bin >> 1) for the entries below
 //            8192, and a running maximum of "old half + 1", as the kernel would keep it
 //   nolds  : the same loop with the LDS part replaced by an XOR
+//   scan   : the count code ibf_count_lists_kernel has since taken: two adds per row and lane that return nothing (an entry that is no
+//            bin is clamped to the lane's own spare dword behind the counters), no running maximum, and per read one scan of the
+//            counters (ds_read_b128, packed 16-bit maximum, one wave reduction) fused with the clear.  Nine waves per CU then
+//   rolling: the scan mode with a rolling refill: when group g (eight rows) of tile t has been counted, the loads of group g of tile
+//            t + 1 are issued into the same registers, so a wave always has R - 8 to R rows in flight, across tile and read edges
 // Prints rows/s and lines/s (2 per row) per setting, best of 3 runs after one warm-up, and the gate of the issue: today's row
 // kernel completes 6.16 G rows/s at 0.946 of its own probe, so the list form can only win above 6.5 G rows/s.
 // build+run on the GPU box:  hipcc -O3 --offload-arch=gfx950 profiles/row_list_probe.hip -o /tmp/row_list_probe && /tmp/row_list_probe
@@ -60,6 +65,96 @@ __global__ __launch_bounds__(256) void fill_rows(uint32_t *__restrict__ table, u
         const uint32_t stride = kBins / n_r;
         table[i] = entry(r, 2 * l, n_r, stride) | (entry(r, 2 * l + 1, n_r, stride) << 16);
     }
+}
+
+constexpr uint32_t kSpareDwords = 64;
+
+typedef unsigned short probe_u16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void add2(uint32_t *cnt, uint32_t v, uint32_t spare)
+{
+    __hip_atomic_fetch_add(&cnt[min((v & 0xFFFFu) >> 1, spare)], 1u << ((v << 4) & 16u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(&cnt[min(v >> 17, spare)], 1u << ((v >> 12) & 16u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ __forceinline__ uint32_t scan_and_clear(uint32_t *cnt, uint32_t lane)
+{
+    uint4 *c4 = reinterpret_cast<uint4 *>(cnt);
+    probe_u16x2 a = {0, 0};
+#pragma unroll
+    for (uint32_t i = 0; i < kBins / 2 / 4 / 64; ++i) {
+        const uint4 q = c4[i * 64 + lane];
+        a = __builtin_elementwise_max(a, __builtin_elementwise_max(__builtin_elementwise_max(__builtin_bit_cast(probe_u16x2, q.x), __builtin_bit_cast(probe_u16x2, q.y)),
+                                                                   __builtin_elementwise_max(__builtin_bit_cast(probe_u16x2, q.z), __builtin_bit_cast(probe_u16x2, q.w))));
+        c4[i * 64 + lane] = make_uint4(0, 0, 0, 0);
+    }
+    uint32_t m = max((uint32_t)a.x, (uint32_t)a.y);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+    return m;
+}
+
+// the scan and rolling modes: kBins / 2 + kSpareDwords dwords of LDS
+template <int R, bool NT, bool ROLLING>
+__global__ __launch_bounds__(64) void list_probe_scan(const uint32_t *__restrict__ table, uint32_t lg_rows, uint32_t reads, uint32_t *out)
+{
+    extern __shared__ uint32_t cnt[];
+    constexpr int G = 8;
+    constexpr uint32_t T = kRowsPerRead / R;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t spare = kBins / 2 + lane;
+    uint32_t best = 0;
+    uint64_t s = mix((uint64_t)blockIdx.x + 1);
+    scan_and_clear(cnt, lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    uint32_t v[R];
+    s += 0x9E3779B97F4A7C15ULL;
+    uint32_t mine = (uint32_t)(mix(s + lane) >> (64 - lg_rows));
+    if constexpr (ROLLING) {
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const uint32_t *p = table + (size_t)(uint32_t)__builtin_amdgcn_readlane((int)mine, u) * kRowDwords + lane;
+            v[u] = NT ? __builtin_nontemporal_load(p) : *p;
+        }
+    }
+#pragma unroll 1
+    for (uint32_t t = 0; t < reads * T; ++t) {
+        if constexpr (!ROLLING) {
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                const uint32_t *p = table + (size_t)(uint32_t)__builtin_amdgcn_readlane((int)mine, u) * kRowDwords + lane;
+                v[u] = NT ? __builtin_nontemporal_load(p) : *p;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        s += 0x9E3779B97F4A7C15ULL;
+        mine = (uint32_t)(mix(s + lane) >> (64 - lg_rows));  // the next tile's rows
+#pragma unroll
+        for (int g = 0; g < R / G; ++g) {
+#pragma unroll
+            for (int u = 0; u < G; ++u) add2(cnt, v[g * G + u], spare);
+            if constexpr (ROLLING) {
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < G; ++u) {
+                    const uint32_t *p = table + (size_t)(uint32_t)__builtin_amdgcn_readlane((int)mine, g * G + u) * kRowDwords + lane;
+                    v[g * G + u] = NT ? __builtin_nontemporal_load(p) : *p;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (t % T == T - 1) {  // a read ends
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            best = max(best, scan_and_clear(cnt, lane));
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        }
+    }
+    uint32_t acc = 0;
+    if constexpr (ROLLING) {
+#pragma unroll
+        for (int u = 0; u < R; ++u) acc ^= v[u];  // the last refill is waited for and used
+    }
+    if ((best ^ acc) == 0x12345678u) out[0] = best;
 }
 
 template <int R, bool NT, bool LDS>
@@ -115,7 +210,7 @@ __global__ __launch_bounds__(64) void list_probe(const uint32_t *__restrict__ ta
     if ((best ^ acc) == 0x12345678u) out[0] = best;
 }
 
-template <int R, bool NT, bool LDS>
+template <int R, bool NT, bool LDS, int MODE = 0>
 static int run(const uint32_t *table, uint32_t lg_rows, uint32_t reads, uint32_t *out, double *rows_per_s)
 {
     const int blocks = 256 * 10 * 8;  // ten waves per CU, eight rounds
@@ -125,7 +220,10 @@ static int run(const uint32_t *table, uint32_t lg_rows, uint32_t reads, uint32_t
     float best = 1e30f;
     for (int rep = 0; rep < 4; ++rep) {
         CHECK(hipEventRecord(a));
-        hipLaunchKernelGGL((list_probe<R, NT, LDS>), dim3(blocks), dim3(64), kBins * 2, 0, table, lg_rows, reads, out);
+        if constexpr (MODE == 0)
+            hipLaunchKernelGGL((list_probe<R, NT, LDS>), dim3(blocks), dim3(64), kBins * 2, 0, table, lg_rows, reads, out);
+        else
+            hipLaunchKernelGGL((list_probe_scan<R, NT, MODE == 2>), dim3(blocks), dim3(64), kBins * 2 + kSpareDwords * 4, 0, table, lg_rows, reads, out);
         CHECK(hipGetLastError());
         CHECK(hipEventRecord(b));
         CHECK(hipEventSynchronize(b));
@@ -136,7 +234,7 @@ static int run(const uint32_t *table, uint32_t lg_rows, uint32_t reads, uint32_t
     const double rows = (double)blocks * reads * kRowsPerRead;
     *rows_per_s = rows / best / 1e6;  // G rows/s
     printf("rows in flight %2d  %-8s  %-8s : %7.2f G rows/s  %7.2f G lines/s  (%.1f ms)\n", R, NT ? "nt" : "temporal",
-           LDS ? "lds adds" : "no lds", *rows_per_s, 2.0 * *rows_per_s, best);
+           MODE == 2 ? "rolling" : MODE == 1 ? "scan" : LDS ? "lds adds" : "no lds", *rows_per_s, 2.0 * *rows_per_s, best);
     fflush(stdout);
     CHECK(hipEventDestroy(a));
     CHECK(hipEventDestroy(b));
@@ -161,7 +259,7 @@ int main(int argc, char **argv)
     CHECK(hipDeviceSynchronize());
     printf("table: 2^%u rows of 256 bytes = %.2f GiB, 72-91 of 128 entries per row; %u reads of %u rows per wave, 10 waves per CU\n", lg_rows,
            bytes / 1073741824.0, reads, kRowsPerRead);
-    double g[8];
+    double g[16];
     int i = 0;
     if (run<32, true, true>(table, lg_rows, reads, out, &g[i++])) return 1;
     if (run<64, true, true>(table, lg_rows, reads, out, &g[i++])) return 1;
@@ -171,6 +269,14 @@ int main(int argc, char **argv)
     if (run<64, true, false>(table, lg_rows, reads, out, &g[i++])) return 1;
     if (run<32, false, false>(table, lg_rows, reads, out, &g[i++])) return 1;
     if (run<64, false, false>(table, lg_rows, reads, out, &g[i++])) return 1;
+    // the count code the kernel has since taken, and the rolling refill on top of it (issue: build it if it gains more than 5 %)
+    if (run<64, true, true, 1>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<64, true, true, 2>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<64, false, true, 1>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<64, false, true, 2>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<32, true, true, 1>(table, lg_rows, reads, out, &g[i++])) return 1;
+    if (run<32, true, true, 2>(table, lg_rows, reads, out, &g[i++])) return 1;
+    printf("rolling over scan, 64 rows in flight, nt: x%.4f\n", g[9] / g[8]);
     double best = 0;
     for (int k = 0; k < 4; ++k) best = g[k] > best ? g[k] : best;
     printf("best with the LDS adds: %.2f G rows/s; gate 6.50 G rows/s (6.16 / 0.946): %s\n", best, best > 6.5 ? "go on" : "stop");

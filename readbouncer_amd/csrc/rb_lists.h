@@ -32,8 +32,9 @@ constexpr bool lines_valid(uint32_t lines) { return lines == 1 || lines == 2 || 
 constexpr uint64_t side_capacity(uint64_t n_rows) { return (n_rows >> (kOverflowShift - 1)) + 64; }
 
 // What one wave of ibf_count_lists_kernel keeps in LDS, and what launch_lists_nt asks for: a 16-bit counter for every bin, two per dword,
-// rounded up to 1 KiB; one spare dword per lane behind them (where an entry that is no bin adds 0); the bases of one 64-k-mer tile as
-// Dna5 ordinals (64 + k - 1 <= 76 at k <= 13).
+// rounded up to 1 KiB (the kernel scans them in 16-byte pieces per lane: whole pieces, and the pad counts nothing); one spare dword per
+// lane behind them, where the entries that are no bin are added -- junk that is never read or cleared; the bases of one 64-k-mer tile
+// as Dna5 ordinals (64 + k - 1 <= 76 at k <= 13).
 constexpr uint32_t kCountSpareDwords = 64;
 constexpr uint32_t kCountStageBytes = 128;
 constexpr uint32_t kLdsPerCuBytes = 160 * 1024;

@@ -15,13 +15,21 @@ struct ListBaseSrc {
     const uint8_t *bytes;
     const uint8_t *nm;
     uint32_t first;
-    __device__ __forceinline__ uint32_t ord(uint32_t i) const
+    // base i in two halves, so that the load can be issued well before the ordinal is needed: what is loaded, and the ordinal from it
+    __device__ __forceinline__ uint32_t raw(uint32_t i) const
     {
-        if (nm == nullptr) return rbspec::dna5_ord(bytes[i]);
+        if (nm == nullptr) return bytes[i];
         const uint32_t b = first + i;
-        const uint32_t code = (bytes[b >> 2] >> ((b & 3u) << 1)) & 3u;
-        return ((nm[b >> 3] >> (b & 7u)) & 1u) ? 4u : code;
+        return (uint32_t)bytes[b >> 2] | ((uint32_t)nm[b >> 3] << 8);
     }
+    __device__ __forceinline__ uint32_t ord_of(uint32_t loaded, uint32_t i) const
+    {
+        if (nm == nullptr) return rbspec::dna5_ord(loaded);
+        const uint32_t b = first + i;
+        const uint32_t code = ((loaded & 0xFFu) >> ((b & 3u) << 1)) & 3u;
+        return ((loaded >> (8u + (b & 7u))) & 1u) ? 4u : code;
+    }
+    __device__ __forceinline__ uint32_t ord(uint32_t i) const { return ord_of(raw(i), i); }
 };
 
 __device__ __forceinline__ ListBaseSrc make_list_base_src(const ReadSrc &r, uint32_t item, uint32_t *len_out)
@@ -49,45 +57,139 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
     return v;
 }
 
-// one listed bin: a returning add into its half of the counter dword, and the lane's running maximum of "what the bin now counts".
-// nb is the lane's bound on bin numbers (n_bins, or 0 for a lane whose dword is no part of the slot): sentinel, overflow mark and every
-// number the counters have no room for fall outside it.  (The overflow rows' form; the lists take list_add / list_seen below.)
-__device__ __forceinline__ void count_bin(uint32_t *cnt, uint32_t bin, uint32_t nb, uint32_t &m)
+// one bin of a dense row: an add into its half of the counter dword; nothing comes back (the maximum is found by list_scan)
+__device__ __forceinline__ void count_bin(uint32_t *cnt, uint32_t bin, uint32_t n_bins)
 {
-    if (bin < nb) {
-        const uint32_t sh = (bin & 1u) << 4;
-        const uint32_t old = __hip_atomic_fetch_add(&cnt[bin >> 1], 1u << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        m = max(m, ((old >> sh) & 0xFFFFu) + 1u);
-    }
+    if (bin < n_bins) __hip_atomic_fetch_add(&cnt[bin >> 1], 1u << ((bin & 1u) << 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// The same without control flow, in two halves, so that a group of rows issues its adds back to back and looks at what came back
-// afterwards (a branch around every add made the wave wait for each one: 128 LDS round trips per tile, one after the other).  An entry
-// that is no bin adds 0 to the lane's own spare dword behind the counters (zero, and it stays zero), so it sees 0 and adds 0 to the maximum.
-__device__ __forceinline__ uint32_t list_add(uint32_t *cnt, uint32_t bin, uint32_t nb, uint32_t spare)
+// The two entries of a slot's dword, without control flow and without a value back, so that a group of slots issues its adds back to
+// back and waits for none of them.  An entry is a bin below n_bins or a sentinel (an overflow slot is blanked to sentinels before it
+// gets here): half its value is the bin's counter dword, or lies far beyond the counters and is clamped to `spare`, the lane's own dword
+// behind them.  What the spares collect is junk that nothing reads.  (No two lanes share a spare: adds to one address serialise.)
+__device__ __forceinline__ void list_add2(uint32_t *cnt, uint32_t v, uint32_t spare)
 {
-    const bool valid = bin < nb;
-    const uint32_t sh = (bin & 1u) << 4;
-    return __hip_atomic_fetch_add(&cnt[valid ? bin >> 1 : spare], (valid ? 1u : 0u) << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void list_seen(uint32_t old, uint32_t bin, uint32_t nb, uint32_t &m)
-{
-    m = max(m, ((old >> ((bin & 1u) << 4)) & 0xFFFFu) + (bin < nb ? 1u : 0u));
+    __hip_atomic_fetch_add(&cnt[min((v & 0xFFFFu) >> 1, spare)], 1u << ((v << 4) & 16u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(&cnt[min(v >> 17, spare)], 1u << ((v >> 12) & 16u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 typedef unsigned int list_u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short list_u16x2 __attribute__((ext_vector_type(2)));
 constexpr uint32_t kListSpareDwords = rblist::kCountSpareDwords;  // one per lane, behind the counters
+
+__device__ __forceinline__ list_u16x2 list_max2(list_u16x2 a, uint32_t dword)
+{
+    return __builtin_elementwise_max(a, __builtin_bit_cast(list_u16x2, dword));
+}
+
+// The largest counter: every lane reads 16-byte pieces of the cnt_dwords counter dwords (a multiple of 256: whole pieces, the same
+// number for every lane) and keeps the packed maximum of their halves; one wave reduction at the end.  The spares are not looked at.
+// CLEAR: the pieces are zeroed behind the read, for the next strand.
+template <bool CLEAR>
+__device__ __forceinline__ uint32_t list_scan(uint32_t *cnt, uint32_t cnt_dwords, uint32_t lane)
+{
+    uint4 *c4 = reinterpret_cast<uint4 *>(cnt);
+    list_u16x2 a = {0, 0};
+    for (uint32_t i = lane; i < cnt_dwords / 4; i += 64) {
+        const uint4 q = c4[i];
+        a = __builtin_elementwise_max(list_max2(list_max2(a, q.x), q.y), list_max2(__builtin_bit_cast(list_u16x2, q.z), q.w));
+        if (CLEAR) c4[i] = make_uint4(0, 0, 0, 0);
+    }
+    return (uint32_t)__builtin_amdgcn_readfirstlane(wave_max_u32(max((uint32_t)a.x, (uint32_t)a.y)));
+}
 
 // One wave, one workgroup, one read; N-free reads only (a wave whose read has a base outside ACGT leaves at once: the three-hash twin
 // ibf_count_rows_kernel<.., false>, launched behind this kernel, writes those).  Per strand the wave keeps a 16-bit counter for every bin
 // in LDS, two per dword, cleared first; per tile of 64 k-mers every lane ranks its own k-mer (base 4, first base most significant; the
 // reverse strand: the rank of the reverse complement), the tile's slots are gathered back to back -- lane l takes dword l of a two-line
 // slot, dwords 2l and 2l + 1 of a four-line slot (two halves of 32 slots then), dword l & 31 of a one-line slot, where lanes 32-63 count
-// nothing -- and every entry below n_bins is one count_bin.  Bins within a slot are distinct, so within one instruction a counter half is
-// touched by one lane only, and the strand's maximum is the wave maximum of the lanes' running maxima: the counters are never scanned.
-// An overflow slot (rb_lists.h) names a dense row of the side table; its set bits are counted one by one after the tile's lists.
+// nothing -- and every entry below n_bins is one add of 1 to its counter, with no value back: adds commute, so a group of eight slots is
+// counted as soon as its loads have landed, and the strand's maximum is one scan of the counters at its end (list_scan).
+// An overflow slot (rb_lists.h) names a dense row of the side table.  Lane 0 folds the first entries of a group's eight slots into one
+// word that says whether any is the mark; only such a group looks at its slots one by one, sets the overflow slots aside and blanks
+// them -- their index entries are no bins -- and the dense rows' set bits are counted one by one after the tile's lists.
 // Pruning (flags & kPruneBound): the second strand is skipped when the first reached n, and it stops at the tile boundary where its
-// maximum so far plus the k-mers still to come cannot pass the first strand's maximum.  Exact: the output is the maximum over both.
+// maximum so far plus the k-mers still to come cannot pass the first strand's maximum, `best`.  That cannot happen while more than
+// `best` k-mers are to come, so only the tile edges behind that point scan the counters.  Exact: the output is the maximum over both.
+
+// One batch of R slots, `first` the tile's k-mer the batch begins at.  FULL: all R slots lie within the strand, and nothing is guarded;
+// otherwise a slot past the end stays a row of sentinels and a group of eight that begins past the end is skipped.
+template <int LINES, bool NT, bool FULL>
+__device__ __forceinline__ void list_batch(const IbfDev &f, uint32_t *cnt, const uint32_t *__restrict__ slots, const uint64_t *__restrict__ side,
+                                           uint32_t side_rows, uint32_t rank, uint32_t first, uint32_t in_tile, uint32_t lane, uint32_t spare)
+{
+    constexpr int DW = LINES == 4 ? 2 : 1;  // dwords per lane and slot
+    constexpr int R = 64 / DW;              // slots gathered back to back: 64 registers of a lane either way
+    constexpr int G = 8;
+    constexpr uint32_t SLOT_DWORDS = LINES * 32;
+    const uint32_t lane_dword = LINES == 1 ? (lane & 31u) : lane * DW;
+    // ---- the gathers, back to back
+    uint32_t v[R][DW];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+#pragma unroll
+        for (int d = 0; d < DW; ++d) v[u][d] = 0xFFFFFFFFu;
+        if (FULL || first + (uint32_t)u < in_tile) {  // wave-uniform
+            const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)rank, (int)((R == 64 ? 0 : first) + u));
+            const uint32_t *base = slots + (size_t)slot * SLOT_DWORDS;  // slot < 4^k: masked digits; wave-uniform
+            if constexpr (DW == 2) {
+                const list_u32x2 *p2 = reinterpret_cast<const list_u32x2 *>(base + lane_dword);
+                const list_u32x2 q = NT ? __builtin_nontemporal_load(p2) : *p2;
+                v[u][0] = q.x;
+                v[u][1] = q.y;
+            } else {
+                v[u][0] = NT ? __builtin_nontemporal_load(base + lane_dword) : base[lane_dword];
+            }
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    uint64_t overflow = 0;  // the batch's overflow slots
+#pragma unroll
+    for (int g = 0; g < R / G; ++g) {
+        if (FULL || first + (uint32_t)(g * G) < in_tile) {  // wave-uniform
+            // entry 0 plus one has bit 15 set for the overflow mark alone: bins are below 0x2000, and a sentinel wraps to 0
+            uint32_t fold = 0;
+#pragma unroll
+            for (int u = 0; u < G; ++u) fold |= v[g * G + u][0] + 1u;
+            if (__builtin_amdgcn_readfirstlane(fold) & 0x8000u) {  // wave-uniform, rare
+#pragma unroll
+                for (int u = 0; u < G; ++u) {
+                    const int s = g * G + u;
+                    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)v[s][0], 0);
+                    if ((d0 & 0xFFFFu) == rblist::kOverflowMark) {  // wave-uniform
+                        overflow |= 1ull << s;
+#pragma unroll
+                        for (int d = 0; d < DW; ++d) v[s][d] = 0xFFFFFFFFu;
+                    }
+                }
+            }
+            if (LINES != 1 || lane < 32) {  // a one-line slot is 32 dwords: the upper half of the wave sits the adds out
+#pragma unroll
+                for (int u = 0; u < G; ++u)
+#pragma unroll
+                    for (int d = 0; d < DW; ++d) list_add2(cnt, v[g * G + u][d], spare);
+            }
+        }
+    }
+    while (overflow) {  // wave-uniform, rare: the slot's index entries once more, then the dense row's set bits one by one
+        const int u = __builtin_ctzll(overflow);
+        overflow &= overflow - 1;
+        const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)rank, (int)(R == 64 ? 0 : first) + u);
+        const uint16_t *entry = reinterpret_cast<const uint16_t *>(slots + (size_t)slot * SLOT_DWORDS);
+        const uint32_t idx = (uint32_t)entry[1] | ((uint32_t)entry[2] << 16);
+        if (idx >= side_rows) continue;  // (the builder never names a row it did not write)
+        const uint64_t *row = side + (size_t)idx * f.stride;
+        for (uint32_t w = lane; w < f.bin_width; w += 64) {
+            uint64_t word = row[w];
+            while (word) {
+                const uint32_t bit = (uint32_t)__builtin_ctzll(word);
+                word &= word - 1;
+                count_bin(cnt, w * 64u + bit, f.n_bins);
+            }
+        }
+    }
+}
+
 template <int LINES, bool NT>
 __global__ __launch_bounds__(64) void ibf_count_lists_kernel(IbfDev f, const uint32_t *__restrict__ slots, const uint64_t *__restrict__ side,
                                                              uint32_t side_rows, ReadSrc src, uint32_t n_reads, uint16_t *__restrict__ out,
@@ -95,9 +197,7 @@ __global__ __launch_bounds__(64) void ibf_count_lists_kernel(IbfDev f, const uin
                                                              uint32_t cnt_dwords)
 {
     static_assert(LINES == 1 || LINES == 2 || LINES == 4, "slot sizes of rb_lists.h");
-    constexpr int DW = LINES == 4 ? 2 : 1;  // dwords per lane and slot
-    constexpr int R = 64 / DW;              // slots gathered back to back: 64 registers of a lane either way
-    constexpr uint32_t SLOT_DWORDS = LINES * 32;
+    constexpr uint32_t R = LINES == 4 ? 32 : 64;  // slots per batch (list_batch)
     extern __shared__ uint32_t s_lds[];
     uint32_t *cnt = s_lds;                                                                   // cnt_dwords counters (a multiple of 256), kListSpareDwords spares
     uint8_t *stage = reinterpret_cast<uint8_t *>(s_lds + cnt_dwords + kListSpareDwords);    // rblist::kCountStageBytes
@@ -114,34 +214,44 @@ __global__ __launch_bounds__(64) void ibf_count_lists_kernel(IbfDev f, const uin
     if (__ballot(outside) != 0ULL) return;  // wave-uniform: the twin's read
 
     const bool bound = (flags & kPruneBound) != 0;
-    const uint32_t nb = (LINES == 1 && lane >= 32) ? 0u : f.n_bins;
-    const uint32_t lane_dword = LINES == 1 ? (lane & 31u) : lane * DW;
     const uint32_t spare = cnt_dwords + lane;
     uint32_t best = 0, stops = 0;
+    {  // the first strand's counters; the second strand's are cleared by the scan that ends the first
+        __builtin_amdgcn_wave_barrier();
+        uint4 *c4 = reinterpret_cast<uint4 *>(cnt);
+        for (uint32_t i = lane; i < cnt_dwords / 4; i += 64) c4[i] = make_uint4(0, 0, 0, 0);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+    }
 #pragma unroll 1
     for (int strand = 0; strand < 2; ++strand) {
         if (bound && strand == 1 && best >= n) break;  // wave-uniform
-        __builtin_amdgcn_wave_barrier();
-        {
-            uint4 *c4 = reinterpret_cast<uint4 *>(cnt);
-            for (uint32_t i = lane; i < (cnt_dwords + kListSpareDwords) / 4; i += 64) c4[i] = make_uint4(0, 0, 0, 0);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        uint32_t m = 0, stopped = n;
+        uint32_t stopped = n, m = 0;
+        // A tile's bases (64 + k - 1 <= 76 at k <= kRowTableMaxK: two per lane) are loaded one tile ahead, before the gathers of the tile
+        // in hand are issued, so their way from memory is not on the way to the next tile's ranks.  Not across an edge where the
+        // strand may stop: that tile loads its own.
+        uint32_t ahead0 = 0, ahead1 = 0;
+        bool ahead = false;
 #pragma unroll 1
         for (uint32_t mt = 0; mt < n; mt += 64) {
-            if (bound && strand == 1) {  // a bin counts at most once per k-mer: nothing to come can pass `best`
-                const uint32_t so_far = __builtin_amdgcn_readfirstlane(wave_max_u32(m));
-                if (so_far + (n - mt) <= best) {
+            // a bin counts at most once per k-mer: nothing to come can pass `best` once so_far + (n - mt) <= best, and so_far >= 0
+            if (bound && strand == 1 && n - mt <= best) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+                m = list_scan<false>(cnt, cnt_dwords, lane);
+                if (m + (n - mt) <= best) {
                     stopped = mt;
                     break;
                 }
             }
             // ---- the tile's bases as Dna5 ordinals, and one rank per lane
             const uint32_t wlen = min(64u + k - 1u, len - mt);
+            if (!ahead) {  // wave-uniform
+                ahead0 = lane < wlen ? seq.raw(mt + lane) : 0u;
+                ahead1 = lane + 64u < wlen ? seq.raw(mt + 64u + lane) : 0u;
+            }
             __builtin_amdgcn_wave_barrier();
-            for (uint32_t i = lane; i < wlen; i += 64) stage[i] = (uint8_t)seq.ord(mt + i);
+            if (lane < wlen) stage[lane] = (uint8_t)seq.ord_of(ahead0, mt + lane);
+            if (lane + 64u < wlen) stage[lane + 64u] = (uint8_t)seq.ord_of(ahead1, mt + 64u + lane);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             __builtin_amdgcn_wave_barrier();
             const uint32_t p = mt + lane;
@@ -155,82 +265,27 @@ __global__ __launch_bounds__(64) void ibf_count_lists_kernel(IbfDev f, const uin
                 }
             }
             const uint32_t in_tile = __builtin_amdgcn_readfirstlane(min(64u, n - mt));
+            ahead = mt + 64u < n && !(bound && strand == 1 && n - (mt + 64u) <= best);
+            if (ahead) {
+                const uint32_t next = min(64u + k - 1u, len - (mt + 64u));
+                ahead0 = lane < next ? seq.raw(mt + 64u + lane) : 0u;
+                ahead1 = lane + 64u < next ? seq.raw(mt + 128u + lane) : 0u;
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll 1
             for (uint32_t first = 0; first < in_tile; first += R) {
-                // ---- the gathers, back to back; a slot past the end of the strand stays a row of sentinels
-                uint32_t v[R][DW];
-#pragma unroll
-                for (int u = 0; u < R; ++u) {
-#pragma unroll
-                    for (int d = 0; d < DW; ++d) v[u][d] = 0xFFFFFFFFu;
-                    if (first + (uint32_t)u < in_tile) {  // wave-uniform
-                        const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)rank, (int)((R == 64 ? 0 : first) + u));
-                        const uint32_t *ptr = slots + (size_t)slot * SLOT_DWORDS + lane_dword;  // slot < 4^k: masked digits
-                        if constexpr (DW == 2) {
-                            const list_u32x2 *p2 = reinterpret_cast<const list_u32x2 *>(ptr);
-                            const list_u32x2 q = NT ? __builtin_nontemporal_load(p2) : *p2;
-                            v[u][0] = q.x;
-                            v[u][1] = q.y;
-                        } else {
-                            v[u][0] = NT ? __builtin_nontemporal_load(ptr) : *ptr;
-                        }
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                // ---- overflow slots are set aside (lane u keeps the side index of slot u) and list nothing
-                uint64_t overflow = 0;
-                uint32_t side_index = 0;
-#pragma unroll
-                for (int u = 0; u < R; ++u) {
-                    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)v[u][0], 0);
-                    if ((d0 & 0xFFFFu) == rblist::kOverflowMark) {  // wave-uniform
-                        const uint32_t d1 = DW == 2 ? (uint32_t)__builtin_amdgcn_readlane((int)v[u][1], 0) : (uint32_t)__builtin_amdgcn_readlane((int)v[u][0], 1);
-                        overflow |= 1ull << u;
-                        if (lane == (uint32_t)u) side_index = (d0 >> 16) | ((d1 & 0xFFFFu) << 16);
-#pragma unroll
-                        for (int d = 0; d < DW; ++d) v[u][d] = 0xFFFFFFFFu;
-                    }
-                }
-                // ---- count: eight slots' adds back to back, then what they returned
-                constexpr int G = 8;
-                if (LINES != 1 || lane < 32)  // a one-line slot is 32 dwords: the upper half of the wave sits the adds out, all of them at once
-#pragma unroll
-                for (int g = 0; g < R / G; ++g) {
-                    uint32_t old[G][DW][2];
-#pragma unroll
-                    for (int u = 0; u < G; ++u)
-#pragma unroll
-                        for (int d = 0; d < DW; ++d) {
-                            old[u][d][0] = list_add(cnt, v[g * G + u][d] & 0xFFFFu, nb, spare);
-                            old[u][d][1] = list_add(cnt, v[g * G + u][d] >> 16, nb, spare);
-                        }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int u = 0; u < G; ++u)
-#pragma unroll
-                        for (int d = 0; d < DW; ++d) {
-                            list_seen(old[u][d][0], v[g * G + u][d] & 0xFFFFu, nb, m);
-                            list_seen(old[u][d][1], v[g * G + u][d] >> 16, nb, m);
-                        }
-                }
-                while (overflow) {  // wave-uniform, rare: the dense row's set bits one by one
-                    const int u = __builtin_ctzll(overflow);
-                    overflow &= overflow - 1;
-                    const uint32_t idx = (uint32_t)__builtin_amdgcn_readlane((int)side_index, u);
-                    if (idx >= side_rows) continue;  // (the builder never names a row it did not write)
-                    const uint64_t *row = side + (size_t)idx * f.stride;
-                    for (uint32_t w = lane; w < f.bin_width; w += 64) {
-                        uint64_t word = row[w];
-                        while (word) {
-                            const uint32_t bit = (uint32_t)__builtin_ctzll(word);
-                            word &= word - 1;
-                            count_bin(cnt, w * 64u + bit, f.n_bins, m);
-                        }
-                    }
-                }
+                if (first + R <= in_tile)  // wave-uniform
+                    list_batch<LINES, NT, true>(f, cnt, slots, side, side_rows, rank, first, in_tile, lane, spare);
+                else
+                    list_batch<LINES, NT, false>(f, cnt, slots, side, side_rows, rank, first, in_tile, lane, spare);
             }
         }
-        best = max(best, (uint32_t)__builtin_amdgcn_readfirstlane(wave_max_u32(m)));
+        if (stopped == n) {  // (a strand that stopped has just scanned)
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            m = strand == 0 ? list_scan<true>(cnt, cnt_dwords, lane) : list_scan<false>(cnt, cnt_dwords, lane);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        }
+        best = max(best, m);
         stops = strand == 0 ? (stopped & 0xFFFFu) : (stops | (stopped << 16));
     }
     if (lane == 0) out[(size_t)read * out_read_stride] = (uint16_t)best;
