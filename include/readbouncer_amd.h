@@ -323,7 +323,9 @@ RB_API int rb_pack_reads(const char *seqs, const uint64_t *offsets, const uint32
  * select_matches leaves at the first bin with fwd >= t or rev >= t (:16-38).  A bin is a fragment_size stretch of a
  * reference record (src/IBF/IBFBuild.cpp:165-204), so the bin number is a locus.  An opt-in second pass over the work
  * items the caller selects; it always counts in full, whatever the engine's pruning / early-decision / merge / phased
- * settings are, and changes nothing rb_classify_batch* returns.  Per (work item, filter), deplete filters first:
+ * settings are, and changes nothing rb_classify_batch* returns.  It reads each filter's own table unless the engine was told
+ * to serve it from a filter's list table (rb_engine_set_pass_lists, readbouncer_amd_tuning.h; off by default): the results are
+ * defined, and come out, the same either way.  Per (work item, filter), deplete filters first:
  *   max_count   u16  M = max over bins b of max(fwd[b], rev[b]) -- the out_maxcount of rb_classify_batch for the same read
  *                    (uint16_t counts: they wrap at 65 536 as seqan::count's vectors do)
  *   best_bin    i32  the LOWEST bin b with max(fwd[b], rev[b]) == M; -1 when M == 0 or the item's status is not RB_OK
@@ -356,8 +358,10 @@ RB_API int rb_locate_batch(rb_engine *e, const char *seqs, const uint64_t *offse
 /* ---- hits: EVERY bin a read hit, per strand, with its k-mer count ---------------------------------
  * The reference has no such call.  This is what seqan::count returns and select_matches walks (src/IBF/IBFClassify.cpp:16-38,
  * 97-98, 149-150): which bins reached the threshold, on which strand, with what count -- the list behind the hit_bins of the
- * locate pass.  An opt-in pass of its own, like locate: it always counts in full from each filter's own table, whatever the
- * engine's pruning / early-decision / merge / phased settings are, and changes nothing any other call returns.
+ * locate pass.  An opt-in pass of its own, like locate: it always counts in full, whatever the engine's pruning /
+ * early-decision / merge / phased settings are, and changes nothing any other call returns; from each filter's own table
+ * unless rb_engine_set_pass_lists (readbouncer_amd_tuning.h; off by default) lets a filter's list table serve it, which
+ * changes no result.
  * Per (work item, filter), deplete filters first: fwd[b], rev[b] = the two uint16_t count vectors of seqan::count under the
  * engine's N rule, t = the threshold; a HIT is a (bin b, strand s) with c_s[b] >= t.  Records are per (bin, strand): a bin that
  * reaches t on both strands yields two.

@@ -200,9 +200,28 @@ typedef struct rb_pass_plan {
     uint32_t nontemporal;        /* locate, hits, prefixes: 1 = the non-temporal twin (blocks of a whole wave beyond the threshold) */
     uint32_t hash_functions;     /* 3: the build with three compile-time hash functions; 0: the run-time hash count */
     uint32_t spans_nontemporal;  /* spans (one wave per query, no geometry, no planes): 1 = its non-temporal twin, at any block width */
-    uint32_t reserved0;
+    uint32_t list_lines;         /* locate and hits only (spans and prefixes are not affected): 0 = the plain build the fields above describe;
+                                    1, 2 or 4 = the list form (rb_engine_set_pass_lists) at that slot size, for this filter, this max_len and
+                                    the engine's setting as it stands -- items the list form does not take still run the plain build */
 } rb_pass_plan;
 RB_API int rb_engine_plan_pass(rb_engine *e, size_t filter_index, uint32_t max_len, rb_pass_plan *out);
+/* The locate and hits passes of readbouncer_amd.h (host and device forms) from a filter's LIST TABLE (below: rb_dibf_list_table_build), opt-in.  The list
+ * form counts an item in full on both strands from the slots the count kernel gathers -- 2 x lines of 128 bytes per k-mer, not h whole
+ * blocks per strand -- and scans its per-bin counters for the maximum, its lowest bin, the bins at the threshold and the records;
+ * results are those of the plain form, bit for bit.  Decided per filter and per call, so an engine may mix the forms: a filter takes it
+ * when the mode allows, the list form serves its geometry and the call's max_len (what RB_ROW_TABLE_LISTS serves: whole-wave blocks in
+ * one column slice of at most 8192 bins, three hash functions, k <= 13, fewer than 65 536 k-mers), the engine is no column shard, the
+ * call's stream is not being captured, and the filter has a list table of the present version of its bits.  Work items with a base
+ * outside ACGT, and items that are not RB_OK, are served from the filter's own table in the same call.
+ *   RB_PASS_LISTS_OFF (default): the passes read each filter's own table, always.
+ *   RB_PASS_LISTS_CURRENT: a filter's list table is used when it has a current one; none is ever built.
+ *   RB_PASS_LISTS_BUILD: a filter without a current table gets one built by the call, under the rules of the count path's list form
+ *     (rb_engine_set_row_table's max_bytes, free memory, density); a refusal means the plain form, not an error.
+ * rb_engine_plan_pass reports the choice in list_lines.  Spans, prefixes and resume are not affected. */
+#define RB_PASS_LISTS_OFF 0
+#define RB_PASS_LISTS_CURRENT 1
+#define RB_PASS_LISTS_BUILD 2
+RB_API int rb_engine_set_pass_lists(rb_engine *e, int mode);
 /* Fits the window lengths of the clock-phased gathers to THIS device: the planner's table was measured on one box, and clocks,
  * firmware and compilers move the optima.  For every table the engine would serve with the phased form on batches of n_reads reads
  * of read_len bases, K1 is timed on synthetic reads with the table's window and with 0.7 / 0.85 / 1.2 / 1.45 x that (same slice

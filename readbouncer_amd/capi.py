@@ -106,6 +106,7 @@ class ListTableInfo(C.Structure):
 
 
 RB_ROW_TABLE_OFF, RB_ROW_TABLE_AUTO, RB_ROW_TABLE_FORCE, RB_ROW_TABLE_LISTS = 0, 1, 2, 3
+RB_PASS_LISTS_OFF, RB_PASS_LISTS_CURRENT, RB_PASS_LISTS_BUILD = 0, 1, 2
 (RB_LIST_REFUSED_NONE, RB_LIST_REFUSED_K, RB_LIST_REFUSED_GEOMETRY, RB_LIST_REFUSED_MAX_BYTES, RB_LIST_REFUSED_FREE, RB_LIST_REFUSED_ALLOC,
  RB_LIST_REFUSED_CAPTURE, RB_LIST_REFUSED_DENSITY, RB_LIST_REFUSED_SIDE_FULL) = range(9)
 LIST_SENTINEL, LIST_OVERFLOW_MARK = 0xFFFF, 0xFFFE  # rb_lists.h
@@ -117,7 +118,7 @@ class PassPlan(C.Structure):
     """rb_pass_plan: the build the query passes take for one filter"""
     _fields_ = [("lanes_per_block_log2", C.c_uint32), ("words_per_lane", C.c_uint32), ("column_slices", C.c_uint32),
                 ("counter_planes", C.c_uint32), ("nontemporal", C.c_uint32), ("hash_functions", C.c_uint32),
-                ("spans_nontemporal", C.c_uint32), ("reserved0", C.c_uint32)]
+                ("spans_nontemporal", C.c_uint32), ("list_lines", C.c_uint32)]
 
 
 class BinRef(C.Structure):
@@ -257,6 +258,7 @@ SIGNATURES = {
     "rb_dibf_row_table_info": (_int, [_vp, C.POINTER(RowTableInfo)]),
     "rb_dibf_row_table_download": (_int, [_vp, _vp, _u64]),
     "rb_engine_set_row_table": (_int, [_vp, _int, _u64]),
+    "rb_engine_set_pass_lists": (_int, [_vp, _int]),
     "rb_dibf_list_table_build": (_int, [_vp, _u64]),
     "rb_dibf_list_table_drop": (_int, [_vp]),
     "rb_dibf_list_table_info": (_int, [_vp, C.POINTER(ListTableInfo)]),
@@ -856,10 +858,11 @@ class Engine:
         return d
 
     def plan_pass(self, filter_index, max_len):
-        """the build locate, hits, prefixes and spans take for that filter on items of at most max_len bases -> dict (rb_pass_plan)"""
+        """the build locate, hits, prefixes and spans take for that filter on items of at most max_len bases -> dict (rb_pass_plan);
+        list_lines: 0, or the slot size at which locate and hits take the filter's list table (set_pass_lists)"""
         p = PassPlan()
         _check(lib().rb_engine_plan_pass(self.h, filter_index, max_len, C.byref(p)), "rb_engine_plan_pass")
-        return {k: getattr(p, k) for k, _ in PassPlan._fields_ if k != "reserved0"}
+        return {k: getattr(p, k) for k, _ in PassPlan._fields_}
 
     def calibrate(self, n_reads=262144, read_len=250, max_ms=0.0):
         """fit the phased windows to this device -> (phased tables found, tables whose window changed)"""
@@ -931,6 +934,11 @@ class Engine:
         """RB_ROW_TABLE_OFF / _AUTO (default) / _FORCE / _LISTS (the list table wherever it serves): whether plain whole-wave launches gather one precomputed row per k-mer from the
         filter's row table, building it when there is none (results identical); max_bytes 0 keeps the limit (default 96 GiB)"""
         _check(lib().rb_engine_set_row_table(self.h, int(mode), int(max_bytes)), "rb_engine_set_row_table")
+
+    def set_pass_lists(self, mode):
+        """RB_PASS_LISTS_OFF (default) / _CURRENT (a filter's list table where it has a current one) / _BUILD (built when there is none):
+        whether locate and hits are served from the list table (results identical; plan_pass reports list_lines)"""
+        _check(lib().rb_engine_set_pass_lists(self.h, int(mode)), "rb_engine_set_pass_lists")
 
     def set_list_min_dense_bytes(self, n_bytes):
         """size of the dense row table from which RB_ROW_TABLE_AUTO prefers the list table (default 512 MiB; 0: always)"""

@@ -247,7 +247,8 @@ struct LocateOut {
     uint32_t *hit_bins;
     uint8_t *status;
 };
-// ... and one filter's launch.  What locate and hits share: always the plain form over the filter's own table, counted in full
+// ... and one filter's launch.  What locate and hits share: the plain form over the filter's own table, counted in full -- and, where the
+// engine chose it (rb_engine_set_pass_lists), the list form in front of it
 struct PlainPassLaunch {
     IbfDev f;
     ReadSrc src;
@@ -257,10 +258,32 @@ struct PlainPassLaunch {
     int lg, wpl, planes, nt;
     const uint16_t *thr;  // the decision kernel's table [thr_len][nf][2]
     uint32_t thr_len, nf, fi;
+    // list form of locate and hits (rb_pass_lists.hip): the filter's list table and its side table as in CountLaunch, or nullptr: the
+    // plain form alone.  list_nt: non-temporal slot gathers (the list table's bytes against the engine's threshold, as the count path).
+    // list_taken / list_plain_lens: what launch_pass_lists_prep made of the call's items
+    const uint16_t *list_table;
+    const uint64_t *list_side;
+    uint32_t list_side_rows, list_lines;
+    int list_nt;
+    const uint8_t *list_taken;
+    const uint32_t *list_plain_lens;
 };
 struct LocateLaunch : PlainPassLaunch {
     LocatePart *part;     // [n_slices][n_items]
 };
+// Which work items the list kernels of locate and hits take (rb_pass_lists.hip, pass_lists_takes: the item is RB_OK and its chunk window
+// holds no base outside ACGT), decided ONCE per call for both sides: taken[item] = 1 for the list kernels' items, and plain_lens[item] is
+// the item's length, or 0 for a taken item -- the lengths the plain kernels are launched with, unchanged themselves, so that they count
+// nothing of what the list kernels count.
+struct PassListsPrep {
+    ReadSrc src;
+    uint32_t n_items;
+    const uint8_t *pre_status;  // chunk_prep's per-item status, or nullptr
+    uint32_t min_len;           // item_status's: the largest k of the engine
+    uint8_t *taken;
+    uint32_t *plain_lens;
+};
+hipError_t launch_pass_lists_prep(const PassListsPrep &a, hipStream_t st);
 // Which build a plain-form launch takes, as host arithmetic: the launchers of rb_kernels.hip instantiate by these two, and
 // rb_engine_plan_pass reports them.  Ten counter planes only with the compile-time three hash functions (*h = 3); *h = 0 is the
 // run-time hash count, always on sixteen planes.  The query passes have a non-temporal twin for blocks of a whole wave only.
@@ -271,6 +294,11 @@ inline void plain_planes_hash(uint32_t n_hash, int planes, int *np, int *h)
 }
 inline bool plain_pass_nt(int lg, int nt) { return lg == 6 && nt != 0; }
 hipError_t launch_ibf_locate(const LocateLaunch &a, hipStream_t st);
+// ... the list form (rb_pass_lists.hip): launch_ibf_locate over a.list_plain_lens -- the items the list kernel leaves, from the filter's
+// own table; a taken item has no k-mer there and gets an empty record -- and then ibf_locate_lists_kernel, whose records of the taken
+// items stand
+bool pass_list_form_serves(const PlainPassLaunch &a);  // list_form_serves for a launch of locate or hits
+hipError_t launch_ibf_locate_lists(const LocateLaunch &a, hipStream_t st);
 hipError_t launch_reduce_locate_slices(const LocatePart *part, uint32_t n_slices, uint32_t n_items, const uint32_t *lens,
                                        const uint8_t *pre_status, uint32_t max_len, uint32_t min_len, const LocateOut &out, uint32_t nf,
                                        uint32_t fidx, hipStream_t st);
@@ -364,6 +392,9 @@ struct HitsLaunch : PlainPassLaunch {
     uint64_t *bin_reads;  // this filter's n_bins counters, or nullptr
 };
 hipError_t launch_ibf_hits(const HitsLaunch &a, hipStream_t st);
+// ... the list form (rb_pass_lists.hip): launch_ibf_hits over a.list_plain_lens, where a taken item is too short to be looked at, and
+// ibf_hits_lists_kernel for the taken items: every segment is written once
+hipError_t launch_ibf_hits_lists(const HitsLaunch &a, hipStream_t st);
 hipError_t launch_finish_hits(const HitsLaunch &a, const uint32_t *lens, const HitsOut &out, hipStream_t st);
 
 // spans pass (rb_spans_batch_device; rb_kernels.hip, ibf_spans_kernel): the caller's output arrays (any may be nullptr) ...

@@ -408,6 +408,8 @@ struct rb_engine {
     // ... and from which size of the DENSE row table auto prefers the list table (rb_engine_set_list_min_dense_bytes): a constant of its
     // own, not nt_threshold_bytes -- below it the dense table is served from the Infinity Cache and lines are not what limits it
     uint64_t list_min_dense_bytes = 512ull << 20;
+    // rb_engine_set_pass_lists: whether locate and hits take a filter's list table (pass_lists_for)
+    int pass_lists = RB_PASS_LISTS_OFF;
     struct CertLoad {
         double set = -1.0;       // what the caller gave (< 0: measure)
         double measured = -1.0;  // load of the filter's fullest bin at `version` (< 0: not measured yet)
@@ -1482,6 +1484,14 @@ int rb_engine_set_row_table(rb_engine *e, int mode, uint64_t max_bytes)
     std::lock_guard<std::mutex> lock(e->mu);
     e->row_mode = mode;
     if (max_bytes) e->row_max_bytes = max_bytes;
+    return RB_OK;
+}
+
+int rb_engine_set_pass_lists(rb_engine *e, int mode)
+{
+    if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->pass_lists = mode;
     return RB_OK;
 }
 
@@ -2767,6 +2777,79 @@ static void fill_plain_launch(const rb_engine *e, size_t fi, const PassInput &in
     a->fi = (uint32_t)fi;
 }
 
+// May locate and hits take this filter's LIST table for the launch `a` (rb_engine_set_pass_lists)?  Per filter, so an engine may mix the
+// two forms: the setting allows it, the list form serves the launch's geometry and the call's max_len (pass_list_form_serves: what the
+// count path's list form serves, one column slice among it), the engine is no column shard, the stream is not being captured (a graph
+// would keep the address of a table the next change of the bits frees), and the filter has a table of the present version of its bits --
+// under RB_PASS_LISTS_BUILD built now through list_table_for, whose refusals mean the plain form.  a->list_table stays null wherever
+// the answer is no.  asking: the question alone (rb_engine_plan_pass) -- no stream, and nothing is built or dropped.
+static int pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, PlainPassLaunch *a)
+{
+    a->list_table = nullptr;
+    a->list_side = nullptr;
+    a->list_side_rows = a->list_lines = 0;
+    a->list_nt = 0;
+    if (e->pass_lists == RB_PASS_LISTS_OFF || e->shard_world != 1 || !pass_list_form_serves(*a)) return RB_OK;
+    rb_dibf *f = e->filters[fi];
+    if (list_table_geometry_refusal(f)) return RB_OK;
+    uint64_t list_bytes = 0;
+    CountLaunch got{};
+    if (e->pass_lists == RB_PASS_LISTS_BUILD && !asking) {
+        const int rc = list_table_for(e, f, st, got, &list_bytes);
+        if (rc != RB_OK) return rc;
+    } else {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (!asking && st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return RB_OK;
+        std::lock_guard<std::mutex> lock(f->row_mu);
+        if (!list_table_current_locked(f)) return RB_OK;
+        got.list_table = f->list_table;
+        got.list_side = f->list_side;
+        got.list_side_rows = f->list_side_rows;
+        got.list_lines = f->list_lines;
+        list_bytes = f->list_bytes;
+    }
+    if (!got.list_table || !got.list_side) return RB_OK;
+    a->list_table = got.list_table;
+    a->list_side = got.list_side;
+    a->list_side_rows = got.list_side_rows;
+    a->list_lines = got.list_lines;
+    a->list_nt = list_bytes > e->nt_threshold_bytes;
+    return RB_OK;
+}
+
+// ... and the list forms' share of a call: which items they take is decided once, for every filter (launch_pass_lists_prep: the status
+// rules and the bases are the call's, not a filter's).  take(): room in the call's workspace when some launch has a list table;
+// run(): the prep kernel, and every such launch learns where its answers are.
+struct PassListsShare {
+    size_t o_taken = 0, o_lens = 0;
+    bool any = false;
+    void take(rb::StageLayout &lay, size_t n_items, bool some_launch_has_a_table)
+    {
+        any = some_launch_has_a_table;
+        if (!any) return;
+        o_taken = lay.take(n_items);
+        o_lens = lay.take(n_items * 4);
+    }
+    int run(const PassCall &c, uint32_t min_len) const
+    {
+        if (!any) return RB_OK;
+        PassListsPrep p{};
+        p.src = c.in.src;
+        p.n_items = (uint32_t)c.in.n_items;
+        p.pre_status = c.in.d_pre_status;
+        p.min_len = min_len;
+        p.taken = (uint8_t *)(c.ws() + o_taken);
+        p.plain_lens = (uint32_t *)(c.ws() + o_lens);
+        RB_HIP(launch_pass_lists_prep(p, c.st));
+        return RB_OK;
+    }
+    void bind(const PassCall &c, PlainPassLaunch *a) const
+    {
+        a->list_taken = (const uint8_t *)(c.ws() + o_taken);
+        a->list_plain_lens = (const uint32_t *)(c.ws() + o_lens);
+    }
+};
+
 // host_maxcount: optional pinned host destination for a copy of the maxcount rows, written by the decision kernel
 static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, int mode,
                                 void *d_maxcount, void *d_best_target, void *d_decision, void *d_status, void *stream,
@@ -3135,6 +3218,15 @@ extern "C" int rb_engine_plan_pass(rb_engine *e, size_t filter_index, uint32_t m
     out->nontemporal = plain_pass_nt(lg, nt) ? 1u : 0u;
     out->hash_functions = (uint32_t)h;
     out->spans_nontemporal = table_beyond_nt_threshold(e, f) ? 1u : 0u;
+    // locate and hits: the list form, for this filter, this max_len and the engine's setting as it stands -- what a call would take, short
+    // of building a table (RB_PASS_LISTS_BUILD reports the table once it stands)
+    PlainPassLaunch a{};
+    PassInput in{};
+    in.src.max_len = in.max_len = max_len;
+    fill_plain_launch(e, filter_index, in, nullptr, 0, &a);
+    const int rc = pass_lists_for(e, filter_index, nullptr, true, &a);
+    if (rc != RB_OK) return rc;
+    out->list_lines = a.list_table ? a.list_lines : 0u;
     return RB_OK;
 }
 
@@ -3631,8 +3723,10 @@ static void host_pass_geometry(rb_engine *e, uint32_t max_len, size_t *nf, size_
 }
 
 // ---- locate: which bin and strand a read matched, and how many bins hit (no counterpart in the reference; see the boundary header).
-// Always the plain form over each filter's OWN table, counted in full: the engine's pruning / early-decision / merge / phased settings
-// do not reach it.  One launch of ibf_locate_kernel per filter plus the merge of its column slices, in sequence on the call's stream.
+// The plain form over each filter's OWN table, counted in full: the engine's pruning / early-decision / merge / phased settings do not
+// reach it.  One launch of ibf_locate_kernel per filter plus the merge of its column slices, in sequence on the call's stream.  Opt-in
+// (rb_engine_set_pass_lists, decided per filter by pass_lists_for): ibf_locate_lists_kernel over the filter's list table for the items
+// the prep kernel names, the plain kernel as it is for the others, and the same merge.
 int rb_locate_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, const rb_locate_out *d_out,
                            void *stream)
 {
@@ -3652,22 +3746,27 @@ int rb_locate_batch_device(rb_engine *e, const rb_batch_desc *desc, double error
     std::vector<LocateLaunch> launches(nf);
     std::vector<size_t> o_part(nf);
     rb::StageLayout lay;
+    const uint32_t min_len = engine_min_len(e);
     for (size_t fi = 0; fi < nf; ++fi) {
         fill_plain_launch(e, fi, c.in, c.thr, c.thr_len, &launches[fi]);
+        if ((rc = pass_lists_for(e, fi, c.st, false, &launches[fi])) != RB_OK) return rc;  // (one column slice wherever the list form serves)
         o_part[fi] = lay.take((size_t)launches[fi].n_slices * n_items * sizeof(LocatePart));
     }
+    PassListsShare lists;
+    lists.take(lay, n_items, std::any_of(launches.begin(), launches.end(), [](const LocateLaunch &a) { return a.list_table != nullptr; }));
     if ((rc = c.start(lay.bytes())) != RB_OK) return rc;
+    if ((rc = lists.run(c, min_len)) != RB_OK) return rc;
     LocateOut out;
     out.max_count = (uint16_t *)d_out->max_count;
     out.best_bin = (int32_t *)d_out->best_bin;
     out.best_strand = (uint8_t *)d_out->best_strand;
     out.hit_bins = (uint32_t *)d_out->hit_bins;
     out.status = (uint8_t *)d_out->status;
-    const uint32_t min_len = engine_min_len(e);
     for (size_t fi = 0; fi < nf; ++fi) {
         LocateLaunch &a = launches[fi];
         a.part = (LocatePart *)(c.ws() + o_part[fi]);
-        RB_HIP(launch_ibf_locate(a, c.st));
+        if (a.list_table) lists.bind(c, &a);
+        RB_HIP(a.list_table ? launch_ibf_locate_lists(a, c.st) : launch_ibf_locate(a, c.st));
         RB_HIP(launch_reduce_locate_slices(a.part, a.n_slices, (uint32_t)n_items, c.in.d_lens, c.in.d_pre_status, c.in.max_len, min_len, out,
                                            (uint32_t)nf, (uint32_t)fi, c.st));
     }
@@ -4112,7 +4211,9 @@ int rb_resume_counts(rb_resume *r, uint32_t slot, size_t filter, uint16_t *out_c
 
 // ---- hits: every (bin, strand) at or above the threshold, with its count (no counterpart in the reference; see the boundary header).
 // Per filter one launch of ibf_hits_kernel over the filter's OWN table, counted in full, plus finish_hits_kernel,
-// in sequence on the call's stream -- so one workspace, sized for the filter with the most column slices, serves every filter.
+// in sequence on the call's stream -- so one workspace, sized for the filter with the most column slices, serves every filter.  Opt-in
+// (rb_engine_set_pass_lists, per filter by pass_lists_for): ibf_hits_lists_kernel over the filter's list table fills the same segments,
+// the plain kernel as it is those of the items it leaves, and finish_hits_kernel merges them as ever.
 int rb_hits_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, uint16_t min_count, uint32_t max_hits,
                          const rb_hits_out *d_out, void *stream)
 {
@@ -4139,12 +4240,16 @@ int rb_hits_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_r
         a.max_hits = cap;
         a.min_len = min_len;
         a.pre_status = c.in.d_pre_status;
+        if ((rc = pass_lists_for(e, fi, c.st, false, &a)) != RB_OK) return rc;
         max_slices = std::max(max_slices, a.n_slices);
     }
     // workspace: per (item, slice, strand) a segment of cap records, and its counter
     rb::StageLayout lay;
     const size_t o_seg = lay.take(n_items * (size_t)max_slices * 2 * (size_t)cap * 8), o_count = lay.take(n_items * (size_t)max_slices * 2 * 4);
+    PassListsShare lists;
+    lists.take(lay, n_items, std::any_of(launches.begin(), launches.end(), [](const HitsLaunch &a) { return a.list_table != nullptr; }));
     if ((rc = c.start(lay.bytes())) != RB_OK) return rc;
+    if ((rc = lists.run(c, min_len)) != RB_OK) return rc;
     HitsOut out;
     out.hits = (rb_u32x2 *)d_out->hits;
     out.n_hits = (uint32_t *)d_out->n_hits;
@@ -4155,7 +4260,8 @@ int rb_hits_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_r
         a.seg = c.ws() + o_seg;
         a.seg_count = (uint32_t *)(c.ws() + o_count);
         a.bin_reads = bin_reads;
-        RB_HIP(launch_ibf_hits(a, c.st));
+        if (a.list_table) lists.bind(c, &a);
+        RB_HIP(a.list_table ? launch_ibf_hits_lists(a, c.st) : launch_ibf_hits(a, c.st));
         RB_HIP(launch_finish_hits(a, c.in.d_lens, out, c.st));
         if (bin_reads) bin_reads += e->filters[fi]->geo.n_bins;
     }

@@ -43,6 +43,13 @@ constexpr uint32_t count_lds_bytes(uint32_t n_bins) { return (count_cnt_dwords(n
 // one wave per workgroup: the workgroups of a CU that the LDS leaves room for
 constexpr uint32_t count_resident_workgroups(uint32_t n_bins) { return kLdsPerCuBytes / count_lds_bytes(n_bins); }
 
+// What one wave of ibf_locate_lists_kernel and ibf_hits_lists_kernel keeps in LDS: the count kernel's counters, spares and stage, and
+// behind them the HIT MASK -- one bit per counter half, so one byte per 16-byte piece of the counters (eight bins), written by the scan
+// that ends the first strand and read by the scan that ends the second.  1 KiB at 8192 bins: nine workgroups per CU, as the count kernel.
+constexpr uint32_t pass_mask_bytes(uint32_t n_bins) { return count_cnt_dwords(n_bins) / 4u; }
+constexpr uint32_t pass_lds_bytes(uint32_t n_bins) { return count_lds_bytes(n_bins) + pass_mask_bytes(n_bins); }
+constexpr uint32_t pass_resident_workgroups(uint32_t n_bins) { return kLdsPerCuBytes / pass_lds_bytes(n_bins); }
+
 // The census's verdict. over[i] = sampled rows with more than 64 << i set bits (i = 0, 1, 2), of `sampled` rows.
 // -> lines of the smallest slot that at most sampled >> kOverflowShift rows overflow, or 0: no slot size serves (the filter is too dense)
 inline uint32_t choose_lines(const uint64_t over[3], uint64_t sampled)

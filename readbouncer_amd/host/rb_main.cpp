@@ -541,6 +541,8 @@ struct IngestOptions
     std::vector<uint32_t> prefix_lens;  // ... the checkpoints in bases, strictly rising (--prefix-lens a,b,c, or made from --prefix-step / --prefix-count)
     uint32_t prefix_step = 0, prefix_count = 0;
     uint32_t max_hits = 64;      // --max-hits N: records kept per (read, filter); n_hits in the report stays exact
+    int pass_lists = RB_PASS_LISTS_CURRENT;  // --pass-lists off|current|build: --report-bins / --report-hits from a filter's list table
+                                             // (rb_engine_set_pass_lists): where it has one, or building one; the files are the same bytes
     std::vector<std::string> bin_maps;  // --bin-map FILE (may repeat): <filter name>.bins.tsv of build --write-bin-map -> a record_id column
     size_t bytes() const { return segment_bytes ? segment_bytes : (segment_mb << 20); }
 };
@@ -978,6 +980,9 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
         unsigned cal_parties = 0, cal_arrived = 0;  // (cal_parties is set before the first classifier starts)
         auto classifier = [&] {
             try {
+                if ((opt.report_bins || opt.report_hits) && !multi && opt.pass_lists != RB_PASS_LISTS_OFF)
+                    interleave::throw_status(rb_engine_set_pass_lists(interleave::detail::engine_for(DepletionFilters, TargetFilters), opt.pass_lists),
+                                             "rb_engine_set_pass_lists");
                 if (opt.calibrate && !multi) {
                     // one engine at a time, and nobody classifies before the last engine is calibrated: an engine timed beside
                     // another thread's classification picks its windows from noise
@@ -1319,6 +1324,17 @@ int main(int argc, char const* argv[])
             opt.max_hits = (uint32_t)v;
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--pass-lists")) {
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            if (!std::strcmp(v, "off")) opt.pass_lists = RB_PASS_LISTS_OFF;
+            else if (!std::strcmp(v, "current")) opt.pass_lists = RB_PASS_LISTS_CURRENT;
+            else if (!std::strcmp(v, "build")) opt.pass_lists = RB_PASS_LISTS_BUILD;
+            else {
+                std::cerr << "ERROR: --pass-lists off|current|build" << std::endl;
+                return 1;
+            }
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--report-prefixes")) opt.report_prefixes = true;
         else if (!std::strcmp(argv[i], "--prefix-lens")) {
             // a,b,c: 1 to 64 checkpoints in bases, none 0, strictly rising
@@ -1412,6 +1428,8 @@ int main(int argc, char const* argv[])
                          "  usage classify: [--report-bins]  classified_bins.tsv: bin, strand, count and hit bins of every classified read\n"
                          "                  [--report-hits [--max-hits 64]]  classified_hits.tsv: every (bin, strand) at or above the threshold of those reads, with\n"
                          "                                    its count, at most --max-hits per (read, filter) (n_hits stays exact); bin_profile.tsv: reads per bin\n"
+                         "                  [--pass-lists off|current|build]  --report-bins and --report-hits from a filter's list table: where it has a current one\n"
+                         "                                    (current, the default), building one where it has none (build), or never (off); the files are the same bytes\n"
                          "                  [--report-spans]  classified_spans.tsv: where along the read the best bin of every matching filter matched, on its best\n"
                          "                                    strand: n_kmers, count, first, last, run_start, run_len, covered; positions in the read's coordinates\n"
                          "                  [--report-prefixes (--prefix-lens a,b,c | --prefix-step N [--prefix-count M])]  classified_prefixes.tsv: for EVERY read of the\n"
