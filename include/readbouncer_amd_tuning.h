@@ -411,6 +411,10 @@ typedef struct rb_list_table_info {
 RB_API int rb_dibf_list_table_build(rb_dibf *f, uint64_t max_bytes);
 RB_API int rb_dibf_list_table_drop(rb_dibf *f);
 RB_API int rb_dibf_list_table_info(rb_dibf *f, rb_list_table_info *out);
+/* The first n_entries 16-bit entries of the table in its CANONICAL form -- per slot the row's bin numbers ascending, 0xFFFF to the end;
+ * an overflow slot is 0xFFFE and the two halves of its side-table index -- and the first n_side_words words of the side table.  The
+ * device itself keeps the slots in another, private form (ready LDS addresses for the count kernels: csrc/rb_lists.h) that no caller
+ * sees: the whole slots that cover the prefix are copied and converted on the host, so a short prefix of a large table stays cheap. */
 RB_API int rb_dibf_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n_entries, uint64_t *side_words, uint64_t n_side_words);
 /* the dense-table size from which RB_ROW_TABLE_AUTO prefers the list form (0: always, where the other rules hold) */
 RB_API int rb_engine_set_list_min_dense_bytes(rb_engine *e, uint64_t bytes);

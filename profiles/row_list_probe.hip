@@ -17,6 +17,10 @@
 //            counters (ds_read_b128, packed 16-bit maximum, one wave reduction) fused with the clear.  Nine waves per CU then
 //   rolling: the scan mode with a rolling refill: when group g (eight rows) of tile t has been counted, the loads of group g of tile
 //            t + 1 are issued into the same registers, so a wave always has R - 8 to R rows in flight, across tile and read edges
+//   ready  : the scan mode over a table in the RESIDENT ("add-ready") form of rb_lists.h: each 16-bit half of a dword holds the LDS byte
+//            offset of a counter dword (even bins in low halves, odd bins in high halves, a half that lists no bin names the lane's
+//            own spare), so the count is `add 1 at v & 0xFFFF` and `add 0x10000 at v >> 16`: two vector instructions per dword around
+//            the two adds.  Third argument `addready`: only `no lds`, then `scan` and `ready` in turn, three times each (two tables)
 // Prints rows/s and lines/s (2 per row) per setting, best of 3 runs after one warm-up, and the gate of the issue: today's row
 // kernel completes 6.16 G rows/s at 0.946 of its own probe, so the list form can only win above 6.5 G rows/s.
 // build+run on the GPU box:  hipcc -O3 --offload-arch=gfx950 profiles/row_list_probe.hip -o /tmp/row_list_probe && /tmp/row_list_probe
@@ -26,6 +30,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #define CHECK(x)                                                                                        \
     do {                                                                                                \
@@ -69,12 +74,52 @@ __global__ __launch_bounds__(256) void fill_rows(uint32_t *__restrict__ table, u
 
 constexpr uint32_t kSpareDwords = 64;
 
+// the same rows in the resident form, one wave per row: lane l holds entries 2l and 2l + 1 of the sorted list; the even bins go to the low
+// halves and the odd bins to the high halves in list order (72-91 entries: neither parity passes 64), the other halves name the spare of
+// the lane that reads the dword
+__global__ __launch_bounds__(64) void fill_rows_ready(uint32_t *__restrict__ table, uint64_t n_rows)
+{
+    __shared__ uint16_t img[2 * kRowDwords];
+    const uint32_t lane = threadIdx.x;
+    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const uint32_t n_r = 72 + (uint32_t)(mix(~r) % 20);
+        const uint32_t stride = kBins / n_r;
+        const uint32_t e[2] = {entry(r, 2 * lane, n_r, stride), entry(r, 2 * lane + 1, n_r, stride)};
+        __builtin_amdgcn_wave_barrier();
+        img[2 * lane] = img[2 * lane + 1] = (uint16_t)((kBins / 2 + lane) * 4);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        const uint64_t below = (1ull << lane) - 1;
+        uint32_t at[2] = {0, 0};  // even and odd bins in the lanes below
+        for (int j = 0; j < 2; ++j) {
+            at[0] += (uint32_t)__popcll(__ballot(e[j] < kBins && !(e[j] & 1u)) & below);
+            at[1] += (uint32_t)__popcll(__ballot(e[j] < kBins && (e[j] & 1u)) & below);
+        }
+        for (int j = 0; j < 2; ++j)
+            if (e[j] < kBins) {
+                const uint32_t par = e[j] & 1u;
+                const uint32_t pos = at[par]++;
+                if (pos < kRowDwords) img[2 * pos + par] = (uint16_t)((e[j] >> 1) * 4);
+            }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        table[r * kRowDwords + lane] = reinterpret_cast<const uint32_t *>(img)[lane];
+    }
+}
+
 typedef unsigned short probe_u16x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ void add2(uint32_t *cnt, uint32_t v, uint32_t spare)
 {
     __hip_atomic_fetch_add(&cnt[min((v & 0xFFFFu) >> 1, spare)], 1u << ((v << 4) & 16u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     __hip_atomic_fetch_add(&cnt[min(v >> 17, spare)], 1u << ((v >> 12) & 16u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ __forceinline__ void add2_ready(uint32_t *cnt, uint32_t v)
+{
+    char *base = reinterpret_cast<char *>(cnt);
+    __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(base + (v & 0xFFFFu)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(base + (v >> 16)), 0x10000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 __device__ __forceinline__ uint32_t scan_and_clear(uint32_t *cnt, uint32_t lane)
@@ -95,7 +140,7 @@ __device__ __forceinline__ uint32_t scan_and_clear(uint32_t *cnt, uint32_t lane)
 }
 
 // the scan and rolling modes: kBins / 2 + kSpareDwords dwords of LDS
-template <int R, bool NT, bool ROLLING>
+template <int R, bool NT, bool ROLLING, bool READY = false>
 __global__ __launch_bounds__(64) void list_probe_scan(const uint32_t *__restrict__ table, uint32_t lg_rows, uint32_t reads, uint32_t *out)
 {
     extern __shared__ uint32_t cnt[];
@@ -132,7 +177,10 @@ __global__ __launch_bounds__(64) void list_probe_scan(const uint32_t *__restrict
 #pragma unroll
         for (int g = 0; g < R / G; ++g) {
 #pragma unroll
-            for (int u = 0; u < G; ++u) add2(cnt, v[g * G + u], spare);
+            for (int u = 0; u < G; ++u) {
+                if constexpr (READY) add2_ready(cnt, v[g * G + u]);
+                else add2(cnt, v[g * G + u], spare);
+            }
             if constexpr (ROLLING) {
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -222,6 +270,8 @@ static int run(const uint32_t *table, uint32_t lg_rows, uint32_t reads, uint32_t
         CHECK(hipEventRecord(a));
         if constexpr (MODE == 0)
             hipLaunchKernelGGL((list_probe<R, NT, LDS>), dim3(blocks), dim3(64), kBins * 2, 0, table, lg_rows, reads, out);
+        else if constexpr (MODE == 3)
+            hipLaunchKernelGGL((list_probe_scan<R, NT, false, true>), dim3(blocks), dim3(64), kBins * 2 + kSpareDwords * 4, 0, table, lg_rows, reads, out);
         else
             hipLaunchKernelGGL((list_probe_scan<R, NT, MODE == 2>), dim3(blocks), dim3(64), kBins * 2 + kSpareDwords * 4, 0, table, lg_rows, reads, out);
         CHECK(hipGetLastError());
@@ -234,7 +284,7 @@ static int run(const uint32_t *table, uint32_t lg_rows, uint32_t reads, uint32_t
     const double rows = (double)blocks * reads * kRowsPerRead;
     *rows_per_s = rows / best / 1e6;  // G rows/s
     printf("rows in flight %2d  %-8s  %-8s : %7.2f G rows/s  %7.2f G lines/s  (%.1f ms)\n", R, NT ? "nt" : "temporal",
-           MODE == 2 ? "rolling" : MODE == 1 ? "scan" : LDS ? "lds adds" : "no lds", *rows_per_s, 2.0 * *rows_per_s, best);
+           MODE == 3 ? "ready" : MODE == 2 ? "rolling" : MODE == 1 ? "scan" : LDS ? "lds adds" : "no lds", *rows_per_s, 2.0 * *rows_per_s, best);
     fflush(stdout);
     CHECK(hipEventDestroy(a));
     CHECK(hipEventDestroy(b));
@@ -245,8 +295,9 @@ int main(int argc, char **argv)
 {
     const uint32_t lg_rows = argc > 1 ? (uint32_t)atoi(argv[1]) : 26;
     const uint32_t reads = argc > 2 ? (uint32_t)atoi(argv[2]) : 48;
-    if (lg_rows < 10 || lg_rows > 26 || reads < 1 || reads > 4096) {
-        printf("usage: row_list_probe [log2 rows 10..26] [reads per wave 1..4096]\n");
+    const bool addready = argc > 3 && !strcmp(argv[3], "addready");
+    if (lg_rows < 10 || lg_rows > 26 || reads < 1 || reads > 4096 || (argc > 3 && !addready)) {
+        printf("usage: row_list_probe [log2 rows 10..26] [reads per wave 1..4096] [addready]\n");
         return 2;
     }
     const uint64_t n_rows = 1ULL << lg_rows;
@@ -261,6 +312,32 @@ int main(int argc, char **argv)
            bytes / 1073741824.0, reads, kRowsPerRead);
     double g[16];
     int i = 0;
+    if (addready) {  // the resident form beside the canonical one: is the two-instruction add worth a kernel change?
+        uint32_t *ready = nullptr;
+        CHECK(hipMalloc(&ready, bytes));
+        hipLaunchKernelGGL(fill_rows_ready, dim3(256 * 64), dim3(64), 0, 0, ready, n_rows);
+        CHECK(hipGetLastError());
+        CHECK(hipDeviceSynchronize());
+        double nolds, scan[3], rdy[3];
+        if (run<64, true, false>(table, lg_rows, reads, out, &nolds)) return 1;
+        for (int rep = 0; rep < 3; ++rep) {
+            if (run<64, true, true, 1>(table, lg_rows, reads, out, &scan[rep])) return 1;
+            if (run<64, true, true, 3>(ready, lg_rows, reads, out, &rdy[rep])) return 1;
+        }
+        double lo[2] = {scan[0], rdy[0]}, hi[2] = {scan[0], rdy[0]};
+        for (int rep = 1; rep < 3; ++rep) {
+            lo[0] = scan[rep] < lo[0] ? scan[rep] : lo[0], hi[0] = scan[rep] > hi[0] ? scan[rep] : hi[0];
+            lo[1] = rdy[rep] < lo[1] ? rdy[rep] : lo[1], hi[1] = rdy[rep] > hi[1] ? rdy[rep] : hi[1];
+        }
+        printf("scan  %.2f .. %.2f G rows/s (spread %.2f %%), ready %.2f .. %.2f G rows/s (spread %.2f %%), no lds %.2f\n", lo[0], hi[0],
+               100.0 * (hi[0] - lo[0]) / lo[0], lo[1], hi[1], 100.0 * (hi[1] - lo[1]) / lo[1], nolds);
+        printf("ready over scan: x%.4f (slowest ready over fastest scan: x%.4f): %s\n", (rdy[0] + rdy[1] + rdy[2]) / (scan[0] + scan[1] + scan[2]),
+               lo[1] / hi[0], lo[1] / hi[0] > 1.0 + (hi[0] - lo[0]) / lo[0] ? "go on" : "stop");
+        CHECK(hipFree(ready));
+        CHECK(hipFree(table));
+        CHECK(hipFree(out));
+        return 0;
+    }
     if (run<32, true, true>(table, lg_rows, reads, out, &g[i++])) return 1;
     if (run<64, true, true>(table, lg_rows, reads, out, &g[i++])) return 1;
     if (run<32, false, true>(table, lg_rows, reads, out, &g[i++])) return 1;

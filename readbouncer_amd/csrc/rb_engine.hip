@@ -1770,7 +1770,20 @@ int rb_dibf_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n_entrie
     if (n_side_words > (uint64_t)f->list_side_rows * f->stride) return rb::fail(RB_ERR_INVALID_ARG, "more words than the side table's rows in use hold");
     int st = check_device(f->device);
     if (st != RB_OK) return st;
-    if (n_entries) RB_HIP(hipMemcpy(entries, f->list_table, n_entries * 2, hipMemcpyDeviceToHost));
+    if (n_entries) {
+        // the device holds the resident form (rb_lists.h): the whole slots that cover the prefix are copied -- no more than asked for,
+        // rounded up to a slot -- and come back as canonical slots, of which the prefix is handed out
+        const uint32_t lines = f->list_lines, cap = rblist::slot_entries(lines);
+        const uint64_t n_slots = (n_entries + cap - 1) / cap;
+        std::vector<uint32_t> resident(n_slots * (cap / 2));
+        RB_HIP(hipMemcpy(resident.data(), f->list_table, resident.size() * 4, hipMemcpyDeviceToHost));
+        uint16_t slot[rblist::kMaxLines * rblist::kEntriesPerLine];
+        for (uint64_t i = 0; i < n_slots; ++i) {
+            if (rblist::decode_resident(resident.data() + i * (cap / 2), lines, (uint32_t)f->geo.n_bins, slot) == -2)
+                return rb::fail(RB_ERR_HIP, "the device's list table holds a slot that no builder writes");
+            std::memcpy(entries + i * cap, slot, (size_t)std::min<uint64_t>(cap, n_entries - i * cap) * 2);
+        }
+    }
     if (n_side_words) RB_HIP(hipMemcpy(side_words, f->list_side, n_side_words * 8, hipMemcpyDeviceToHost));
     return RB_OK;
 }

@@ -8,6 +8,8 @@
 // A row with more set bits than a slot holds is an OVERFLOW slot: entry 0 is kOverflowMark, entries 1 and 2 are the low and the high half
 // of the index of its dense row (`stride` 64-bit words, as in the row table) in the table's side table, the rest is kSentinel.
 // Bin numbers are below kMaxBins, so neither mark is a bin.
+// That is the CANONICAL form: what rb_dibf_list_table_download returns and the tests read.  The device keeps the same slots in the
+// RESIDENT form (below, encode_resident / decode_resident), whose entries are ready-made LDS addresses for the count kernels.
 #pragma once
 #include <cstdint>
 
@@ -106,6 +108,100 @@ inline bool encode_slot(const uint64_t *row, uint32_t n_words, uint32_t n_bins, 
     slot[1] = (uint16_t)(side_index & 0xFFFFu);
     slot[2] = (uint16_t)(side_index >> 16);
     return false;
+}
+
+// ---- THE RESIDENT ("add-ready") FORM: what ibf_list_table_kernel writes and list_batch (rb_lists_device.h) reads; private to the
+// device.  Slot size, slot count, side table and census are the canonical form's; only the 32 bits of a slot's dwords mean something else.
+// Everything a count kernel would compute from a bin number depends on the filter alone, so the table holds it computed: each 16-bit
+// HALF of a dword is, in bits 15:2, the LDS byte offset of a counter dword -- counters as count_lds_bytes lays them out: dword bin >> 1,
+// half bin & 1, from offset 0 -- and the half's POSITION is the bin's parity: even bins in low halves, odd bins in high halves.  The
+// kernel adds the constant 1 at `v & 0xFFFF` and the constant 1 << 16 at `v >> 16`.  A half that lists no bin holds the offset of a
+// SPARE dword behind the counters, the one of the lane that reads the dword (resident_spare_dword: no two lanes of one add share one).
+// Bits 1:0 of a half are flags, zero in nearly every slot; a group of slots whose dwords OR to no flag takes the two-instruction path.
+//   kResidentSwapped  : the half lists a bin of the OTHER parity (a row that fits the slot, but whose even or odd bins alone exceed half
+//                       of it, puts the excess there)
+//   kResidentOverflow : in the low half of dword 0 alone: an overflow slot.  Dword 1 is the whole index of its dense row in the side
+//                       table, every other half a spare.
+// Order within a slot is free (adds commute); the builders here and on the device fill each parity's halves from dword 0 up.
+constexpr uint32_t kResidentSwapped = 1u;
+constexpr uint32_t kResidentOverflow = 2u;
+constexpr uint32_t kResidentFlags = 0x00030003u;  // of a dword
+constexpr uint32_t kResidentOffset = 0xFFFCu;     // of a half
+
+// the spare that the non-bin halves of dword `dword` of a slot name: lane l reads dword l of a one- or two-line slot (l < 32 of one
+// line), dwords 2 l and 2 l + 1 of a four-line slot, each dword in an add instruction of its own
+constexpr uint32_t resident_spare_dword(uint32_t n_bins, uint32_t lines, uint32_t dword)
+{
+    return count_cnt_dwords(n_bins) + (lines == 4 ? dword >> 1 : dword);
+}
+constexpr uint32_t resident_blank(uint32_t n_bins, uint32_t lines, uint32_t dword)
+{
+    return (resident_spare_dword(n_bins, lines, dword) * 4u) * 0x10001u;
+}
+static_assert((count_cnt_dwords(kMaxBins) + kCountSpareDwords) * 4u <= kResidentOffset + 4u, "a counter's byte offset fits bits 15:2 of a half");
+
+// A canonical slot (what encode_slot writes, of a filter of n_bins bins) as lines * 32 resident dwords.  -> false: not such a slot
+inline bool encode_resident(const uint16_t *slot, uint32_t lines, uint32_t n_bins, uint32_t *out)
+{
+    const uint32_t cap = slot_entries(lines), half = cap / 2;
+    for (uint32_t d = 0; d < half; ++d) out[d] = resident_blank(n_bins, lines, d);
+    if (slot[0] == kOverflowMark) {
+        out[0] |= kResidentOverflow;
+        out[1] = (uint32_t)slot[1] | ((uint32_t)slot[2] << 16);
+        return true;
+    }
+    uint32_t n[2] = {0, 0}, total = 0;
+    while (total < cap && slot[total] != kSentinel) {
+        if (slot[total] >= n_bins) return false;
+        ++n[slot[total++] & 1u];
+    }
+    uint32_t rank[2] = {0, 0};
+    for (uint32_t i = 0; i < total; ++i) {
+        const uint32_t par = slot[i] & 1u, off = (uint32_t)(slot[i] >> 1) * 4u, r = rank[par]++;
+        // its own parity's halves first; what they cannot take goes behind the other parity's bins, flagged
+        const uint32_t d = r < half ? r : n[par ^ 1u] + (r - half);
+        const uint32_t in = r < half ? par : par ^ 1u;
+        const uint32_t h = r < half ? off : off | kResidentSwapped;
+        out[d] = in ? (out[d] & 0x0000FFFFu) | (h << 16) : (out[d] & 0xFFFF0000u) | h;
+    }
+    return true;
+}
+
+// ... and back: the canonical slot (ascending bins, sentinels, or mark and index) of lines * 32 resident dwords.  -> as decode_slot:
+// the number of bins, -1 for an overflow slot, -2 for what no builder writes (an offset that is neither a counter of a bin below
+// n_bins nor the dword's spare, a bin twice, a flag out of place)
+inline int decode_resident(const uint32_t *in, uint32_t lines, uint32_t n_bins, uint16_t *slot)
+{
+    const uint32_t cap = slot_entries(lines), half = cap / 2;
+    for (uint32_t i = 0; i < cap; ++i) slot[i] = kSentinel;
+    if (in[0] & kResidentOverflow) {
+        for (uint32_t d = 0; d < half; ++d)
+            if (d != 1 && (in[d] & ~kResidentOverflow) != resident_blank(n_bins, lines, d)) return -2;
+        slot[0] = kOverflowMark;
+        slot[1] = (uint16_t)(in[1] & 0xFFFFu);
+        slot[2] = (uint16_t)(in[1] >> 16);
+        return -1;
+    }
+    uint64_t seen[kMaxBins / 64] = {};
+    uint32_t n = 0;
+    for (uint32_t d = 0; d < half; ++d)
+        for (uint32_t pos = 0; pos < 2; ++pos) {
+            const uint32_t h = (in[d] >> (16u * pos)) & 0xFFFFu, dw = (h & kResidentOffset) >> 2;
+            if (h & kResidentOverflow) return -2;
+            if (dw >= count_cnt_dwords(n_bins)) {
+                if (h != resident_spare_dword(n_bins, lines, d) * 4u) return -2;
+                continue;
+            }
+            const uint32_t bin = dw * 2u + (pos ^ (h & kResidentSwapped));
+            if (bin >= n_bins || ((seen[bin / 64] >> (bin % 64)) & 1ull)) return -2;
+            seen[bin / 64] |= 1ull << (bin % 64);
+            ++n;
+        }
+    uint32_t at = 0;
+    for (uint32_t w = 0; w < kMaxBins / 64 && at < n; ++w)
+        for (uint32_t b = 0; b < 64; ++b)
+            if ((seen[w] >> b) & 1ull) slot[at++] = (uint16_t)(w * 64 + b);
+    return (int)n;
 }
 
 }  // namespace rblist

@@ -17,11 +17,13 @@ namespace rb {
 // in LDS, two per dword, cleared first; per tile of 64 k-mers every lane ranks its own k-mer (base 4, first base most significant; the
 // reverse strand: the rank of the reverse complement), the tile's slots are gathered back to back -- lane l takes dword l of a two-line
 // slot, dwords 2l and 2l + 1 of a four-line slot (two halves of 32 slots then), dword l & 31 of a one-line slot, where lanes 32-63 count
-// nothing -- and every entry below n_bins is one add of 1 to its counter, with no value back: adds commute, so a group of eight slots is
-// counted as soon as its loads have landed, and the strand's maximum is one scan of the counters at its end (list_scan).
-// An overflow slot (rb_lists.h) names a dense row of the side table.  Lane 0 folds the first entries of a group's eight slots into one
-// word that says whether any is the mark; only such a group looks at its slots one by one, sets the overflow slots aside and blanks
-// them -- their index entries are no bins -- and the dense rows' set bits are counted one by one after the tile's lists.
+// nothing -- and every half of a dword is one add to the LDS address it holds, with no value back (the table is in the RESIDENT form of
+// rb_lists.h: the address arithmetic was done when the table was built): adds commute, so a group of eight slots is counted as soon as
+// its loads have landed, and the strand's maximum is one scan of the counters at its end (list_scan).
+// An overflow slot (rb_lists.h) names a dense row of the side table, and a row with too many bins of one parity has swapped halves; both
+// carry a flag.  Every lane ORs the dwords it holds of a group's eight slots and one wave-wide test of the flag bits says whether any is
+// set; only such a group looks at its slots one by one, sets the overflow slots aside and blanks them -- their index is no address --
+// adds the swapped halves with the other constant, and the dense rows' set bits are counted one by one after the tile's lists.
 // Pruning (flags & kPruneBound): the second strand is skipped when the first reached n, and it stops at the tile boundary where its
 // maximum so far plus the k-mers still to come cannot pass the first strand's maximum, `best`.  That cannot happen while more than
 // `best` k-mers are to come, so only the tile edges behind that point scan the counters.  Exact: the output is the maximum over both.
@@ -130,9 +132,11 @@ __global__ __launch_bounds__(64) void ibf_count_lists_kernel(IbfDev f, const uin
     }
 }
 
-// The list table of a filter, one wave per slot (the waves stride over the slots, as ibf_row_table_kernel's over its rows): the AND of
-// the k-mer's h blocks, word `lane` and word `lane + 64` of it per lane (a block of at most 128 words), a wave prefix sum of the popcounts,
-// and every lane writes the bin numbers of its set bits at its offset -- into the slot's image in LDS, which starts as all sentinels and
+// The list table of a filter in the RESIDENT form (rb_lists.h), one wave per slot (the waves stride over the slots, as
+// ibf_row_table_kernel's over its rows): the AND of the k-mer's h blocks, word `lane` and word `lane + 64` of it per lane (a block of at
+// most 128 words); one wave prefix sum of the lanes' even and odd populations, packed into one word; and every lane writes the counter
+// offsets of its set bits -- even bins into the low halves from dword 0 up, odd bins into the high halves, what one parity's halves
+// cannot take into the other's free halves with the swapped flag -- into the slot's image in LDS, which starts as the dwords' spares and
 // leaves as whole dwords.  Pad words and the bits behind n_bins list nothing.  A row with more set bits than the slot holds takes the next
 // row of the side table (an atomic counter; the order may vary from build to build, the rows may not) and leaves an overflow slot; past
 // `side_cap` it writes no row, and the host, which reads the counter, refuses the table.
@@ -149,12 +153,14 @@ __global__ __launch_bounds__(256) void ibf_list_table_kernel(IbfDev f, uint32_t 
     const uint32_t W = f.bin_width;
     const uint32_t nh = f.n_hash < rbspec::kMaxHash ? f.n_hash : rbspec::kMaxHash;
     const uint32_t rem = f.n_bins & 63u;
+    const uint32_t cnt_dwords = rblist::count_cnt_dwords(f.n_bins);
+    constexpr uint64_t kEven = 0x5555555555555555ULL;  // bin 64 w + b is even where b is
     uint16_t *img = s_slot[wave];
     for (uint64_t r = (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * step; r < n_rows; r += waves * step) {  // wave-uniform
         uint64_t v = 0;
         for (uint32_t i = 0; i < f.k; ++i) v = v * 5u + ((r >> (2u * (f.k - 1u - i))) & 3u);
         uint64_t word[2];
-        uint32_t c[2], incl[2], total[2];
+        uint32_t mine = 0;  // the lane's even bins, and its odd bins << 16 (at most 64 each)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const uint32_t w = lane + 64u * j;
@@ -168,37 +174,46 @@ __global__ __launch_bounds__(256) void ibf_list_table_kernel(IbfDev f, uint32_t 
                 if (w == W - 1 && rem) acc &= (1ULL << rem) - 1;
             }
             word[j] = acc;
-            c[j] = (uint32_t)__popcll(acc);
-            uint32_t s = c[j];
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = (uint32_t)__shfl_up((int)s, d, 64);
-                if (lane >= (uint32_t)d) s += o;
-            }
-            incl[j] = s;
-            total[j] = (uint32_t)__builtin_amdgcn_readlane((int)s, 63);
+            mine += (uint32_t)__popcll(acc & kEven) + ((uint32_t)__popcll(acc & ~kEven) << 16);
         }
-        const uint32_t set = total[0] + total[1];
+        uint32_t incl = mine;  // at most 4096 in either half
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
+            if (lane >= (uint32_t)d) incl += o;
+        }
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        const uint32_t n_par[2] = {total & 0xFFFFu, total >> 16};
+        const uint32_t set = n_par[0] + n_par[1];
         if (lines == 0) {
             if (lane == 0)
                 for (uint32_t i = 0; i < 3; ++i)
                     if (set > (64u << i)) atomicAdd(&counters[1 + i], 1u);
             continue;
         }
-        const uint32_t cap = lines * rblist::kEntriesPerLine;
+        const uint32_t cap = lines * rblist::kEntriesPerLine, half = cap / 2;
         __builtin_amdgcn_wave_barrier();
-        reinterpret_cast<uint2 *>(img)[lane] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);  // 4 entries per lane: all kMaxLines lines
+        {  // dwords 2 lane and 2 lane + 1 of the image, all kMaxLines lines: their spares in both halves
+            const uint32_t d = 2u * lane;
+            const uint32_t s0 = cnt_dwords + (lines == 4 ? d >> 1 : d), s1 = cnt_dwords + (lines == 4 ? d >> 1 : d + 1u);
+            reinterpret_cast<uint2 *>(img)[lane] = make_uint2((s0 * 4u) * 0x10001u, (s1 * 4u) * 0x10001u);
+        }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         __builtin_amdgcn_wave_barrier();
         if (set <= cap) {
+            uint32_t rank[2] = {(incl - mine) & 0xFFFFu, (incl - mine) >> 16};
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                uint32_t at = (j ? total[0] : 0u) + incl[j] - c[j];
                 uint64_t bits = word[j];
                 while (bits) {
                     const uint32_t bit = (uint32_t)__builtin_ctzll(bits);
                     bits &= bits - 1;
-                    img[at++] = (uint16_t)((lane + 64u * j) * 64u + bit);  // at < set <= cap
+                    const uint32_t par = bit & 1u;
+                    const uint32_t off = ((lane + 64u * j) * 32u + (bit >> 1)) * 4u;  // counter dword bin >> 1
+                    const uint32_t at = par ? rank[1]++ : rank[0]++;
+                    // at < n_par[par]; past `half`, n_par[par ^ 1] + (at - half) < set - half <= half: every index below is < cap
+                    if (at < half) img[2u * at + par] = (uint16_t)off;
+                    else img[2u * (n_par[par ^ 1u] + (at - half)) + (par ^ 1u)] = (uint16_t)(off | rblist::kResidentSwapped);
                 }
             }
         } else {
@@ -206,9 +221,9 @@ __global__ __launch_bounds__(256) void ibf_list_table_kernel(IbfDev f, uint32_t 
             if (lane == 0) idx = atomicAdd(&counters[0], 1u);
             idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)idx);
             if (lane == 0) {
-                img[0] = rblist::kOverflowMark;
-                img[1] = (uint16_t)(idx & 0xFFFFu);
-                img[2] = (uint16_t)(idx >> 16);
+                img[0] |= (uint16_t)rblist::kResidentOverflow;
+                img[2] = (uint16_t)(idx & 0xFFFFu);
+                img[3] = (uint16_t)(idx >> 16);
             }
             if (idx < side_cap) {
 #pragma unroll

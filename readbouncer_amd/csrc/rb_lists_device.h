@@ -62,14 +62,34 @@ __device__ __forceinline__ void count_bin(uint32_t *cnt, uint32_t bin, uint32_t 
     if (bin < n_bins) __hip_atomic_fetch_add(&cnt[bin >> 1], 1u << ((bin & 1u) << 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// The two entries of a slot's dword, without control flow and without a value back, so that a group of slots issues its adds back to
-// back and waits for none of them.  An entry is a bin below n_bins or a sentinel (an overflow slot is blanked to sentinels before it
-// gets here): half its value is the bin's counter dword, or lies far beyond the counters and is clamped to `spare`, the lane's own dword
-// behind them.  What the spares collect is junk that nothing reads.  (No two lanes share a spare: adds to one address serialise.)
-__device__ __forceinline__ void list_add2(uint32_t *cnt, uint32_t v, uint32_t spare)
+// The two halves of a slot's dword in the resident form (rb_lists.h), from a group of slots that carries no flag: each half IS the byte
+// offset of a counter dword -- a bin's, or the spare of the lane that holds the dword, where junk collects that nothing reads -- and its
+// place is the parity, so the low half adds 1 and the high half 1 << 16.  No control flow and no value back: a group of slots issues
+// its adds back to back and waits for none of them.  One vector instruction per add forms the address (the counters' base plus a
+// 16-bit half).  (No two lanes share a spare: adds to one address serialise.)
+__device__ __forceinline__ void list_add2(uint32_t *cnt, uint32_t v)
 {
-    __hip_atomic_fetch_add(&cnt[min((v & 0xFFFFu) >> 1, spare)], 1u << ((v << 4) & 16u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __hip_atomic_fetch_add(&cnt[min(v >> 17, spare)], 1u << ((v >> 12) & 16u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    char *base = reinterpret_cast<char *>(cnt);
+    __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(base + (v & 0xFFFFu)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(base + (v >> 16)), 0x10000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// A dword with a swapped half (kResidentSwapped: a bin of the other parity): that half is added here with the other constant and
+// replaced by the lane's spare, so that list_add2 finds no flag.  `counts`: the lane takes part in the adds.
+__device__ __forceinline__ uint32_t list_add_swapped(uint32_t *cnt, uint32_t v, uint32_t spare_off, bool counts)
+{
+    char *base = reinterpret_cast<char *>(cnt);
+    if (v & rblist::kResidentSwapped) {
+        if (counts)
+            __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(base + (v & rblist::kResidentOffset)), 0x10000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        v = (v & 0xFFFF0000u) | spare_off;
+    }
+    if (v & (rblist::kResidentSwapped << 16)) {
+        if (counts)
+            __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(base + ((v >> 16) & rblist::kResidentOffset)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        v = (v & 0x0000FFFFu) | (spare_off << 16);
+    }
+    return v;
 }
 
 typedef unsigned int list_u32x2 __attribute__((ext_vector_type(2)));
@@ -98,7 +118,9 @@ __device__ __forceinline__ uint32_t list_scan(uint32_t *cnt, uint32_t cnt_dwords
 }
 
 // One batch of R slots, `first` the tile's k-mer the batch begins at.  FULL: all R slots lie within the strand, and nothing is guarded;
-// otherwise a slot past the end stays a row of sentinels and a group of eight that begins past the end is skipped.
+// otherwise a slot past the end stays blank (the lane's spare in both halves) and a group of eight that begins past the end is skipped.
+// `spare` is the lane's spare dword, cnt_dwords + lane: what the table's non-bin halves name in the dwords this lane reads
+// (rblist::resident_spare_dword), so a blanked slot adds where an empty one would.
 template <int LINES, bool NT, bool FULL>
 __device__ __forceinline__ void list_batch(const IbfDev &f, uint32_t *cnt, const uint32_t *__restrict__ slots, const uint64_t *__restrict__ side,
                                            uint32_t side_rows, uint32_t rank, uint32_t first, uint32_t in_tile, uint32_t lane, uint32_t spare)
@@ -108,12 +130,13 @@ __device__ __forceinline__ void list_batch(const IbfDev &f, uint32_t *cnt, const
     constexpr int G = 8;
     constexpr uint32_t SLOT_DWORDS = LINES * 32;
     const uint32_t lane_dword = LINES == 1 ? (lane & 31u) : lane * DW;
+    const uint32_t spare_off = spare * 4u, blank = spare_off * 0x10001u;
     // ---- the gathers, back to back
     uint32_t v[R][DW];
 #pragma unroll
     for (int u = 0; u < R; ++u) {
 #pragma unroll
-        for (int d = 0; d < DW; ++d) v[u][d] = 0xFFFFFFFFu;
+        for (int d = 0; d < DW; ++d) v[u][d] = blank;
         if (FULL || first + (uint32_t)u < in_tile) {  // wave-uniform
             const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)rank, (int)((R == 64 ? 0 : first) + u));
             const uint32_t *base = slots + (size_t)slot * SLOT_DWORDS;  // slot < 4^k: masked digits; wave-uniform
@@ -132,19 +155,27 @@ __device__ __forceinline__ void list_batch(const IbfDev &f, uint32_t *cnt, const
 #pragma unroll
     for (int g = 0; g < R / G; ++g) {
         if (FULL || first + (uint32_t)(g * G) < in_tile) {  // wave-uniform
-            // entry 0 plus one has bit 15 set for the overflow mark alone: bins are below 0x2000, and a sentinel wraps to 0
+            // the group's dwords ORed: a flag in any lane (rb_lists.h: an overflow slot, a swapped half) sends the group down the
+            // careful path, which leaves its slots without one
             uint32_t fold = 0;
 #pragma unroll
-            for (int u = 0; u < G; ++u) fold |= v[g * G + u][0] + 1u;
-            if (__builtin_amdgcn_readfirstlane(fold) & 0x8000u) {  // wave-uniform, rare
+            for (int u = 0; u < G; ++u)
+#pragma unroll
+                for (int d = 0; d < DW; ++d) fold |= v[g * G + u][d];
+            if (__builtin_expect(__ballot((fold & rblist::kResidentFlags) != 0u) != 0ULL, 0)) {  // wave-uniform, rare
+                const bool counts = LINES != 1 || lane < 32;
 #pragma unroll
                 for (int u = 0; u < G; ++u) {
                     const int s = g * G + u;
-                    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)v[s][0], 0);
-                    if ((d0 & 0xFFFFu) == rblist::kOverflowMark) {  // wave-uniform
+                    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)v[s][0], 0);  // dword 0 of the slot
+                    if (d0 & rblist::kResidentOverflow) {  // wave-uniform: set aside, and blanked (its index is no address)
                         overflow |= 1ull << s;
 #pragma unroll
-                        for (int d = 0; d < DW; ++d) v[s][d] = 0xFFFFFFFFu;
+                        for (int d = 0; d < DW; ++d) v[s][d] = blank;
+                    } else {
+#pragma unroll
+                        for (int d = 0; d < DW; ++d)
+                            if (v[s][d] & rblist::kResidentFlags) v[s][d] = list_add_swapped(cnt, v[s][d], spare_off, counts);
                     }
                 }
             }
@@ -152,16 +183,15 @@ __device__ __forceinline__ void list_batch(const IbfDev &f, uint32_t *cnt, const
 #pragma unroll
                 for (int u = 0; u < G; ++u)
 #pragma unroll
-                    for (int d = 0; d < DW; ++d) list_add2(cnt, v[g * G + u][d], spare);
+                    for (int d = 0; d < DW; ++d) list_add2(cnt, v[g * G + u][d]);
             }
         }
     }
-    while (overflow) {  // wave-uniform, rare: the slot's index entries once more, then the dense row's set bits one by one
+    while (overflow) {  // wave-uniform, rare: the slot's index dword once more, then the dense row's set bits one by one
         const int u = __builtin_ctzll(overflow);
         overflow &= overflow - 1;
         const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)rank, (int)(R == 64 ? 0 : first) + u);
-        const uint16_t *entry = reinterpret_cast<const uint16_t *>(slots + (size_t)slot * SLOT_DWORDS);
-        const uint32_t idx = (uint32_t)entry[1] | ((uint32_t)entry[2] << 16);
+        const uint32_t idx = slots[(size_t)slot * SLOT_DWORDS + 1];
         if (idx >= side_rows) continue;  // (the builder never names a row it did not write)
         const uint64_t *row = side + (size_t)idx * f.stride;
         for (uint32_t w = lane; w < f.bin_width; w += 64) {
