@@ -2,7 +2,10 @@
 RB_ROW_TABLE_LISTS.  Only this size reaches the strided loop of ibf_list_table_kernel (more slots than its 2^22 waves), a census that
 samples (every 1024th row), slot byte offsets beyond 2^32 in the builder and in the count kernel's gather address, and ranks 0 and
 4^13 - 1.  The fixture is tests/row_rig.py's WideCase on a filter of 16 381 blocks (with 1021, three rows in a thousand are the AND of
-two blocks only and no slot size is allowed that many overflows: tests/row_lists_rig.py); a small batch, bit for bit against the oracle."""
+two blocks only and no slot size is allowed that many overflows: tests/row_lists_rig.py); a small batch, bit for bit against the oracle.
+The same table then serves locate and hits (RB_PASS_LISTS_CURRENT): list_count_strand, the strand loop of their kernels, loads a tile's
+bases with lanes 0 to 11 of its second load at k = 13 and forms ranks of 26 bits -- the case's reads and strands of 1, 63, 64, 65 and 129
+k-mers, all-A and all-T, on either strand, through tests/test_gpu_pass_lists.py's run_both."""
 import numpy as np
 import pytest
 
@@ -10,8 +13,10 @@ pytestmark = pytest.mark.gpu
 
 from readbouncer_amd import capi
 from tests import helpers as H
+from tests import pass_lists_edges_rig as ER
 from tests import row_lists_rig as LR
 from tests import row_rig as RR
+from tests import test_gpu_pass_lists as GP
 from tests import test_gpu_row_lists as TL
 from tests import test_gpu_row_table as RT
 
@@ -43,6 +48,15 @@ def test_slots_beyond_32_bit_offsets():
         assert info["builds"] == 1 and info["refused"] == 0 and info["rows"] == 4 ** K and info["lines"] == 2 and info["bytes"] == table, info
         assert info["census_rows"] == 65536 and info["census_over"][0] > 32768 and info["census_over"][1] <= 64  # 81 bins per row
         assert 0 < info["side_rows"] <= info["side_capacity"] == 4 ** K // 512 + 64
+        # locate and hits from the table that is there now: every counter of both strands (min_count 1, room for every bin)
+        pe = GP.lists_engine([d])
+        cached = ER.CachedCounts(o)
+        reads = list(case.reads) + ER.strand_reads(K)
+        for nt in (0, 1):
+            pe.set_nt_threshold(0 if nt else RT.NT_NEVER)
+            GP.run_both(pe, [cached], reads, [2], ("k = 13, locate and hits", nt))
+        pe.destroy()
+        assert d.list_table_info()["builds"] == 1
         # the head of the table against the AND of the oracle's blocks, overflow slots followed into the side table; the tail is what
         # the all-T read gathered
         slots = np.zeros(HEAD * 128, dtype=np.uint16)
