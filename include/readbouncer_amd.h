@@ -505,7 +505,9 @@ RB_API int rb_prefix_batch(rb_engine *e, const char *seqs, const uint64_t *offse
  * are kept.  Error rate and significance may differ from call to call: the state holds counts, not decisions.  The counts follow the
  * engine's N rule (rb_engine_set_revcomp_of_n) as it stood when each chunk was fed.
  * Like locate and prefixes an opt-in pass of its own: it always counts in full from each filter's own table, whatever the engine's
- * pruning / early-decision / merge / phased / row-table settings are, and changes nothing any other call returns.
+ * pruning / early-decision / merge / phased / row-table settings are, and changes nothing any other call returns -- unless the set's
+ * own rb_resume_set_lists (readbouncer_amd_tuning.h; off by default) lets a filter's list table serve a call's N-free items, which
+ * changes no result and no byte of a slot.
  * PER ITEM, vetted on the device before any address is formed from it, the slot left exactly as it was, status, decision 0,
  * best_target -1 and total_len 0 in the row, the other items of the batch unaffected:
  *   RB_ERR_INVALID_ARG  slot >= n_slots; a chunk longer than max_chunk_len; a total that would exceed max_total_len

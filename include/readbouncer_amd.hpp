@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "readbouncer_amd.h"
+#include "readbouncer_amd_tuning.h"
 
 namespace interleave
 {
@@ -577,6 +578,17 @@ public:
     ResumableCounts& operator=(const ResumableCounts&) = delete;
 
     uint64_t bytes() const { return rb_resume_bytes(slots_); }
+
+    // RB_PASS_LISTS_OFF (default) / _CURRENT / _BUILD: whether a feed's N-free items are counted from a filter's list table and merged
+    // into the slot (rb_resume_set_lists, readbouncer_amd_tuning.h); results and the slots' contents do not depend on it
+    void set_lists(int mode) { throw_status(rb_resume_set_lists(slots_, mode), "rb_resume_set_lists"); }
+    // what a feed takes for one filter as things stand: the plain build, and list_lines (0 = the plain form alone)
+    rb_resume_plan_info plan(size_t filter) const
+    {
+        rb_resume_plan_info p{};
+        throw_status(rb_resume_plan(slots_, filter, &p), "rb_resume_plan");
+        return p;
+    }
 
     // read i = seqs[offsets[i] .. offsets[i] + lens[i]) is the new chunk of slot slots[i]; flags (RB_RESUME_* per item) may be null
     ResumeResult feed_flat(const ClassifyConfig& conf, const char* seqs, const uint64_t* offsets, const uint32_t* lens, size_t n,

@@ -217,11 +217,33 @@ RB_API int rb_engine_plan_pass(rb_engine *e, size_t filter_index, uint32_t max_l
  *   RB_PASS_LISTS_CURRENT: a filter's list table is used when it has a current one; none is ever built.
  *   RB_PASS_LISTS_BUILD: a filter without a current table gets one built by the call, under the rules of the count path's list form
  *     (rb_engine_set_row_table's max_bytes, free memory, density); a refusal means the plain form, not an error.
- * rb_engine_plan_pass reports the choice in list_lines.  Spans, prefixes and resume are not affected. */
+ * rb_engine_plan_pass reports the choice in list_lines.  Spans, prefixes and resume are not affected (resume has a setting of its
+ * own, per slot set: rb_resume_set_lists below). */
 #define RB_PASS_LISTS_OFF 0
 #define RB_PASS_LISTS_CURRENT 1
 #define RB_PASS_LISTS_BUILD 2
 RB_API int rb_engine_set_pass_lists(rb_engine *e, int mode);
+/* The resume pass of readbouncer_amd.h (host and device forms) from a filter's list table, opt-in PER SLOT SET -- the
+ * engine's setting above does not reach it.  mode is RB_PASS_LISTS_OFF (the default) / _CURRENT / _BUILD with the meaning above; any other
+ * value is RB_ERR_INVALID_ARG.  Decided per filter and per call by the rules of locate and hits, with max_chunk_len + 31 bases (the
+ * stitched "tail + chunk") as the call's bound: whole-wave blocks in one column slice of at most 8192 bins, three hash functions,
+ * k <= 13, fewer than 65 536 k-mers, no column shard, no stream capture, a list table of the present version of the filter's bits.  An
+ * engine may mix list-served and plain-served filters in one call.  For a served filter, an item that is not refused and whose stitched
+ * string holds no base outside ACGT -- any length; a tail that carries an N from an earlier chunk counts -- has its new k-mers counted
+ * from the list table (2 x lines of 128 bytes per k-mer) into 16-bit counters on chip, which are then added onto the slot's sixteen
+ * bit-sliced planes, exactly at the uint16_t wrap; every other item runs the plain form in the same call.  The slot format is the plain
+ * form's: results, the count vectors read back and the slots' bytes are identical whichever form served which feed, so the setting may change
+ * between calls on live slots.  FIRST, PEEK, refusals, the duplicate-slot check and the staleness check are as without it. */
+RB_API int rb_resume_set_lists(rb_resume *r, int mode);
+/* What a resume call takes for filter `filter_index` of the set's engine, as things stand now: the plain build (ibf_resume_kernel always
+ * has sixteen planes) and list_lines -- 0 = the plain form alone; 1, 2 or 4 = the list form at that slot size for the items it takes.
+ * Host arithmetic only: nothing is built or dropped (RB_PASS_LISTS_BUILD reports the table once a call has built it). */
+typedef struct rb_resume_plan_info {
+    uint32_t lanes_per_block_log2, words_per_lane, column_slices;
+    uint32_t nontemporal;   /* 1 = the plain build's non-temporal twin (blocks of a whole wave beyond the threshold) */
+    uint32_t list_lines;
+} rb_resume_plan_info;
+RB_API int rb_resume_plan(rb_resume *r, size_t filter_index, rb_resume_plan_info *out);
 /* Fits the window lengths of the clock-phased gathers to THIS device: the planner's table was measured on one box, and clocks,
  * firmware and compilers move the optima.  For every table the engine would serve with the phased form on batches of n_reads reads
  * of read_len bases, K1 is timed on synthetic reads with the table's window and with 0.7 / 0.85 / 1.2 / 1.45 x that (same slice

@@ -20,7 +20,16 @@ Reported: (r)/(c), (r)/(b), (r)/(p) beside the same-setting spread of (b).
 Method (measuring guide): one warm-up round, then REPS alternated rounds (r, b, p, c with pruning, c without, c without rows, r, ...), hipEvent kernel
 time of rb_engine_kernel_time (summed over the four calls of (r) and of (c)), medians, min and max stated.  The rows of the four feeds
 are compared with the chunked calls' before anything is timed.
-usage: python profiles/resume_cost.py [--legs c3,readme] [--reps 5] [--reads 250000] [--out profiles/resume/cost.txt]"""
+usage: python profiles/resume_cost.py [--legs c3,readme] [--reps 5] [--reads 250000] [--out profiles/resume/cost.txt]
+
+--lists: the LIST FORM of the pass (rb_resume_set_lists) instead, APPENDED to the file under a heading of its own.  Per leg, one process,
+one slot set, alternated rounds of
+  (r0) the four feeds under RB_PASS_LISTS_OFF
+  (rl) the four feeds under the list form (RB_PASS_LISTS_BUILD: the warm-up builds the table where the filter has none; the plan's
+       list_lines is printed -- 0 on the README shape, whose narrow filters do not qualify: the control, (rl)/(r0) = 1.000 expected)
+  (c)  the four chunked rb_classify_batch_device_ex calls as the engine runs them today (bound pruning on, row table AUTO)
+Expectation to confirm or refute on c3: a feed gathers two lines per k-mer as locate's list form does (34.4 ms per 1 M items of 360 bp),
+plus 32 KiB read and 32 KiB written per item -- the first feed (FIRST) reads none.  The rows of both forms are compared before timing."""
 import argparse
 import os
 import statistics
@@ -126,26 +135,92 @@ def run_leg(name, n_reads, reps, torch, say):
     torch.cuda.empty_cache()
 
 
+def run_lists_leg(name, n_reads, reps, torch, say):
+    dep_keys, tgt_keys = LEGS[name]
+    built = {k: synth.build_device_filter(0, synth.WORKLOADS[k], *SEEDS[k], n_segments=512 if k.startswith("mock_") else 2048) for k in dep_keys + tgt_keys}
+    dep, tgt = [built[k][0] for k in dep_keys], [built[k][0] for k in tgt_keys]
+    nf, P = len(dep) + len(tgt), len(CHECKPOINTS)
+    eng = capi.Engine(0, dep, tgt)
+    eng.set_timing(1)
+    rs = eng.resume(n_reads, CHUNK, READ_LEN)
+    dev = torch.device("cuda:0")
+    seqs, offs, lens = synth.make_reads_device(77, n_reads, READ_LEN, built[(dep_keys + tgt_keys)[0]][1], dev)
+    slots = torch.arange(n_reads, dtype=torch.int32, device=dev)
+    first = torch.full((n_reads,), capi.RB_RESUME_FIRST, dtype=torch.uint8, device=dev)
+    out = {key: (torch.zeros((P, n_reads, nf), dtype=torch.int16, device=dev), torch.zeros((P, n_reads), dtype=torch.uint8, device=dev))
+           for key in ("r0", "rl", "c")}
+    r_best, r_len = (torch.zeros((P, n_reads), dtype=torch.int32, device=dev) for _ in range(2))
+    r_st = torch.zeros((P, n_reads), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+
+    def feeds(key, mode):
+        def go():
+            rs.set_lists(mode)
+            for p in range(P):
+                rs.feed_device(seqs.data_ptr(), offs.data_ptr(), lens.data_ptr(), n_reads, slots.data_ptr(), first.data_ptr() if p == 0 else None,
+                               chunk_start=p * CHUNK, chunk_length=CHUNK, d_max_count=out[key][0][p].data_ptr(), d_decision=out[key][1][p].data_ptr(),
+                               d_best_target=r_best[p].data_ptr(), d_status=r_st[p].data_ptr(), d_total_len=r_len[p].data_ptr())
+        return go
+
+    def chunked():
+        for p, c in enumerate(CHECKPOINTS):
+            eng.classify_device_ex(seqs.data_ptr(), offs.data_ptr(), lens.data_ptr(), n_reads, READ_LEN, chunk_length=c,
+                                   d_maxcount=out["c"][0][p].data_ptr(), d_decision=out["c"][1][p].data_ptr())
+
+    legs = (("r0", feeds("r0", capi.RB_PASS_LISTS_OFF)), ("rl", feeds("rl", capi.RB_PASS_LISTS_BUILD)), ("c", chunked))
+    for _, fn in legs:  # warm-up (builds the list table under BUILD)
+        kernel_ms(eng, fn)
+    torch.cuda.synchronize()
+    lines = [rs.plan(j)["list_lines"] for j in range(nf)]
+    for key in ("rl", "c"):
+        assert torch.equal(out["r0"][0], out[key][0]) and torch.equal(out["r0"][1], out[key][1]), "rows of (%s) differ from the plain feeds'" % key
+    assert int(r_st.max()) == 0
+    ms = {key: [] for key, _ in legs}
+    for _ in range(reps):  # alternated
+        for key, fn in legs:
+            ms[key].append(kernel_ms(eng, fn))
+    med = {key: statistics.median(v) for key, v in ms.items()}
+    spread = {key: max(v) - min(v) for key, v in ms.items()}
+    say("%s: %d reads of %d bp in %d chunks of %d, %d filter(s), %d slots = %.3f GB of HBM, list_lines per filter %s, %d alternated repetitions" %
+        (name, n_reads, READ_LEN, P, CHUNK, nf, n_reads, rs.bytes / 1e9, lines, reps))
+    for key, what in (("r0", "(r0) four feeds, setting off          "), ("rl", "(rl) four feeds, list form            "),
+                      ("c", "(c)  four chunked classify, as today  ")):
+        say("  %s: median %.3f ms  (min %.3f, max %.3f, spread %.3f)" % (what, med[key], min(ms[key]), max(ms[key]), spread[key]))
+    say("  (rl)/(r0) = %.4f   (rl)/(c) = %.4f   (r0)/(c) = %.4f   (r0) - (rl) = %.3f ms = %.1f spreads of (r0)" %
+        (med["rl"] / med["r0"], med["rl"] / med["c"], med["r0"] / med["c"], med["r0"] - med["rl"],
+         (med["r0"] - med["rl"]) / spread["r0"] if spread["r0"] > 0 else float("inf")))
+    rs.destroy()
+    eng.destroy()
+    for k in built:
+        built[k][0].free()
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default="c3,readme")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--reads", type=int, default=250_000)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resume", "cost.txt"))
+    ap.add_argument("--lists", action="store_true", help="the list form against the plain feeds and the chunked calls, appended to --out")
     args = ap.parse_args()
     assert args.reps >= 5, "at least five alternated repetitions"
     import torch
     if capi.device_count() <= 0:
         sys.exit("resume_cost.py needs a GPU")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as fh:
+    with open(args.out, "a" if args.lists else "w") as fh:
         def say(line):
             print(line, flush=True)
             fh.write(line + "\n")
             fh.flush()
-        say("resume cost -- %s, library %s" % (torch.cuda.get_device_name(0), os.path.basename(capi.LIB_PATH)))
+        if args.lists:
+            say("")
+            say("resume cost, list form (rb_resume_set_lists) -- %s, library %s" % (torch.cuda.get_device_name(0), os.path.basename(capi.LIB_PATH)))
+        else:
+            say("resume cost -- %s, library %s" % (torch.cuda.get_device_name(0), os.path.basename(capi.LIB_PATH)))
         for leg in args.legs.split(","):
-            run_leg(leg.strip(), args.reads, args.reps, torch, say)
+            (run_lists_leg if args.lists else run_leg)(leg.strip(), args.reads, args.reps, torch, say)
 
 
 if __name__ == "__main__":

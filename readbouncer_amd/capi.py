@@ -121,6 +121,12 @@ class PassPlan(C.Structure):
                 ("spans_nontemporal", C.c_uint32), ("list_lines", C.c_uint32)]
 
 
+class ResumePlan(C.Structure):
+    """rb_resume_plan_info: what a resume call takes for one filter of the set"""
+    _fields_ = [("lanes_per_block_log2", C.c_uint32), ("words_per_lane", C.c_uint32), ("column_slices", C.c_uint32),
+                ("nontemporal", C.c_uint32), ("list_lines", C.c_uint32)]
+
+
 class BinRef(C.Structure):
     """rb_bin_ref: one (source filter, bin) of an assemble plan -- 8 bytes"""
     _fields_ = [("filter", C.c_uint32), ("bin", C.c_uint32)]
@@ -208,6 +214,8 @@ SIGNATURES = {
     "rb_resume_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _vp, _vp, _dbl, _dbl, _int, C.POINTER(ResumeOut), _vp]),
     "rb_resume_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _dbl, _dbl, _int, C.POINTER(ResumeOut)]),
     "rb_resume_counts": (_int, [_vp, _u32, _sz, _vp, _vp]),
+    "rb_resume_set_lists": (_int, [_vp, _int]),
+    "rb_resume_plan": (_int, [_vp, _sz, C.POINTER(ResumePlan)]),
     "rb_hits_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _dbl, _dbl, C.c_uint16, C.c_uint32, C.POINTER(HitsOut), _vp]),
     "rb_hits_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _dbl, _dbl, C.c_uint16, C.c_uint32, C.POINTER(HitsOut)]),
     "rb_spans_batch_device": (_int, [_vp, C.POINTER(BatchDesc), _sz, _vp, _sz, C.c_uint32, C.POINTER(SpansOut), _vp]),
@@ -991,6 +999,18 @@ class Resume:
     @property
     def bytes(self):
         return int(lib().rb_resume_bytes(self.h))
+
+    def set_lists(self, mode):
+        """RB_PASS_LISTS_OFF (default) / _CURRENT / _BUILD for THIS slot set (rb_resume_set_lists): whether a feed's N-free items are
+        counted from a filter's list table and merged into the slot; results and the slots' contents do not depend on it"""
+        _check(lib().rb_resume_set_lists(self.h, int(mode)), "rb_resume_set_lists")
+
+    def plan(self, filter_index):
+        """what a feed takes for that filter as things stand -> dict (rb_resume_plan_info); list_lines: 0 = the plain form alone, else the
+        slot size at which the list form serves the items it takes"""
+        p = ResumePlan()
+        _check(lib().rb_resume_plan(self.h, filter_index, C.byref(p)), "rb_resume_plan")
+        return {name: int(getattr(p, name)) for name, _ in ResumePlan._fields_}
 
     def feed(self, seqs, offsets, lens, slots, flags=None, error_rate=0.1, significance=0.95, mode=RB_MODE_CHECK_UNBLOCK):
         """read i is the new chunk of slot slots[i] (rb_resume_batch): host buffers in, a dict of host numpy arrays out --

@@ -348,8 +348,17 @@ struct ResumeSlots {
 struct ResumeLaunch : PlainPassLaunch {
     ResumeSlots slots;
     uint16_t *part;  // [n_slices][n_items]
+    const uint8_t *list_plain_ctl;  // list form: slots.ctl with kResumeSkip set for the items of list_taken (launch_resume_lists_prep)
 };
 hipError_t launch_ibf_resume(const ResumeLaunch &a, hipStream_t st);
+// ... the list form (rb_resume_lists.hip; rb_resume_set_lists).  Which items it takes, once per call after the prep kernel below: taken[item]
+// = 1 when the item is not refused and its stitched string holds no base outside ACGT (any length), and plain_ctl[item] = ctl[item], with
+// kResumeSkip for a taken item.  launch_ibf_resume_lists is launch_ibf_resume over list_plain_ctl -- a taken item gets a zero partial there
+// and no address of its slot is formed -- and then ibf_resume_lists_kernel<LINES, NT>, which counts a taken item's new k-mers from the
+// list table into LDS and merges them into the slot's planes (rb_resume_planes.h), overwriting the item's partial of slice 0.
+hipError_t launch_resume_lists_prep(const ReadSrc &src, uint32_t n_items, const uint8_t *pre_status, const uint8_t *ctl, uint8_t *taken,
+                                    uint8_t *plain_ctl, hipStream_t st);
+hipError_t launch_ibf_resume_lists(const ResumeLaunch &a, hipStream_t st);
 // ... and the small kernels around the pass.  Prep: vets item i (slot number, chunk length, total), writes its stitched string as ASCII at
 // stitched + i * stitch_stride, its length, the bytes offset, the total the row stands for, its pre-status and its ctl bits.
 struct ResumePrep {

@@ -2796,18 +2796,19 @@ static void fill_plain_launch(const rb_engine *e, size_t fi, const PassInput &in
 // would keep the address of a table the next change of the bits frees), and the filter has a table of the present version of its bits --
 // under RB_PASS_LISTS_BUILD built now through list_table_for, whose refusals mean the plain form.  a->list_table stays null wherever
 // the answer is no.  asking: the question alone (rb_engine_plan_pass) -- no stream, and nothing is built or dropped.
-static int pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, PlainPassLaunch *a)
+// lists_for: the same under a setting the caller names -- the engine's for locate and hits, a slot set's own for resume (rb_resume_set_lists).
+static int lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, int mode, PlainPassLaunch *a)
 {
     a->list_table = nullptr;
     a->list_side = nullptr;
     a->list_side_rows = a->list_lines = 0;
     a->list_nt = 0;
-    if (e->pass_lists == RB_PASS_LISTS_OFF || e->shard_world != 1 || !pass_list_form_serves(*a)) return RB_OK;
+    if (mode == RB_PASS_LISTS_OFF || e->shard_world != 1 || !pass_list_form_serves(*a)) return RB_OK;
     rb_dibf *f = e->filters[fi];
     if (list_table_geometry_refusal(f)) return RB_OK;
     uint64_t list_bytes = 0;
     CountLaunch got{};
-    if (e->pass_lists == RB_PASS_LISTS_BUILD && !asking) {
+    if (mode == RB_PASS_LISTS_BUILD && !asking) {
         const int rc = list_table_for(e, f, st, got, &list_bytes);
         if (rc != RB_OK) return rc;
     } else {
@@ -2828,6 +2829,10 @@ static int pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, 
     a->list_lines = got.list_lines;
     a->list_nt = list_bytes > e->nt_threshold_bytes;
     return RB_OK;
+}
+static int pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, PlainPassLaunch *a)
+{
+    return lists_for(e, fi, st, asking, e->pass_lists, a);
 }
 
 // ... and the list forms' share of a call: which items they take is decided once, for every filter (launch_pass_lists_prep: the status
@@ -3969,6 +3974,8 @@ struct rb_resume {
     uint64_t slot_words = 0;
     uint64_t *d_state = nullptr;
     ResumeMeta *d_meta = nullptr;
+    // rb_resume_set_lists: whether a call's N-free items are counted from a filter's list table and merged into the slot (resume_lists_for)
+    int lists = RB_PASS_LISTS_OFF;
 };
 
 static int check_resume_args(const rb_resume_out *out, int mode)
@@ -3999,6 +4006,45 @@ static int check_resume_fresh(const rb_resume *r)
     return RB_OK;
 }
 
+// What one filter's resume launch is, short of the slots and the partials: the plain launch over items of at most max_chunk_len +
+// kResumeMaxTail bases on sixteen planes, and -- under the set's own setting, by the rules of locate and hits (lists_for) -- the filter's
+// list table.  asking: rb_resume_plan's question; nothing is built or dropped.
+static int resume_lists_for(rb_resume *r, size_t fi, const PassInput &in, const uint16_t *thr, uint32_t thr_len, hipStream_t st, bool asking,
+                            ResumeLaunch *a)
+{
+    fill_plain_launch(r->e, fi, in, thr, thr_len, a);
+    a->planes = (int)kResumePlanes;
+    return lists_for(r->e, fi, st, asking, r->lists, a);
+}
+
+int rb_resume_set_lists(rb_resume *r, int mode)
+{
+    if (!r || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
+    std::lock_guard<std::mutex> lock(r->e->mu);
+    r->lists = mode;
+    return RB_OK;
+}
+
+int rb_resume_plan(rb_resume *r, size_t filter_index, rb_resume_plan_info *out)
+{
+    if (!r || !out || filter_index >= r->per.size()) return rb::fail(RB_ERR_INVALID_ARG, "rb_resume_plan: bad argument");
+    rb_engine *e = r->e;
+    std::lock_guard<std::mutex> lock(e->mu);
+    std::memset(out, 0, sizeof *out);
+    if (filter_index >= e->filters.size()) return rb::fail(RB_ERR_INVALID_ARG, "rb_resume_plan: the engine lost the filter");
+    PassInput in{};
+    in.src.max_len = in.max_len = r->max_chunk_len + kResumeMaxTail;
+    ResumeLaunch a{};
+    const int rc = resume_lists_for(r, filter_index, in, nullptr, 0, nullptr, true, &a);
+    if (rc != RB_OK) return rc;
+    out->lanes_per_block_log2 = (uint32_t)a.lg;
+    out->words_per_lane = (uint32_t)a.wpl;
+    out->column_slices = a.n_slices;
+    out->nontemporal = plain_pass_nt(a.lg, a.nt) ? 1u : 0u;
+    out->list_lines = a.list_table ? a.list_lines : 0u;
+    return RB_OK;
+}
+
 int rb_resume_batch_device(rb_resume *r, const rb_batch_desc *desc, const void *d_slots, const void *d_flags, double error_rate,
                            double significance, int mode, const rb_resume_out *d_out, void *stream)
 {
@@ -4026,6 +4072,16 @@ int rb_resume_batch_device(rb_resume *r, const rb_batch_desc *desc, const void *
     const size_t o_soff = lay.take(n * 8), o_slen = lay.take(n * 4), o_tot = lay.take(n * 4), o_pre = lay.take(n), o_ctl = lay.take(n);
     const size_t o_seq = lay.take(n * (size_t)stride), o_part = lay.take((size_t)max_slices * n * 2);
     const size_t o_max = lay.take(d_out->max_count ? 0 : n * nf * 2);
+    // the list form (rb_resume_set_lists), decided per filter before anything is launched; room for who-takes-which-item only when some
+    // filter is served.  (the input's addresses are filled in below: the decision reads its bound alone)
+    c.in.src.max_len = c.in.max_len = r->max_chunk_len + kResumeMaxTail;
+    std::vector<ResumeLaunch> launches(nf);
+    bool any_lists = false;
+    for (size_t fi = 0; fi < nf; ++fi) {
+        if ((rc = resume_lists_for(r, fi, c.in, c.thr, c.thr_len, c.st, false, &launches[fi])) != RB_OK) return rc;
+        any_lists |= launches[fi].list_table != nullptr;
+    }
+    const size_t o_taken = lay.take(any_lists ? n : 0), o_pctl = lay.take(any_lists ? n : 0);
     if ((rc = c.start(lay.bytes())) != RB_OK) return rc;
     char *ws = c.ws();
     uint16_t *part = (uint16_t *)(ws + o_part);
@@ -4064,12 +4120,14 @@ int rb_resume_batch_device(rb_resume *r, const rb_batch_desc *desc, const void *
     c.in.d_lens = prep.st_lens;
     c.in.max_len = c.in.src.max_len;
     c.in.n_items = n;
+    uint8_t *taken = (uint8_t *)(ws + o_taken), *plain_ctl = (uint8_t *)(ws + o_pctl);
+    if (any_lists) RB_HIP(launch_resume_lists_prep(c.in.src, (uint32_t)n, prep.pre_status, prep.ctl, taken, plain_ctl, c.st));
     for (size_t fi = 0; fi < nf; ++fi) {
         const rb_resume::PerFilter &p = r->per[fi];
-        ResumeLaunch a{};
-        fill_plain_launch(e, fi, c.in, c.thr, c.thr_len, &a);
+        ResumeLaunch &a = launches[fi];
+        a.src = c.in.src;
+        a.n_items = (uint32_t)n;
         if (a.lg != p.lg || a.wpl != p.wpl || a.n_slices != p.n_slices) return rb::fail(RB_ERR_INVALID_ARG, "filter geometry moved under the slots");
-        a.planes = (int)kResumePlanes;
         a.slots.state = r->d_state;
         a.slots.slot = prep.slot;
         a.slots.ctl = prep.ctl;
@@ -4077,7 +4135,13 @@ int rb_resume_batch_device(rb_resume *r, const rb_batch_desc *desc, const void *
         a.slots.filter_off = p.off;
         a.slots.pad_cols = p.pad_cols;
         a.part = part;
-        RB_HIP(launch_ibf_resume(a, c.st));
+        if (a.list_table) {  // the plain kernel over plain_ctl, then the list kernel for the taken items
+            a.list_taken = taken;
+            a.list_plain_ctl = plain_ctl;
+            RB_HIP(launch_ibf_resume_lists(a, c.st));
+        } else {
+            RB_HIP(launch_ibf_resume(a, c.st));
+        }
         RB_HIP(launch_reduce_slices(part, a.n_slices, (uint32_t)n, max_count, (uint32_t)nf, (uint32_t)fi, c.st));
     }
     if (d_out->decision || d_out->best_target || d_out->status) {

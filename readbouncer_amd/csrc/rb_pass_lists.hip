@@ -1,32 +1,15 @@
 // rb_pass_lists.hip -- the LIST FORMS of the locate and hits passes (rb_engine_set_pass_lists): the kernels that serve them from a filter's
 // list table (rb_lists.h) with the wave of ibf_count_lists_kernel, and the small kernel that says which work items they take.  A translation
-// unit of its own beside rb_lists.hip, whose device code it shares through rb_lists_device.h.
+// unit of its own beside rb_lists.hip, whose device code it shares through rb_lists_device.h; what it shares in turn with the list form of
+// the resume pass (rb_resume_lists.hip) -- pass_lists_takes and list_count_strand -- is in rb_pass_lists_device.h.
 #include <hip/hip_runtime.h>
 
 #include "rb_device.h"
 #include "rb_lists.h"
 #include "rb_lists_device.h"
+#include "rb_pass_lists_device.h"
 
 namespace rb {
-
-// Which work items the list kernels take: the item is RB_OK (item_status's rules: chunk_prep's verdict, the declared bound, the engine's
-// largest k) and its chunk window holds no base outside ACGT, which is what the list table has slots for.  Called by a whole wave for
-// one item; the answer is wave-uniform.
-__device__ __forceinline__ bool pass_lists_takes(const ReadSrc &r, uint32_t item, const uint8_t *pre_status, uint32_t min_len, uint32_t lane)
-{
-    const uint32_t len = r.lens[item];
-    if ((pre_status && pre_status[item] != RB_OK) || len > r.max_len || len < min_len) return false;
-    const uint32_t rid = r.ids ? r.ids[item] : item;
-    bool outside = false;
-    if (r.nmask) {  // packed input: a base is outside exactly when its bit of the N bitmap is set
-        const uint8_t *nm = r.nmask + r.nmask_offsets[rid];
-        for (uint32_t i = lane; i < len; i += 64) outside |= ((nm[(r.base_off + i) >> 3] >> ((r.base_off + i) & 7u)) & 1u) != 0;
-    } else {
-        const uint8_t *s = r.seqs + r.offsets[rid] + r.base_off;
-        for (uint32_t i = lane; i < len; i += 64) outside |= rbspec::dna5_ord(s[i]) > 3u;
-    }
-    return __ballot(outside) == 0ULL;
-}
 
 // ... decided once per call, one wave per item: the ONE predicate of both sides.  The list kernels read taken[]; the plain kernels are
 // launched as they are, with plain_lens[] for the items' lengths -- 0 for a taken item, so they count nothing of it.
@@ -57,56 +40,6 @@ hipError_t launch_pass_lists_prep(const PassListsPrep &a, hipStream_t st)
 // items the prep kernel marked in taken[]; the plain kernels take the others.  LDS: the count kernel's counters, spares and stage, then
 // the hit mask (rblist::pass_lds_bytes), one byte per 16-byte piece of the counters: bit j of byte i is bin 8 i + j.  The lane that scans
 // piece i on the first strand scans it on the second.
-
-// One strand of an item, counted in full: the tile loop of ibf_count_lists_kernel without the bound, the strand skip and the stop.
-template <int LINES, bool NT>
-__device__ __forceinline__ void list_count_strand(const IbfDev &f, uint32_t *cnt, uint8_t *stage, const uint32_t *__restrict__ slots,
-                                                  const uint64_t *__restrict__ side, uint32_t side_rows, const ListBaseSrc &seq, uint32_t len,
-                                                  uint32_t n, int strand, uint32_t lane, uint32_t spare)
-{
-    constexpr uint32_t R = LINES == 4 ? 32 : 64;  // slots per batch (list_batch)
-    const uint32_t k = f.k;
-    uint32_t ahead0 = 0, ahead1 = 0;  // a tile's bases, loaded one tile ahead
-    bool ahead = false;
-#pragma unroll 1
-    for (uint32_t mt = 0; mt < n; mt += 64) {
-        const uint32_t wlen = min(64u + k - 1u, len - mt);
-        if (!ahead) {  // wave-uniform
-            ahead0 = lane < wlen ? seq.raw(mt + lane) : 0u;
-            ahead1 = lane + 64u < wlen ? seq.raw(mt + 64u + lane) : 0u;
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (lane < wlen) stage[lane] = (uint8_t)seq.ord_of(ahead0, mt + lane);
-        if (lane + 64u < wlen) stage[lane + 64u] = (uint8_t)seq.ord_of(ahead1, mt + 64u + lane);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        const uint32_t p = mt + lane;
-        uint32_t rank = 0;
-        if (p < n) {
-            const uint8_t *b = stage + lane;
-            if (strand == 0) {
-                for (uint32_t i = 0; i < k; ++i) rank = (rank << 2) | (b[i] & 3u);
-            } else {
-                for (uint32_t i = 0; i < k; ++i) rank = (rank << 2) | (rbspec::dna5_comp(b[k - 1 - i], f.comp_n) & 3u);
-            }
-        }
-        const uint32_t in_tile = __builtin_amdgcn_readfirstlane(min(64u, n - mt));
-        ahead = mt + 64u < n;
-        if (ahead) {
-            const uint32_t next = min(64u + k - 1u, len - (mt + 64u));
-            ahead0 = lane < next ? seq.raw(mt + 64u + lane) : 0u;
-            ahead1 = lane + 64u < next ? seq.raw(mt + 128u + lane) : 0u;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll 1
-        for (uint32_t first = 0; first < in_tile; first += R) {
-            if (first + R <= in_tile)  // wave-uniform
-                list_batch<LINES, NT, true>(f, cnt, slots, side, side_rows, rank, first, in_tile, lane, spare);
-            else
-                list_batch<LINES, NT, false>(f, cnt, slots, side, side_rows, rank, first, in_tile, lane, spare);
-        }
-    }
-}
 
 // A 16-byte piece of the counters, eight bins: counter j (a compile-time place), the largest of the eight, and the bits of those at or
 // above t among the bins that exist.  A pad counter -- behind n_bins -- is never added to, and `valid` keeps it out even at t == 0.
