@@ -464,8 +464,9 @@ RB_API int rb_spans_batch(rb_engine *e, const char *seqs, const uint64_t *offset
  * has one): decision, best target and status -- RB_ERR_SHORT_READ for a prefix shorter than k, RB_ERR_BAD_CHUNK, RB_ERR_INVALID_ARG for a
  * row longer than max_len included -- and max_count wherever the row's status is RB_OK.  A checkpoint at or beyond the item's end
  * repeats the whole-item row; prefix_len says so.  All three modes.
- * Like locate an opt-in pass of its own: it always counts in full from each filter's own table, whatever the engine's pruning /
- * early-decision / merge / phased settings are, and changes nothing any other call returns.
+ * Like locate an opt-in pass of its own: it always counts in full, whatever the engine's pruning / early-decision / merge / phased
+ * settings are, and changes nothing any other call returns; from each filter's own table unless rb_engine_set_prefix_lists
+ * (readbouncer_amd_tuning.h; off by default) lets a filter's list table serve it, which returns the same bytes.
  * RB_ERR_INVALID_ARG, with an rb_last_error() that names the fault: null arguments, n_prefixes of 0 or above RB_PREFIX_MAX, a
  * checkpoint of 0, a list that is not strictly rising, an rb_prefix_out with no output, an unknown mode, a column-sharded engine. */
 #define RB_PREFIX_MAX 64

@@ -190,7 +190,8 @@ typedef struct rb_plan_info {
 } rb_plan_info;
 RB_API int rb_engine_plan(rb_engine *e, size_t filter_index, size_t n_reads, uint32_t max_len, rb_plan_info *out);
 /* The same question for the query passes of readbouncer_amd.h (locate, hits, prefixes and spans, host and device forms),
- * which none of the settings above but rb_engine_set_nt_threshold reaches: the build a call on items of at most max_len bases takes
+ * which none of the settings above but rb_engine_set_nt_threshold reaches (the list settings below are their own: rb_engine_set_pass_lists
+ * for locate and hits, rb_engine_set_prefix_lists for prefixes): the build a call on items of at most max_len bases takes
  * for filter `filter_index` (prefixes: no item is longer than the last checkpoint), filled by the functions the launches themselves go
  * through.  Host arithmetic only; for the tests, which pin every build of a pass to the oracle and need to know which one a launch
  * took. */
@@ -200,7 +201,7 @@ typedef struct rb_pass_plan {
     uint32_t nontemporal;        /* locate, hits, prefixes: 1 = the non-temporal twin (blocks of a whole wave beyond the threshold) */
     uint32_t hash_functions;     /* 3: the build with three compile-time hash functions; 0: the run-time hash count */
     uint32_t spans_nontemporal;  /* spans (one wave per query, no geometry, no planes): 1 = its non-temporal twin, at any block width */
-    uint32_t list_lines;         /* locate and hits only (spans and prefixes are not affected): 0 = the plain build the fields above describe;
+    uint32_t list_lines;         /* locate and hits only (spans are not affected; prefixes answer in rb_engine_plan_prefix): 0 = the plain build the fields above describe;
                                     1, 2 or 4 = the list form (rb_engine_set_pass_lists) at that slot size, for this filter, this max_len and
                                     the engine's setting as it stands -- items the list form does not take still run the plain build */
 } rb_pass_plan;
@@ -218,7 +219,7 @@ RB_API int rb_engine_plan_pass(rb_engine *e, size_t filter_index, uint32_t max_l
  *   RB_PASS_LISTS_BUILD: a filter without a current table gets one built by the call, under the rules of the count path's list form
  *     (rb_engine_set_row_table's max_bytes, free memory, density); a refusal means the plain form, not an error.
  * rb_engine_plan_pass reports the choice in list_lines.  Spans, prefixes and resume are not affected (resume has a setting of its
- * own, per slot set: rb_resume_set_lists below). */
+ * own, per slot set: rb_resume_set_lists below; so have prefixes, per engine: rb_engine_set_prefix_lists below). */
 #define RB_PASS_LISTS_OFF 0
 #define RB_PASS_LISTS_CURRENT 1
 #define RB_PASS_LISTS_BUILD 2
@@ -244,6 +245,31 @@ typedef struct rb_resume_plan_info {
     uint32_t list_lines;
 } rb_resume_plan_info;
 RB_API int rb_resume_plan(rb_resume *r, size_t filter_index, rb_resume_plan_info *out);
+/* The prefix pass of readbouncer_amd.h (host and device forms) from a filter's list table, opt-in with a setting of ITS
+ * OWN: rb_engine_set_pass_lists does not reach the prefix pass, and this setting does not reach locate or hits.  mode is
+ * RB_PASS_LISTS_OFF (the default) / _CURRENT / _BUILD with the meaning above; any other value is RB_ERR_INVALID_ARG.  Decided per filter
+ * and per call by the rules of locate and hits, with min(the call's max_len, the last checkpoint) as the call's bound -- so "fewer than
+ * 65 536 k-mers" is asked of the last checkpoint, not of the reads -- whole-wave blocks in one column slice of at most 8192 bins, three
+ * hash functions, k <= 13, no column shard, no stream capture, a list table of the present version of the filter's bits.  For a served
+ * filter, an item whose status so far is RB_OK, whose w = min(length, last checkpoint) bases lie within the call's bound and are all
+ * ACGT -- any length; a base outside ACGT BEHIND the last checkpoint does not matter -- has the k-mers between two checkpoints counted from
+ * the list table (2 x lines of 128 bytes per k-mer) into 16-bit counters on chip, which are scanned for their maximum at every checkpoint
+ * that adds a k-mer; every other item runs the plain form in the same call.  Results are the plain form's, bit for bit. */
+RB_API int rb_engine_set_prefix_lists(rb_engine *e, int mode);
+/* What a prefix call takes for filter `filter_index` on items of at most max_len bases with `last_checkpoint` as its last checkpoint, as
+ * things stand now: the plain build (the fields of rb_pass_plan for min(max_len, last_checkpoint) bases) and list_lines -- 0 = the plain
+ * form alone; 1, 2 or 4 = the list form at that slot size for the items it takes.  Host arithmetic only: nothing is built or dropped
+ * (RB_PASS_LISTS_BUILD reports the table once a call has built it). */
+typedef struct rb_prefix_plan_info {
+    uint32_t lanes_per_block_log2, words_per_lane, column_slices;
+    uint32_t counter_planes, nontemporal, hash_functions;   /* as rb_pass_plan's */
+    uint32_t list_lines;
+} rb_prefix_plan_info;
+RB_API int rb_engine_plan_prefix(rb_engine *e, size_t filter_index, uint32_t max_len, uint32_t last_checkpoint, rb_prefix_plan_info *out);
+/* The work items the list form of the prefix pass took (*listed) and left to the plain form (*plain) since the last reset, summed over
+ * the calls in which at least one filter was list-served (counted on the device by the kernel that decides it; a call with no list-served
+ * filter counts nothing).  Either pointer may be NULL.  reset != 0 zeroes both afterwards.  Waits for the engine's own stream. */
+RB_API int rb_engine_prefix_lists_items(rb_engine *e, uint64_t *listed, uint64_t *plain, int reset);
 /* Fits the window lengths of the clock-phased gathers to THIS device: the planner's table was measured on one box, and clocks,
  * firmware and compilers move the optima.  For every table the engine would serve with the phased form on batches of n_reads reads
  * of read_len bases, K1 is timed on synthetic reads with the table's window and with 0.7 / 0.85 / 1.2 / 1.45 x that (same slice

@@ -127,6 +127,12 @@ class ResumePlan(C.Structure):
                 ("nontemporal", C.c_uint32), ("list_lines", C.c_uint32)]
 
 
+class PrefixPlan(C.Structure):
+    """rb_prefix_plan_info: what a prefix call takes for one filter"""
+    _fields_ = [("lanes_per_block_log2", C.c_uint32), ("words_per_lane", C.c_uint32), ("column_slices", C.c_uint32),
+                ("counter_planes", C.c_uint32), ("nontemporal", C.c_uint32), ("hash_functions", C.c_uint32), ("list_lines", C.c_uint32)]
+
+
 class BinRef(C.Structure):
     """rb_bin_ref: one (source filter, bin) of an assemble plan -- 8 bytes"""
     _fields_ = [("filter", C.c_uint32), ("bin", C.c_uint32)]
@@ -267,6 +273,9 @@ SIGNATURES = {
     "rb_dibf_row_table_download": (_int, [_vp, _vp, _u64]),
     "rb_engine_set_row_table": (_int, [_vp, _int, _u64]),
     "rb_engine_set_pass_lists": (_int, [_vp, _int]),
+    "rb_engine_set_prefix_lists": (_int, [_vp, _int]),
+    "rb_engine_plan_prefix": (_int, [_vp, _sz, _u32, _u32, C.POINTER(PrefixPlan)]),
+    "rb_engine_prefix_lists_items": (_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _int]),
     "rb_dibf_list_table_build": (_int, [_vp, _u64]),
     "rb_dibf_list_table_drop": (_int, [_vp]),
     "rb_dibf_list_table_info": (_int, [_vp, C.POINTER(ListTableInfo)]),
@@ -947,6 +956,25 @@ class Engine:
         """RB_PASS_LISTS_OFF (default) / _CURRENT (a filter's list table where it has a current one) / _BUILD (built when there is none):
         whether locate and hits are served from the list table (results identical; plan_pass reports list_lines)"""
         _check(lib().rb_engine_set_pass_lists(self.h, int(mode)), "rb_engine_set_pass_lists")
+
+    def set_prefix_lists(self, mode):
+        """RB_PASS_LISTS_OFF (default) / _CURRENT / _BUILD for the prefix pass alone (rb_engine_set_prefix_lists): whether prefixes are
+        served from a filter's list table (results identical; plan_prefix reports list_lines)"""
+        _check(lib().rb_engine_set_prefix_lists(self.h, int(mode)), "rb_engine_set_prefix_lists")
+
+    def plan_prefix(self, filter_index, max_len, last_checkpoint):
+        """what a prefix call takes for that filter on items of at most max_len bases with that last checkpoint -> dict
+        (rb_prefix_plan_info); list_lines: 0 = the plain form alone, else the list form's slot size"""
+        p = PrefixPlan()
+        _check(lib().rb_engine_plan_prefix(self.h, filter_index, int(max_len), int(last_checkpoint), C.byref(p)), "rb_engine_plan_prefix")
+        return {name: int(getattr(p, name)) for name, _ in PrefixPlan._fields_}
+
+    def prefix_lists_items(self, reset=False):
+        """-> (items the list form of the prefix pass took, items it left to the plain form) since the last reset, over the calls in
+        which some filter was list-served (rb_engine_prefix_lists_items)"""
+        listed, plain = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rb_engine_prefix_lists_items(self.h, C.byref(listed), C.byref(plain), int(bool(reset))), "rb_engine_prefix_lists_items")
+        return int(listed.value), int(plain.value)
 
     def set_list_min_dense_bytes(self, n_bytes):
         """size of the dense row table from which RB_ROW_TABLE_AUTO prefers the list table (default 512 MiB; 0: always)"""

@@ -316,6 +316,22 @@ struct PrefixLaunch : PlainPassLaunch {
     uint16_t *part;  // [n_slices][n_items][cps.n]
 };
 hipError_t launch_ibf_prefix(const PrefixLaunch &a, hipStream_t st);
+// ... the list form (rb_prefix_lists.hip; rb_engine_set_prefix_lists).  Which items it takes, once per call: with w = min(lens[item], c_last),
+// taken[item] = 1 when the item's pre-status is RB_OK, w <= src.max_len and the first w bases of its chunk window are all ACGT -- any
+// length, below k and empty included; plain_lens[item] is the item's length, or 0 for a taken item.  counters[0] += the items taken,
+// counters[1] += the items left.  launch_ibf_prefix_lists is launch_ibf_prefix over a.list_plain_lens and then
+// ibf_prefix_lists_kernel<LINES, NT>, which overwrites the taken items' partials of slice 0 (of one).
+struct PrefixListsPrep {
+    ReadSrc src;
+    uint32_t n_items;
+    const uint8_t *pre_status;  // chunk_prep's per-item status, or nullptr
+    uint32_t c_last;            // the last checkpoint
+    uint8_t *taken;
+    uint32_t *plain_lens;
+    uint64_t *counters;         // two, the engine's
+};
+hipError_t launch_prefix_lists_prep(const PrefixListsPrep &a, hipStream_t st);
+hipError_t launch_ibf_prefix_lists(const PrefixLaunch &a, hipStream_t st);
 // max_count [n_items][cps.n][nf] <- the maximum over the slices; for fidx == 0 also prefix_len / row_pre [n_items][cps.n]
 hipError_t launch_finish_prefix(const PrefixLaunch &a, const uint32_t *lens, const uint8_t *pre_status, uint16_t *max_count, uint32_t *prefix_len,
                                 uint8_t *row_pre, hipStream_t st);

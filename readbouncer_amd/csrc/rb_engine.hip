@@ -410,6 +410,10 @@ struct rb_engine {
     uint64_t list_min_dense_bytes = 512ull << 20;
     // rb_engine_set_pass_lists: whether locate and hits take a filter's list table (pass_lists_for)
     int pass_lists = RB_PASS_LISTS_OFF;
+    // rb_engine_set_prefix_lists: the same for the prefix pass, a setting of its own; and where its prep kernel counts the items the list
+    // form took and left (rb_engine_prefix_lists_items): two uint64_t, zeroed when the block is made
+    int prefix_lists = RB_PASS_LISTS_OFF;
+    DevBuf d_prefix_items;
     struct CertLoad {
         double set = -1.0;       // what the caller gave (< 0: measure)
         double measured = -1.0;  // load of the filter's fullest bin at `version` (< 0: not measured yet)
@@ -1256,7 +1260,7 @@ void rb_engine_destroy(rb_engine *e)
     }
     for (void *r : e->thr_retired_dev) (void)hipFree(r);
     for (PinnedBuf &h : e->thr_retired_host) h.release();
-    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_efflens, &e->d_prestatus, &e->d_pass_ws, &e->d_pass_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
+    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_prefix_items, &e->d_efflens, &e->d_prestatus, &e->d_pass_ws, &e->d_pass_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
                       &e->d_decision, &e->d_status})
         b->release();
     e->h_in.release();
@@ -1492,6 +1496,14 @@ int rb_engine_set_pass_lists(rb_engine *e, int mode)
     if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
     std::lock_guard<std::mutex> lock(e->mu);
     e->pass_lists = mode;
+    return RB_OK;
+}
+
+int rb_engine_set_prefix_lists(rb_engine *e, int mode)
+{
+    if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->prefix_lists = mode;
     return RB_OK;
 }
 
@@ -3248,6 +3260,50 @@ extern "C" int rb_engine_plan_pass(rb_engine *e, size_t filter_index, uint32_t m
     return RB_OK;
 }
 
+// The prefix pass's answer to the same question: the plain build for items of at most min(max_len, last_checkpoint) bases -- the bound of
+// a prefix call -- and, under rb_engine_set_prefix_lists as it stands, the list form's slot size.  Nothing is built or dropped.
+extern "C" int rb_engine_plan_prefix(rb_engine *e, size_t filter_index, uint32_t max_len, uint32_t last_checkpoint, rb_prefix_plan_info *out)
+{
+    if (!e || !out || filter_index >= e->filters.size() || last_checkpoint == 0) return rb::fail(RB_ERR_INVALID_ARG, "rb_engine_plan_prefix: bad argument");
+    std::lock_guard<std::mutex> lock(e->mu);
+    std::memset(out, 0, sizeof *out);
+    PrefixLaunch a{};
+    PassInput in{};
+    in.src.max_len = in.max_len = std::min(max_len, last_checkpoint);
+    fill_plain_launch(e, filter_index, in, nullptr, 0, &a);
+    const int rc = lists_for(e, filter_index, nullptr, true, e->prefix_lists, &a);
+    if (rc != RB_OK) return rc;
+    int np = 0, h = 0;
+    plain_planes_hash((uint32_t)e->filters[filter_index]->geo.n_hash, a.planes, &np, &h);
+    out->lanes_per_block_log2 = (uint32_t)a.lg;
+    out->words_per_lane = (uint32_t)a.wpl;
+    out->column_slices = a.n_slices;
+    out->counter_planes = (uint32_t)np;
+    out->nontemporal = plain_pass_nt(a.lg, a.nt) ? 1u : 0u;
+    out->hash_functions = (uint32_t)h;
+    out->list_lines = a.list_table ? a.list_lines : 0u;
+    return RB_OK;
+}
+
+// The items the list form of the prefix pass took and left since the last reset, over the calls in which some filter was list-served
+// (their prep kernel counts them on the device).  Waits for the engine's own stream.
+extern "C" int rb_engine_prefix_lists_items(rb_engine *e, uint64_t *listed, uint64_t *plain, int reset)
+{
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    const int rc = check_device(e->device);
+    if (rc != RB_OK) return rc;
+    std::lock_guard<std::mutex> lock(e->mu);
+    uint64_t got[2] = {0, 0};
+    RB_HIP(hipStreamSynchronize(e->stream));
+    if (e->d_prefix_items.p) {
+        RB_HIP(hipMemcpy(got, e->d_prefix_items.p, sizeof got, hipMemcpyDeviceToHost));
+        if (reset) RB_HIP(hipMemset(e->d_prefix_items.p, 0, sizeof got));
+    }
+    if (listed) *listed = got[0];
+    if (plain) *plain = got[1];
+    return RB_OK;
+}
+
 // Fits the windows of the clock-phased gathers to THIS device: the planner's table was measured on one box;
 // clocks, firmware and compilers move the optima.  For every table the engine would serve with the phased form on a batch of
 // n_reads reads of read_len bases, K1 of the whole engine is timed on synthetic reads with the rule's window and with the window
@@ -3828,9 +3884,11 @@ int rb_locate_batch(rb_engine *e, const char *seqs, const uint64_t *offsets, con
 }
 
 // ---- prefixes: a work item's maxima and decision at every prefix checkpoint, from one walk over its k-mers (see the boundary header).
-// Always the plain form over each filter's OWN table, counted in full, like locate.  Per filter one launch of ibf_prefix_kernel plus the
+// The plain form over each filter's OWN table, counted in full, like locate.  Per filter one launch of ibf_prefix_kernel plus the
 // merge of its column slices, in sequence on the call's stream (one block of partial maxima, sized for the filter with the most slices,
-// serves every filter); then the decision kernel itself over the n_items x P rows, with the rows' prefix lengths as its `lens`.
+// serves every filter); then the decision kernel itself over the n_items x P rows, with the rows' prefix lengths as its `lens`.  Opt-in
+// (rb_engine_set_prefix_lists, decided per filter by lists_for with the call's bound min(max_len, c_last)): ibf_prefix_lists_kernel over
+// the filter's list table for the items prefix_lists_prep_kernel names, the plain kernel as it is for the others, and the same merge.
 static int check_prefix_args(const rb_prefix_out *out, const uint32_t *prefix_lens, uint32_t n_prefixes, int mode)
 {
     if (!out) return rb::fail(RB_ERR_INVALID_ARG, "null output struct");
@@ -3873,8 +3931,10 @@ int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32
         fill_plain_launch(e, fi, c.in, c.thr, c.thr_len, &a);
         a.cps.n = n_prefixes;
         for (uint32_t p = 0; p < kMaxPrefixes; ++p) a.cps.c[p] = p < n_prefixes ? prefix_lens[p] : 0u;
+        if ((rc = lists_for(e, fi, c.st, false, e->prefix_lists, &a)) != RB_OK) return rc;  // (one column slice wherever the list form serves)
         max_slices = std::max(max_slices, a.n_slices);
     }
+    const bool any_lists = std::any_of(launches.begin(), launches.end(), [](const PrefixLaunch &a) { return a.list_table != nullptr; });
     // workspace: the partial maxima u16[max_slices][n_items][P] and the rows' pre-status, and the outputs a later stage reads where the
     // caller left them out
     const bool decides = d_out->decision || d_out->best_target || d_out->status || d_out->first_decided;
@@ -3883,8 +3943,24 @@ int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32
     const size_t o_len = lay.take(d_out->prefix_len ? 0 : rows * 4), o_max = lay.take(d_out->max_count ? 0 : rows * nf * 2);
     const size_t o_dec = lay.take(d_out->first_decided && !d_out->decision ? rows : 0);
     const size_t o_st = lay.take(d_out->first_decided && !d_out->status ? rows : 0);
+    const size_t o_taken = lay.take(any_lists ? n_items : 0), o_plain = lay.take(any_lists ? n_items * 4 : 0);
+    if (any_lists && !e->d_prefix_items.p) {  // the two counters, zero from their first call on
+        if ((rc = e->d_prefix_items.ensure(16)) != RB_OK) return rc;
+        RB_HIP(hipMemsetAsync(e->d_prefix_items.p, 0, 16, c.st));
+    }
     if ((rc = c.start(lay.bytes())) != RB_OK) return rc;
     char *ws = c.ws();
+    if (any_lists) {  // which items the list kernels take: once, for every filter
+        PrefixListsPrep p{};
+        p.src = c.in.src;
+        p.n_items = (uint32_t)n_items;
+        p.pre_status = c.in.d_pre_status;
+        p.c_last = prefix_lens[P - 1];
+        p.taken = (uint8_t *)(ws + o_taken);
+        p.plain_lens = (uint32_t *)(ws + o_plain);
+        p.counters = (uint64_t *)e->d_prefix_items.p;
+        RB_HIP(launch_prefix_lists_prep(p, c.st));
+    }
     uint16_t *part = (uint16_t *)(ws + o_part);
     uint32_t *row_len = d_out->prefix_len ? (uint32_t *)d_out->prefix_len : (uint32_t *)(ws + o_len);
     uint16_t *max_count = d_out->max_count ? (uint16_t *)d_out->max_count : (uint16_t *)(ws + o_max);
@@ -3895,7 +3971,11 @@ int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32
     for (size_t fi = 0; fi < nf; ++fi) {
         PrefixLaunch &a = launches[fi];
         a.part = part;
-        RB_HIP(launch_ibf_prefix(a, c.st));
+        if (a.list_table) {
+            a.list_taken = (const uint8_t *)(ws + o_taken);
+            a.list_plain_lens = (const uint32_t *)(ws + o_plain);
+        }
+        RB_HIP(a.list_table ? launch_ibf_prefix_lists(a, c.st) : launch_ibf_prefix(a, c.st));
         RB_HIP(launch_finish_prefix(a, c.in.d_lens, c.in.d_pre_status, max_count, row_len, row_pre, c.st));
     }
     if (decides) {

@@ -1,6 +1,6 @@
 // rb_pass_lists_device.h -- the device code the list forms of the query passes share beyond rb_lists_device.h: which work items a list
 // kernel takes, and one strand of an item counted in full.  Included by rb_pass_lists.hip (locate and hits) and rb_resume_lists.hip
-// (resume); HIP translation units only.
+// (resume); rb_prefix_lists.hip (prefixes) adds the ranged count below.  HIP translation units only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,6 +63,59 @@ __device__ __forceinline__ void list_count_strand(const IbfDev &f, uint32_t *cnt
         }
         const uint32_t in_tile = __builtin_amdgcn_readfirstlane(min(64u, n - mt));
         ahead = mt + 64u < n;
+        if (ahead) {
+            const uint32_t next = min(64u + k - 1u, len - (mt + 64u));
+            ahead0 = lane < next ? seq.raw(mt + 64u + lane) : 0u;
+            ahead1 = lane + 64u < next ? seq.raw(mt + 128u + lane) : 0u;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll 1
+        for (uint32_t first = 0; first < in_tile; first += R) {
+            if (first + R <= in_tile)  // wave-uniform
+                list_batch<LINES, NT, true>(f, cnt, slots, side, side_rows, rank, first, in_tile, lane, spare);
+            else
+                list_batch<LINES, NT, false>(f, cnt, slots, side, side_rows, rank, first, in_tile, lane, spare);
+        }
+    }
+}
+
+// The RANGED count (the list form of the prefix pass): the k-mers [n_from, n_to) of one strand of the item's first `len` bases, n_to ==
+// len - k + 1 -- list_count_strand's tile loop begun at k-mer n_from instead of 0, so a tile starts wherever the last checkpoint ended,
+// at a multiple of 64 or not: ListBaseSrc::raw / ord_of address single bases at any offset.  The counters are added to, not cleared.
+// Kept beside list_count_strand and not under it, so that the kernels of locate, hits and resume compile as they did.
+template <int LINES, bool NT>
+__device__ __forceinline__ void list_count_range(const IbfDev &f, uint32_t *cnt, uint8_t *stage, const uint32_t *__restrict__ slots,
+                                                 const uint64_t *__restrict__ side, uint32_t side_rows, const ListBaseSrc &seq, uint32_t len,
+                                                 uint32_t n_from, uint32_t n_to, int strand, uint32_t lane, uint32_t spare)
+{
+    constexpr uint32_t R = LINES == 4 ? 32 : 64;  // slots per batch (list_batch)
+    const uint32_t k = f.k;
+    uint32_t ahead0 = 0, ahead1 = 0;  // a tile's bases, loaded one tile ahead
+    bool ahead = false;
+#pragma unroll 1
+    for (uint32_t mt = n_from; mt < n_to; mt += 64) {
+        const uint32_t wlen = min(64u + k - 1u, len - mt);
+        if (!ahead) {  // wave-uniform
+            ahead0 = lane < wlen ? seq.raw(mt + lane) : 0u;
+            ahead1 = lane + 64u < wlen ? seq.raw(mt + 64u + lane) : 0u;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane < wlen) stage[lane] = (uint8_t)seq.ord_of(ahead0, mt + lane);
+        if (lane + 64u < wlen) stage[lane + 64u] = (uint8_t)seq.ord_of(ahead1, mt + 64u + lane);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t p = mt + lane;
+        uint32_t rank = 0;
+        if (p < n_to) {
+            const uint8_t *b = stage + lane;
+            if (strand == 0) {
+                for (uint32_t i = 0; i < k; ++i) rank = (rank << 2) | (b[i] & 3u);
+            } else {
+                for (uint32_t i = 0; i < k; ++i) rank = (rank << 2) | (rbspec::dna5_comp(b[k - 1 - i], f.comp_n) & 3u);
+            }
+        }
+        const uint32_t in_tile = __builtin_amdgcn_readfirstlane(min(64u, n_to - mt));
+        ahead = mt + 64u < n_to;
         if (ahead) {
             const uint32_t next = min(64u + k - 1u, len - (mt + 64u));
             ahead0 = lane < next ? seq.raw(mt + 64u + lane) : 0u;
