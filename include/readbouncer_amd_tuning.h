@@ -469,6 +469,46 @@ RB_API int rb_engine_set_list_min_dense_bytes(rb_engine *e, uint64_t bytes);
 /* rows of the side table of list tables built from now on (process-wide; 0: the default, 4^k / 512 + 64) */
 RB_API void rb_set_list_side_capacity(uint32_t rows);
 
+/* WIDE LIST TABLE of a resident filter: the list table's idea for filters of 8193 to 32 256 bins (blocks of up to 504 words), which the
+ * list table refuses (RB_LIST_REFUSED_GEOMETRY) -- GRCh38 at the default fragment size has about 31 000.  A second object beside the
+ * list table with calls and a setting of its own, off by default.  Per N-free k-mer one slot of 4, 6 or 8 lines of 128 bytes with the
+ * row's bin numbers as 16-bit entries, chosen by the list table's census rule (the smallest slot that at most one in 1024 of up to
+ * 65 536 sampled rows overflows; census_over counts rows with more than 256, 384 and 512 set bits); overflowing rows keep a dense row in
+ * a side table.  ibf_count_wide_lists_kernel gathers that slot instead of h blocks of up to 32 lines each, one workgroup of four waves
+ * per read sharing one array of 16-bit counters in LDS; k-mers with a base outside ACGT are counted in the same kernel from the
+ * filter's own table.  Serves h = 3, k <= 13, reads of fewer than 65 536 k-mers; results are identical to the plain kernel's.
+ *   rb_dibf_wide_list_table_build / _drop / _info / _download: as the list table's calls; refusals are RB_LIST_REFUSED_* (GEOMETRY: not
+ *     8193 to 32 256 bins, or h != 3; DENSITY: too dense even for eight lines).  _download returns the canonical form (rows x lines x 64
+ *     entries of uint16_t: bins ascending, then 0xFFFF; an overflow slot is 0xFFFE and the two halves of its side-table index).
+ *   rb_engine_set_wide_lists: RB_PASS_LISTS_OFF (default: nothing changes for any call) / _CURRENT (a filter's wide table is used where
+ *     it has a current one; none is built) / _BUILD (a classify call builds it when the batch alone repays the build in 128-byte lines --
+ *     items x 2 x k-mers x (L x h - 8) >= 4^k x (L x h + 8), L = lines per block -- the table fits the max_bytes of
+ *     rb_engine_set_row_table and half of the free device memory, and the stream is not being captured; a refusal is remembered for the
+ *     bits and max_bytes it was given for, and means the plain kernel).  Any other value is RB_ERR_INVALID_ARG.  Taken by classify calls
+ *     alone, and only by launches that row_policy's rule (a) admits -- no latency form, fused micro-batch, early-decision mode, column
+ *     shard -- with no prune trace asked for; locate, hits, spans, prefix and resume do not read the wide table.  rb_engine_plan names
+ *     ibf_count_wide_lists_kernel where a call would take it. */
+typedef struct rb_wide_list_table_info {
+    uint64_t bytes, rows;    /* of the current table's slots; 0: none */
+    uint64_t side_bytes;     /* of its side table */
+    uint32_t lines;          /* 128-byte lines per slot: 4, 6 or 8 */
+    uint32_t side_rows;      /* overflow rows in use */
+    uint32_t side_capacity;  /* ... and how many the side table holds */
+    uint32_t refused;        /* RB_LIST_REFUSED_*: why the last build did not happen */
+    uint32_t builds;         /* tables built for this filter so far */
+    uint32_t stride_words;   /* words per row of the side table (the filter's block stride) */
+    uint64_t census_rows, census_over[3]; /* rows the last census looked at, and how many of them had more than 256, 384, 512 bits set */
+    double build_ms;         /* kernel time of the last build, census included */
+    double alloc_s;          /* seconds its allocations took */
+} rb_wide_list_table_info;
+RB_API int rb_dibf_wide_list_table_build(rb_dibf *f, uint64_t max_bytes);
+RB_API int rb_dibf_wide_list_table_drop(rb_dibf *f);
+RB_API int rb_dibf_wide_list_table_info(rb_dibf *f, rb_wide_list_table_info *out);
+RB_API int rb_dibf_wide_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n_entries, uint64_t *side_words, uint64_t n_side_words);
+RB_API int rb_engine_set_wide_lists(rb_engine *e, int mode);
+/* rows of the side table of wide list tables built from now on (process-wide; 0: the default, 4^k / 512 + 64) */
+RB_API void rb_set_wide_list_side_capacity(uint32_t rows);
+
 /* How the eight XCDs walk the slices of a phased table (each has an L2 of its own, so each reloads every slice): bit 0 of `mode` -- at
  * any time every XCD works on a different slice (slice = (window + XCD number) mod slices); bit 1 -- the XCDs' windows start an eighth
  * of a window apart, so that they refill their L2s one after the other instead of all in the same instant.  0 (default): one clock, one

@@ -105,6 +105,11 @@ class ListTableInfo(C.Structure):
                 ("census_rows", C.c_uint64), ("census_over", C.c_uint64 * 3), ("build_ms", C.c_double), ("alloc_s", C.c_double)]
 
 
+class WideListTableInfo(C.Structure):
+    """rb_wide_list_table_info (census_over: rows with more than 256, 384, 512 set bits)"""
+    _fields_ = list(ListTableInfo._fields_)
+
+
 RB_ROW_TABLE_OFF, RB_ROW_TABLE_AUTO, RB_ROW_TABLE_FORCE, RB_ROW_TABLE_LISTS = 0, 1, 2, 3
 RB_PASS_LISTS_OFF, RB_PASS_LISTS_CURRENT, RB_PASS_LISTS_BUILD = 0, 1, 2
 (RB_LIST_REFUSED_NONE, RB_LIST_REFUSED_K, RB_LIST_REFUSED_GEOMETRY, RB_LIST_REFUSED_MAX_BYTES, RB_LIST_REFUSED_FREE, RB_LIST_REFUSED_ALLOC,
@@ -282,6 +287,12 @@ SIGNATURES = {
     "rb_dibf_list_table_download": (_int, [_vp, _vp, _u64, _vp, _u64]),
     "rb_engine_set_list_min_dense_bytes": (_int, [_vp, _u64]),
     "rb_set_list_side_capacity": (None, [C.c_uint32]),
+    "rb_dibf_wide_list_table_build": (_int, [_vp, _u64]),
+    "rb_dibf_wide_list_table_drop": (_int, [_vp]),
+    "rb_dibf_wide_list_table_info": (_int, [_vp, C.POINTER(WideListTableInfo)]),
+    "rb_dibf_wide_list_table_download": (_int, [_vp, _vp, _u64, _vp, _u64]),
+    "rb_engine_set_wide_lists": (_int, [_vp, _int]),
+    "rb_set_wide_list_side_capacity": (None, [C.c_uint32]),
     "rb_dibf_placement": (_int, [_vp, C.POINTER(_u32), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "rb_dibf_placement_cost": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_u64), C.POINTER(_u32)]),
     "rb_engine_set_merge": (_int, [_vp, _int]),
@@ -530,6 +541,32 @@ class DeviceIBF:
         _check(lib().rb_dibf_list_table_download(self.h, _ptr(slots) if len(slots) else None, len(slots), _ptr(side) if len(side) else None,
                                                  len(side)), "rb_dibf_list_table_download")
         return (slots.reshape(i["rows"], -1) if i["rows"] else slots), side.reshape(i["side_rows"], i["stride_words"])  # (a table none of whose rows overflow has no side rows)
+
+    def wide_list_table_build(self, max_bytes=0):
+        """build the wide list table (filters of 8193 to 32 256 bins: per N-free k-mer the sorted bin numbers of its row, in slots of 4, 6
+        or 8 lines) unless a current one exists -> wide_list_table_info()"""
+        _check(lib().rb_dibf_wide_list_table_build(self.h, int(max_bytes)), "rb_dibf_wide_list_table_build")
+        return self.wide_list_table_info()
+
+    def wide_list_table_drop(self):
+        _check(lib().rb_dibf_wide_list_table_drop(self.h), "rb_dibf_wide_list_table_drop")
+
+    def wide_list_table_info(self):
+        """-> dict (rb_wide_list_table_info)"""
+        i = WideListTableInfo()
+        _check(lib().rb_dibf_wide_list_table_info(self.h, C.byref(i)), "rb_dibf_wide_list_table_info")
+        d = {k: getattr(i, k) for k, _ in WideListTableInfo._fields_}
+        d["census_over"] = list(i.census_over)
+        return d
+
+    def wide_list_table_download(self):
+        """-> (np.uint16[rows, 64 x lines]: the canonical slots, np.uint64[side rows in use, stride words]: the dense rows overflow slots name)"""
+        i = self.wide_list_table_info()
+        slots = np.zeros(i["bytes"] // 2, dtype=np.uint16)
+        side = np.zeros(i["side_rows"] * i["stride_words"], dtype=np.uint64)
+        _check(lib().rb_dibf_wide_list_table_download(self.h, _ptr(slots) if len(slots) else None, len(slots),
+                                                      _ptr(side) if len(side) else None, len(side)), "rb_dibf_wide_list_table_download")
+        return (slots.reshape(i["rows"], -1) if i["rows"] else slots), side.reshape(i["side_rows"], i["stride_words"])
 
     def placement(self):
         """-> (allocations probed for this table: 0 = not placed by trial, GB/s of the kept one, GB/s of the slowest one)"""
@@ -956,6 +993,11 @@ class Engine:
         """RB_PASS_LISTS_OFF (default) / _CURRENT (a filter's list table where it has a current one) / _BUILD (built when there is none):
         whether locate and hits are served from the list table (results identical; plan_pass reports list_lines)"""
         _check(lib().rb_engine_set_pass_lists(self.h, int(mode)), "rb_engine_set_pass_lists")
+
+    def set_wide_lists(self, mode):
+        """RB_PASS_LISTS_OFF (default) / _CURRENT / _BUILD: whether classify calls count a filter of 8193 to 32 256 bins from its wide
+        list table (rb_engine_set_wide_lists; results identical; plan() names ibf_count_wide_lists_kernel)"""
+        _check(lib().rb_engine_set_wide_lists(self.h, int(mode)), "rb_engine_set_wide_lists")
 
     def set_prefix_lists(self, mode):
         """RB_PASS_LISTS_OFF (default) / _CURRENT / _BUILD for the prefix pass alone (rb_engine_set_prefix_lists): whether prefixes are

@@ -463,6 +463,28 @@ hipError_t launch_list_census(const IbfDev &f, uint32_t *counters, uint64_t n_ro
 // counters[0] += such slots; counters start zeroed
 hipError_t launch_list_table(const IbfDev &f, uint16_t *slots, uint64_t *side, uint32_t *counters, uint64_t n_rows, uint32_t lines, uint32_t side_cap,
                              hipStream_t st);
+// Wide list form (rb_wide_lists.hip, ibf_count_wide_lists_kernel; rb_wide_lists.h): filters of 8193 to 32 256 bins from a table of their
+// own, one workgroup of several waves per read, every item written once (k-mers with a base outside ACGT are counted in the kernel).
+struct WideCountLaunch {
+    IbfDev f;
+    ReadSrc src;
+    uint32_t n_reads;
+    uint16_t *out;
+    uint32_t out_read_stride;
+    int nt;           // non-temporal slot gathers
+    int bound_prune;  // the second strand is skipped when the first reached n
+    const uint32_t *slots;  // the filter's wide list table, `lines` lines per slot (resident form)
+    const uint64_t *side;   // ... and its side table of side_rows dense rows
+    uint32_t side_rows, lines;
+};
+bool wide_form_serves(const IbfDev &f, uint32_t max_len);
+hipError_t launch_ibf_count_wide_lists(const WideCountLaunch &a, hipStream_t st);
+// counters[1 + i] += rows among 0, step, 2 step, ... < n_rows with more than 64 x rbwide::kWideLines[i] set bits; counters start zeroed
+hipError_t launch_wide_list_census(const IbfDev &f, uint32_t *counters, uint64_t n_rows, uint64_t step, hipStream_t st);
+// slots <- the wide list table at `lines` lines per slot, side <- the dense rows of the slots that overflow (at most side_cap are
+// written), counters[0] += such slots; counters start zeroed
+hipError_t launch_wide_list_table(const IbfDev &f, uint32_t *slots, uint64_t *side, uint32_t *counters, uint64_t n_rows, uint32_t lines,
+                                  uint32_t side_cap, hipStream_t st);
 hipError_t launch_ibf_count_max_merged(const CountLaunch &a, const MergeMap &map, hipStream_t st);
 // block b of a filter (width words at stride s_src, n_bins bins) -> bits [dst_bit, dst_bit + n_bins) of block b of dst (ORed in: dst starts zeroed)
 hipError_t launch_invert_words(const uint64_t *src, uint64_t *dst, uint64_t n_words, hipStream_t st);

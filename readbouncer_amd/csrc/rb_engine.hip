@@ -22,6 +22,7 @@
 #include "rb_io.h"
 #include "rb_phase_plan.h"
 #include "rb_lists.h"
+#include "rb_wide_lists.h"
 #include "rb_stage.h"
 
 using namespace rb;
@@ -78,6 +79,17 @@ struct rb_dibf {
     uint64_t list_refused_version = 0;  // ... and the bits it was refused for: an engine does not ask again until they change
     uint64_t list_refused_max_bytes = 0;  // ... and the max_bytes of that build (list_refusal_stands_locked)
     uint32_t list_builds = 0;
+    // WIDE LIST TABLE (rb_dibf_wide_list_table_build; rb_wide_lists.h, rb_wide_lists.hip): the list table's idea for filters of 8193 to
+    // 32 256 bins, slots of wide_lines lines in the resident form.  A second object beside the list table: owned, guarded (row_mu) and dropped alike.
+    uint32_t *wide_table = nullptr;
+    uint64_t *wide_side = nullptr;
+    uint64_t wide_version = 0, wide_rows = 0, wide_bytes = 0, wide_side_bytes = 0;
+    uint32_t wide_lines = 0, wide_side_rows = 0, wide_side_cap = 0;
+    uint64_t wide_census_rows = 0, wide_census_over[3] = {0, 0, 0};
+    double wide_build_ms = 0.0, wide_alloc_s = 0.0;
+    uint32_t wide_refused = 0;            // RB_LIST_REFUSED_*, remembered as the list table's (wide_refusal_stands_locked)
+    uint64_t wide_refused_version = 0, wide_refused_max_bytes = 0;
+    uint32_t wide_builds = 0;
 };
 
 static void dibf_row_drop_locked(rb_dibf *f)
@@ -103,6 +115,19 @@ static void dibf_list_drop_locked(rb_dibf *f)
     f->list_lines = f->list_side_rows = f->list_side_cap = 0;
 }
 
+static void dibf_wide_drop_locked(rb_dibf *f)
+{
+    if (f->wide_table || f->wide_side) {
+        (void)hipSetDevice(f->device);
+        if (f->wide_table) (void)hipFree(f->wide_table);  // (waits for the kernels that read it)
+        if (f->wide_side) (void)hipFree(f->wide_side);
+    }
+    f->wide_table = nullptr;
+    f->wide_side = nullptr;
+    f->wide_rows = f->wide_bytes = f->wide_side_bytes = 0;
+    f->wide_lines = f->wide_side_rows = f->wide_side_cap = 0;
+}
+
 // the one signal for "the bits of this filter are no longer what they were": engines measure its load again (cert_allowance), merged copies
 // go stale, and the row table is dropped
 static void dibf_changed(rb_dibf *f)
@@ -111,6 +136,7 @@ static void dibf_changed(rb_dibf *f)
     std::lock_guard<std::mutex> lock(f->row_mu);
     dibf_row_drop_locked(f);
     dibf_list_drop_locked(f);
+    dibf_wide_drop_locked(f);
 }
 
 // Tables of 1 GiB and more are PLACED BY TRIAL: the same table allocated at another moment of one process gathers 1.7-2.9 % slower or
@@ -414,6 +440,8 @@ struct rb_engine {
     // form took and left (rb_engine_prefix_lists_items): two uint64_t, zeroed when the block is made
     int prefix_lists = RB_PASS_LISTS_OFF;
     DevBuf d_prefix_items;
+    // rb_engine_set_wide_lists: whether classify calls count a filter of 8193 to 32 256 bins from its wide list table (wide_policy)
+    int wide_lists = RB_PASS_LISTS_OFF;
     struct CertLoad {
         double set = -1.0;       // what the caller gave (< 0: measure)
         double measured = -1.0;  // load of the filter's fullest bin at `version` (< 0: not measured yet)
@@ -866,6 +894,7 @@ void rb_dibf_free(rb_dibf *f)
     }
     dibf_row_drop_locked(f);  // (nobody else holds a filter that is being freed)
     dibf_list_drop_locked(f);
+    dibf_wide_drop_locked(f);
     delete f;
 }
 
@@ -1507,6 +1536,14 @@ int rb_engine_set_prefix_lists(rb_engine *e, int mode)
     return RB_OK;
 }
 
+int rb_engine_set_wide_lists(rb_engine *e, int mode)
+{
+    if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->wide_lists = mode;
+    return RB_OK;
+}
+
 // bytes of the row table of a filter (0: k too large for one)
 static uint64_t row_table_want_bytes(const rb_dibf *f)
 {
@@ -1797,6 +1834,178 @@ int rb_dibf_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n_entrie
         }
     }
     if (n_side_words) RB_HIP(hipMemcpy(side_words, f->list_side, n_side_words * 8, hipMemcpyDeviceToHost));
+    return RB_OK;
+}
+
+// ---- the wide list table (rb_wide_lists.h): the list table's census, slot size, build and refusals for filters of 8193 to 32 256 bins
+static std::atomic<uint32_t> g_wide_side_capacity{0};
+
+void rb_set_wide_list_side_capacity(uint32_t rows) { g_wide_side_capacity.store(rows); }
+
+static bool wide_table_current_locked(const rb_dibf *f) { return f->wide_table && f->wide_version == f->version.load(); }
+
+// (list_refusal_stands_locked for the wide table)
+static bool wide_refusal_stands_locked(const rb_dibf *f, uint64_t max_bytes)
+{
+    if (f->wide_refused == RB_LIST_REFUSED_NONE || f->wide_refused == RB_LIST_REFUSED_CAPTURE) return false;
+    if (f->wide_refused_version != f->version.load()) return false;
+    return f->wide_refused != RB_LIST_REFUSED_MAX_BYTES || max_bytes == f->wide_refused_max_bytes;
+}
+
+// why a filter can have no wide list table whatever its bits (RB_LIST_REFUSED_NONE: it can)
+static uint32_t wide_table_geometry_refusal(const rb_dibf *f)
+{
+    if (f->geo.kmer_size == 0 || f->geo.kmer_size > kRowTableMaxK) return RB_LIST_REFUSED_K;
+    if (!rbwide::bins_served(f->geo.n_bins) || f->geo.bin_width != (f->geo.n_bins + 63) / 64 || f->geo.n_hash != 3) return RB_LIST_REFUSED_GEOMETRY;
+    return RB_LIST_REFUSED_NONE;
+}
+
+// Builds the table unless a current one exists.  RB_OK whether it was built or refused (f->wide_refused says which); an error only where
+// the runtime fails.
+static int dibf_wide_build(rb_dibf *f, uint64_t max_bytes)
+{
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (wide_table_current_locked(f)) return RB_OK;
+    dibf_wide_drop_locked(f);  // stale
+    const uint64_t version = f->version.load();
+    f->wide_refused_version = version;
+    f->wide_refused_max_bytes = max_bytes;
+    f->wide_refused = wide_table_geometry_refusal(f);
+    if (f->wide_refused) return RB_OK;
+    int st = check_device(f->device);
+    if (st != RB_OK) return st;
+    const uint64_t n_rows = 1ull << (2 * f->geo.kmer_size);
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t *d_counters = nullptr;
+    uint32_t counters[4] = {0, 0, 0, 0};
+    RB_HIP(hipMalloc((void **)&d_counters, sizeof counters));
+    auto fail_hip = [&](hipError_t e, uint32_t *slots, uint64_t *side) {
+        (void)hipFree(d_counters);
+        if (slots) (void)hipFree(slots);
+        if (side) (void)hipFree(side);
+        return rb::fail(RB_ERR_HIP, std::string("wide list table: ") + hipGetErrorString(e));
+    };
+    // the census: how many of up to 2^16 rows, evenly spaced, overflow each slot size
+    const uint64_t step = std::max<uint64_t>(1, n_rows / rblist::kCensusRows);
+    hipError_t e = hipMemset(d_counters, 0, sizeof counters);
+    if (e == hipSuccess) e = launch_wide_list_census(f->dev, d_counters, n_rows, step, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip(e, nullptr, nullptr);
+    f->wide_census_rows = (n_rows + step - 1) / step;
+    for (int i = 0; i < 3; ++i) f->wide_census_over[i] = counters[1 + i];
+    const uint32_t lines = rbwide::choose_lines(f->wide_census_over, f->wide_census_rows);
+    if (!lines) {
+        (void)hipFree(d_counters);
+        f->wide_refused = RB_LIST_REFUSED_DENSITY;
+        return RB_OK;
+    }
+    const uint32_t cap_set = g_wide_side_capacity.load();
+    const uint64_t side_cap = cap_set ? cap_set : rbwide::side_capacity(n_rows);
+    const uint64_t bytes = n_rows * rbwide::slot_bytes(lines), side_bytes = side_cap * f->stride * 8;
+    size_t free_b = 0, total_b = 0;
+    if (max_bytes && bytes + side_bytes > max_bytes) f->wide_refused = RB_LIST_REFUSED_MAX_BYTES;
+    else if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + side_bytes > (uint64_t)free_b / 2) f->wide_refused = RB_LIST_REFUSED_FREE;
+    if (f->wide_refused) {
+        (void)hipGetLastError();
+        (void)hipFree(d_counters);
+        return RB_OK;
+    }
+    const auto t_alloc = std::chrono::steady_clock::now();
+    uint32_t *slots = nullptr;
+    uint64_t *side = nullptr;
+    if (hipMalloc((void **)&slots, bytes) != hipSuccess || hipMalloc((void **)&side, side_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        if (slots) (void)hipFree(slots);
+        (void)hipFree(d_counters);
+        f->wide_refused = RB_LIST_REFUSED_ALLOC;
+        return RB_OK;
+    }
+    f->wide_alloc_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc).count();
+    e = hipMemset(d_counters, 0, sizeof counters);
+    if (e == hipSuccess) e = launch_wide_list_table(f->dev, slots, side, d_counters, n_rows, lines, (uint32_t)side_cap, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip(e, slots, side);
+    (void)hipFree(d_counters);
+    f->wide_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - f->wide_alloc_s * 1e3;
+    if (counters[0] > side_cap) {  // rows were left unwritten: nothing is ever counted from such a table
+        (void)hipFree(slots);
+        (void)hipFree(side);
+        f->wide_refused = RB_LIST_REFUSED_SIDE_FULL;
+        return RB_OK;
+    }
+    f->wide_table = slots;
+    f->wide_side = side;
+    f->wide_rows = n_rows;
+    f->wide_bytes = bytes;
+    f->wide_side_bytes = side_bytes;
+    f->wide_lines = lines;
+    f->wide_side_rows = counters[0];
+    f->wide_side_cap = (uint32_t)side_cap;
+    f->wide_version = version;
+    f->wide_builds += 1;
+    return RB_OK;
+}
+
+int rb_dibf_wide_list_table_build(rb_dibf *f, uint64_t max_bytes)
+{
+    if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
+    return dibf_wide_build(f, max_bytes);
+}
+
+int rb_dibf_wide_list_table_drop(rb_dibf *f)
+{
+    if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    dibf_wide_drop_locked(f);
+    f->wide_refused = RB_LIST_REFUSED_NONE;  // the next call may ask again
+    return RB_OK;
+}
+
+int rb_dibf_wide_list_table_info(rb_dibf *f, rb_wide_list_table_info *out)
+{
+    if (!f || !out) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    std::memset(out, 0, sizeof *out);
+    if (wide_table_current_locked(f)) {
+        out->bytes = f->wide_bytes;
+        out->rows = f->wide_rows;
+        out->side_bytes = f->wide_side_bytes;
+        out->lines = f->wide_lines;
+        out->side_rows = f->wide_side_rows;
+        out->side_capacity = f->wide_side_cap;
+    }
+    out->refused = f->wide_refused;
+    out->builds = f->wide_builds;
+    out->stride_words = (uint32_t)f->stride;
+    out->census_rows = f->wide_census_rows;
+    for (int i = 0; i < 3; ++i) out->census_over[i] = f->wide_census_over[i];
+    out->build_ms = f->wide_build_ms;
+    out->alloc_s = f->wide_alloc_s;
+    return RB_OK;
+}
+
+int rb_dibf_wide_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n_entries, uint64_t *side_words, uint64_t n_side_words)
+{
+    if (!f || (!entries && n_entries) || (!side_words && n_side_words)) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (!wide_table_current_locked(f)) return rb::fail(RB_ERR_INVALID_ARG, "the filter has no current wide list table");
+    if (n_entries > f->wide_bytes / 2) return rb::fail(RB_ERR_INVALID_ARG, "more entries than the wide list table holds");
+    if (n_side_words > (uint64_t)f->wide_side_rows * f->stride) return rb::fail(RB_ERR_INVALID_ARG, "more words than the side table's rows in use hold");
+    int st = check_device(f->device);
+    if (st != RB_OK) return st;
+    if (n_entries) {  // whole resident slots that cover the prefix, converted on the host (as rb_dibf_list_table_download)
+        const uint32_t lines = f->wide_lines, cap = rbwide::slot_entries(lines);
+        const uint64_t n_slots = (n_entries + cap - 1) / cap;
+        std::vector<uint32_t> resident(n_slots * (cap / 2));
+        RB_HIP(hipMemcpy(resident.data(), f->wide_table, resident.size() * 4, hipMemcpyDeviceToHost));
+        uint16_t slot[rbwide::kWideMaxLines * rblist::kEntriesPerLine];
+        for (uint64_t i = 0; i < n_slots; ++i) {
+            if (rbwide::decode_resident(resident.data() + i * (cap / 2), lines, (uint32_t)f->geo.n_bins, slot) == -2)
+                return rb::fail(RB_ERR_HIP, "the device's wide list table holds a slot that no builder writes");
+            std::memcpy(entries + i * cap, slot, (size_t)std::min<uint64_t>(cap, n_entries - i * cap) * 2);
+        }
+    }
+    if (n_side_words) RB_HIP(hipMemcpy(side_words, f->wide_side, n_side_words * 8, hipMemcpyDeviceToHost));
     return RB_OK;
 }
 
@@ -2312,6 +2521,68 @@ static int list_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, CountLaunch 
     if (rc != RB_OK) return rc;
     std::lock_guard<std::mutex> lock(f->row_mu);
     if (list_table_current_locked(f)) take();
+    return RB_OK;
+}
+
+// May this launch count from the filter's WIDE list table (rb_engine_set_wide_lists)?  Host arithmetic on the planned launch, shared by
+// the call and by rb_engine_plan: the setting allows it; the geometry serves (8193 to 32 256 bins, h = 3, k <= 13, strands below 65 536
+// k-mers); rule (a) of row_policy -- a plain whole-wave launch on its own: no latency form, no fused micro-batch, no early-decision
+// mode, no column shard -- and no trace asked for; a current table exists, or the setting is BUILD, this version of the bits was not
+// refused one, the smallest table fits max_bytes and the batch alone repays the build in 128-byte lines: a k-mer costs L x h lines today
+// (L lines per block) and at most 8 from a slot, the build reads 4^k x L x h lines and writes at most 4^k x 8.  Free memory and a
+// capturing stream are settled where the table is built (wide_table_for).
+static bool wide_policy(const rb_engine *e, rb_dibf *f, const CountLaunch &a, size_t n_reads, uint32_t max_len)
+{
+    if (e->wide_lists == RB_PASS_LISTS_OFF || e->early_decision || e->shard_world != 1 || e->prune_trace) return false;
+    if (a.lg != 6 || a.split_waves >= 2 || a.phase.n_slices != 0 || a.n_fused != 0 || a.early_thr) return false;
+    if (wide_table_geometry_refusal(f)) return false;
+    const uint64_t k = f->geo.kmer_size, h = f->geo.n_hash;
+    if (max_len == 0 || max_len >= k + rbwide::kWideMaxKmers) return false;
+    if (e->filters.size() > 1 && n_reads <= e->split_threshold) return false;  // a micro-batch that is fused with other filters
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (wide_table_current_locked(f)) return true;
+    if (e->wide_lists != RB_PASS_LISTS_BUILD || wide_refusal_stands_locked(f, e->row_max_bytes)) return false;
+    const uint64_t n_rows = 1ull << (2 * k);
+    if (n_rows * rbwide::slot_bytes(rbwide::kWideLines[0]) > e->row_max_bytes) return false;
+    const uint64_t L = (f->stride * 8 + rblist::kLineBytes - 1) / rblist::kLineBytes, kmers = max_len >= k ? max_len - k + 1 : 0;
+    if (L * h <= rbwide::kWideMaxLines) return false;
+    return (uint64_t)n_reads * 2 * kmers * (L * h - rbwide::kWideMaxLines) >= n_rows * (L * h + rbwide::kWideMaxLines);
+}
+
+// ... and the table for such a launch: the filter's current one, built now under BUILD when there is none.  w.slots stays null where
+// there is none: the call takes the plain kernel.  Never under capture, as the row table (the graph would keep an address that the next
+// change of the bits frees).
+static int wide_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, WideCountLaunch &w, uint64_t *wide_bytes)
+{
+    *wide_bytes = 0;
+    w.slots = nullptr;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    auto take = [&]() {
+        w.slots = f->wide_table;
+        w.side = f->wide_side;
+        w.side_rows = f->wide_side_rows;
+        w.lines = f->wide_lines;
+        *wide_bytes = f->wide_bytes;
+    };
+    {
+        std::lock_guard<std::mutex> lock(f->row_mu);
+        const bool current = wide_table_current_locked(f);
+        if (!current && !capturing) dibf_wide_drop_locked(f);
+        if (capturing) {
+            if (!current) f->wide_refused = RB_LIST_REFUSED_CAPTURE;
+            return RB_OK;
+        }
+        if (current) {
+            take();
+            return RB_OK;
+        }
+        if (e->wide_lists != RB_PASS_LISTS_BUILD || wide_refusal_stands_locked(f, e->row_max_bytes)) return RB_OK;
+    }
+    int rc = dibf_wide_build(f, e->row_max_bytes);
+    if (rc != RB_OK) return rc;
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (wide_table_current_locked(f)) take();
     return RB_OK;
 }
 
@@ -3057,6 +3328,25 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
         const bool fuses = a.n_slices == 1 && !fan_out && nf > 1 && n_reads <= e->split_threshold;
         // the row form first: it has nothing to certify, so the filter's load is not measured for it, and its gathers go to the row table,
         // whose size -- not the filter's -- says whether they are non-temporal
+        // the wide list form (off by default): the whole filter in one launch, whatever column slices the plain kernel would take
+        if (e->wide_lists != RB_PASS_LISTS_OFF && wide_policy(e, e->filters[fi], a, n_reads, max_len)) {
+            WideCountLaunch w{};
+            uint64_t wide_bytes = 0;
+            if ((rc = wide_table_for(e, e->filters[fi], fs, w, &wide_bytes)) != RB_OK) return rc;
+            if (w.slots) {
+                fold_ok = false;
+                w.f = a.f;
+                w.src = a.src;
+                w.src.max_len = max_len;
+                w.n_reads = a.n_reads;
+                w.out = maxcount + fi;
+                w.out_read_stride = (uint32_t)nf;
+                w.nt = wide_bytes > e->nt_threshold_bytes;
+                w.bound_prune = a.bound_prune;
+                RB_HIP(launch_ibf_count_wide_lists(w, fs));
+                continue;
+            }
+        }
         if (list_policy(e, e->filters[fi], a, n_reads, max_len)) {  // the list table before the dense one; refused: on to the row rule
             uint64_t list_bytes = 0;
             if ((rc = list_table_for(e, e->filters[fi], fs, a, &list_bytes)) != RB_OK) return rc;
@@ -3187,7 +3477,17 @@ extern "C" int rb_engine_plan(rb_engine *e, size_t filter_index, size_t n_reads,
     else if (merged_plain) form = "ibf_count_max_merged_kernel";
     else if (a.phase.n_slices) form = a.multi_reads ? "ibf_count_max_phased_multi_kernel" : "ibf_count_max_phased_kernel";
     bool lists_planned = false;
-    if (!g && list_policy(e, e->filters[filter_index], a, n_reads, max_len)) {
+    if (!g && e->wide_lists != RB_PASS_LISTS_OFF && wide_policy(e, e->filters[filter_index], a, n_reads, max_len)) {
+        // the wide list form: the filter has its table, or the call would build it (before the census: six lines per slot)
+        rb_dibf *fm = e->filters[filter_index];
+        std::lock_guard<std::mutex> rows_lock(fm->row_mu);
+        lists_planned = true;
+        form = "ibf_count_wide_lists_kernel";
+        out->row_table_bytes = wide_table_current_locked(fm) ? fm->wide_bytes : (1ull << (2 * fm->geo.kmer_size)) * rbwide::slot_bytes(6);
+        out->nontemporal = out->row_table_bytes > e->nt_threshold_bytes ? 1u : 0u;
+        out->column_slices = 1;
+    }
+    if (!g && !lists_planned && list_policy(e, e->filters[filter_index], a, n_reads, max_len)) {
         // the list form, when the filter has its table or the call could build it: not where this version of the bits was refused one
         rb_dibf *fm = e->filters[filter_index];
         std::lock_guard<std::mutex> rows_lock(fm->row_mu);

@@ -543,6 +543,8 @@ struct IngestOptions
     uint32_t max_hits = 64;      // --max-hits N: records kept per (read, filter); n_hits in the report stays exact
     int pass_lists = RB_PASS_LISTS_CURRENT;  // --pass-lists off|current|build: --report-bins / --report-hits from a filter's list table
                                              // (rb_engine_set_pass_lists): where it has one, or building one; the files are the same bytes
+    int wide_lists = RB_PASS_LISTS_OFF;      // --wide-lists off|current|build: classify counts filters of 8193 to 32 256 bins from their wide
+                                             // list table (rb_engine_set_wide_lists); the files are the same bytes
     int prefix_lists = RB_PASS_LISTS_OFF;    // --prefix-lists off|current|build: --report-prefixes from a filter's list table
                                              // (rb_engine_set_prefix_lists); the files are the same bytes
     std::vector<std::string> bin_maps;  // --bin-map FILE (may repeat): <filter name>.bins.tsv of build --write-bin-map -> a record_id column
@@ -985,6 +987,9 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                 if ((opt.report_bins || opt.report_hits) && !multi && opt.pass_lists != RB_PASS_LISTS_OFF)
                     interleave::throw_status(rb_engine_set_pass_lists(interleave::detail::engine_for(DepletionFilters, TargetFilters), opt.pass_lists),
                                              "rb_engine_set_pass_lists");
+                if (!multi && opt.wide_lists != RB_PASS_LISTS_OFF)
+                    interleave::throw_status(rb_engine_set_wide_lists(interleave::detail::engine_for(DepletionFilters, TargetFilters), opt.wide_lists),
+                                             "rb_engine_set_wide_lists");
                 if (opt.report_prefixes && !multi && opt.prefix_lists != RB_PASS_LISTS_OFF)
                     interleave::throw_status(rb_engine_set_prefix_lists(interleave::detail::engine_for(DepletionFilters, TargetFilters), opt.prefix_lists),
                                              "rb_engine_set_prefix_lists");
@@ -1351,6 +1356,17 @@ int main(int argc, char const* argv[])
             }
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--wide-lists")) {
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            if (!std::strcmp(v, "off")) opt.wide_lists = RB_PASS_LISTS_OFF;
+            else if (!std::strcmp(v, "current")) opt.wide_lists = RB_PASS_LISTS_CURRENT;
+            else if (!std::strcmp(v, "build")) opt.wide_lists = RB_PASS_LISTS_BUILD;
+            else {
+                std::cerr << "ERROR: --wide-lists off|current|build" << std::endl;
+                return 1;
+            }
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--report-prefixes")) opt.report_prefixes = true;
         else if (!std::strcmp(argv[i], "--prefix-lens")) {
             // a,b,c: 1 to 64 checkpoints in bases, none 0, strictly rising
@@ -1455,6 +1471,8 @@ int main(int argc, char const* argv[])
                          "                                    decided there, changed against the checkpoint before\n"
                          "                  [--prefix-lists off|current|build]  --report-prefixes from a filter's list table: never (off, the default), where it has a\n"
                          "                                    current one (current), or building one where it has none (build); the files are the same bytes\n"
+                         "                  [--wide-lists off|current|build]  count filters of 8193 to 32256 bins from their wide list table: never (off, the default),\n"
+                         "                                    where one is current (current), or building it when the batch repays it (build); the files are the same bytes\n"
                          "                  [--bin-map <name>.bins.tsv ...]  adds the record id of the bin to these reports\n"
                          "                  [--filter-stats]  per-bin occupancy of every filter built: a summary and <name>.binstats.tsv (give the flag last, or\n"
                          "                                    before another flag: a bare word after it is taken as a file; a build's exit code stays 0 whatever the bins hold)\n"
