@@ -486,8 +486,21 @@ RB_API void rb_set_list_side_capacity(uint32_t rows);
  *     rb_engine_set_row_table and half of the free device memory, and the stream is not being captured; a refusal is remembered for the
  *     bits and max_bytes it was given for, and means the plain kernel).  Any other value is RB_ERR_INVALID_ARG.  Taken by classify calls
  *     alone, and only by launches that row_policy's rule (a) admits -- no latency form, fused micro-batch, early-decision mode, column
- *     shard -- with no prune trace asked for; locate, hits, spans, prefix and resume do not read the wide table.  rb_engine_plan names
- *     ibf_count_wide_lists_kernel where a call would take it. */
+ *     shard -- with no prune trace asked for; locate and hits read the wide table under a setting of their own (below); spans, prefix and
+ *     resume do not read it.  rb_engine_plan names ibf_count_wide_lists_kernel where a call would take it.
+ *   rb_engine_set_wide_pass_lists: the same three values for the locate and hits calls of the boundary header, off by default and a
+ *     setting of its OWN: rb_engine_set_wide_lists does not reach locate or hits, this setting does not reach classify, and
+ *     rb_engine_set_pass_lists does not reach filters beyond 8192 bins.  Decided per filter and per call (an engine may mix wide-served,
+ *     list-served and plain-served filters in one call): the mode allows it, the geometry serves the call's max_len (h = 3, k <= 13,
+ *     fewer than 65 536 k-mers per strand), the engine is no column shard, the stream is not being captured, and the filter has a wide
+ *     table of the present version of its bits -- under _BUILD built by the call under the rules a classify call has (the repay
+ *     inequality with this call's items and max_len, max_bytes, half of the free memory, remembered refusals); a refusal means the plain
+ *     form, never an error.  ibf_locate_wide_lists_kernel / ibf_hits_wide_lists_kernel then serve the items that are RB_OK -- whatever
+ *     their bases: a k-mer with an N is counted in the kernel -- one workgroup of four waves per item, both strands counted in full, and
+ *     the plain kernels the others; every output is the plain form's, byte for byte.  Any other value is RB_ERR_INVALID_ARG.
+ *   rb_engine_wide_pass_lines: *lines_out = 4, 6 or 8 -- the slot size a locate or hits call on items of at most max_len bases would take
+ *     for this filter as things stand -- or 0: the plain (or the list) form.  Host arithmetic only; nothing is built or dropped, so under
+ *     _BUILD it reports the table once it stands.  rb_pass_plan is unchanged, and its list_lines stays 0 for these filters. */
 typedef struct rb_wide_list_table_info {
     uint64_t bytes, rows;    /* of the current table's slots; 0: none */
     uint64_t side_bytes;     /* of its side table */
@@ -506,6 +519,8 @@ RB_API int rb_dibf_wide_list_table_drop(rb_dibf *f);
 RB_API int rb_dibf_wide_list_table_info(rb_dibf *f, rb_wide_list_table_info *out);
 RB_API int rb_dibf_wide_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n_entries, uint64_t *side_words, uint64_t n_side_words);
 RB_API int rb_engine_set_wide_lists(rb_engine *e, int mode);
+RB_API int rb_engine_set_wide_pass_lists(rb_engine *e, int mode);
+RB_API int rb_engine_wide_pass_lines(rb_engine *e, size_t filter_index, uint32_t max_len, uint32_t *lines_out);
 /* rows of the side table of wide list tables built from now on (process-wide; 0: the default, 4^k / 512 + 64) */
 RB_API void rb_set_wide_list_side_capacity(uint32_t rows);
 

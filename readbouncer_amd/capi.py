@@ -292,6 +292,8 @@ SIGNATURES = {
     "rb_dibf_wide_list_table_info": (_int, [_vp, C.POINTER(WideListTableInfo)]),
     "rb_dibf_wide_list_table_download": (_int, [_vp, _vp, _u64, _vp, _u64]),
     "rb_engine_set_wide_lists": (_int, [_vp, _int]),
+    "rb_engine_set_wide_pass_lists": (_int, [_vp, _int]),
+    "rb_engine_wide_pass_lines": (_int, [_vp, _sz, _u32, C.POINTER(C.c_uint32)]),
     "rb_set_wide_list_side_capacity": (None, [C.c_uint32]),
     "rb_dibf_placement": (_int, [_vp, C.POINTER(_u32), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "rb_dibf_placement_cost": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_u64), C.POINTER(_u32)]),
@@ -998,6 +1000,19 @@ class Engine:
         """RB_PASS_LISTS_OFF (default) / _CURRENT / _BUILD: whether classify calls count a filter of 8193 to 32 256 bins from its wide
         list table (rb_engine_set_wide_lists; results identical; plan() names ibf_count_wide_lists_kernel)"""
         _check(lib().rb_engine_set_wide_lists(self.h, int(mode)), "rb_engine_set_wide_lists")
+
+    def set_wide_pass_lists(self, mode):
+        """RB_PASS_LISTS_OFF (default) / _CURRENT / _BUILD for locate and hits on filters of 8193 to 32 256 bins
+        (rb_engine_set_wide_pass_lists): whether they are served from the filter's wide list table (results identical; a setting of its
+        own beside set_wide_lists and set_pass_lists; wide_pass_lines reports the slot size)"""
+        _check(lib().rb_engine_set_wide_pass_lists(self.h, int(mode)), "rb_engine_set_wide_pass_lists")
+
+    def wide_pass_lines(self, filter_index, max_len):
+        """0, or the slot size (4, 6 or 8 lines) at which a locate or hits call on items of at most max_len bases would take the filter's
+        wide list table as things stand (rb_engine_wide_pass_lines: host arithmetic, nothing is built)"""
+        lines = C.c_uint32(0)
+        _check(lib().rb_engine_wide_pass_lines(self.h, filter_index, max_len, C.byref(lines)), "rb_engine_wide_pass_lines")
+        return int(lines.value)
 
     def set_prefix_lists(self, mode):
         """RB_PASS_LISTS_OFF (default) / _CURRENT / _BUILD for the prefix pass alone (rb_engine_set_prefix_lists): whether prefixes are

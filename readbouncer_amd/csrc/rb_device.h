@@ -267,6 +267,13 @@ struct PlainPassLaunch {
     int list_nt;
     const uint8_t *list_taken;
     const uint32_t *list_plain_lens;
+    // wide list form of locate and hits (rb_wide_pass_lists.hip): the filter's wide list table and its side table as in WideCountLaunch,
+    // or nullptr.  A filter has one table or the other (their bin counts do not meet); list_taken / list_plain_lens are then what
+    // launch_wide_pass_lists_prep made of the call's items
+    const uint32_t *wide_table;
+    const uint64_t *wide_side;
+    uint32_t wide_side_rows, wide_lines;
+    int wide_nt;
 };
 struct LocateLaunch : PlainPassLaunch {
     LocatePart *part;     // [n_slices][n_items]
@@ -299,6 +306,12 @@ hipError_t launch_ibf_locate(const LocateLaunch &a, hipStream_t st);
 // items stand
 bool pass_list_form_serves(const PlainPassLaunch &a);  // list_form_serves for a launch of locate or hits
 hipError_t launch_ibf_locate_lists(const LocateLaunch &a, hipStream_t st);
+// ... the wide list form (rb_wide_pass_lists.hip).  Which items it takes, once per call: taken[item] = 1 when the item is RB_OK (the
+// status rules alone: the wide kernels count a k-mer with a base outside ACGT themselves), plain_lens[] as launch_pass_lists_prep's.
+// launch_ibf_locate_wide_lists is launch_ibf_locate over a.list_plain_lens and then ibf_locate_wide_lists_kernel, which writes a taken
+// item's record into slice 0 and an empty record into every other slice of the a.n_slices the merge reads
+hipError_t launch_wide_pass_lists_prep(const PassListsPrep &a, hipStream_t st);
+hipError_t launch_ibf_locate_wide_lists(const LocateLaunch &a, hipStream_t st);
 hipError_t launch_reduce_locate_slices(const LocatePart *part, uint32_t n_slices, uint32_t n_items, const uint32_t *lens,
                                        const uint8_t *pre_status, uint32_t max_len, uint32_t min_len, const LocateOut &out, uint32_t nf,
                                        uint32_t fidx, hipStream_t st);
@@ -420,6 +433,9 @@ hipError_t launch_ibf_hits(const HitsLaunch &a, hipStream_t st);
 // ... the list form (rb_pass_lists.hip): launch_ibf_hits over a.list_plain_lens, where a taken item is too short to be looked at, and
 // ibf_hits_lists_kernel for the taken items: every segment is written once
 hipError_t launch_ibf_hits_lists(const HitsLaunch &a, hipStream_t st);
+// ... the wide list form (rb_wide_pass_lists.hip): as above, and ibf_hits_wide_lists_kernel writes a taken item's segments and counters of
+// slice 0 and a zero counter for every other slice -- the plain kernel writes nothing for an item it leaves
+hipError_t launch_ibf_hits_wide_lists(const HitsLaunch &a, hipStream_t st);
 hipError_t launch_finish_hits(const HitsLaunch &a, const uint32_t *lens, const HitsOut &out, hipStream_t st);
 
 // spans pass (rb_spans_batch_device; rb_kernels.hip, ibf_spans_kernel): the caller's output arrays (any may be nullptr) ...

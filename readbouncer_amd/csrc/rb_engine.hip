@@ -442,6 +442,8 @@ struct rb_engine {
     DevBuf d_prefix_items;
     // rb_engine_set_wide_lists: whether classify calls count a filter of 8193 to 32 256 bins from its wide list table (wide_policy)
     int wide_lists = RB_PASS_LISTS_OFF;
+    // rb_engine_set_wide_pass_lists: whether locate and hits take such a filter's wide list table (wide_pass_lists_for)
+    int wide_pass_lists = RB_PASS_LISTS_OFF;
     struct CertLoad {
         double set = -1.0;       // what the caller gave (< 0: measure)
         double measured = -1.0;  // load of the filter's fullest bin at `version` (< 0: not measured yet)
@@ -1544,6 +1546,14 @@ int rb_engine_set_wide_lists(rb_engine *e, int mode)
     return RB_OK;
 }
 
+int rb_engine_set_wide_pass_lists(rb_engine *e, int mode)
+{
+    if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->wide_pass_lists = mode;
+    return RB_OK;
+}
+
 // bytes of the row table of a filter (0: k too large for one)
 static uint64_t row_table_want_bytes(const rb_dibf *f)
 {
@@ -2531,28 +2541,37 @@ static int list_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, CountLaunch 
 // refused one, the smallest table fits max_bytes and the batch alone repays the build in 128-byte lines: a k-mer costs L x h lines today
 // (L lines per block) and at most 8 from a slot, the build reads 4^k x L x h lines and writes at most 4^k x 8.  Free memory and a
 // capturing stream are settled where the table is built (wide_table_for).
+// The table's side of that, shared with locate and hits (wide_pass_lists_for), under the setting `mode` of the caller's side: a current
+// table, or BUILD with no standing refusal, max_bytes and the repay inequality for `n_items` items of at most max_len bases.
+static bool wide_table_admitted_locked(const rb_engine *e, const rb_dibf *f, int mode, size_t n_items, uint32_t max_len)
+{
+    if (wide_table_current_locked(f)) return true;
+    if (mode != RB_PASS_LISTS_BUILD || wide_refusal_stands_locked(f, e->row_max_bytes)) return false;
+    const uint64_t k = f->geo.kmer_size, h = f->geo.n_hash;
+    const uint64_t n_rows = 1ull << (2 * k);
+    if (n_rows * rbwide::slot_bytes(rbwide::kWideLines[0]) > e->row_max_bytes) return false;
+    const uint64_t L = (f->stride * 8 + rblist::kLineBytes - 1) / rblist::kLineBytes, kmers = max_len >= k ? max_len - k + 1 : 0;
+    if (L * h <= rbwide::kWideMaxLines) return false;
+    return (uint64_t)n_items * 2 * kmers * (L * h - rbwide::kWideMaxLines) >= n_rows * (L * h + rbwide::kWideMaxLines);
+}
+
 static bool wide_policy(const rb_engine *e, rb_dibf *f, const CountLaunch &a, size_t n_reads, uint32_t max_len)
 {
     if (e->wide_lists == RB_PASS_LISTS_OFF || e->early_decision || e->shard_world != 1 || e->prune_trace) return false;
     if (a.lg != 6 || a.split_waves >= 2 || a.phase.n_slices != 0 || a.n_fused != 0 || a.early_thr) return false;
     if (wide_table_geometry_refusal(f)) return false;
-    const uint64_t k = f->geo.kmer_size, h = f->geo.n_hash;
+    const uint64_t k = f->geo.kmer_size;
     if (max_len == 0 || max_len >= k + rbwide::kWideMaxKmers) return false;
     if (e->filters.size() > 1 && n_reads <= e->split_threshold) return false;  // a micro-batch that is fused with other filters
     std::lock_guard<std::mutex> lock(f->row_mu);
-    if (wide_table_current_locked(f)) return true;
-    if (e->wide_lists != RB_PASS_LISTS_BUILD || wide_refusal_stands_locked(f, e->row_max_bytes)) return false;
-    const uint64_t n_rows = 1ull << (2 * k);
-    if (n_rows * rbwide::slot_bytes(rbwide::kWideLines[0]) > e->row_max_bytes) return false;
-    const uint64_t L = (f->stride * 8 + rblist::kLineBytes - 1) / rblist::kLineBytes, kmers = max_len >= k ? max_len - k + 1 : 0;
-    if (L * h <= rbwide::kWideMaxLines) return false;
-    return (uint64_t)n_reads * 2 * kmers * (L * h - rbwide::kWideMaxLines) >= n_rows * (L * h + rbwide::kWideMaxLines);
+    return wide_table_admitted_locked(e, f, e->wide_lists, n_reads, max_len);
 }
 
 // ... and the table for such a launch: the filter's current one, built now under BUILD when there is none.  w.slots stays null where
 // there is none: the call takes the plain kernel.  Never under capture, as the row table (the graph would keep an address that the next
-// change of the bits frees).
-static int wide_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, WideCountLaunch &w, uint64_t *wide_bytes)
+// change of the bits frees).  `mode`: the setting of the caller's side -- rb_engine_set_wide_lists for a classify call,
+// rb_engine_set_wide_pass_lists for locate and hits.
+static int wide_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, int mode, WideCountLaunch &w, uint64_t *wide_bytes)
 {
     *wide_bytes = 0;
     w.slots = nullptr;
@@ -2577,7 +2596,7 @@ static int wide_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, WideCountLau
             take();
             return RB_OK;
         }
-        if (e->wide_lists != RB_PASS_LISTS_BUILD || wide_refusal_stands_locked(f, e->row_max_bytes)) return RB_OK;
+        if (mode != RB_PASS_LISTS_BUILD || wide_refusal_stands_locked(f, e->row_max_bytes)) return RB_OK;
     }
     int rc = dibf_wide_build(f, e->row_max_bytes);
     if (rc != RB_OK) return rc;
@@ -3118,12 +3137,58 @@ static int pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, 
     return lists_for(e, fi, st, asking, e->pass_lists, a);
 }
 
+// May locate and hits take this filter's WIDE list table for the launch `a` (rb_engine_set_wide_pass_lists)?  Per filter and per call, as
+// pass_lists_for, and a setting of its own: the mode allows it, wide_form_serves holds for the call's max_len, the engine is no column
+// shard, the stream is not being captured, and the filter has a wide table of the present version of its bits -- under
+// RB_PASS_LISTS_BUILD built now through wide_table_for, by the rules a classify call has (wide_table_admitted_locked with this call's
+// items and max_len: remembered refusals, max_bytes, the repay inequality; half of the free memory where it is built), whose refusals
+// mean the plain form.  a->wide_table stays null wherever the answer is no.  asking: the question alone (rb_engine_wide_pass_lines) --
+// no stream, and nothing is built or dropped, so BUILD reports the table once it stands.
+static int wide_pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, size_t n_items, PlainPassLaunch *a)
+{
+    a->wide_table = nullptr;
+    a->wide_side = nullptr;
+    a->wide_side_rows = a->wide_lines = 0;
+    a->wide_nt = 0;
+    const int mode = e->wide_pass_lists;
+    if (mode == RB_PASS_LISTS_OFF || e->shard_world != 1 || !wide_form_serves(a->f, a->src.max_len)) return RB_OK;
+    rb_dibf *f = e->filters[fi];
+    if (wide_table_geometry_refusal(f) || a->col_begin != 0 || a->col_end != a->f.bin_width) return RB_OK;
+    WideCountLaunch got{};
+    uint64_t wide_bytes = 0;
+    if (asking) {
+        std::lock_guard<std::mutex> lock(f->row_mu);
+        if (!wide_table_current_locked(f)) return RB_OK;
+        got.slots = f->wide_table;
+        got.side = f->wide_side;
+        got.side_rows = f->wide_side_rows;
+        got.lines = f->wide_lines;
+        wide_bytes = f->wide_bytes;
+    } else {
+        {
+            std::lock_guard<std::mutex> lock(f->row_mu);
+            if (!wide_table_admitted_locked(e, f, mode, n_items, a->src.max_len)) return RB_OK;
+        }
+        const int rc = wide_table_for(e, f, st, mode, got, &wide_bytes);
+        if (rc != RB_OK) return rc;
+    }
+    if (!got.slots || !got.side) return RB_OK;
+    a->wide_table = got.slots;
+    a->wide_side = got.side;
+    a->wide_side_rows = got.side_rows;
+    a->wide_lines = got.lines;
+    a->wide_nt = wide_bytes > e->nt_threshold_bytes;
+    return RB_OK;
+}
+
 // ... and the list forms' share of a call: which items they take is decided once, for every filter (launch_pass_lists_prep: the status
 // rules and the bases are the call's, not a filter's).  take(): room in the call's workspace when some launch has a list table;
-// run(): the prep kernel, and every such launch learns where its answers are.
+// run(): the prep kernel, and every such launch learns where its answers are.  wide: the share of the wide forms, whose rule is another
+// (launch_wide_pass_lists_prep: the status rules alone), so a call with filters of both kinds keeps two.
 struct PassListsShare {
     size_t o_taken = 0, o_lens = 0;
     bool any = false;
+    bool wide = false;
     void take(rb::StageLayout &lay, size_t n_items, bool some_launch_has_a_table)
     {
         any = some_launch_has_a_table;
@@ -3141,7 +3206,7 @@ struct PassListsShare {
         p.min_len = min_len;
         p.taken = (uint8_t *)(c.ws() + o_taken);
         p.plain_lens = (uint32_t *)(c.ws() + o_lens);
-        RB_HIP(launch_pass_lists_prep(p, c.st));
+        RB_HIP(wide ? launch_wide_pass_lists_prep(p, c.st) : launch_pass_lists_prep(p, c.st));
         return RB_OK;
     }
     void bind(const PassCall &c, PlainPassLaunch *a) const
@@ -3332,7 +3397,7 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
         if (e->wide_lists != RB_PASS_LISTS_OFF && wide_policy(e, e->filters[fi], a, n_reads, max_len)) {
             WideCountLaunch w{};
             uint64_t wide_bytes = 0;
-            if ((rc = wide_table_for(e, e->filters[fi], fs, w, &wide_bytes)) != RB_OK) return rc;
+            if ((rc = wide_table_for(e, e->filters[fi], fs, e->wide_lists, w, &wide_bytes)) != RB_OK) return rc;
             if (w.slots) {
                 fold_ok = false;
                 w.f = a.f;
@@ -3557,6 +3622,23 @@ extern "C" int rb_engine_plan_pass(rb_engine *e, size_t filter_index, uint32_t m
     const int rc = pass_lists_for(e, filter_index, nullptr, true, &a);
     if (rc != RB_OK) return rc;
     out->list_lines = a.list_table ? a.list_lines : 0u;
+    return RB_OK;
+}
+
+// ... and the WIDE list form's answer, a call of its own (rb_pass_plan is not changed, and its list_lines stays 0 for these filters): the
+// slot size a locate or hits call on items of at most max_len bases would take for this filter under rb_engine_set_wide_pass_lists as
+// things stand, or 0.  Host arithmetic only: nothing is built or dropped.
+extern "C" int rb_engine_wide_pass_lines(rb_engine *e, size_t filter_index, uint32_t max_len, uint32_t *lines_out)
+{
+    if (!e || !lines_out || filter_index >= e->filters.size()) return rb::fail(RB_ERR_INVALID_ARG, "rb_engine_wide_pass_lines: bad argument");
+    std::lock_guard<std::mutex> lock(e->mu);
+    PlainPassLaunch a{};
+    PassInput in{};
+    in.src.max_len = in.max_len = max_len;
+    fill_plain_launch(e, filter_index, in, nullptr, 0, &a);
+    const int rc = wide_pass_lists_for(e, filter_index, nullptr, true, 0, &a);
+    if (rc != RB_OK) return rc;
+    *lines_out = a.wide_table ? a.wide_lines : 0u;
     return RB_OK;
 }
 
@@ -4100,7 +4182,9 @@ static void host_pass_geometry(rb_engine *e, uint32_t max_len, size_t *nf, size_
 // The plain form over each filter's OWN table, counted in full: the engine's pruning / early-decision / merge / phased settings do not
 // reach it.  One launch of ibf_locate_kernel per filter plus the merge of its column slices, in sequence on the call's stream.  Opt-in
 // (rb_engine_set_pass_lists, decided per filter by pass_lists_for): ibf_locate_lists_kernel over the filter's list table for the items
-// the prep kernel names, the plain kernel as it is for the others, and the same merge.
+// the prep kernel names, the plain kernel as it is for the others, and the same merge.  Filters of 8193 to 32 256 bins: opt-in of their own
+// (rb_engine_set_wide_pass_lists, wide_pass_lists_for), ibf_locate_wide_lists_kernel over the filter's wide list table, which writes a taken
+// item's record in every column slice.
 int rb_locate_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, const rb_locate_out *d_out,
                            void *stream)
 {
@@ -4124,12 +4208,16 @@ int rb_locate_batch_device(rb_engine *e, const rb_batch_desc *desc, double error
     for (size_t fi = 0; fi < nf; ++fi) {
         fill_plain_launch(e, fi, c.in, c.thr, c.thr_len, &launches[fi]);
         if ((rc = pass_lists_for(e, fi, c.st, false, &launches[fi])) != RB_OK) return rc;  // (one column slice wherever the list form serves)
+        if ((rc = wide_pass_lists_for(e, fi, c.st, false, n_items, &launches[fi])) != RB_OK) return rc;  // (several where the wide form does)
         o_part[fi] = lay.take((size_t)launches[fi].n_slices * n_items * sizeof(LocatePart));
     }
-    PassListsShare lists;
+    PassListsShare lists, wide;
+    wide.wide = true;
     lists.take(lay, n_items, std::any_of(launches.begin(), launches.end(), [](const LocateLaunch &a) { return a.list_table != nullptr; }));
+    wide.take(lay, n_items, std::any_of(launches.begin(), launches.end(), [](const LocateLaunch &a) { return a.wide_table != nullptr; }));
     if ((rc = c.start(lay.bytes())) != RB_OK) return rc;
     if ((rc = lists.run(c, min_len)) != RB_OK) return rc;
+    if ((rc = wide.run(c, min_len)) != RB_OK) return rc;
     LocateOut out;
     out.max_count = (uint16_t *)d_out->max_count;
     out.best_bin = (int32_t *)d_out->best_bin;
@@ -4140,7 +4228,8 @@ int rb_locate_batch_device(rb_engine *e, const rb_batch_desc *desc, double error
         LocateLaunch &a = launches[fi];
         a.part = (LocatePart *)(c.ws() + o_part[fi]);
         if (a.list_table) lists.bind(c, &a);
-        RB_HIP(a.list_table ? launch_ibf_locate_lists(a, c.st) : launch_ibf_locate(a, c.st));
+        else if (a.wide_table) wide.bind(c, &a);
+        RB_HIP(a.list_table ? launch_ibf_locate_lists(a, c.st) : a.wide_table ? launch_ibf_locate_wide_lists(a, c.st) : launch_ibf_locate(a, c.st));
         RB_HIP(launch_reduce_locate_slices(a.part, a.n_slices, (uint32_t)n_items, c.in.d_lens, c.in.d_pre_status, c.in.max_len, min_len, out,
                                            (uint32_t)nf, (uint32_t)fi, c.st));
     }
@@ -4670,7 +4759,8 @@ int rb_resume_counts(rb_resume *r, uint32_t slot, size_t filter, uint16_t *out_c
 // Per filter one launch of ibf_hits_kernel over the filter's OWN table, counted in full, plus finish_hits_kernel,
 // in sequence on the call's stream -- so one workspace, sized for the filter with the most column slices, serves every filter.  Opt-in
 // (rb_engine_set_pass_lists, per filter by pass_lists_for): ibf_hits_lists_kernel over the filter's list table fills the same segments,
-// the plain kernel as it is those of the items it leaves, and finish_hits_kernel merges them as ever.
+// the plain kernel as it is those of the items it leaves, and finish_hits_kernel merges them as ever.  Filters of 8193 to 32 256 bins:
+// rb_engine_set_wide_pass_lists, ibf_hits_wide_lists_kernel over the wide list table, segments in slice 0 and every slice's counter.
 int rb_hits_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_rate, double significance, uint16_t min_count, uint32_t max_hits,
                          const rb_hits_out *d_out, void *stream)
 {
@@ -4698,15 +4788,19 @@ int rb_hits_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_r
         a.min_len = min_len;
         a.pre_status = c.in.d_pre_status;
         if ((rc = pass_lists_for(e, fi, c.st, false, &a)) != RB_OK) return rc;
+        if ((rc = wide_pass_lists_for(e, fi, c.st, false, n_items, &a)) != RB_OK) return rc;
         max_slices = std::max(max_slices, a.n_slices);
     }
     // workspace: per (item, slice, strand) a segment of cap records, and its counter
     rb::StageLayout lay;
     const size_t o_seg = lay.take(n_items * (size_t)max_slices * 2 * (size_t)cap * 8), o_count = lay.take(n_items * (size_t)max_slices * 2 * 4);
-    PassListsShare lists;
+    PassListsShare lists, wide;
+    wide.wide = true;
     lists.take(lay, n_items, std::any_of(launches.begin(), launches.end(), [](const HitsLaunch &a) { return a.list_table != nullptr; }));
+    wide.take(lay, n_items, std::any_of(launches.begin(), launches.end(), [](const HitsLaunch &a) { return a.wide_table != nullptr; }));
     if ((rc = c.start(lay.bytes())) != RB_OK) return rc;
     if ((rc = lists.run(c, min_len)) != RB_OK) return rc;
+    if ((rc = wide.run(c, min_len)) != RB_OK) return rc;
     HitsOut out;
     out.hits = (rb_u32x2 *)d_out->hits;
     out.n_hits = (uint32_t *)d_out->n_hits;
@@ -4718,7 +4812,8 @@ int rb_hits_batch_device(rb_engine *e, const rb_batch_desc *desc, double error_r
         a.seg_count = (uint32_t *)(c.ws() + o_count);
         a.bin_reads = bin_reads;
         if (a.list_table) lists.bind(c, &a);
-        RB_HIP(a.list_table ? launch_ibf_hits_lists(a, c.st) : launch_ibf_hits(a, c.st));
+        else if (a.wide_table) wide.bind(c, &a);
+        RB_HIP(a.list_table ? launch_ibf_hits_lists(a, c.st) : a.wide_table ? launch_ibf_hits_wide_lists(a, c.st) : launch_ibf_hits(a, c.st));
         RB_HIP(launch_finish_hits(a, c.in.d_lens, out, c.st));
         if (bin_reads) bin_reads += e->filters[fi]->geo.n_bins;
     }

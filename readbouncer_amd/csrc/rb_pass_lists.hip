@@ -41,35 +41,6 @@ hipError_t launch_pass_lists_prep(const PassListsPrep &a, hipStream_t st)
 // the hit mask (rblist::pass_lds_bytes), one byte per 16-byte piece of the counters: bit j of byte i is bin 8 i + j.  The lane that scans
 // piece i on the first strand scans it on the second.
 
-// A 16-byte piece of the counters, eight bins: counter j (a compile-time place), the largest of the eight, and the bits of those at or
-// above t among the bins that exist.  A pad counter -- behind n_bins -- is never added to, and `valid` keeps it out even at t == 0.
-__device__ __forceinline__ uint32_t piece_counter(const uint4 &q, int j)
-{
-    const uint32_t d = j < 2 ? q.x : j < 4 ? q.y : j < 6 ? q.z : q.w;
-    return (j & 1) ? d >> 16 : d & 0xFFFFu;
-}
-__device__ __forceinline__ uint32_t piece_max(const uint4 &q)
-{
-    const list_u16x2 a = __builtin_elementwise_max(list_max2(__builtin_bit_cast(list_u16x2, q.x), q.y), list_max2(__builtin_bit_cast(list_u16x2, q.z), q.w));
-    return max((uint32_t)a.x, (uint32_t)a.y);
-}
-__device__ __forceinline__ uint32_t piece_hits(const uint4 &q, uint32_t piece, uint32_t t, uint32_t n_bins)
-{
-    const uint32_t first = piece * 8u;
-    const uint32_t valid = first >= n_bins ? 0u : (n_bins - first >= 8u ? 0xFFu : (1u << (n_bins - first)) - 1u);
-    uint32_t bits = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bits |= (piece_counter(q, j) >= t ? 1u : 0u) << j;
-    return bits & valid;
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-    return v;
-}
-
 // LOCATE's scan of a strand's counters, lane l at the pieces l, l + 64, ... as list_scan.  -> wave-uniform (maximum << 16) | (0xFFFF - the
 // lowest bin at it), 0 when nothing counted: a lane's pieces rise, so only a LARGER counter moves its first bin, and the wave's largest key
 // is the largest maximum at its lowest bin.  FIRST (the forward strand): the bits of the bins at or above t go to the mask and the piece is

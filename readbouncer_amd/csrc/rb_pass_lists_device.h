@@ -1,6 +1,7 @@
 // rb_pass_lists_device.h -- the device code the list forms of the query passes share beyond rb_lists_device.h: which work items a list
-// kernel takes, and one strand of an item counted in full.  Included by rb_pass_lists.hip (locate and hits) and rb_resume_lists.hip
-// (resume); rb_prefix_lists.hip (prefixes) adds the ranged count below.  HIP translation units only.
+// kernel takes, what a scan reads off a 16-byte piece of the counters, and one strand of an item counted in full.  Included by
+// rb_pass_lists.hip (locate and hits), rb_wide_pass_lists.hip (their wide forms, for the pieces) and rb_resume_lists.hip (resume);
+// rb_prefix_lists.hip (prefixes) adds the ranged count below.  HIP translation units only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +28,35 @@ __device__ __forceinline__ bool pass_lists_takes(const ReadSrc &r, uint32_t item
         for (uint32_t i = lane; i < len; i += 64) outside |= rbspec::dna5_ord(s[i]) > 3u;
     }
     return __ballot(outside) == 0ULL;
+}
+
+// A 16-byte piece of the counters, eight bins: counter j (a compile-time place), the largest of the eight, and the bits of those at or
+// above t among the bins that exist.  A pad counter -- behind n_bins -- is never added to, and `valid` keeps it out even at t == 0.
+__device__ __forceinline__ uint32_t piece_counter(const uint4 &q, int j)
+{
+    const uint32_t d = j < 2 ? q.x : j < 4 ? q.y : j < 6 ? q.z : q.w;
+    return (j & 1) ? d >> 16 : d & 0xFFFFu;
+}
+__device__ __forceinline__ uint32_t piece_max(const uint4 &q)
+{
+    const list_u16x2 a = __builtin_elementwise_max(list_max2(__builtin_bit_cast(list_u16x2, q.x), q.y), list_max2(__builtin_bit_cast(list_u16x2, q.z), q.w));
+    return max((uint32_t)a.x, (uint32_t)a.y);
+}
+__device__ __forceinline__ uint32_t piece_hits(const uint4 &q, uint32_t piece, uint32_t t, uint32_t n_bins)
+{
+    const uint32_t first = piece * 8u;
+    const uint32_t valid = first >= n_bins ? 0u : (n_bins - first >= 8u ? 0xFFu : (1u << (n_bins - first)) - 1u);
+    uint32_t bits = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bits |= (piece_counter(q, j) >= t ? 1u : 0u) << j;
+    return bits & valid;
+}
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
+    return v;
 }
 
 // One strand of an item, counted in full: the tile loop of ibf_count_lists_kernel without the bound, the strand skip and the stop.

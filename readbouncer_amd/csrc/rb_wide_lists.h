@@ -71,6 +71,17 @@ constexpr uint32_t count_resident_workgroups(uint32_t n_bins, uint32_t waves = k
     return rblist::kLdsPerCuBytes / count_lds_bytes(n_bins, waves);
 }
 static_assert(count_lds_bytes(kWideMaxBins) <= 64u * 1024u, "no more than a workgroup may declare without asking");
+// ... and a workgroup of the wide forms of locate and hits (rb_wide_pass_lists.hip): the same areas and nothing more -- their hit mask
+// lives in registers, and what the waves exchange goes through the partial maxima's 64 bytes
+constexpr uint32_t pass_lds_bytes(uint32_t n_bins, uint32_t waves = kWideWaves) { return count_lds_bytes(n_bins, waves); }
+// How their scans share the counters: cnt_dwords / 256 rounds of 64 consecutive 16-byte pieces (512 bins), wave w at the rounds
+// [w x per, (w + 1) x per) that exist.  A thread keeps one mask byte per round of its wave: per <= kWidePassMaskBytes.
+constexpr uint32_t kWidePassMaskBytes = 16;
+constexpr uint32_t pass_rounds(uint32_t n_bins) { return cnt_dwords(n_bins) / 256u; }
+constexpr uint32_t pass_rounds_per_wave(uint32_t n_bins, uint32_t waves = kWideWaves) { return (pass_rounds(n_bins) + waves - 1u) / waves; }
+constexpr uint32_t pass_wave_of_bin(uint32_t n_bins, uint32_t bin, uint32_t waves = kWideWaves) { return (bin / 512u) / pass_rounds_per_wave(n_bins, waves); }
+static_assert(pass_rounds_per_wave(kWideMaxBins) <= kWidePassMaskBytes, "a thread's pieces fit its mask bytes");
+static_assert(2u * kWideWaves * 4u <= kWideReduceBytes, "two dwords per wave of the pass kernels fit the partial maxima's area");
 
 // The census's verdict, rblist::choose_lines's rule.  over[i] = sampled rows with more than 64 x kWideLines[i] set bits.
 // -> lines of the smallest slot that at most sampled >> kOverflowShift rows overflow, or 0: too dense for every slot size

@@ -1,7 +1,8 @@
 // rb_wide_lists.hip -- the WIDE LIST FORM of the plain count kernel, for filters of 8193 to 32 256 bins (rb_wide_lists.h): the filter's
 // wide list table -- per N-free k-mer the bins of its row, the AND of its h blocks, in one slot of 4, 6 or 8 lines -- its builder and
 // census, and the kernel that counts from it.  A translation unit of its own beside rb_lists.hip, whose device helpers
-// (rb_lists_device.h: how a read's bases are found, the adds, the packed maximum) it shares.
+// (rb_lists_device.h: how a read's bases are found, the adds, the packed maximum) it shares; what it shares in turn with the wide forms
+// of locate and hits (rb_wide_pass_lists.hip) -- a batch of slot gathers, a strand counted in full -- is in rb_wide_lists_device.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,106 +11,9 @@
 #include "rb_lists.h"
 #include "rb_lists_device.h"
 #include "rb_wide_lists.h"
+#include "rb_wide_lists_device.h"
 
 namespace rb {
-
-template <int DW>
-struct WideVec;
-template <>
-struct WideVec<2> {
-    typedef unsigned int type __attribute__((ext_vector_type(2)));
-};
-template <>
-struct WideVec<3> {
-    typedef unsigned int type __attribute__((ext_vector_type(3), aligned(4)));  // lane l of a six-line slot begins at byte 12 l
-};
-template <>
-struct WideVec<4> {
-    typedef unsigned int type __attribute__((ext_vector_type(4)));
-};
-
-// the set bits of a dense row (an overflow slot's, or the AND of the blocks of a k-mer that has no slot), word `lane`, `lane + 64`, ...
-// of it per lane, counted one by one
-__device__ __forceinline__ void wide_count_word(uint32_t *cnt, uint64_t word, uint32_t w, uint32_t n_bins)
-{
-    while (word) {
-        const uint32_t bit = (uint32_t)__builtin_ctzll(word);
-        word &= word - 1;
-        count_bin(cnt, w * 64u + bit, n_bins);
-    }
-}
-
-// One batch of 16 slots of a wave's tile, slots first .. first + 15: `listed` says which of the tile's k-mers have a slot to count (in
-// the strand, no base outside ACGT).  FULL: all 16 have, and nothing is guarded.  Lane l takes dwords DW l .. DW l + DW - 1 of every
-// slot in ONE load (8, 12 or 16 bytes: an eight-line slot is a dwordx4 per lane), the loads are issued back to back, and a group of
-// eight slots is added as soon as its loads have landed (list_batch's order, so the waits are counted).  Flags as in list_batch: the
-// group's dwords ORed, one wave-wide test, and only a flagged group looks at its slots one by one.
-template <int LINES, bool NT, bool FULL>
-__device__ __forceinline__ void wide_batch(const IbfDev &f, uint32_t *cnt, const uint32_t *__restrict__ slots, const uint64_t *__restrict__ side,
-                                           uint32_t side_rows, uint32_t rank, uint64_t listed, uint32_t first, uint32_t lane, uint32_t spare)
-{
-    constexpr int DW = LINES / 2;
-    constexpr int R = 16;
-    constexpr int G = 8;
-    constexpr uint32_t SLOT_DWORDS = LINES * 32;
-    typedef typename WideVec<DW>::type vec_t;
-    const uint32_t spare_off = spare * 4u, blank = spare_off * 0x10001u;
-    uint32_t v[R][DW];
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-#pragma unroll
-        for (int d = 0; d < DW; ++d) v[u][d] = blank;
-        if (FULL || ((listed >> (first + (uint32_t)u)) & 1ull)) {  // wave-uniform
-            const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)rank, (int)(first + (uint32_t)u));
-            const uint32_t *base = slots + (uint64_t)slot * SLOT_DWORDS;  // slot < 4^k: masked digits; 64-bit: 4^13 slots of 1 KiB are 64 GiB
-            const vec_t *p = reinterpret_cast<const vec_t *>(base + lane * (uint32_t)DW);
-            const vec_t q = NT ? __builtin_nontemporal_load(p) : *p;
-#pragma unroll
-            for (int d = 0; d < DW; ++d) v[u][d] = q[d];
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    uint32_t overflow = 0;  // the batch's overflow slots
-#pragma unroll
-    for (int g = 0; g < R / G; ++g) {
-        if (FULL || ((listed >> (first + (uint32_t)(g * G))) & 0xFFull)) {  // wave-uniform
-            uint32_t fold = 0;
-#pragma unroll
-            for (int u = 0; u < G; ++u)
-#pragma unroll
-                for (int d = 0; d < DW; ++d) fold |= v[g * G + u][d];
-            if (__builtin_expect(__ballot((fold & rblist::kResidentFlags) != 0u) != 0ULL, 0)) {  // wave-uniform, rare
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const int s = g * G + u;
-                    const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)v[s][0], 0);  // dword 0 of the slot
-                    if (d0 & rblist::kResidentOverflow) {  // wave-uniform: set aside, and blanked (its index is no address)
-                        overflow |= 1u << s;
-#pragma unroll
-                        for (int d = 0; d < DW; ++d) v[s][d] = blank;
-                    } else {
-#pragma unroll
-                        for (int d = 0; d < DW; ++d)
-                            if (v[s][d] & rblist::kResidentFlags) v[s][d] = list_add_swapped(cnt, v[s][d], spare_off, true);
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < G; ++u)
-#pragma unroll
-                for (int d = 0; d < DW; ++d) list_add2(cnt, v[g * G + u][d]);
-        }
-    }
-    while (overflow) {  // wave-uniform, rare: the slot's index dword once more, then the dense row's set bits one by one
-        const int u = __builtin_ctz(overflow);
-        overflow &= overflow - 1;
-        const uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)rank, (int)first + u);
-        const uint32_t idx = slots[(uint64_t)slot * SLOT_DWORDS + 1];
-        if (idx >= side_rows) continue;  // (the builder never names a row it did not write)
-        const uint64_t *row = side + (uint64_t)idx * f.stride;
-        for (uint32_t w = lane; w < f.bin_width; w += 64) wide_count_word(cnt, row[w], w, f.n_bins);
-    }
-}
 
 // One WORKGROUP of NW waves, one read.  At 31 000 bins the 16-bit counters of a strand take 62 KiB, so a CU holds two workgroups: with
 // one wave each, as ibf_count_lists_kernel has, that would be two waves per CU.  So the NW waves of a workgroup share ONE counter array
@@ -150,6 +54,8 @@ __global__ __launch_bounds__(64 * NW) void ibf_count_wide_lists_kernel(IbfDev f,
 #pragma unroll 1
     for (int strand = 0; strand < 2; ++strand) {
         if (bound && strand == 1 && best >= n) break;  // the same `best` in every wave
+        // (the tile loop stands here and not as a call of wide_count_strand, which is this loop for the kernels that count a strand in
+        // full: the call compiles to other instructions -- ten to fourteen more -- and this kernel keeps the measured ones)
 #pragma unroll 1
         for (uint32_t mt = wave * 64u; mt < n; mt += 64u * NW) {  // wave-uniform
             // ---- the tile's bases as Dna5 ordinals, and one rank per lane

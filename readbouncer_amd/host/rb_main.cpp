@@ -545,6 +545,9 @@ struct IngestOptions
                                              // (rb_engine_set_pass_lists): where it has one, or building one; the files are the same bytes
     int wide_lists = RB_PASS_LISTS_OFF;      // --wide-lists off|current|build: classify counts filters of 8193 to 32 256 bins from their wide
                                              // list table (rb_engine_set_wide_lists); the files are the same bytes
+    int wide_pass_lists = RB_PASS_LISTS_CURRENT;  // --wide-pass-lists off|current|build: --report-bins / --report-hits from such a filter's wide
+                                             // list table (rb_engine_set_wide_pass_lists) where it has one -- one exists only if the run asked for it
+                                             // with --wide-lists build -- or building one; the files are the same bytes
     int prefix_lists = RB_PASS_LISTS_OFF;    // --prefix-lists off|current|build: --report-prefixes from a filter's list table
                                              // (rb_engine_set_prefix_lists); the files are the same bytes
     std::vector<std::string> bin_maps;  // --bin-map FILE (may repeat): <filter name>.bins.tsv of build --write-bin-map -> a record_id column
@@ -990,6 +993,9 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                 if (!multi && opt.wide_lists != RB_PASS_LISTS_OFF)
                     interleave::throw_status(rb_engine_set_wide_lists(interleave::detail::engine_for(DepletionFilters, TargetFilters), opt.wide_lists),
                                              "rb_engine_set_wide_lists");
+                if ((opt.report_bins || opt.report_hits) && !multi && opt.wide_pass_lists != RB_PASS_LISTS_OFF)
+                    interleave::throw_status(rb_engine_set_wide_pass_lists(interleave::detail::engine_for(DepletionFilters, TargetFilters), opt.wide_pass_lists),
+                                             "rb_engine_set_wide_pass_lists");
                 if (opt.report_prefixes && !multi && opt.prefix_lists != RB_PASS_LISTS_OFF)
                     interleave::throw_status(rb_engine_set_prefix_lists(interleave::detail::engine_for(DepletionFilters, TargetFilters), opt.prefix_lists),
                                              "rb_engine_set_prefix_lists");
@@ -1363,6 +1369,17 @@ int main(int argc, char const* argv[])
             else if (!std::strcmp(v, "build")) opt.wide_lists = RB_PASS_LISTS_BUILD;
             else {
                 std::cerr << "ERROR: --wide-lists off|current|build" << std::endl;
+                return 1;
+            }
+            ++i;
+        }
+        else if (!std::strcmp(argv[i], "--wide-pass-lists")) {
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            if (!std::strcmp(v, "off")) opt.wide_pass_lists = RB_PASS_LISTS_OFF;
+            else if (!std::strcmp(v, "current")) opt.wide_pass_lists = RB_PASS_LISTS_CURRENT;
+            else if (!std::strcmp(v, "build")) opt.wide_pass_lists = RB_PASS_LISTS_BUILD;
+            else {
+                std::cerr << "ERROR: --wide-pass-lists off|current|build" << std::endl;
                 return 1;
             }
             ++i;
