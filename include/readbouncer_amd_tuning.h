@@ -486,8 +486,8 @@ RB_API void rb_set_list_side_capacity(uint32_t rows);
  *     rb_engine_set_row_table and half of the free device memory, and the stream is not being captured; a refusal is remembered for the
  *     bits and max_bytes it was given for, and means the plain kernel).  Any other value is RB_ERR_INVALID_ARG.  Taken by classify calls
  *     alone, and only by launches that row_policy's rule (a) admits -- no latency form, fused micro-batch, early-decision mode, column
- *     shard -- with no prune trace asked for; locate and hits read the wide table under a setting of their own (below); spans, prefix and
- *     resume do not read it.  rb_engine_plan names ibf_count_wide_lists_kernel where a call would take it.
+ *     shard -- with no prune trace asked for; locate and hits, and the prefix pass, read the wide table under settings of their own (below);
+ *     spans and resume do not read it.  rb_engine_plan names ibf_count_wide_lists_kernel where a call would take it.
  *   rb_engine_set_wide_pass_lists: the same three values for the locate and hits calls of the boundary header, off by default and a
  *     setting of its OWN: rb_engine_set_wide_lists does not reach locate or hits, this setting does not reach classify, and
  *     rb_engine_set_pass_lists does not reach filters beyond 8192 bins.  Decided per filter and per call (an engine may mix wide-served,
@@ -500,7 +500,20 @@ RB_API void rb_set_list_side_capacity(uint32_t rows);
  *     the plain kernels the others; every output is the plain form's, byte for byte.  Any other value is RB_ERR_INVALID_ARG.
  *   rb_engine_wide_pass_lines: *lines_out = 4, 6 or 8 -- the slot size a locate or hits call on items of at most max_len bases would take
  *     for this filter as things stand -- or 0: the plain (or the list) form.  Host arithmetic only; nothing is built or dropped, so under
- *     _BUILD it reports the table once it stands.  rb_pass_plan is unchanged, and its list_lines stays 0 for these filters. */
+ *     _BUILD it reports the table once it stands.  rb_pass_plan is unchanged, and its list_lines stays 0 for these filters.
+ *   rb_engine_set_wide_prefix_lists: the same three values for the prefix calls of the boundary header, off by
+ *     default and a setting of its OWN: rb_engine_set_prefix_lists, rb_engine_set_wide_pass_lists and rb_engine_set_wide_lists do not
+ *     reach it, and it reaches none of them.  Decided per filter and per call by rb_engine_set_wide_pass_lists's rules with this mode
+ *     and the call's bound min(max_len, last checkpoint): at most 65 535 k-mers per strand at the last checkpoint.
+ *     ibf_prefix_wide_lists_kernel then serves the items whose status so far is RB_OK and whose first min(len, last checkpoint) bases lie
+ *     within the bound -- any length, and whatever their bases -- one workgroup of four waves per item, and the plain kernel the
+ *     others; a filter served by neither list form runs the plain form in the same call.  Every output is the plain form's, byte for
+ *     byte.  Any other value is RB_ERR_INVALID_ARG.
+ *   rb_engine_wide_prefix_lines: *lines_out = 4, 6 or 8 -- the slot size a prefix call on items of at most max_len bases with that last
+ *     checkpoint would take for this filter as things stand -- or 0.  Host arithmetic only; nothing is built or dropped.
+ *     rb_prefix_plan_info is unchanged, and its list_lines stays 0 for these filters.
+ *   rb_engine_wide_prefix_lists_items: rb_engine_prefix_lists_items for this form, counters of its own: the items the wide form took and
+ *     left since the last reset, over the calls in which some filter was wide-served.  Waits for the engine's stream. */
 typedef struct rb_wide_list_table_info {
     uint64_t bytes, rows;    /* of the current table's slots; 0: none */
     uint64_t side_bytes;     /* of its side table */
@@ -521,6 +534,9 @@ RB_API int rb_dibf_wide_list_table_download(rb_dibf *f, uint16_t *entries, uint6
 RB_API int rb_engine_set_wide_lists(rb_engine *e, int mode);
 RB_API int rb_engine_set_wide_pass_lists(rb_engine *e, int mode);
 RB_API int rb_engine_wide_pass_lines(rb_engine *e, size_t filter_index, uint32_t max_len, uint32_t *lines_out);
+RB_API int rb_engine_set_wide_prefix_lists(rb_engine *e, int mode);
+RB_API int rb_engine_wide_prefix_lines(rb_engine *e, size_t filter_index, uint32_t max_len, uint32_t last_checkpoint, uint32_t *lines_out);
+RB_API int rb_engine_wide_prefix_lists_items(rb_engine *e, uint64_t *listed, uint64_t *plain, int reset);
 /* rows of the side table of wide list tables built from now on (process-wide; 0: the default, 4^k / 512 + 64) */
 RB_API void rb_set_wide_list_side_capacity(uint32_t rows);
 

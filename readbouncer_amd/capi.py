@@ -294,6 +294,9 @@ SIGNATURES = {
     "rb_engine_set_wide_lists": (_int, [_vp, _int]),
     "rb_engine_set_wide_pass_lists": (_int, [_vp, _int]),
     "rb_engine_wide_pass_lines": (_int, [_vp, _sz, _u32, C.POINTER(C.c_uint32)]),
+    "rb_engine_set_wide_prefix_lists": (_int, [_vp, _int]),
+    "rb_engine_wide_prefix_lines": (_int, [_vp, _sz, _u32, _u32, C.POINTER(C.c_uint32)]),
+    "rb_engine_wide_prefix_lists_items": (_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _int]),
     "rb_set_wide_list_side_capacity": (None, [C.c_uint32]),
     "rb_dibf_placement": (_int, [_vp, C.POINTER(_u32), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "rb_dibf_placement_cost": (_int, [_vp, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_u64), C.POINTER(_u32)]),
@@ -1013,6 +1016,28 @@ class Engine:
         lines = C.c_uint32(0)
         _check(lib().rb_engine_wide_pass_lines(self.h, filter_index, max_len, C.byref(lines)), "rb_engine_wide_pass_lines")
         return int(lines.value)
+
+    def set_wide_prefix_lists(self, mode):
+        """RB_PASS_LISTS_OFF (default) / _CURRENT / _BUILD for the prefix pass on filters of 8193 to 32 256 bins
+        (rb_engine_set_wide_prefix_lists): whether prefixes are served from the filter's wide list table (results identical; a setting
+        of its own beside set_prefix_lists, set_wide_pass_lists and set_wide_lists; wide_prefix_lines reports the slot size)"""
+        _check(lib().rb_engine_set_wide_prefix_lists(self.h, int(mode)), "rb_engine_set_wide_prefix_lists")
+
+    def wide_prefix_lines(self, filter_index, max_len, last_checkpoint):
+        """0, or the slot size (4, 6 or 8 lines) at which a prefix call on items of at most max_len bases with that last checkpoint would
+        take the filter's wide list table as things stand (rb_engine_wide_prefix_lines: host arithmetic, nothing is built)"""
+        lines = C.c_uint32(0)
+        _check(lib().rb_engine_wide_prefix_lines(self.h, filter_index, int(max_len), int(last_checkpoint), C.byref(lines)),
+               "rb_engine_wide_prefix_lines")
+        return int(lines.value)
+
+    def wide_prefix_lists_items(self, reset=False):
+        """-> (items the wide list form of the prefix pass took, items it left to the plain form) since the last reset, over the calls
+        in which some filter was wide-served (rb_engine_wide_prefix_lists_items; the list form's pair is prefix_lists_items)"""
+        listed, plain = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rb_engine_wide_prefix_lists_items(self.h, C.byref(listed), C.byref(plain), int(bool(reset))),
+               "rb_engine_wide_prefix_lists_items")
+        return int(listed.value), int(plain.value)
 
     def set_prefix_lists(self, mode):
         """RB_PASS_LISTS_OFF (default) / _CURRENT / _BUILD for the prefix pass alone (rb_engine_set_prefix_lists): whether prefixes are

@@ -345,6 +345,12 @@ struct PrefixListsPrep {
 };
 hipError_t launch_prefix_lists_prep(const PrefixListsPrep &a, hipStream_t st);
 hipError_t launch_ibf_prefix_lists(const PrefixLaunch &a, hipStream_t st);
+// ... the wide list form (rb_wide_prefix_lists.hip; rb_engine_set_wide_prefix_lists).  Which items it takes: the list form's rule without the
+// look at the bases -- the pre-status is RB_OK and w <= src.max_len -- with taken[], plain_lens[] and counters[] (two of this form's own)
+// as above.  launch_ibf_prefix_wide_lists is launch_ibf_prefix over a.list_plain_lens and then ibf_prefix_wide_lists_kernel<LINES, NT>,
+// which writes a taken item's partials into slice 0 and zeros into every other slice of the a.n_slices the merge reads.
+hipError_t launch_wide_prefix_lists_prep(const PrefixListsPrep &a, hipStream_t st);
+hipError_t launch_ibf_prefix_wide_lists(const PrefixLaunch &a, hipStream_t st);
 // max_count [n_items][cps.n][nf] <- the maximum over the slices; for fidx == 0 also prefix_len / row_pre [n_items][cps.n]
 hipError_t launch_finish_prefix(const PrefixLaunch &a, const uint32_t *lens, const uint8_t *pre_status, uint16_t *max_count, uint32_t *prefix_len,
                                 uint8_t *row_pre, hipStream_t st);

@@ -444,6 +444,10 @@ struct rb_engine {
     int wide_lists = RB_PASS_LISTS_OFF;
     // rb_engine_set_wide_pass_lists: whether locate and hits take such a filter's wide list table (wide_pass_lists_for)
     int wide_pass_lists = RB_PASS_LISTS_OFF;
+    // rb_engine_set_wide_prefix_lists: the same for the prefix pass, a setting of its own (wide_lists_for with this mode); and where its
+    // prep kernel counts the items the wide form took and left (rb_engine_wide_prefix_lists_items): two uint64_t of its own
+    int wide_prefix_lists = RB_PASS_LISTS_OFF;
+    DevBuf d_wide_prefix_items;
     struct CertLoad {
         double set = -1.0;       // what the caller gave (< 0: measure)
         double measured = -1.0;  // load of the filter's fullest bin at `version` (< 0: not measured yet)
@@ -1291,7 +1295,7 @@ void rb_engine_destroy(rb_engine *e)
     }
     for (void *r : e->thr_retired_dev) (void)hipFree(r);
     for (PinnedBuf &h : e->thr_retired_host) h.release();
-    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_prefix_items, &e->d_efflens, &e->d_prestatus, &e->d_pass_ws, &e->d_pass_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
+    for (DevBuf *b : {&e->d_split_ws, &e->d_split_tickets, &e->d_done_count, &e->d_prefix_items, &e->d_wide_prefix_items, &e->d_efflens, &e->d_prestatus, &e->d_pass_ws, &e->d_pass_io, &e->d_maxcount, &e->d_seqs, &e->d_offsets, &e->d_lens, &e->d_best,
                       &e->d_decision, &e->d_status})
         b->release();
     e->h_in.release();
@@ -1551,6 +1555,14 @@ int rb_engine_set_wide_pass_lists(rb_engine *e, int mode)
     if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
     std::lock_guard<std::mutex> lock(e->mu);
     e->wide_pass_lists = mode;
+    return RB_OK;
+}
+
+int rb_engine_set_wide_prefix_lists(rb_engine *e, int mode)
+{
+    if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->wide_prefix_lists = mode;
     return RB_OK;
 }
 
@@ -3144,13 +3156,14 @@ static int pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, 
 // items and max_len: remembered refusals, max_bytes, the repay inequality; half of the free memory where it is built), whose refusals
 // mean the plain form.  a->wide_table stays null wherever the answer is no.  asking: the question alone (rb_engine_wide_pass_lines) --
 // no stream, and nothing is built or dropped, so BUILD reports the table once it stands.
-static int wide_pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, size_t n_items, PlainPassLaunch *a)
+// wide_lists_for: the same under a setting the caller names -- the engine's for locate and hits, and the prefix pass's own
+// (rb_engine_set_wide_prefix_lists), whose launch carries the call's bound min(max_len, c_last) as its max_len.
+static int wide_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, int mode, size_t n_items, PlainPassLaunch *a)
 {
     a->wide_table = nullptr;
     a->wide_side = nullptr;
     a->wide_side_rows = a->wide_lines = 0;
     a->wide_nt = 0;
-    const int mode = e->wide_pass_lists;
     if (mode == RB_PASS_LISTS_OFF || e->shard_world != 1 || !wide_form_serves(a->f, a->src.max_len)) return RB_OK;
     rb_dibf *f = e->filters[fi];
     if (wide_table_geometry_refusal(f) || a->col_begin != 0 || a->col_end != a->f.bin_width) return RB_OK;
@@ -3179,6 +3192,10 @@ static int wide_pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool ask
     a->wide_lines = got.lines;
     a->wide_nt = wide_bytes > e->nt_threshold_bytes;
     return RB_OK;
+}
+static int wide_pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, size_t n_items, PlainPassLaunch *a)
+{
+    return wide_lists_for(e, fi, st, asking, e->wide_pass_lists, n_items, a);
 }
 
 // ... and the list forms' share of a call: which items they take is decided once, for every filter (launch_pass_lists_prep: the status
@@ -3667,6 +3684,24 @@ extern "C" int rb_engine_plan_prefix(rb_engine *e, size_t filter_index, uint32_t
     return RB_OK;
 }
 
+// ... and the WIDE list form's answer for a prefix call, a call of its own (rb_prefix_plan_info is not changed, and its list_lines stays 0
+// for these filters): the slot size a prefix call with this bound would take under rb_engine_set_wide_prefix_lists as things stand, or 0.
+// Host arithmetic only: nothing is built or dropped.
+extern "C" int rb_engine_wide_prefix_lines(rb_engine *e, size_t filter_index, uint32_t max_len, uint32_t last_checkpoint, uint32_t *lines_out)
+{
+    if (!e || !lines_out || filter_index >= e->filters.size() || last_checkpoint == 0)
+        return rb::fail(RB_ERR_INVALID_ARG, "rb_engine_wide_prefix_lines: bad argument");
+    std::lock_guard<std::mutex> lock(e->mu);
+    PrefixLaunch a{};
+    PassInput in{};
+    in.src.max_len = in.max_len = std::min(max_len, last_checkpoint);
+    fill_plain_launch(e, filter_index, in, nullptr, 0, &a);
+    const int rc = wide_lists_for(e, filter_index, nullptr, true, e->wide_prefix_lists, 0, &a);
+    if (rc != RB_OK) return rc;
+    *lines_out = a.wide_table ? a.wide_lines : 0u;
+    return RB_OK;
+}
+
 // The items the list form of the prefix pass took and left since the last reset, over the calls in which some filter was list-served
 // (their prep kernel counts them on the device).  Waits for the engine's own stream.
 extern "C" int rb_engine_prefix_lists_items(rb_engine *e, uint64_t *listed, uint64_t *plain, int reset)
@@ -3680,6 +3715,24 @@ extern "C" int rb_engine_prefix_lists_items(rb_engine *e, uint64_t *listed, uint
     if (e->d_prefix_items.p) {
         RB_HIP(hipMemcpy(got, e->d_prefix_items.p, sizeof got, hipMemcpyDeviceToHost));
         if (reset) RB_HIP(hipMemset(e->d_prefix_items.p, 0, sizeof got));
+    }
+    if (listed) *listed = got[0];
+    if (plain) *plain = got[1];
+    return RB_OK;
+}
+
+// ... and the wide list form's pair, counters of its own: over the calls in which some filter was wide-served.
+extern "C" int rb_engine_wide_prefix_lists_items(rb_engine *e, uint64_t *listed, uint64_t *plain, int reset)
+{
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    const int rc = check_device(e->device);
+    if (rc != RB_OK) return rc;
+    std::lock_guard<std::mutex> lock(e->mu);
+    uint64_t got[2] = {0, 0};
+    RB_HIP(hipStreamSynchronize(e->stream));
+    if (e->d_wide_prefix_items.p) {
+        RB_HIP(hipMemcpy(got, e->d_wide_prefix_items.p, sizeof got, hipMemcpyDeviceToHost));
+        if (reset) RB_HIP(hipMemset(e->d_wide_prefix_items.p, 0, sizeof got));
     }
     if (listed) *listed = got[0];
     if (plain) *plain = got[1];
@@ -4321,9 +4374,13 @@ int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32
         a.cps.n = n_prefixes;
         for (uint32_t p = 0; p < kMaxPrefixes; ++p) a.cps.c[p] = p < n_prefixes ? prefix_lens[p] : 0u;
         if ((rc = lists_for(e, fi, c.st, false, e->prefix_lists, &a)) != RB_OK) return rc;  // (one column slice wherever the list form serves)
+        // (a filter has one table or the other: their bin counts do not meet)
+        if ((rc = wide_lists_for(e, fi, c.st, false, e->wide_prefix_lists, n_items, &a)) != RB_OK) return rc;
         max_slices = std::max(max_slices, a.n_slices);
     }
     const bool any_lists = std::any_of(launches.begin(), launches.end(), [](const PrefixLaunch &a) { return a.list_table != nullptr; });
+    // ... and the wide form's share, whose take rule is another (no look at the bases): a call with filters of both kinds keeps two
+    const bool any_wide = std::any_of(launches.begin(), launches.end(), [](const PrefixLaunch &a) { return a.wide_table != nullptr; });
     // workspace: the partial maxima u16[max_slices][n_items][P] and the rows' pre-status, and the outputs a later stage reads where the
     // caller left them out
     const bool decides = d_out->decision || d_out->best_target || d_out->status || d_out->first_decided;
@@ -4333,6 +4390,11 @@ int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32
     const size_t o_dec = lay.take(d_out->first_decided && !d_out->decision ? rows : 0);
     const size_t o_st = lay.take(d_out->first_decided && !d_out->status ? rows : 0);
     const size_t o_taken = lay.take(any_lists ? n_items : 0), o_plain = lay.take(any_lists ? n_items * 4 : 0);
+    const size_t o_wtaken = lay.take(any_wide ? n_items : 0), o_wplain = lay.take(any_wide ? n_items * 4 : 0);
+    if (any_wide && !e->d_wide_prefix_items.p) {
+        if ((rc = e->d_wide_prefix_items.ensure(16)) != RB_OK) return rc;
+        RB_HIP(hipMemsetAsync(e->d_wide_prefix_items.p, 0, 16, c.st));
+    }
     if (any_lists && !e->d_prefix_items.p) {  // the two counters, zero from their first call on
         if ((rc = e->d_prefix_items.ensure(16)) != RB_OK) return rc;
         RB_HIP(hipMemsetAsync(e->d_prefix_items.p, 0, 16, c.st));
@@ -4350,6 +4412,17 @@ int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32
         p.counters = (uint64_t *)e->d_prefix_items.p;
         RB_HIP(launch_prefix_lists_prep(p, c.st));
     }
+    if (any_wide) {  // ... and the wide kernels
+        PrefixListsPrep p{};
+        p.src = c.in.src;
+        p.n_items = (uint32_t)n_items;
+        p.pre_status = c.in.d_pre_status;
+        p.c_last = prefix_lens[P - 1];
+        p.taken = (uint8_t *)(ws + o_wtaken);
+        p.plain_lens = (uint32_t *)(ws + o_wplain);
+        p.counters = (uint64_t *)e->d_wide_prefix_items.p;
+        RB_HIP(launch_wide_prefix_lists_prep(p, c.st));
+    }
     uint16_t *part = (uint16_t *)(ws + o_part);
     uint32_t *row_len = d_out->prefix_len ? (uint32_t *)d_out->prefix_len : (uint32_t *)(ws + o_len);
     uint16_t *max_count = d_out->max_count ? (uint16_t *)d_out->max_count : (uint16_t *)(ws + o_max);
@@ -4364,7 +4437,11 @@ int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32
             a.list_taken = (const uint8_t *)(ws + o_taken);
             a.list_plain_lens = (const uint32_t *)(ws + o_plain);
         }
-        RB_HIP(a.list_table ? launch_ibf_prefix_lists(a, c.st) : launch_ibf_prefix(a, c.st));
+        if (a.wide_table) {
+            a.list_taken = (const uint8_t *)(ws + o_wtaken);
+            a.list_plain_lens = (const uint32_t *)(ws + o_wplain);
+        }
+        RB_HIP(a.wide_table ? launch_ibf_prefix_wide_lists(a, c.st) : a.list_table ? launch_ibf_prefix_lists(a, c.st) : launch_ibf_prefix(a, c.st));
         RB_HIP(launch_finish_prefix(a, c.in.d_lens, c.in.d_pre_status, max_count, row_len, row_pre, c.st));
     }
     if (decides) {

@@ -1,6 +1,7 @@
 // rb_wide_lists_device.h -- the device code the wide list kernels share beyond rb_lists_device.h: a lane's share of a slot, the set bits
-// of a dense row, one batch of slot gathers, and one strand of an item counted in full by a workgroup.  Included by rb_wide_lists.hip
-// (the count kernel and the table) and rb_wide_pass_lists.hip (the wide forms of locate and hits); HIP translation units only.
+// of a dense row, one batch of slot gathers, one strand of an item counted in full by a workgroup, a range of it, and a wave's share of a
+// scan.  Included by rb_wide_lists.hip (the count kernel and the table), rb_wide_pass_lists.hip (the wide forms of locate and hits) and
+// rb_wide_prefix_lists.hip (the wide form of the prefix pass); HIP translation units only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -113,6 +114,7 @@ __device__ __forceinline__ void wide_batch(const IbfDev &f, uint32_t *cnt, const
 // ibf_count_wide_lists_kernel -- tile t of the strand to wave t mod NW, each wave staging its own tile's bases in `stage` (its own area),
 // a k-mer with a base outside ACGT counted from the filter's own table -- without the bound and the strand skip, which stand around the
 // loop there.  The caller puts the workgroup's barrier behind it.  `nh`: min(f.n_hash, rbspec::kMaxHash).
+// (wide_count_range below is this loop over a range: keep the two in step.)
 template <int LINES, bool NT, int NW>
 __device__ __forceinline__ void wide_count_strand(const IbfDev &f, uint32_t *cnt, uint8_t *stage, const uint32_t *__restrict__ slots,
                                                   const uint64_t *__restrict__ side, uint32_t side_rows, const ListBaseSrc &seq, uint32_t len,
@@ -148,6 +150,94 @@ __device__ __forceinline__ void wide_count_strand(const IbfDev &f, uint32_t *cnt
         const uint64_t listed = __ballot(p < n && !outside);
         uint64_t unlisted = __ballot(p < n && outside);
         const uint32_t in_tile = min(64u, n - mt);
+#pragma unroll 1
+        for (uint32_t first = 0; first < in_tile; first += 16) {
+            const uint32_t sub = (uint32_t)(listed >> first) & 0xFFFFu;
+            if (sub == 0xFFFFu)  // wave-uniform
+                wide_batch<LINES, NT, true>(f, cnt, slots, side, side_rows, rank, listed, first, lane, spare);
+            else if (sub)
+                wide_batch<LINES, NT, false>(f, cnt, slots, side, side_rows, rank, listed, first, lane, spare);
+        }
+        while (__builtin_expect(unlisted != 0ULL, 0)) {  // wave-uniform, rare: a k-mer with a base outside ACGT, from the filter's own table
+            const uint32_t u = (uint32_t)__builtin_ctzll(unlisted);
+            unlisted &= unlisted - 1;
+            const uint8_t *b = stage + u;
+            uint64_t value = 0;
+            if (strand == 0) {
+                for (uint32_t i = 0; i < k; ++i) value = value * 5u + b[i];
+            } else {
+                for (uint32_t i = 0; i < k; ++i) value = value * 5u + rbspec::dna5_comp(b[k - 1 - i], f.comp_n);
+            }
+            uint32_t blk[rbspec::kMaxHash];
+#pragma unroll
+            for (uint32_t h = 0; h < rbspec::kMaxHash; ++h)
+                blk[h] = h < nh ? rbspec::block_index(value, f.precalc[h], f.n_blocks, f.magic, f.pow2_mask) : 0u;
+            for (uint32_t w = lane; w < f.bin_width; w += 64) {
+                uint64_t acc = ~0ULL;
+#pragma unroll
+                for (uint32_t h = 0; h < rbspec::kMaxHash; ++h)
+                    if (h < nh) acc &= f.words[(uint64_t)blk[h] * f.stride + w];
+                wide_count_word(cnt, acc, w, f.n_bins);
+            }
+        }
+    }
+}
+
+// A wave's share of a scan of the counters (the wide forms of locate, hits and prefixes; the scheme is set out in rb_wide_pass_lists.hip
+// and restated for the host in rb_wide_lists.h): cnt_dwords / 256 rounds of 64 consecutive 16-byte pieces, wave w at the rounds
+// [w x per, (w + 1) x per) that exist, per = ceil(rounds / NW).
+template <int NW>
+struct WideShare {
+    uint32_t r0, r1;  // the wave's rounds [r0, r1)
+    __device__ __forceinline__ WideShare(uint32_t cnt_dwords, uint32_t wave)
+    {
+        const uint32_t rounds = cnt_dwords / 256u, per = (rounds + NW - 1) / NW;
+        r0 = min(wave * per, rounds);
+        r1 = min(r0 + per, rounds);
+    }
+};
+
+// The RANGED count (the wide list form of the prefix pass): the k-mers [n_from, n_to) of one strand of the item's first `len` bases, n_to
+// == len - k + 1 -- wide_count_strand's tile loop over the RANGE: tile t of the range to wave t mod NW, so wave w starts at k-mer n_from +
+// 64 w, at a multiple of 64 or not (ListBaseSrc::ord addresses single bases at any offset), and a range shorter than a tile is wave 0's
+// alone.  The counters are added to, not cleared; the caller puts the workgroup's barrier behind it.  Kept beside wide_count_strand and
+// not under it, so that the count, locate and hits kernels compile as they did: the two loops must be kept in step.
+template <int LINES, bool NT, int NW>
+__device__ __forceinline__ void wide_count_range(const IbfDev &f, uint32_t *cnt, uint8_t *stage, const uint32_t *__restrict__ slots,
+                                                 const uint64_t *__restrict__ side, uint32_t side_rows, const ListBaseSrc &seq, uint32_t len,
+                                                 uint32_t n_from, uint32_t n_to, int strand, uint32_t wave, uint32_t lane, uint32_t spare,
+                                                 uint32_t nh)
+{
+    const uint32_t k = f.k;
+#pragma unroll 1
+    for (uint32_t mt = n_from + wave * 64u; mt < n_to; mt += 64u * NW) {  // wave-uniform; n_to <= kWideMaxKmers: no wrap
+        // ---- the tile's bases as Dna5 ordinals, and one rank per lane
+        const uint32_t wlen = min(64u + k - 1u, len - mt);
+        __builtin_amdgcn_wave_barrier();
+        if (lane < wlen) stage[lane] = (uint8_t)seq.ord(mt + lane);
+        if (lane + 64u < wlen) stage[lane + 64u] = (uint8_t)seq.ord(mt + 64u + lane);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t p = mt + lane;
+        uint32_t rank = 0;
+        bool outside = false;
+        if (p < n_to) {
+            const uint8_t *b = stage + lane;
+            if (strand == 0) {
+                for (uint32_t i = 0; i < k; ++i) {
+                    outside |= b[i] > 3u;
+                    rank = (rank << 2) | (b[i] & 3u);
+                }
+            } else {
+                for (uint32_t i = 0; i < k; ++i) {
+                    outside |= b[k - 1 - i] > 3u;
+                    rank = (rank << 2) | ((3u - b[k - 1 - i]) & 3u);
+                }
+            }
+        }
+        const uint64_t listed = __ballot(p < n_to && !outside);
+        uint64_t unlisted = __ballot(p < n_to && outside);
+        const uint32_t in_tile = min(64u, n_to - mt);
 #pragma unroll 1
         for (uint32_t first = 0; first < in_tile; first += 16) {
             const uint32_t sub = (uint32_t)(listed >> first) & 0xFFFFu;

@@ -46,16 +46,7 @@ hipError_t launch_wide_pass_lists_prep(const PassListsPrep &a, hipStream_t st)
 // bins, where the one-wave forms' mask of a byte per piece would add 4032), and the thread that scans a piece on the first strand scans
 // it on the second: its at most 16 pieces are 16 bytes, two 64-bit registers, byte j the piece of its wave's round j.
 // Exchanges across the waves go through red[] (kWideReduceBytes behind the stage areas): two dwords per wave.
-template <int NW>
-struct WideShare {
-    uint32_t r0, r1;  // the wave's rounds [r0, r1)
-    __device__ __forceinline__ WideShare(uint32_t cnt_dwords, uint32_t wave)
-    {
-        const uint32_t rounds = cnt_dwords / 256u, per = (rounds + NW - 1) / NW;
-        r0 = min(wave * per, rounds);
-        r1 = min(r0 + per, rounds);
-    }
-};
+// (WideShare<NW> itself is in rb_wide_lists_device.h, shared with the wide form of the prefix pass.)
 static_assert(rbwide::pass_rounds_per_wave(rbwide::kWideMaxBins) <= rbwide::kWidePassMaskBytes && rbwide::kWidePassMaskBytes == 16,
               "a thread's pieces fit the two 64-bit registers of its mask (rb_wide_lists.h restates the shares for the host)");
 

@@ -550,6 +550,8 @@ struct IngestOptions
                                              // with --wide-lists build -- or building one; the files are the same bytes
     int prefix_lists = RB_PASS_LISTS_OFF;    // --prefix-lists off|current|build: --report-prefixes from a filter's list table
                                              // (rb_engine_set_prefix_lists); the files are the same bytes
+    int wide_prefix_lists = RB_PASS_LISTS_OFF;  // --wide-prefix-lists off|current|build: --report-prefixes from a wide list table
+                                             // (rb_engine_set_wide_prefix_lists), filters of 8193 to 32256 bins; the files are the same bytes
     std::vector<std::string> bin_maps;  // --bin-map FILE (may repeat): <filter name>.bins.tsv of build --write-bin-map -> a record_id column
     size_t bytes() const { return segment_bytes ? segment_bytes : (segment_mb << 20); }
 };
@@ -999,6 +1001,9 @@ static void classify_reads(ConfigReader& config, std::vector<interleave::IBFMeta
                 if (opt.report_prefixes && !multi && opt.prefix_lists != RB_PASS_LISTS_OFF)
                     interleave::throw_status(rb_engine_set_prefix_lists(interleave::detail::engine_for(DepletionFilters, TargetFilters), opt.prefix_lists),
                                              "rb_engine_set_prefix_lists");
+                if (opt.report_prefixes && !multi && opt.wide_prefix_lists != RB_PASS_LISTS_OFF)
+                    interleave::throw_status(rb_engine_set_wide_prefix_lists(interleave::detail::engine_for(DepletionFilters, TargetFilters), opt.wide_prefix_lists),
+                                             "rb_engine_set_wide_prefix_lists");
                 if (opt.calibrate && !multi) {
                     // one engine at a time, and nobody classifies before the last engine is calibrated: an engine timed beside
                     // another thread's classification picks its windows from noise
@@ -1351,6 +1356,17 @@ int main(int argc, char const* argv[])
             }
             ++i;
         }
+        else if (!std::strcmp(argv[i], "--wide-prefix-lists")) {
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            if (!std::strcmp(v, "off")) opt.wide_prefix_lists = RB_PASS_LISTS_OFF;
+            else if (!std::strcmp(v, "current")) opt.wide_prefix_lists = RB_PASS_LISTS_CURRENT;
+            else if (!std::strcmp(v, "build")) opt.wide_prefix_lists = RB_PASS_LISTS_BUILD;
+            else {
+                std::cerr << "ERROR: --wide-prefix-lists off|current|build" << std::endl;
+                return 1;
+            }
+            ++i;
+        }
         else if (!std::strcmp(argv[i], "--prefix-lists")) {
             const char* v = i + 1 < argc ? argv[i + 1] : "";
             if (!std::strcmp(v, "off")) opt.prefix_lists = RB_PASS_LISTS_OFF;
@@ -1488,6 +1504,9 @@ int main(int argc, char const* argv[])
                          "                                    decided there, changed against the checkpoint before\n"
                          "                  [--prefix-lists off|current|build]  --report-prefixes from a filter's list table: never (off, the default), where it has a\n"
                          "                                    current one (current), or building one where it has none (build); the files are the same bytes\n"
+                         "                  [--wide-prefix-lists off|current|build]  --report-prefixes from the wide list table of a filter of 8193 to 32256 bins:\n"
+                         "                                    never (off, the default), where one is current (current; --wide-lists build makes one), or building it\n"
+                         "                                    when the batch repays it (build); the files are the same bytes\n"
                          "                  [--wide-lists off|current|build]  count filters of 8193 to 32256 bins from their wide list table: never (off, the default),\n"
                          "                                    where one is current (current), or building it when the batch repays it (build); the files are the same bytes\n"
                          "                  [--bin-map <name>.bins.tsv ...]  adds the record id of the bin to these reports\n"
