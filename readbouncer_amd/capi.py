@@ -98,16 +98,20 @@ class RowTableInfo(C.Structure):
                 ("refused", C.c_uint32), ("builds", C.c_uint32)]
 
 
+# rb_list_table_info and rb_wide_list_table_info: one layout under two names
+_LIST_TABLE_INFO_FIELDS = [("bytes", C.c_uint64), ("rows", C.c_uint64), ("side_bytes", C.c_uint64), ("lines", C.c_uint32), ("side_rows", C.c_uint32),
+                           ("side_capacity", C.c_uint32), ("refused", C.c_uint32), ("builds", C.c_uint32), ("stride_words", C.c_uint32),
+                           ("census_rows", C.c_uint64), ("census_over", C.c_uint64 * 3), ("build_ms", C.c_double), ("alloc_s", C.c_double)]
+
+
 class ListTableInfo(C.Structure):
     """rb_list_table_info"""
-    _fields_ = [("bytes", C.c_uint64), ("rows", C.c_uint64), ("side_bytes", C.c_uint64), ("lines", C.c_uint32), ("side_rows", C.c_uint32),
-                ("side_capacity", C.c_uint32), ("refused", C.c_uint32), ("builds", C.c_uint32), ("stride_words", C.c_uint32),
-                ("census_rows", C.c_uint64), ("census_over", C.c_uint64 * 3), ("build_ms", C.c_double), ("alloc_s", C.c_double)]
+    _fields_ = _LIST_TABLE_INFO_FIELDS
 
 
 class WideListTableInfo(C.Structure):
     """rb_wide_list_table_info (census_over: rows with more than 256, 384, 512 set bits)"""
-    _fields_ = list(ListTableInfo._fields_)
+    _fields_ = _LIST_TABLE_INFO_FIELDS
 
 
 RB_ROW_TABLE_OFF, RB_ROW_TABLE_AUTO, RB_ROW_TABLE_FORCE, RB_ROW_TABLE_LISTS = 0, 1, 2, 3
@@ -521,57 +525,56 @@ class DeviceIBF:
         _check(lib().rb_dibf_row_table_download(self.h, _ptr(out), len(out)), "rb_dibf_row_table_download")
         return out.reshape(i["rows"], -1) if i["rows"] else out
 
+    def _list_table(self, prefix, op, max_bytes=0):
+        """build / drop / info / download of rb_dibf_<prefix>_*: the list table ("list_table") and the wide one ("wide_list_table")"""
+        def call(what, *args):
+            _check(getattr(lib(), "rb_dibf_%s_%s" % (prefix, what))(self.h, *args), "rb_dibf_%s_%s" % (prefix, what))
+        if op == "drop":
+            return call("drop")
+        if op == "build":
+            call("build", int(max_bytes))
+        i = (WideListTableInfo if prefix == "wide_list_table" else ListTableInfo)()
+        call("info", C.byref(i))
+        d = {k: getattr(i, k) for k, _ in _LIST_TABLE_INFO_FIELDS}
+        d["census_over"] = list(i.census_over)
+        if op != "download":
+            return d
+        slots = np.zeros(d["bytes"] // 2, dtype=np.uint16)
+        side = np.zeros(d["side_rows"] * d["stride_words"], dtype=np.uint64)
+        call("download", _ptr(slots) if len(slots) else None, len(slots), _ptr(side) if len(side) else None, len(side))
+        return (slots.reshape(d["rows"], -1) if d["rows"] else slots), side.reshape(d["side_rows"], d["stride_words"])  # (a table none of whose rows overflow has no side rows)
+
     def list_table_build(self, max_bytes=0):
         """build the list table (per N-free k-mer the sorted bin numbers of its row, in slots of 1, 2 or 4 lines) unless a current one
         exists -> list_table_info()"""
-        _check(lib().rb_dibf_list_table_build(self.h, int(max_bytes)), "rb_dibf_list_table_build")
-        return self.list_table_info()
+        return self._list_table("list_table", "build", max_bytes)
 
     def list_table_drop(self):
-        _check(lib().rb_dibf_list_table_drop(self.h), "rb_dibf_list_table_drop")
+        self._list_table("list_table", "drop")
 
     def list_table_info(self):
         """-> dict (rb_list_table_info)"""
-        i = ListTableInfo()
-        _check(lib().rb_dibf_list_table_info(self.h, C.byref(i)), "rb_dibf_list_table_info")
-        d = {k: getattr(i, k) for k, _ in ListTableInfo._fields_}
-        d["census_over"] = list(i.census_over)
-        return d
+        return self._list_table("list_table", "info")
 
     def list_table_download(self):
         """-> (np.uint16[rows, 64 x lines]: the slots, np.uint64[side rows in use, stride words]: the dense rows overflow slots name)"""
-        i = self.list_table_info()
-        slots = np.zeros(i["bytes"] // 2, dtype=np.uint16)
-        side = np.zeros(i["side_rows"] * i["stride_words"], dtype=np.uint64)
-        _check(lib().rb_dibf_list_table_download(self.h, _ptr(slots) if len(slots) else None, len(slots), _ptr(side) if len(side) else None,
-                                                 len(side)), "rb_dibf_list_table_download")
-        return (slots.reshape(i["rows"], -1) if i["rows"] else slots), side.reshape(i["side_rows"], i["stride_words"])  # (a table none of whose rows overflow has no side rows)
+        return self._list_table("list_table", "download")
 
     def wide_list_table_build(self, max_bytes=0):
         """build the wide list table (filters of 8193 to 32 256 bins: per N-free k-mer the sorted bin numbers of its row, in slots of 4, 6
         or 8 lines) unless a current one exists -> wide_list_table_info()"""
-        _check(lib().rb_dibf_wide_list_table_build(self.h, int(max_bytes)), "rb_dibf_wide_list_table_build")
-        return self.wide_list_table_info()
+        return self._list_table("wide_list_table", "build", max_bytes)
 
     def wide_list_table_drop(self):
-        _check(lib().rb_dibf_wide_list_table_drop(self.h), "rb_dibf_wide_list_table_drop")
+        self._list_table("wide_list_table", "drop")
 
     def wide_list_table_info(self):
         """-> dict (rb_wide_list_table_info)"""
-        i = WideListTableInfo()
-        _check(lib().rb_dibf_wide_list_table_info(self.h, C.byref(i)), "rb_dibf_wide_list_table_info")
-        d = {k: getattr(i, k) for k, _ in WideListTableInfo._fields_}
-        d["census_over"] = list(i.census_over)
-        return d
+        return self._list_table("wide_list_table", "info")
 
     def wide_list_table_download(self):
         """-> (np.uint16[rows, 64 x lines]: the canonical slots, np.uint64[side rows in use, stride words]: the dense rows overflow slots name)"""
-        i = self.wide_list_table_info()
-        slots = np.zeros(i["bytes"] // 2, dtype=np.uint16)
-        side = np.zeros(i["side_rows"] * i["stride_words"], dtype=np.uint64)
-        _check(lib().rb_dibf_wide_list_table_download(self.h, _ptr(slots) if len(slots) else None, len(slots),
-                                                      _ptr(side) if len(side) else None, len(side)), "rb_dibf_wide_list_table_download")
-        return (slots.reshape(i["rows"], -1) if i["rows"] else slots), side.reshape(i["side_rows"], i["stride_words"])
+        return self._list_table("wide_list_table", "download")
 
     def placement(self):
         """-> (allocations probed for this table: 0 = not placed by trial, GB/s of the kept one, GB/s of the slowest one)"""

@@ -10,6 +10,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +24,7 @@
 #include "rb_phase_plan.h"
 #include "rb_lists.h"
 #include "rb_wide_lists.h"
+#include "rb_list_tables.h"
 #include "rb_stage.h"
 
 using namespace rb;
@@ -67,29 +69,13 @@ struct rb_dibf {
     double row_build_ms = 0.0, row_alloc_s = 0.0;
     uint32_t row_refused = 0;  // why the last build did not happen (RB_ROW_REFUSED_*)
     uint32_t row_builds = 0;   // tables built for this filter so far
-    // LIST TABLE (rb_dibf_list_table_build; rb_lists.h, rb_lists.hip): the same rows as sorted lists of bin numbers, one slot of list_lines
-    // lines per N-free k-mer, and the dense rows of the slots that overflow in list_side.  Owned, guarded (row_mu) and dropped as the row table.
-    uint16_t *list_table = nullptr;
-    uint64_t *list_side = nullptr;
-    uint64_t list_version = 0, list_rows = 0, list_bytes = 0, list_side_bytes = 0;
-    uint32_t list_lines = 0, list_side_rows = 0, list_side_cap = 0;
-    uint64_t list_census_rows = 0, list_census_over[3] = {0, 0, 0};
-    double list_build_ms = 0.0, list_alloc_s = 0.0;
-    uint32_t list_refused = 0;          // why the last build did not happen (RB_LIST_REFUSED_*)
-    uint64_t list_refused_version = 0;  // ... and the bits it was refused for: an engine does not ask again until they change
-    uint64_t list_refused_max_bytes = 0;  // ... and the max_bytes of that build (list_refusal_stands_locked)
-    uint32_t list_builds = 0;
+    // LIST TABLE (rb_dibf_list_table_build; rb_lists.h, rb_lists.hip): the same rows as sorted lists of bin numbers, one slot of `lines`
+    // lines per N-free k-mer, and the dense rows of the slots that overflow in `side`.  Owned, guarded (row_mu) and dropped as the row table.
+    rbtables::ListTableState list;
     // WIDE LIST TABLE (rb_dibf_wide_list_table_build; rb_wide_lists.h, rb_wide_lists.hip): the list table's idea for filters of 8193 to
-    // 32 256 bins, slots of wide_lines lines in the resident form.  A second object beside the list table: owned, guarded (row_mu) and dropped alike.
-    uint32_t *wide_table = nullptr;
-    uint64_t *wide_side = nullptr;
-    uint64_t wide_version = 0, wide_rows = 0, wide_bytes = 0, wide_side_bytes = 0;
-    uint32_t wide_lines = 0, wide_side_rows = 0, wide_side_cap = 0;
-    uint64_t wide_census_rows = 0, wide_census_over[3] = {0, 0, 0};
-    double wide_build_ms = 0.0, wide_alloc_s = 0.0;
-    uint32_t wide_refused = 0;            // RB_LIST_REFUSED_*, remembered as the list table's (wide_refusal_stands_locked)
-    uint64_t wide_refused_version = 0, wide_refused_max_bytes = 0;
-    uint32_t wide_builds = 0;
+    // 32 256 bins.  A second object beside the list table, and the same object on the host: one state (rb_list_tables.h) in two kinds
+    // (ListTableKind below), owned, guarded (row_mu) and dropped alike.
+    rbtables::ListTableState wide;
 };
 
 static void dibf_row_drop_locked(rb_dibf *f)
@@ -102,30 +88,15 @@ static void dibf_row_drop_locked(rb_dibf *f)
     f->row_rows = f->row_bytes = 0;
 }
 
-static void dibf_list_drop_locked(rb_dibf *f)
+// either list table of the filter (f->list, f->wide): the memory goes, what the state remembers of builds and refusals stays
+static void dibf_list_table_drop_locked(rb_dibf *f, rbtables::ListTableState &s)
 {
-    if (f->list_table || f->list_side) {
+    if (s.table || s.side) {
         (void)hipSetDevice(f->device);
-        if (f->list_table) (void)hipFree(f->list_table);  // (waits for the kernels that read it)
-        if (f->list_side) (void)hipFree(f->list_side);
+        if (s.table) (void)hipFree(s.table);  // (waits for the kernels that read it)
+        if (s.side) (void)hipFree(s.side);
     }
-    f->list_table = nullptr;
-    f->list_side = nullptr;
-    f->list_rows = f->list_bytes = f->list_side_bytes = 0;
-    f->list_lines = f->list_side_rows = f->list_side_cap = 0;
-}
-
-static void dibf_wide_drop_locked(rb_dibf *f)
-{
-    if (f->wide_table || f->wide_side) {
-        (void)hipSetDevice(f->device);
-        if (f->wide_table) (void)hipFree(f->wide_table);  // (waits for the kernels that read it)
-        if (f->wide_side) (void)hipFree(f->wide_side);
-    }
-    f->wide_table = nullptr;
-    f->wide_side = nullptr;
-    f->wide_rows = f->wide_bytes = f->wide_side_bytes = 0;
-    f->wide_lines = f->wide_side_rows = f->wide_side_cap = 0;
+    rbtables::clear_dropped(s);
 }
 
 // the one signal for "the bits of this filter are no longer what they were": engines measure its load again (cert_allowance), merged copies
@@ -135,8 +106,8 @@ static void dibf_changed(rb_dibf *f)
     f->version.fetch_add(1);
     std::lock_guard<std::mutex> lock(f->row_mu);
     dibf_row_drop_locked(f);
-    dibf_list_drop_locked(f);
-    dibf_wide_drop_locked(f);
+    dibf_list_table_drop_locked(f, f->list);
+    dibf_list_table_drop_locked(f, f->wide);
 }
 
 // Tables of 1 GiB and more are PLACED BY TRIAL: the same table allocated at another moment of one process gathers 1.7-2.9 % slower or
@@ -899,8 +870,8 @@ void rb_dibf_free(rb_dibf *f)
         (void)hipFree(f->d_words);
     }
     dibf_row_drop_locked(f);  // (nobody else holds a filter that is being freed)
-    dibf_list_drop_locked(f);
-    dibf_wide_drop_locked(f);
+    dibf_list_table_drop_locked(f, f->list);
+    dibf_list_table_drop_locked(f, f->wide);
     delete f;
 }
 
@@ -1526,45 +1497,20 @@ int rb_engine_set_row_table(rb_engine *e, int mode, uint64_t max_bytes)
     return RB_OK;
 }
 
-int rb_engine_set_pass_lists(rb_engine *e, int mode)
+// the six OFF / CURRENT / BUILD settings: an engine's five, and a slot set's own (rb_resume_set_lists).  field: null with a null handle
+static int set_lists_mode(rb_engine *e, int *field, int mode)
 {
     if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
     std::lock_guard<std::mutex> lock(e->mu);
-    e->pass_lists = mode;
+    *field = mode;
     return RB_OK;
 }
 
-int rb_engine_set_prefix_lists(rb_engine *e, int mode)
-{
-    if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
-    std::lock_guard<std::mutex> lock(e->mu);
-    e->prefix_lists = mode;
-    return RB_OK;
-}
-
-int rb_engine_set_wide_lists(rb_engine *e, int mode)
-{
-    if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
-    std::lock_guard<std::mutex> lock(e->mu);
-    e->wide_lists = mode;
-    return RB_OK;
-}
-
-int rb_engine_set_wide_pass_lists(rb_engine *e, int mode)
-{
-    if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
-    std::lock_guard<std::mutex> lock(e->mu);
-    e->wide_pass_lists = mode;
-    return RB_OK;
-}
-
-int rb_engine_set_wide_prefix_lists(rb_engine *e, int mode)
-{
-    if (!e || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
-    std::lock_guard<std::mutex> lock(e->mu);
-    e->wide_prefix_lists = mode;
-    return RB_OK;
-}
+int rb_engine_set_pass_lists(rb_engine *e, int mode) { return set_lists_mode(e, e ? &e->pass_lists : nullptr, mode); }
+int rb_engine_set_prefix_lists(rb_engine *e, int mode) { return set_lists_mode(e, e ? &e->prefix_lists : nullptr, mode); }
+int rb_engine_set_wide_lists(rb_engine *e, int mode) { return set_lists_mode(e, e ? &e->wide_lists : nullptr, mode); }
+int rb_engine_set_wide_pass_lists(rb_engine *e, int mode) { return set_lists_mode(e, e ? &e->wide_pass_lists : nullptr, mode); }
+int rb_engine_set_wide_prefix_lists(rb_engine *e, int mode) { return set_lists_mode(e, e ? &e->wide_prefix_lists : nullptr, mode); }
 
 // bytes of the row table of a filter (0: k too large for one)
 static uint64_t row_table_want_bytes(const rb_dibf *f)
@@ -1674,10 +1620,11 @@ int rb_dibf_row_table_download(rb_dibf *f, uint64_t *words, uint64_t n_words)
     return RB_OK;
 }
 
-// ---- the list table (rb_lists.h): census, slot size, build
-static std::atomic<uint32_t> g_list_side_capacity{0};
+// ---- the list table (rb_lists.h) and the wide list table (rb_wide_lists.h): census, slot size, build, refusals -- once, for a KIND
+static std::atomic<uint32_t> g_list_side_capacity{0}, g_wide_side_capacity{0};
 
 void rb_set_list_side_capacity(uint32_t rows) { g_list_side_capacity.store(rows); }
+void rb_set_wide_list_side_capacity(uint32_t rows) { g_wide_side_capacity.store(rows); }
 
 int rb_engine_set_list_min_dense_bytes(rb_engine *e, uint64_t bytes)
 {
@@ -1685,19 +1632,6 @@ int rb_engine_set_list_min_dense_bytes(rb_engine *e, uint64_t bytes)
     std::lock_guard<std::mutex> lock(e->mu);
     e->list_min_dense_bytes = bytes;
     return RB_OK;
-}
-
-static bool list_table_current_locked(const rb_dibf *f) { return f->list_table && f->list_version == f->version.load(); }
-
-// Does the last refusal still stand for a call that allows the table `max_bytes`?  Every refusal but the one of a capturing stream is
-// remembered for the version of the bits it was given for, so that neither a call nor rb_engine_plan takes the census again only to be
-// refused again: density and a full side table are properties of the bits; a table beyond max_bytes stays beyond it until the caller
-// allows more; want of memory stands until the bits change or rb_dibf_list_table_build / _drop is called (what the row table does).
-static bool list_refusal_stands_locked(const rb_dibf *f, uint64_t max_bytes)
-{
-    if (f->list_refused == RB_LIST_REFUSED_NONE || f->list_refused == RB_LIST_REFUSED_CAPTURE) return false;
-    if (f->list_refused_version != f->version.load()) return false;
-    return f->list_refused != RB_LIST_REFUSED_MAX_BYTES || max_bytes == f->list_refused_max_bytes;
 }
 
 // why a filter can have no list table whatever its bits (RB_LIST_REFUSED_NONE: it can)
@@ -1708,173 +1642,7 @@ static uint32_t list_table_geometry_refusal(const rb_dibf *f)
     return RB_LIST_REFUSED_NONE;
 }
 
-// Builds the table unless a current one exists.  RB_OK whether it was built or refused (f->list_refused says which); an error only where
-// the runtime fails.
-static int dibf_list_build(rb_dibf *f, uint64_t max_bytes)
-{
-    std::lock_guard<std::mutex> lock(f->row_mu);
-    if (list_table_current_locked(f)) return RB_OK;
-    dibf_list_drop_locked(f);  // stale
-    const uint64_t version = f->version.load();
-    f->list_refused_version = version;
-    f->list_refused_max_bytes = max_bytes;
-    f->list_refused = list_table_geometry_refusal(f);
-    if (f->list_refused) return RB_OK;
-    int st = check_device(f->device);
-    if (st != RB_OK) return st;
-    const uint64_t n_rows = 1ull << (2 * f->geo.kmer_size);
-    const auto t0 = std::chrono::steady_clock::now();
-    uint32_t *d_counters = nullptr;
-    uint32_t counters[4] = {0, 0, 0, 0};
-    RB_HIP(hipMalloc((void **)&d_counters, sizeof counters));
-    auto fail_hip = [&](hipError_t e, uint16_t *slots, uint64_t *side) {
-        (void)hipFree(d_counters);
-        if (slots) (void)hipFree(slots);
-        if (side) (void)hipFree(side);
-        return rb::fail(RB_ERR_HIP, std::string("list table: ") + hipGetErrorString(e));
-    };
-    // the census: how many of up to 2^16 rows, evenly spaced, overflow each slot size
-    const uint64_t step = std::max<uint64_t>(1, n_rows / rblist::kCensusRows);
-    hipError_t e = hipMemset(d_counters, 0, sizeof counters);
-    if (e == hipSuccess) e = launch_list_census(f->dev, d_counters, n_rows, step, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail_hip(e, nullptr, nullptr);
-    f->list_census_rows = (n_rows + step - 1) / step;
-    for (int i = 0; i < 3; ++i) f->list_census_over[i] = counters[1 + i];
-    const uint32_t lines = rblist::choose_lines(f->list_census_over, f->list_census_rows);
-    if (!lines) {
-        (void)hipFree(d_counters);
-        f->list_refused = RB_LIST_REFUSED_DENSITY;
-        return RB_OK;
-    }
-    const uint32_t cap_set = g_list_side_capacity.load();
-    const uint64_t side_cap = cap_set ? cap_set : rblist::side_capacity(n_rows);
-    const uint64_t bytes = n_rows * rblist::slot_bytes(lines), side_bytes = side_cap * f->stride * 8;
-    size_t free_b = 0, total_b = 0;
-    if (max_bytes && bytes + side_bytes > max_bytes) f->list_refused = RB_LIST_REFUSED_MAX_BYTES;
-    else if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + side_bytes > (uint64_t)free_b / 2) f->list_refused = RB_LIST_REFUSED_FREE;
-    if (f->list_refused) {
-        (void)hipGetLastError();
-        (void)hipFree(d_counters);
-        return RB_OK;
-    }
-    const auto t_alloc = std::chrono::steady_clock::now();
-    uint16_t *slots = nullptr;
-    uint64_t *side = nullptr;
-    if (hipMalloc((void **)&slots, bytes) != hipSuccess || hipMalloc((void **)&side, side_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        if (slots) (void)hipFree(slots);
-        (void)hipFree(d_counters);
-        f->list_refused = RB_LIST_REFUSED_ALLOC;
-        return RB_OK;
-    }
-    f->list_alloc_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc).count();
-    e = hipMemset(d_counters, 0, sizeof counters);
-    if (e == hipSuccess) e = launch_list_table(f->dev, slots, side, d_counters, n_rows, lines, (uint32_t)side_cap, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail_hip(e, slots, side);
-    (void)hipFree(d_counters);
-    f->list_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - f->list_alloc_s * 1e3;
-    if (counters[0] > side_cap) {  // rows were left unwritten: nothing is ever counted from such a table
-        (void)hipFree(slots);
-        (void)hipFree(side);
-        f->list_refused = RB_LIST_REFUSED_SIDE_FULL;
-        return RB_OK;
-    }
-    f->list_table = slots;
-    f->list_side = side;
-    f->list_rows = n_rows;
-    f->list_bytes = bytes;
-    f->list_side_bytes = side_bytes;
-    f->list_lines = lines;
-    f->list_side_rows = counters[0];
-    f->list_side_cap = (uint32_t)side_cap;
-    f->list_version = version;
-    f->list_builds += 1;
-    return RB_OK;
-}
-
-int rb_dibf_list_table_build(rb_dibf *f, uint64_t max_bytes)
-{
-    if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
-    return dibf_list_build(f, max_bytes);
-}
-
-int rb_dibf_list_table_drop(rb_dibf *f)
-{
-    if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
-    std::lock_guard<std::mutex> lock(f->row_mu);
-    dibf_list_drop_locked(f);
-    f->list_refused = RB_LIST_REFUSED_NONE;  // the next call may ask again
-    return RB_OK;
-}
-
-int rb_dibf_list_table_info(rb_dibf *f, rb_list_table_info *out)
-{
-    if (!f || !out) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(f->row_mu);
-    std::memset(out, 0, sizeof *out);
-    if (list_table_current_locked(f)) {
-        out->bytes = f->list_bytes;
-        out->rows = f->list_rows;
-        out->side_bytes = f->list_side_bytes;
-        out->lines = f->list_lines;
-        out->side_rows = f->list_side_rows;
-        out->side_capacity = f->list_side_cap;
-    }
-    out->refused = f->list_refused;
-    out->builds = f->list_builds;
-    out->stride_words = (uint32_t)f->stride;
-    out->census_rows = f->list_census_rows;
-    for (int i = 0; i < 3; ++i) out->census_over[i] = f->list_census_over[i];
-    out->build_ms = f->list_build_ms;
-    out->alloc_s = f->list_alloc_s;
-    return RB_OK;
-}
-
-int rb_dibf_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n_entries, uint64_t *side_words, uint64_t n_side_words)
-{
-    if (!f || (!entries && n_entries) || (!side_words && n_side_words)) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(f->row_mu);
-    if (!list_table_current_locked(f)) return rb::fail(RB_ERR_INVALID_ARG, "the filter has no current list table");
-    if (n_entries > f->list_bytes / 2) return rb::fail(RB_ERR_INVALID_ARG, "more entries than the list table holds");
-    if (n_side_words > (uint64_t)f->list_side_rows * f->stride) return rb::fail(RB_ERR_INVALID_ARG, "more words than the side table's rows in use hold");
-    int st = check_device(f->device);
-    if (st != RB_OK) return st;
-    if (n_entries) {
-        // the device holds the resident form (rb_lists.h): the whole slots that cover the prefix are copied -- no more than asked for,
-        // rounded up to a slot -- and come back as canonical slots, of which the prefix is handed out
-        const uint32_t lines = f->list_lines, cap = rblist::slot_entries(lines);
-        const uint64_t n_slots = (n_entries + cap - 1) / cap;
-        std::vector<uint32_t> resident(n_slots * (cap / 2));
-        RB_HIP(hipMemcpy(resident.data(), f->list_table, resident.size() * 4, hipMemcpyDeviceToHost));
-        uint16_t slot[rblist::kMaxLines * rblist::kEntriesPerLine];
-        for (uint64_t i = 0; i < n_slots; ++i) {
-            if (rblist::decode_resident(resident.data() + i * (cap / 2), lines, (uint32_t)f->geo.n_bins, slot) == -2)
-                return rb::fail(RB_ERR_HIP, "the device's list table holds a slot that no builder writes");
-            std::memcpy(entries + i * cap, slot, (size_t)std::min<uint64_t>(cap, n_entries - i * cap) * 2);
-        }
-    }
-    if (n_side_words) RB_HIP(hipMemcpy(side_words, f->list_side, n_side_words * 8, hipMemcpyDeviceToHost));
-    return RB_OK;
-}
-
-// ---- the wide list table (rb_wide_lists.h): the list table's census, slot size, build and refusals for filters of 8193 to 32 256 bins
-static std::atomic<uint32_t> g_wide_side_capacity{0};
-
-void rb_set_wide_list_side_capacity(uint32_t rows) { g_wide_side_capacity.store(rows); }
-
-static bool wide_table_current_locked(const rb_dibf *f) { return f->wide_table && f->wide_version == f->version.load(); }
-
-// (list_refusal_stands_locked for the wide table)
-static bool wide_refusal_stands_locked(const rb_dibf *f, uint64_t max_bytes)
-{
-    if (f->wide_refused == RB_LIST_REFUSED_NONE || f->wide_refused == RB_LIST_REFUSED_CAPTURE) return false;
-    if (f->wide_refused_version != f->version.load()) return false;
-    return f->wide_refused != RB_LIST_REFUSED_MAX_BYTES || max_bytes == f->wide_refused_max_bytes;
-}
-
-// why a filter can have no wide list table whatever its bits (RB_LIST_REFUSED_NONE: it can)
+// ... and no wide list table
 static uint32_t wide_table_geometry_refusal(const rb_dibf *f)
 {
     if (f->geo.kmer_size == 0 || f->geo.kmer_size > kRowTableMaxK) return RB_LIST_REFUSED_K;
@@ -1882,18 +1650,52 @@ static uint32_t wide_table_geometry_refusal(const rb_dibf *f)
     return RB_LIST_REFUSED_NONE;
 }
 
-// Builds the table unless a current one exists.  RB_OK whether it was built or refused (f->wide_refused says which); an error only where
-// the runtime fails.
-static int dibf_wide_build(rb_dibf *f, uint64_t max_bytes)
+// What tells the two tables apart on the host: everything else -- the state, the decision (rb_list_tables.h), drop, build, info, download
+// and the table a call takes -- is written once below and handed one of the two kinds.
+struct ListTableKind {
+    const char *name;  // in messages
+    uint32_t (*geometry_refusal)(const rb_dibf *);
+    uint32_t (*choose_lines)(const uint64_t over[3], uint64_t sampled);
+    uint64_t (*slot_bytes)(uint32_t lines);
+    uint32_t (*slot_entries)(uint32_t lines);
+    uint64_t (*side_capacity)(uint64_t n_rows);  // the default, and what rb_set_*_side_capacity puts in its place
+    std::atomic<uint32_t> *side_capacity_set;
+    hipError_t (*census)(const IbfDev &f, uint32_t *counters, uint64_t n_rows, uint64_t step, hipStream_t st);
+    hipError_t (*build)(const IbfDev &f, uint32_t *slots, uint64_t *side, uint32_t *counters, uint64_t n_rows, uint32_t lines, uint32_t side_cap, hipStream_t st);
+    int (*decode_resident)(const uint32_t *in, uint32_t lines, uint32_t n_bins, uint16_t *slot);
+    rbtables::ListTableState rb_dibf::*state;
+};
+
+static const ListTableKind kListKind = {
+    "list table", list_table_geometry_refusal, rblist::choose_lines, rblist::slot_bytes, rblist::slot_entries, rblist::side_capacity,
+    &g_list_side_capacity, launch_list_census,
+    [](const IbfDev &f, uint32_t *slots, uint64_t *side, uint32_t *counters, uint64_t n_rows, uint32_t lines, uint32_t side_cap, hipStream_t st) {
+        return launch_list_table(f, (uint16_t *)slots, side, counters, n_rows, lines, side_cap, st);
+    },
+    rblist::decode_resident, &rb_dibf::list};
+
+static const ListTableKind kWideKind = {
+    "wide list table", wide_table_geometry_refusal, rbwide::choose_lines, rbwide::slot_bytes, rbwide::slot_entries, rbwide::side_capacity,
+    &g_wide_side_capacity, launch_wide_list_census, launch_wide_list_table,
+    rbwide::decode_resident, &rb_dibf::wide};
+
+static bool list_table_current_locked(const ListTableKind &k, const rb_dibf *f) { return rbtables::current(f->*k.state, f->version.load()); }
+static bool list_refusal_stands_locked(const ListTableKind &k, const rb_dibf *f, uint64_t max_bytes) { return rbtables::refusal_stands(f->*k.state, f->version.load(), max_bytes); }
+
+// Builds the table unless a current one exists.  RB_OK whether it was built or refused (the state's `refused` says which); an error only
+// where the runtime fails.
+static int dibf_list_table_build(const ListTableKind &k, rb_dibf *f, uint64_t max_bytes)
 {
+    if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
     std::lock_guard<std::mutex> lock(f->row_mu);
-    if (wide_table_current_locked(f)) return RB_OK;
-    dibf_wide_drop_locked(f);  // stale
+    rbtables::ListTableState &s = f->*k.state;
+    if (list_table_current_locked(k, f)) return RB_OK;
+    dibf_list_table_drop_locked(f, s);  // stale
     const uint64_t version = f->version.load();
-    f->wide_refused_version = version;
-    f->wide_refused_max_bytes = max_bytes;
-    f->wide_refused = wide_table_geometry_refusal(f);
-    if (f->wide_refused) return RB_OK;
+    s.refused_version = version;
+    s.refused_max_bytes = max_bytes;
+    s.refused = k.geometry_refusal(f);
+    if (s.refused) return RB_OK;
     int st = check_device(f->device);
     if (st != RB_OK) return st;
     const uint64_t n_rows = 1ull << (2 * f->geo.kmer_size);
@@ -1905,29 +1707,29 @@ static int dibf_wide_build(rb_dibf *f, uint64_t max_bytes)
         (void)hipFree(d_counters);
         if (slots) (void)hipFree(slots);
         if (side) (void)hipFree(side);
-        return rb::fail(RB_ERR_HIP, std::string("wide list table: ") + hipGetErrorString(e));
+        return rb::fail(RB_ERR_HIP, std::string(k.name) + ": " + hipGetErrorString(e));
     };
     // the census: how many of up to 2^16 rows, evenly spaced, overflow each slot size
     const uint64_t step = std::max<uint64_t>(1, n_rows / rblist::kCensusRows);
     hipError_t e = hipMemset(d_counters, 0, sizeof counters);
-    if (e == hipSuccess) e = launch_wide_list_census(f->dev, d_counters, n_rows, step, nullptr);
+    if (e == hipSuccess) e = k.census(f->dev, d_counters, n_rows, step, nullptr);
     if (e == hipSuccess) e = hipMemcpy(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail_hip(e, nullptr, nullptr);
-    f->wide_census_rows = (n_rows + step - 1) / step;
-    for (int i = 0; i < 3; ++i) f->wide_census_over[i] = counters[1 + i];
-    const uint32_t lines = rbwide::choose_lines(f->wide_census_over, f->wide_census_rows);
+    s.census_rows = (n_rows + step - 1) / step;
+    for (int i = 0; i < 3; ++i) s.census_over[i] = counters[1 + i];
+    const uint32_t lines = k.choose_lines(s.census_over, s.census_rows);
     if (!lines) {
         (void)hipFree(d_counters);
-        f->wide_refused = RB_LIST_REFUSED_DENSITY;
+        s.refused = RB_LIST_REFUSED_DENSITY;
         return RB_OK;
     }
-    const uint32_t cap_set = g_wide_side_capacity.load();
-    const uint64_t side_cap = cap_set ? cap_set : rbwide::side_capacity(n_rows);
-    const uint64_t bytes = n_rows * rbwide::slot_bytes(lines), side_bytes = side_cap * f->stride * 8;
+    const uint32_t cap_set = k.side_capacity_set->load();
+    const uint64_t side_cap = cap_set ? cap_set : k.side_capacity(n_rows);
+    const uint64_t bytes = n_rows * k.slot_bytes(lines), side_bytes = side_cap * f->stride * 8;
     size_t free_b = 0, total_b = 0;
-    if (max_bytes && bytes + side_bytes > max_bytes) f->wide_refused = RB_LIST_REFUSED_MAX_BYTES;
-    else if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + side_bytes > (uint64_t)free_b / 2) f->wide_refused = RB_LIST_REFUSED_FREE;
-    if (f->wide_refused) {
+    if (max_bytes && bytes + side_bytes > max_bytes) s.refused = RB_LIST_REFUSED_MAX_BYTES;
+    else if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + side_bytes > (uint64_t)free_b / 2) s.refused = RB_LIST_REFUSED_FREE;
+    if (s.refused) {
         (void)hipGetLastError();
         (void)hipFree(d_counters);
         return RB_OK;
@@ -1939,97 +1741,117 @@ static int dibf_wide_build(rb_dibf *f, uint64_t max_bytes)
         (void)hipGetLastError();
         if (slots) (void)hipFree(slots);
         (void)hipFree(d_counters);
-        f->wide_refused = RB_LIST_REFUSED_ALLOC;
+        s.refused = RB_LIST_REFUSED_ALLOC;
         return RB_OK;
     }
-    f->wide_alloc_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc).count();
+    s.alloc_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc).count();
     e = hipMemset(d_counters, 0, sizeof counters);
-    if (e == hipSuccess) e = launch_wide_list_table(f->dev, slots, side, d_counters, n_rows, lines, (uint32_t)side_cap, nullptr);
+    if (e == hipSuccess) e = k.build(f->dev, slots, side, d_counters, n_rows, lines, (uint32_t)side_cap, nullptr);
     if (e == hipSuccess) e = hipMemcpy(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail_hip(e, slots, side);
     (void)hipFree(d_counters);
-    f->wide_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - f->wide_alloc_s * 1e3;
+    s.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - s.alloc_s * 1e3;
     if (counters[0] > side_cap) {  // rows were left unwritten: nothing is ever counted from such a table
         (void)hipFree(slots);
         (void)hipFree(side);
-        f->wide_refused = RB_LIST_REFUSED_SIDE_FULL;
+        s.refused = RB_LIST_REFUSED_SIDE_FULL;
         return RB_OK;
     }
-    f->wide_table = slots;
-    f->wide_side = side;
-    f->wide_rows = n_rows;
-    f->wide_bytes = bytes;
-    f->wide_side_bytes = side_bytes;
-    f->wide_lines = lines;
-    f->wide_side_rows = counters[0];
-    f->wide_side_cap = (uint32_t)side_cap;
-    f->wide_version = version;
-    f->wide_builds += 1;
+    s.table = slots;
+    s.side = side;
+    s.rows = n_rows;
+    s.bytes = bytes;
+    s.side_bytes = side_bytes;
+    s.lines = lines;
+    s.side_rows = counters[0];
+    s.side_cap = (uint32_t)side_cap;
+    s.version = version;
+    s.builds += 1;
     return RB_OK;
 }
 
-int rb_dibf_wide_list_table_build(rb_dibf *f, uint64_t max_bytes)
-{
-    if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
-    return dibf_wide_build(f, max_bytes);
-}
-
-int rb_dibf_wide_list_table_drop(rb_dibf *f)
+static int dibf_list_table_drop(const ListTableKind &k, rb_dibf *f)
 {
     if (!f) return rb::fail(RB_ERR_INVALID_ARG, "null filter");
     std::lock_guard<std::mutex> lock(f->row_mu);
-    dibf_wide_drop_locked(f);
-    f->wide_refused = RB_LIST_REFUSED_NONE;  // the next call may ask again
+    dibf_list_table_drop_locked(f, f->*k.state);
+    (f->*k.state).refused = RB_LIST_REFUSED_NONE;  // the next call may ask again
     return RB_OK;
 }
 
-int rb_dibf_wide_list_table_info(rb_dibf *f, rb_wide_list_table_info *out)
+// One fill for the two public structs: rb_wide_list_table_info is rb_list_table_info under another name, field for field.
+#define RB_SAME_FIELD(m)                                                                                   \
+    static_assert(offsetof(rb_list_table_info, m) == offsetof(rb_wide_list_table_info, m) &&               \
+                      sizeof(rb_list_table_info::m) == sizeof(rb_wide_list_table_info::m),                 \
+                  "rb_wide_list_table_info." #m " lies where rb_list_table_info." #m " does")
+static_assert(sizeof(rb_list_table_info) == sizeof(rb_wide_list_table_info), "the two info structs are one layout");
+RB_SAME_FIELD(bytes); RB_SAME_FIELD(rows); RB_SAME_FIELD(side_bytes); RB_SAME_FIELD(lines); RB_SAME_FIELD(side_rows);
+RB_SAME_FIELD(side_capacity); RB_SAME_FIELD(refused); RB_SAME_FIELD(builds); RB_SAME_FIELD(stride_words); RB_SAME_FIELD(census_rows);
+RB_SAME_FIELD(census_over); RB_SAME_FIELD(build_ms); RB_SAME_FIELD(alloc_s);
+#undef RB_SAME_FIELD
+
+static int dibf_list_table_info(const ListTableKind &k, rb_dibf *f, rb_list_table_info *out)
 {
     if (!f || !out) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> lock(f->row_mu);
+    const rbtables::ListTableState &s = f->*k.state;
     std::memset(out, 0, sizeof *out);
-    if (wide_table_current_locked(f)) {
-        out->bytes = f->wide_bytes;
-        out->rows = f->wide_rows;
-        out->side_bytes = f->wide_side_bytes;
-        out->lines = f->wide_lines;
-        out->side_rows = f->wide_side_rows;
-        out->side_capacity = f->wide_side_cap;
+    if (list_table_current_locked(k, f)) {
+        out->bytes = s.bytes;
+        out->rows = s.rows;
+        out->side_bytes = s.side_bytes;
+        out->lines = s.lines;
+        out->side_rows = s.side_rows;
+        out->side_capacity = s.side_cap;
     }
-    out->refused = f->wide_refused;
-    out->builds = f->wide_builds;
+    out->refused = s.refused;
+    out->builds = s.builds;
     out->stride_words = (uint32_t)f->stride;
-    out->census_rows = f->wide_census_rows;
-    for (int i = 0; i < 3; ++i) out->census_over[i] = f->wide_census_over[i];
-    out->build_ms = f->wide_build_ms;
-    out->alloc_s = f->wide_alloc_s;
+    out->census_rows = s.census_rows;
+    for (int i = 0; i < 3; ++i) out->census_over[i] = s.census_over[i];
+    out->build_ms = s.build_ms;
+    out->alloc_s = s.alloc_s;
     return RB_OK;
 }
 
-int rb_dibf_wide_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n_entries, uint64_t *side_words, uint64_t n_side_words)
+static int dibf_list_table_download(const ListTableKind &k, rb_dibf *f, uint16_t *entries, uint64_t n_entries, uint64_t *side_words, uint64_t n_side_words)
 {
     if (!f || (!entries && n_entries) || (!side_words && n_side_words)) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> lock(f->row_mu);
-    if (!wide_table_current_locked(f)) return rb::fail(RB_ERR_INVALID_ARG, "the filter has no current wide list table");
-    if (n_entries > f->wide_bytes / 2) return rb::fail(RB_ERR_INVALID_ARG, "more entries than the wide list table holds");
-    if (n_side_words > (uint64_t)f->wide_side_rows * f->stride) return rb::fail(RB_ERR_INVALID_ARG, "more words than the side table's rows in use hold");
+    const rbtables::ListTableState &s = f->*k.state;
+    const std::string name = k.name;
+    if (!list_table_current_locked(k, f)) return rb::fail(RB_ERR_INVALID_ARG, "the filter has no current " + name);
+    if (n_entries > s.bytes / 2) return rb::fail(RB_ERR_INVALID_ARG, "more entries than the " + name + " holds");
+    if (n_side_words > (uint64_t)s.side_rows * f->stride) return rb::fail(RB_ERR_INVALID_ARG, "more words than the side table's rows in use hold");
     int st = check_device(f->device);
     if (st != RB_OK) return st;
-    if (n_entries) {  // whole resident slots that cover the prefix, converted on the host (as rb_dibf_list_table_download)
-        const uint32_t lines = f->wide_lines, cap = rbwide::slot_entries(lines);
+    if (n_entries) {
+        // the device holds the resident form (rb_lists.h, rb_wide_lists.h): the whole slots that cover the prefix are copied -- no more than
+        // asked for, rounded up to a slot -- and come back as canonical slots, of which the prefix is handed out
+        const uint32_t lines = s.lines, cap = k.slot_entries(lines);
         const uint64_t n_slots = (n_entries + cap - 1) / cap;
         std::vector<uint32_t> resident(n_slots * (cap / 2));
-        RB_HIP(hipMemcpy(resident.data(), f->wide_table, resident.size() * 4, hipMemcpyDeviceToHost));
-        uint16_t slot[rbwide::kWideMaxLines * rblist::kEntriesPerLine];
+        RB_HIP(hipMemcpy(resident.data(), s.table, resident.size() * 4, hipMemcpyDeviceToHost));
+        uint16_t slot[std::max(rblist::kMaxLines, rbwide::kWideMaxLines) * rblist::kEntriesPerLine];  // (the largest slot of either kind)
         for (uint64_t i = 0; i < n_slots; ++i) {
-            if (rbwide::decode_resident(resident.data() + i * (cap / 2), lines, (uint32_t)f->geo.n_bins, slot) == -2)
-                return rb::fail(RB_ERR_HIP, "the device's wide list table holds a slot that no builder writes");
+            if (k.decode_resident(resident.data() + i * (cap / 2), lines, (uint32_t)f->geo.n_bins, slot) == -2)
+                return rb::fail(RB_ERR_HIP, "the device's " + name + " holds a slot that no builder writes");
             std::memcpy(entries + i * cap, slot, (size_t)std::min<uint64_t>(cap, n_entries - i * cap) * 2);
         }
     }
-    if (n_side_words) RB_HIP(hipMemcpy(side_words, f->wide_side, n_side_words * 8, hipMemcpyDeviceToHost));
+    if (n_side_words) RB_HIP(hipMemcpy(side_words, s.side, n_side_words * 8, hipMemcpyDeviceToHost));
     return RB_OK;
 }
+
+int rb_dibf_list_table_build(rb_dibf *f, uint64_t max_bytes) { return dibf_list_table_build(kListKind, f, max_bytes); }
+int rb_dibf_list_table_drop(rb_dibf *f) { return dibf_list_table_drop(kListKind, f); }
+int rb_dibf_list_table_info(rb_dibf *f, rb_list_table_info *out) { return dibf_list_table_info(kListKind, f, out); }
+int rb_dibf_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n, uint64_t *side_words, uint64_t n_side) { return dibf_list_table_download(kListKind, f, entries, n, side_words, n_side); }
+
+int rb_dibf_wide_list_table_build(rb_dibf *f, uint64_t max_bytes) { return dibf_list_table_build(kWideKind, f, max_bytes); }
+int rb_dibf_wide_list_table_drop(rb_dibf *f) { return dibf_list_table_drop(kWideKind, f); }
+int rb_dibf_wide_list_table_info(rb_dibf *f, rb_wide_list_table_info *out) { return dibf_list_table_info(kWideKind, f, reinterpret_cast<rb_list_table_info *>(out)); }
+int rb_dibf_wide_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n, uint64_t *side_words, uint64_t n_side) { return dibf_list_table_download(kWideKind, f, entries, n, side_words, n_side); }
 
 int rb_engine_set_cert_load(rb_engine *e, size_t filter_index, double load)
 {
@@ -2500,49 +2322,61 @@ static bool list_policy(const rb_engine *e, rb_dibf *f, const CountLaunch &a, si
         if (e->prune_trace) return false;
         if (row_table_want_bytes(f) <= e->list_min_dense_bytes) return false;
         std::lock_guard<std::mutex> lock(f->row_mu);
-        if (list_table_current_locked(f)) return true;
+        if (list_table_current_locked(kListKind, f)) return true;
         const uint64_t k = f->geo.kmer_size, h = f->geo.n_hash, L = (f->stride * 8 + rblist::kLineBytes - 1) / rblist::kLineBytes;
         const uint64_t kmers = max_len >= k ? max_len - k + 1 : 0;
         const uint64_t per_kmer = row_table_current_locked(f) ? L : L * h;
-        if (per_kmer <= rblist::kMaxLines) return false;
-        if ((uint64_t)n_reads * 2 * kmers * (per_kmer - rblist::kMaxLines) < n_rows * (L * h + rblist::kMaxLines)) return false;
+        if (!rbtables::repays(n_reads, kmers, per_kmer, rblist::kMaxLines, n_rows, L * h)) return false;
     }
     return true;
 }
 
-// ... and the table for such a launch: the filter's current one, built now when there is none and this version of the bits has not been
-// refused one already.  a.list_table stays null where there is none: the call goes on to the row table's rule.  Never under capture, as
-// the row table.
-static int list_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, CountLaunch &a, uint64_t *list_bytes)
+// What a call takes of a filter's list table of either kind: the launch structs of the two forms are filled from it
+struct ListTableTaken {
+    const uint32_t *slots = nullptr;
+    const uint64_t *side = nullptr;
+    uint32_t side_rows = 0, lines = 0;
+    uint64_t bytes = 0;
+};
+
+static void list_table_take_locked(const rbtables::ListTableState &s, ListTableTaken *t)
 {
-    *list_bytes = 0;
+    t->slots = s.table;
+    t->side = s.side;
+    t->side_rows = s.side_rows;
+    t->lines = s.lines;
+    t->bytes = s.bytes;
+}
+
+// the question alone (rb_engine_plan_pass and its like): the current table or nothing -- no stream, and nothing is built or dropped
+static void list_table_peek(const ListTableKind &k, rb_dibf *f, ListTableTaken *t)
+{
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (list_table_current_locked(k, f)) list_table_take_locked(f->*k.state, t);
+}
+
+// ... and the table for a launch that may count from one: the filter's current one, built now when there is none, the caller's side may
+// build (may_build: always on the classify path of the list table, where row_mode has decided; RB_PASS_LISTS_BUILD for the wide table and
+// for the passes) and this version of the bits has not been refused one already.  t->slots stays null where there is none: the call goes
+// on to the row table's rule or to the plain kernel.  Never under capture, as the row table.  What happens when is rbtables::table_call.
+static int list_table_for(const ListTableKind &k, rb_engine *e, rb_dibf *f, hipStream_t st, bool may_build, ListTableTaken *t)
+{
+    *t = ListTableTaken{};
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     const bool capturing = st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    auto take = [&]() {
-        a.list_table = f->list_table;
-        a.list_side = f->list_side;
-        a.list_side_rows = f->list_side_rows;
-        a.list_lines = f->list_lines;
-        *list_bytes = f->list_bytes;
-    };
+    rbtables::ListTableState &s = f->*k.state;
     {
         std::lock_guard<std::mutex> lock(f->row_mu);
-        const bool current = list_table_current_locked(f);
-        if (!current && !capturing) dibf_list_drop_locked(f);
-        if (capturing) {
-            if (!current) f->list_refused = RB_LIST_REFUSED_CAPTURE;
-            return RB_OK;
-        }
-        if (current) {
-            take();
-            return RB_OK;
-        }
-        if (list_refusal_stands_locked(f, e->row_max_bytes)) return RB_OK;
+        const rbtables::TableCall c = rbtables::table_call(list_table_current_locked(k, f), capturing, may_build,
+                                                           list_refusal_stands_locked(k, f, e->row_max_bytes));
+        if (c.record_capture) s.refused = RB_LIST_REFUSED_CAPTURE;
+        if (c.drop_stale) dibf_list_table_drop_locked(f, s);
+        if (c.take) list_table_take_locked(s, t);
+        if (!c.build) return RB_OK;
     }
-    int rc = dibf_list_build(f, e->row_max_bytes);
+    int rc = dibf_list_table_build(k, f, e->row_max_bytes);
     if (rc != RB_OK) return rc;
-    std::lock_guard<std::mutex> lock(f->row_mu);
-    if (list_table_current_locked(f)) take();
+    list_table_peek(k, f, t);
     return RB_OK;
 }
 
@@ -2552,19 +2386,18 @@ static int list_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, CountLaunch 
 // mode, no column shard -- and no trace asked for; a current table exists, or the setting is BUILD, this version of the bits was not
 // refused one, the smallest table fits max_bytes and the batch alone repays the build in 128-byte lines: a k-mer costs L x h lines today
 // (L lines per block) and at most 8 from a slot, the build reads 4^k x L x h lines and writes at most 4^k x 8.  Free memory and a
-// capturing stream are settled where the table is built (wide_table_for).
+// capturing stream are settled where the table is built (list_table_for).
 // The table's side of that, shared with locate and hits (wide_pass_lists_for), under the setting `mode` of the caller's side: a current
 // table, or BUILD with no standing refusal, max_bytes and the repay inequality for `n_items` items of at most max_len bases.
 static bool wide_table_admitted_locked(const rb_engine *e, const rb_dibf *f, int mode, size_t n_items, uint32_t max_len)
 {
-    if (wide_table_current_locked(f)) return true;
-    if (mode != RB_PASS_LISTS_BUILD || wide_refusal_stands_locked(f, e->row_max_bytes)) return false;
+    if (list_table_current_locked(kWideKind, f)) return true;
+    if (mode != RB_PASS_LISTS_BUILD || list_refusal_stands_locked(kWideKind, f, e->row_max_bytes)) return false;
     const uint64_t k = f->geo.kmer_size, h = f->geo.n_hash;
     const uint64_t n_rows = 1ull << (2 * k);
     if (n_rows * rbwide::slot_bytes(rbwide::kWideLines[0]) > e->row_max_bytes) return false;
     const uint64_t L = (f->stride * 8 + rblist::kLineBytes - 1) / rblist::kLineBytes, kmers = max_len >= k ? max_len - k + 1 : 0;
-    if (L * h <= rbwide::kWideMaxLines) return false;
-    return (uint64_t)n_items * 2 * kmers * (L * h - rbwide::kWideMaxLines) >= n_rows * (L * h + rbwide::kWideMaxLines);
+    return rbtables::repays(n_items, kmers, L * h, rbwide::kWideMaxLines, n_rows, L * h);
 }
 
 static bool wide_policy(const rb_engine *e, rb_dibf *f, const CountLaunch &a, size_t n_reads, uint32_t max_len)
@@ -2577,44 +2410,6 @@ static bool wide_policy(const rb_engine *e, rb_dibf *f, const CountLaunch &a, si
     if (e->filters.size() > 1 && n_reads <= e->split_threshold) return false;  // a micro-batch that is fused with other filters
     std::lock_guard<std::mutex> lock(f->row_mu);
     return wide_table_admitted_locked(e, f, e->wide_lists, n_reads, max_len);
-}
-
-// ... and the table for such a launch: the filter's current one, built now under BUILD when there is none.  w.slots stays null where
-// there is none: the call takes the plain kernel.  Never under capture, as the row table (the graph would keep an address that the next
-// change of the bits frees).  `mode`: the setting of the caller's side -- rb_engine_set_wide_lists for a classify call,
-// rb_engine_set_wide_pass_lists for locate and hits.
-static int wide_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, int mode, WideCountLaunch &w, uint64_t *wide_bytes)
-{
-    *wide_bytes = 0;
-    w.slots = nullptr;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    auto take = [&]() {
-        w.slots = f->wide_table;
-        w.side = f->wide_side;
-        w.side_rows = f->wide_side_rows;
-        w.lines = f->wide_lines;
-        *wide_bytes = f->wide_bytes;
-    };
-    {
-        std::lock_guard<std::mutex> lock(f->row_mu);
-        const bool current = wide_table_current_locked(f);
-        if (!current && !capturing) dibf_wide_drop_locked(f);
-        if (capturing) {
-            if (!current) f->wide_refused = RB_LIST_REFUSED_CAPTURE;
-            return RB_OK;
-        }
-        if (current) {
-            take();
-            return RB_OK;
-        }
-        if (mode != RB_PASS_LISTS_BUILD || wide_refusal_stands_locked(f, e->row_max_bytes)) return RB_OK;
-    }
-    int rc = dibf_wide_build(f, e->row_max_bytes);
-    if (rc != RB_OK) return rc;
-    std::lock_guard<std::mutex> lock(f->row_mu);
-    if (wide_table_current_locked(f)) take();
-    return RB_OK;
 }
 
 static int ensure_split_ws(rb_engine *e, CountLaunch &a, size_t n_filters, hipStream_t st);
@@ -3104,6 +2899,14 @@ static void fill_plain_launch(const rb_engine *e, size_t fi, const PassInput &in
     a->fi = (uint32_t)fi;
 }
 
+// The table of either kind for a query pass under the setting `mode` (CURRENT or BUILD) of the caller's side.  asking: the question alone.
+static int pass_table_for(const ListTableKind &k, rb_engine *e, rb_dibf *f, hipStream_t st, bool asking, int mode, ListTableTaken *t)
+{
+    if (!asking) return list_table_for(k, e, f, st, mode == RB_PASS_LISTS_BUILD, t);
+    list_table_peek(k, f, t);
+    return RB_OK;
+}
+
 // May locate and hits take this filter's LIST table for the launch `a` (rb_engine_set_pass_lists)?  Per filter, so an engine may mix the
 // two forms: the setting allows it, the list form serves the launch's geometry and the call's max_len (pass_list_form_serves: what the
 // count path's list form serves, one column slice among it), the engine is no column shard, the stream is not being captured (a graph
@@ -3120,28 +2923,15 @@ static int lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, int m
     if (mode == RB_PASS_LISTS_OFF || e->shard_world != 1 || !pass_list_form_serves(*a)) return RB_OK;
     rb_dibf *f = e->filters[fi];
     if (list_table_geometry_refusal(f)) return RB_OK;
-    uint64_t list_bytes = 0;
-    CountLaunch got{};
-    if (mode == RB_PASS_LISTS_BUILD && !asking) {
-        const int rc = list_table_for(e, f, st, got, &list_bytes);
-        if (rc != RB_OK) return rc;
-    } else {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (!asking && st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return RB_OK;
-        std::lock_guard<std::mutex> lock(f->row_mu);
-        if (!list_table_current_locked(f)) return RB_OK;
-        got.list_table = f->list_table;
-        got.list_side = f->list_side;
-        got.list_side_rows = f->list_side_rows;
-        got.list_lines = f->list_lines;
-        list_bytes = f->list_bytes;
-    }
-    if (!got.list_table || !got.list_side) return RB_OK;
-    a->list_table = got.list_table;
-    a->list_side = got.list_side;
-    a->list_side_rows = got.list_side_rows;
-    a->list_lines = got.list_lines;
-    a->list_nt = list_bytes > e->nt_threshold_bytes;
+    ListTableTaken got;
+    const int rc = pass_table_for(kListKind, e, f, st, asking, mode, &got);
+    if (rc != RB_OK) return rc;
+    if (!got.slots || !got.side) return RB_OK;
+    a->list_table = (const uint16_t *)got.slots;
+    a->list_side = got.side;
+    a->list_side_rows = got.side_rows;
+    a->list_lines = got.lines;
+    a->list_nt = got.bytes > e->nt_threshold_bytes;
     return RB_OK;
 }
 static int pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, PlainPassLaunch *a)
@@ -3152,7 +2942,7 @@ static int pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, 
 // May locate and hits take this filter's WIDE list table for the launch `a` (rb_engine_set_wide_pass_lists)?  Per filter and per call, as
 // pass_lists_for, and a setting of its own: the mode allows it, wide_form_serves holds for the call's max_len, the engine is no column
 // shard, the stream is not being captured, and the filter has a wide table of the present version of its bits -- under
-// RB_PASS_LISTS_BUILD built now through wide_table_for, by the rules a classify call has (wide_table_admitted_locked with this call's
+// RB_PASS_LISTS_BUILD built now through list_table_for, by the rules a classify call has (wide_table_admitted_locked with this call's
 // items and max_len: remembered refusals, max_bytes, the repay inequality; half of the free memory where it is built), whose refusals
 // mean the plain form.  a->wide_table stays null wherever the answer is no.  asking: the question alone (rb_engine_wide_pass_lines) --
 // no stream, and nothing is built or dropped, so BUILD reports the table once it stands.
@@ -3167,30 +2957,19 @@ static int wide_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, 
     if (mode == RB_PASS_LISTS_OFF || e->shard_world != 1 || !wide_form_serves(a->f, a->src.max_len)) return RB_OK;
     rb_dibf *f = e->filters[fi];
     if (wide_table_geometry_refusal(f) || a->col_begin != 0 || a->col_end != a->f.bin_width) return RB_OK;
-    WideCountLaunch got{};
-    uint64_t wide_bytes = 0;
-    if (asking) {
+    if (!asking) {
         std::lock_guard<std::mutex> lock(f->row_mu);
-        if (!wide_table_current_locked(f)) return RB_OK;
-        got.slots = f->wide_table;
-        got.side = f->wide_side;
-        got.side_rows = f->wide_side_rows;
-        got.lines = f->wide_lines;
-        wide_bytes = f->wide_bytes;
-    } else {
-        {
-            std::lock_guard<std::mutex> lock(f->row_mu);
-            if (!wide_table_admitted_locked(e, f, mode, n_items, a->src.max_len)) return RB_OK;
-        }
-        const int rc = wide_table_for(e, f, st, mode, got, &wide_bytes);
-        if (rc != RB_OK) return rc;
+        if (!wide_table_admitted_locked(e, f, mode, n_items, a->src.max_len)) return RB_OK;
     }
+    ListTableTaken got;
+    const int rc = pass_table_for(kWideKind, e, f, st, asking, mode, &got);
+    if (rc != RB_OK) return rc;
     if (!got.slots || !got.side) return RB_OK;
     a->wide_table = got.slots;
     a->wide_side = got.side;
     a->wide_side_rows = got.side_rows;
     a->wide_lines = got.lines;
-    a->wide_nt = wide_bytes > e->nt_threshold_bytes;
+    a->wide_nt = got.bytes > e->nt_threshold_bytes;
     return RB_OK;
 }
 static int wide_pass_lists_for(rb_engine *e, size_t fi, hipStream_t st, bool asking, size_t n_items, PlainPassLaunch *a)
@@ -3412,27 +3191,37 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
         // whose size -- not the filter's -- says whether they are non-temporal
         // the wide list form (off by default): the whole filter in one launch, whatever column slices the plain kernel would take
         if (e->wide_lists != RB_PASS_LISTS_OFF && wide_policy(e, e->filters[fi], a, n_reads, max_len)) {
-            WideCountLaunch w{};
-            uint64_t wide_bytes = 0;
-            if ((rc = wide_table_for(e, e->filters[fi], fs, e->wide_lists, w, &wide_bytes)) != RB_OK) return rc;
-            if (w.slots) {
+            ListTableTaken t;
+            if ((rc = list_table_for(kWideKind, e, e->filters[fi], fs, e->wide_lists == RB_PASS_LISTS_BUILD, &t)) != RB_OK) return rc;
+            if (t.slots) {
                 fold_ok = false;
+                WideCountLaunch w{};
+                w.slots = t.slots;
+                w.side = t.side;
+                w.side_rows = t.side_rows;
+                w.lines = t.lines;
                 w.f = a.f;
                 w.src = a.src;
                 w.src.max_len = max_len;
                 w.n_reads = a.n_reads;
                 w.out = maxcount + fi;
                 w.out_read_stride = (uint32_t)nf;
-                w.nt = wide_bytes > e->nt_threshold_bytes;
+                w.nt = t.bytes > e->nt_threshold_bytes;
                 w.bound_prune = a.bound_prune;
                 RB_HIP(launch_ibf_count_wide_lists(w, fs));
                 continue;
             }
         }
         if (list_policy(e, e->filters[fi], a, n_reads, max_len)) {  // the list table before the dense one; refused: on to the row rule
-            uint64_t list_bytes = 0;
-            if ((rc = list_table_for(e, e->filters[fi], fs, a, &list_bytes)) != RB_OK) return rc;
-            if (a.list_table) a.nt = list_bytes > e->nt_threshold_bytes;
+            ListTableTaken t;
+            if ((rc = list_table_for(kListKind, e, e->filters[fi], fs, true, &t)) != RB_OK) return rc;
+            if (t.slots) {
+                a.list_table = (const uint16_t *)t.slots;
+                a.list_side = t.side;
+                a.list_side_rows = t.side_rows;
+                a.list_lines = t.lines;
+                a.nt = t.bytes > e->nt_threshold_bytes;
+            }
         }
         if (!a.list_table && row_policy(e, f, a, n_reads, max_len)) {
             uint64_t row_bytes = 0;
@@ -3565,7 +3354,7 @@ extern "C" int rb_engine_plan(rb_engine *e, size_t filter_index, size_t n_reads,
         std::lock_guard<std::mutex> rows_lock(fm->row_mu);
         lists_planned = true;
         form = "ibf_count_wide_lists_kernel";
-        out->row_table_bytes = wide_table_current_locked(fm) ? fm->wide_bytes : (1ull << (2 * fm->geo.kmer_size)) * rbwide::slot_bytes(6);
+        out->row_table_bytes = list_table_current_locked(kWideKind, fm) ? fm->wide.bytes : (1ull << (2 * fm->geo.kmer_size)) * rbwide::slot_bytes(6);
         out->nontemporal = out->row_table_bytes > e->nt_threshold_bytes ? 1u : 0u;
         out->column_slices = 1;
     }
@@ -3573,12 +3362,12 @@ extern "C" int rb_engine_plan(rb_engine *e, size_t filter_index, size_t n_reads,
         // the list form, when the filter has its table or the call could build it: not where this version of the bits was refused one
         rb_dibf *fm = e->filters[filter_index];
         std::lock_guard<std::mutex> rows_lock(fm->row_mu);
-        const bool current = list_table_current_locked(fm);
-        if (current || !list_refusal_stands_locked(fm, e->row_max_bytes)) {  // (what list_table_for asks before it builds)
+        const bool current = list_table_current_locked(kListKind, fm);
+        if (current || !list_refusal_stands_locked(kListKind, fm, e->row_max_bytes)) {  // (what list_table_for asks before it builds)
             lists_planned = true;
             form = "ibf_count_lists_kernel";
             // (before the census: two lines per slot, what a filter at its design load gets)
-            out->row_table_bytes = current ? fm->list_bytes : (1ull << (2 * fm->geo.kmer_size)) * rblist::slot_bytes(2);
+            out->row_table_bytes = current ? fm->list.bytes : (1ull << (2 * fm->geo.kmer_size)) * rblist::slot_bytes(2);
             out->nontemporal = out->row_table_bytes > e->nt_threshold_bytes ? 1u : 0u;
         }
     }
@@ -3703,8 +3492,8 @@ extern "C" int rb_engine_wide_prefix_lines(rb_engine *e, size_t filter_index, ui
 }
 
 // The items the list form of the prefix pass took and left since the last reset, over the calls in which some filter was list-served
-// (their prep kernel counts them on the device).  Waits for the engine's own stream.
-extern "C" int rb_engine_prefix_lists_items(rb_engine *e, uint64_t *listed, uint64_t *plain, int reset)
+// (their prep kernel counts them on the device).  Waits for the engine's own stream.  items: the form's pair of counters
+static int prefix_items_read(rb_engine *e, DevBuf rb_engine::*items, uint64_t *listed, uint64_t *plain, int reset)
 {
     if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
     const int rc = check_device(e->device);
@@ -3712,32 +3501,17 @@ extern "C" int rb_engine_prefix_lists_items(rb_engine *e, uint64_t *listed, uint
     std::lock_guard<std::mutex> lock(e->mu);
     uint64_t got[2] = {0, 0};
     RB_HIP(hipStreamSynchronize(e->stream));
-    if (e->d_prefix_items.p) {
-        RB_HIP(hipMemcpy(got, e->d_prefix_items.p, sizeof got, hipMemcpyDeviceToHost));
-        if (reset) RB_HIP(hipMemset(e->d_prefix_items.p, 0, sizeof got));
+    if ((e->*items).p) {
+        RB_HIP(hipMemcpy(got, (e->*items).p, sizeof got, hipMemcpyDeviceToHost));
+        if (reset) RB_HIP(hipMemset((e->*items).p, 0, sizeof got));
     }
     if (listed) *listed = got[0];
     if (plain) *plain = got[1];
     return RB_OK;
 }
-
+extern "C" int rb_engine_prefix_lists_items(rb_engine *e, uint64_t *listed, uint64_t *plain, int reset) { return prefix_items_read(e, &rb_engine::d_prefix_items, listed, plain, reset); }
 // ... and the wide list form's pair, counters of its own: over the calls in which some filter was wide-served.
-extern "C" int rb_engine_wide_prefix_lists_items(rb_engine *e, uint64_t *listed, uint64_t *plain, int reset)
-{
-    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
-    const int rc = check_device(e->device);
-    if (rc != RB_OK) return rc;
-    std::lock_guard<std::mutex> lock(e->mu);
-    uint64_t got[2] = {0, 0};
-    RB_HIP(hipStreamSynchronize(e->stream));
-    if (e->d_wide_prefix_items.p) {
-        RB_HIP(hipMemcpy(got, e->d_wide_prefix_items.p, sizeof got, hipMemcpyDeviceToHost));
-        if (reset) RB_HIP(hipMemset(e->d_wide_prefix_items.p, 0, sizeof got));
-    }
-    if (listed) *listed = got[0];
-    if (plain) *plain = got[1];
-    return RB_OK;
-}
+extern "C" int rb_engine_wide_prefix_lists_items(rb_engine *e, uint64_t *listed, uint64_t *plain, int reset) { return prefix_items_read(e, &rb_engine::d_wide_prefix_items, listed, plain, reset); }
 
 // Fits the windows of the clock-phased gathers to THIS device: the planner's table was measured on one box;
 // clocks, firmware and compilers move the optima.  For every table the engine would serve with the phased form on a batch of
@@ -4378,9 +4152,17 @@ int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32
         if ((rc = wide_lists_for(e, fi, c.st, false, e->wide_prefix_lists, n_items, &a)) != RB_OK) return rc;
         max_slices = std::max(max_slices, a.n_slices);
     }
-    const bool any_lists = std::any_of(launches.begin(), launches.end(), [](const PrefixLaunch &a) { return a.list_table != nullptr; });
-    // ... and the wide form's share, whose take rule is another (no look at the bases): a call with filters of both kinds keeps two
-    const bool any_wide = std::any_of(launches.begin(), launches.end(), [](const PrefixLaunch &a) { return a.wide_table != nullptr; });
+    // The list forms' shares of the call: which items a form's kernels take is decided once, for every filter, by the form's prep kernel,
+    // which also counts them (two counters per form, zero from their first call on).  The wide form's take rule is another (no look at the
+    // bases), so a call with filters of both kinds keeps two shares.
+    struct Share {
+        bool any;
+        DevBuf *items;
+        hipError_t (*prep)(const PrefixListsPrep &, hipStream_t);
+        size_t o_taken = 0, o_plain = 0;
+    } shares[2] = {
+        {std::any_of(launches.begin(), launches.end(), [](const PrefixLaunch &a) { return a.list_table != nullptr; }), &e->d_prefix_items, launch_prefix_lists_prep},
+        {std::any_of(launches.begin(), launches.end(), [](const PrefixLaunch &a) { return a.wide_table != nullptr; }), &e->d_wide_prefix_items, launch_wide_prefix_lists_prep}};
     // workspace: the partial maxima u16[max_slices][n_items][P] and the rows' pre-status, and the outputs a later stage reads where the
     // caller left them out
     const bool decides = d_out->decision || d_out->best_target || d_out->status || d_out->first_decided;
@@ -4389,39 +4171,27 @@ int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32
     const size_t o_len = lay.take(d_out->prefix_len ? 0 : rows * 4), o_max = lay.take(d_out->max_count ? 0 : rows * nf * 2);
     const size_t o_dec = lay.take(d_out->first_decided && !d_out->decision ? rows : 0);
     const size_t o_st = lay.take(d_out->first_decided && !d_out->status ? rows : 0);
-    const size_t o_taken = lay.take(any_lists ? n_items : 0), o_plain = lay.take(any_lists ? n_items * 4 : 0);
-    const size_t o_wtaken = lay.take(any_wide ? n_items : 0), o_wplain = lay.take(any_wide ? n_items * 4 : 0);
-    if (any_wide && !e->d_wide_prefix_items.p) {
-        if ((rc = e->d_wide_prefix_items.ensure(16)) != RB_OK) return rc;
-        RB_HIP(hipMemsetAsync(e->d_wide_prefix_items.p, 0, 16, c.st));
-    }
-    if (any_lists && !e->d_prefix_items.p) {  // the two counters, zero from their first call on
-        if ((rc = e->d_prefix_items.ensure(16)) != RB_OK) return rc;
-        RB_HIP(hipMemsetAsync(e->d_prefix_items.p, 0, 16, c.st));
+    for (Share &s : shares) {
+        s.o_taken = lay.take(s.any ? n_items : 0);
+        s.o_plain = lay.take(s.any ? n_items * 4 : 0);
+        if (s.any && !s.items->p) {
+            if ((rc = s.items->ensure(16)) != RB_OK) return rc;
+            RB_HIP(hipMemsetAsync(s.items->p, 0, 16, c.st));
+        }
     }
     if ((rc = c.start(lay.bytes())) != RB_OK) return rc;
     char *ws = c.ws();
-    if (any_lists) {  // which items the list kernels take: once, for every filter
+    for (const Share &s : shares) {
+        if (!s.any) continue;
         PrefixListsPrep p{};
         p.src = c.in.src;
         p.n_items = (uint32_t)n_items;
         p.pre_status = c.in.d_pre_status;
         p.c_last = prefix_lens[P - 1];
-        p.taken = (uint8_t *)(ws + o_taken);
-        p.plain_lens = (uint32_t *)(ws + o_plain);
-        p.counters = (uint64_t *)e->d_prefix_items.p;
-        RB_HIP(launch_prefix_lists_prep(p, c.st));
-    }
-    if (any_wide) {  // ... and the wide kernels
-        PrefixListsPrep p{};
-        p.src = c.in.src;
-        p.n_items = (uint32_t)n_items;
-        p.pre_status = c.in.d_pre_status;
-        p.c_last = prefix_lens[P - 1];
-        p.taken = (uint8_t *)(ws + o_wtaken);
-        p.plain_lens = (uint32_t *)(ws + o_wplain);
-        p.counters = (uint64_t *)e->d_wide_prefix_items.p;
-        RB_HIP(launch_wide_prefix_lists_prep(p, c.st));
+        p.taken = (uint8_t *)(ws + s.o_taken);
+        p.plain_lens = (uint32_t *)(ws + s.o_plain);
+        p.counters = (uint64_t *)s.items->p;
+        RB_HIP(s.prep(p, c.st));
     }
     uint16_t *part = (uint16_t *)(ws + o_part);
     uint32_t *row_len = d_out->prefix_len ? (uint32_t *)d_out->prefix_len : (uint32_t *)(ws + o_len);
@@ -4433,13 +4203,10 @@ int rb_prefix_batch_device(rb_engine *e, const rb_batch_desc *desc, const uint32
     for (size_t fi = 0; fi < nf; ++fi) {
         PrefixLaunch &a = launches[fi];
         a.part = part;
-        if (a.list_table) {
-            a.list_taken = (const uint8_t *)(ws + o_taken);
-            a.list_plain_lens = (const uint32_t *)(ws + o_plain);
-        }
-        if (a.wide_table) {
-            a.list_taken = (const uint8_t *)(ws + o_wtaken);
-            a.list_plain_lens = (const uint32_t *)(ws + o_wplain);
+        if (a.list_table || a.wide_table) {  // (a filter has one table or the other: their bin counts do not meet)
+            const Share &s = shares[a.wide_table ? 1 : 0];
+            a.list_taken = (const uint8_t *)(ws + s.o_taken);
+            a.list_plain_lens = (const uint32_t *)(ws + s.o_plain);
         }
         RB_HIP(a.wide_table ? launch_ibf_prefix_wide_lists(a, c.st) : a.list_table ? launch_ibf_prefix_lists(a, c.st) : launch_ibf_prefix(a, c.st));
         RB_HIP(launch_finish_prefix(a, c.in.d_lens, c.in.d_pre_status, max_count, row_len, row_pre, c.st));
@@ -4563,13 +4330,7 @@ static int resume_lists_for(rb_resume *r, size_t fi, const PassInput &in, const 
     return lists_for(r->e, fi, st, asking, r->lists, a);
 }
 
-int rb_resume_set_lists(rb_resume *r, int mode)
-{
-    if (!r || mode < RB_PASS_LISTS_OFF || mode > RB_PASS_LISTS_BUILD) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (current) or 2 (build)");
-    std::lock_guard<std::mutex> lock(r->e->mu);
-    r->lists = mode;
-    return RB_OK;
-}
+int rb_resume_set_lists(rb_resume *r, int mode) { return set_lists_mode(r ? r->e : nullptr, r ? &r->lists : nullptr, mode); }
 
 int rb_resume_plan(rb_resume *r, size_t filter_index, rb_resume_plan_info *out)
 {

@@ -1295,6 +1295,16 @@ static int run_program(ConfigReader& config, const IngestOptions& opt, const std
     return 2;
 }
 
+// the value of an off|current|build option (RB_PASS_LISTS_*); false: none of the three
+static bool lists_mode_arg(const char* v, int* out)
+{
+    if (!std::strcmp(v, "off")) *out = RB_PASS_LISTS_OFF;
+    else if (!std::strcmp(v, "current")) *out = RB_PASS_LISTS_CURRENT;
+    else if (!std::strcmp(v, "build")) *out = RB_PASS_LISTS_BUILD;
+    else return false;
+    return true;
+}
+
 int main(int argc, char const* argv[])
 {
     std::string config_path;
@@ -1346,55 +1356,35 @@ int main(int argc, char const* argv[])
             ++i;
         }
         else if (!std::strcmp(argv[i], "--pass-lists")) {
-            const char* v = i + 1 < argc ? argv[i + 1] : "";
-            if (!std::strcmp(v, "off")) opt.pass_lists = RB_PASS_LISTS_OFF;
-            else if (!std::strcmp(v, "current")) opt.pass_lists = RB_PASS_LISTS_CURRENT;
-            else if (!std::strcmp(v, "build")) opt.pass_lists = RB_PASS_LISTS_BUILD;
-            else {
+            if (!lists_mode_arg(i + 1 < argc ? argv[i + 1] : "", &opt.pass_lists)) {
                 std::cerr << "ERROR: --pass-lists off|current|build" << std::endl;
                 return 1;
             }
             ++i;
         }
         else if (!std::strcmp(argv[i], "--wide-prefix-lists")) {
-            const char* v = i + 1 < argc ? argv[i + 1] : "";
-            if (!std::strcmp(v, "off")) opt.wide_prefix_lists = RB_PASS_LISTS_OFF;
-            else if (!std::strcmp(v, "current")) opt.wide_prefix_lists = RB_PASS_LISTS_CURRENT;
-            else if (!std::strcmp(v, "build")) opt.wide_prefix_lists = RB_PASS_LISTS_BUILD;
-            else {
+            if (!lists_mode_arg(i + 1 < argc ? argv[i + 1] : "", &opt.wide_prefix_lists)) {
                 std::cerr << "ERROR: --wide-prefix-lists off|current|build" << std::endl;
                 return 1;
             }
             ++i;
         }
         else if (!std::strcmp(argv[i], "--prefix-lists")) {
-            const char* v = i + 1 < argc ? argv[i + 1] : "";
-            if (!std::strcmp(v, "off")) opt.prefix_lists = RB_PASS_LISTS_OFF;
-            else if (!std::strcmp(v, "current")) opt.prefix_lists = RB_PASS_LISTS_CURRENT;
-            else if (!std::strcmp(v, "build")) opt.prefix_lists = RB_PASS_LISTS_BUILD;
-            else {
+            if (!lists_mode_arg(i + 1 < argc ? argv[i + 1] : "", &opt.prefix_lists)) {
                 std::cerr << "ERROR: --prefix-lists off|current|build" << std::endl;
                 return 1;
             }
             ++i;
         }
         else if (!std::strcmp(argv[i], "--wide-lists")) {
-            const char* v = i + 1 < argc ? argv[i + 1] : "";
-            if (!std::strcmp(v, "off")) opt.wide_lists = RB_PASS_LISTS_OFF;
-            else if (!std::strcmp(v, "current")) opt.wide_lists = RB_PASS_LISTS_CURRENT;
-            else if (!std::strcmp(v, "build")) opt.wide_lists = RB_PASS_LISTS_BUILD;
-            else {
+            if (!lists_mode_arg(i + 1 < argc ? argv[i + 1] : "", &opt.wide_lists)) {
                 std::cerr << "ERROR: --wide-lists off|current|build" << std::endl;
                 return 1;
             }
             ++i;
         }
         else if (!std::strcmp(argv[i], "--wide-pass-lists")) {
-            const char* v = i + 1 < argc ? argv[i + 1] : "";
-            if (!std::strcmp(v, "off")) opt.wide_pass_lists = RB_PASS_LISTS_OFF;
-            else if (!std::strcmp(v, "current")) opt.wide_pass_lists = RB_PASS_LISTS_CURRENT;
-            else if (!std::strcmp(v, "build")) opt.wide_pass_lists = RB_PASS_LISTS_BUILD;
-            else {
+            if (!lists_mode_arg(i + 1 < argc ? argv[i + 1] : "", &opt.wide_pass_lists)) {
                 std::cerr << "ERROR: --wide-pass-lists off|current|build" << std::endl;
                 return 1;
             }

@@ -198,6 +198,38 @@ def test_off_and_current_never_build_and_build_builds_once(small):
     d.free()
 
 
+def test_an_insert_drops_the_table_and_the_next_call_rebuilds_it(small):
+    """the list table's test of this name (tests/test_gpu_row_lists.py), for the wide table: both go through one drop and one build"""
+    c, batch, ref = small
+    d = upload(c.o)
+    bld, cur = engine([d], BUILD), engine([d], CURRENT)
+    check(bld, batch, ref, "before the insert", WIDE_KERNEL, repeats=1)
+    info = d.wide_list_table_info()
+    assert info["builds"] == 1 and info["bytes"] == 4 ** K * info["lines"] * 128 and info["refused"] == capi.RB_LIST_REFUSED_NONE, info
+    read = WR.random_dna(np.random.default_rng(6), 300)
+    d.insert(read, [0], [len(read)], [8191])
+    info = d.wide_list_table_info()
+    assert info["bytes"] == 0 and info["rows"] == 0 and info["builds"] == 1, info  # the table went with the bits it was built from
+    rng = np.random.default_rng(44)
+    batch2 = H.pack_reads([read, WR.revcomp(read)] + c.n_reads() + [WR.random_dna(rng, 400) for _ in range(48)])
+    after = RT.reference(RT.oracle_view(d), batch2)
+    assert after[0][0, 0] == after[0][1, 0] == len(read) - K + 1  # the changed filter: every k-mer of the inserted sequence, on both strands
+    n2, max_len2 = len(batch2[2]), int(batch2[2].max())
+    plain = engine([d], OFF)
+    want = plain.plan(0, n2, max_len2)["kernel"]
+    plain.destroy()
+    assert want != WIDE_KERNEL
+    check(cur, batch2, after, "current, after the insert", want, repeats=1)  # CURRENT takes the plain kernel and builds nothing
+    info = d.wide_list_table_info()
+    assert info["builds"] == 1 and info["bytes"] == 0, info
+    check(bld, batch2, after, "build, after the insert", WIDE_KERNEL, repeats=1)
+    info = d.wide_list_table_info()
+    assert info["builds"] == 2 and info["refused"] == capi.RB_LIST_REFUSED_NONE and info["bytes"] == 4 ** K * info["lines"] * 128, info
+    check(cur, batch2, after, "current, with the new table", WIDE_KERNEL, repeats=1)
+    assert d.wide_list_table_info()["builds"] == 2
+    bld.destroy(), cur.destroy(), d.free()
+
+
 def test_a_batch_that_does_not_repay_the_build_and_a_trace_take_the_plain_kernel(small):
     torch = pytest.importorskip("torch")
     c, batch, ref = small
