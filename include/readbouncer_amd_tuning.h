@@ -469,6 +469,54 @@ RB_API int rb_engine_set_list_min_dense_bytes(rb_engine *e, uint64_t bytes);
 /* rows of the side table of list tables built from now on (process-wide; 0: the default, 4^k / 512 + 64) */
 RB_API void rb_set_list_side_capacity(uint32_t rows);
 
+/* PAIR TABLE of a resident filter: the lists of a k-mer AND of its reverse complement in one slot of three lines (384 bytes), so that a
+ * read's two strands cost three lines per k-mer where the list table's two-line slots cost four.  One slot per N-free k-mer x, indexed by
+ * the rank of x itself (every pair is stored twice: 4^k x 384 bytes, 24 GiB at k = 13); ibf_count_pair_lists_kernel ranks the forward
+ * strand only and counts into one LDS dword per bin, the low half the forward strand's count and the high half the reverse strand's, one
+ * workgroup of four waves per read.  A pair that leaves more than 64 entries behind the first 64 of either list takes a TAIL line of 128
+ * bytes in a side array (up to 254 entries in all), one beyond that a pair of dense rows in the side table; the census samples up to 65 536
+ * pairs and refuses the table (RB_LIST_REFUSED_DENSITY) where more than one in 32 needs a tail or more than one in 1024 dense rows.
+ * Serves what the list table serves, with three hash functions; results are identical.  No strand is skipped and none stops early -- both
+ * are fetched together -- so bound pruning changes nothing, and a call with a prune trace keeps the list form.
+ *   rb_dibf_pair_table_build / _drop / _info: as the list table's calls.  _download: the first n_entries entries of the CANONICAL form,
+ *     256 per slot -- the slot's bins of row(x) ascending, 0xFFFF, its bins of row(rc(x)) ascending, 0xFFFF to entry 252; entries 253 and
+ *     254 are the halves of an index and entry 255 is 0xFFFD (a tail slot: the index of its tail line) or 0xFFFE (a dense slot, which lists
+ *     nothing: the index of the first of its two rows in the side table), 0xFFFF otherwise -- the first n_tail_dwords dwords of the tail
+ *     lines as the device holds them (32 per line; a 16-bit half is 4 x bin, + 1 for a bin of row(rc(x)), or beyond 4 x the bin count:
+ *     nothing; first what is left of row(x), then of row(rc(x))), and the first n_side_words words of the side table.
+ *   rb_engine_set_row_table(RB_ROW_TABLE_PAIRS): the pair form wherever it serves, else as RB_ROW_TABLE_LISTS.
+ *   RB_ROW_TABLE_AUTO takes the pair table instead of the list table when the list rules (a)-(e) hold with the pair table's lines and
+ *     bytes, the list table's census on the same sample would choose two lines (a one-line list table already costs two lines per k-mer),
+ *     the pair census serves, and the pair table is at least rb_engine_set_pair_min_bytes (default 1 GiB: k <= 10 keeps the list table)
+ *     large.  The locate, hits, prefix and resume passes keep reading the list table under their own settings. */
+#define RB_ROW_TABLE_PAIRS 4
+typedef struct rb_pair_table_info {
+    uint64_t bytes, rows;    /* of the current table's slots; 0: none */
+    uint64_t side_bytes;     /* of its side table (dense rows) */
+    uint64_t tail_bytes;     /* of its tail lines */
+    uint32_t lines;          /* 128-byte lines per slot: 3 */
+    uint32_t side_rows;      /* dense rows in use (two per dense slot) */
+    uint32_t side_capacity;  /* ... and how many the side table holds */
+    uint32_t tail_rows;      /* tail lines in use */
+    uint32_t tail_capacity;  /* ... and how many the tail array holds */
+    uint32_t refused;        /* RB_LIST_REFUSED_*: why the last build did not happen */
+    uint32_t builds;         /* tables built for this filter so far */
+    uint32_t stride_words;   /* words per row of the side table (the filter's block stride) */
+    uint64_t census_rows, census_over[3]; /* pairs the last census looked at; how many need a tail or more, how many dense rows, and how
+                                             many have more than 128 bins in row(x) */
+    uint64_t census_one_line; /* ... and how many have more than 64 bins in row(x) */
+    double build_ms;         /* kernel time of the last build, census included */
+    double alloc_s;          /* seconds its allocations took */
+} rb_pair_table_info;
+RB_API int rb_dibf_pair_table_build(rb_dibf *f, uint64_t max_bytes);
+RB_API int rb_dibf_pair_table_drop(rb_dibf *f);
+RB_API int rb_dibf_pair_table_info(rb_dibf *f, rb_pair_table_info *out);
+RB_API int rb_dibf_pair_table_download(rb_dibf *f, uint16_t *entries, uint64_t n_entries, uint32_t *tail_dwords, uint64_t n_tail_dwords,
+                                       uint64_t *side_words, uint64_t n_side_words);
+RB_API int rb_engine_set_pair_min_bytes(rb_engine *e, uint64_t bytes);
+/* dense rows and tail lines of pair tables built from now on (process-wide; 0: the defaults, 2 x (4^k / 512 + 64) and 4^k / 16 + 64) */
+RB_API void rb_set_pair_side_capacity(uint32_t rows, uint32_t tails);
+
 /* WIDE LIST TABLE of a resident filter: the list table's idea for filters of 8193 to 32 256 bins (blocks of up to 504 words), which the
  * list table refuses (RB_LIST_REFUSED_GEOMETRY) -- GRCh38 at the default fragment size has about 31 000.  A second object beside the
  * list table with calls and a setting of its own, off by default.  Per N-free k-mer one slot of 4, 6 or 8 lines of 128 bytes with the

@@ -21,6 +21,14 @@
 //            offset of a counter dword (even bins in low halves, odd bins in high halves, a half that lists no bin names the lane's
 //            own spare), so the count is `add 1 at v & 0xFFFF` and `add 0x10000 at v >> 16`: two vector instructions per dword around
 //            the two adds.  Third argument `addready`: only `no lds`, then `scan` and `ready` in turn, three times each (two tables)
+//   pair   : step 0 of the pair table: one slot of 384 bytes (three lines) per k-mer holds the lists of the k-mer AND of its reverse
+//            complement, 2^26 slots = 24 GiB.  One counter dword per bin (low half forward strand, high half reverse strand: 32 KiB, four
+//            workgroups per CU), a read is 352 k-mers.  Lines 0-1 are positional (dword l: A[l] in the low half, B[l] in the high half:
+//            `ready`'s two instructions per dword), line 2 holds what is left of both lists, bit 0 of a half naming list B, and is loaded
+//            for two slots per instruction (lanes 0-31 and 32-63).  One workgroup of NW waves per read on one counter array, tile t of
+//            the read to wave t mod NW; NW = 1 with the next tile's gathers issued before the current tile's adds ("two-tile"), and 1, 2,
+//            4 with one tile in flight.  Third argument `pair`: `ready` and the pair settings in turn, three rounds, and the gate: a
+//            k-mer's slot in at most 0.90 of the time `ready` takes for its two rows, in every round (the lines predict 0.75)
 // Prints rows/s and lines/s (2 per row) per setting, best of 3 runs after one warm-up, and the gate of the issue: today's row
 // kernel completes 6.16 G rows/s at 0.946 of its own probe, so the list form can only win above 6.5 G rows/s.
 // build+run on the GPU box:  hipcc -O3 --offload-arch=gfx950 profiles/row_list_probe.hip -o /tmp/row_list_probe && /tmp/row_list_probe
@@ -258,6 +266,201 @@ __global__ __launch_bounds__(64) void list_probe(const uint32_t *__restrict__ ta
     if ((best ^ acc) == 0x12345678u) out[0] = best;
 }
 
+// ---- the pair mode: one 384-byte slot per k-mer for BOTH strands (the pair table's step 0)
+constexpr uint32_t kPairDwords = 96;                  // three lines
+constexpr uint32_t kPairKmers = kRowsPerRead / 2;     // 352 k-mers per read: five tiles of 64 and one of 32
+constexpr uint32_t kPairTiles = (kPairKmers + 63) / 64;
+constexpr uint32_t kPairLds = (kBins + kSpareDwords) * 4;  // one counter dword per bin (low half forward, high half reverse) and the spares
+
+// half q of a pair slot: lines 0-1 are positional (dword l: A[l] low, B[l] high; both lists have 72-91 entries, so none is blank), line 2
+// holds A[64..nA) then B[64..nB) with bit 0 naming list B, then spares (16-54 of its 64 halves are used)
+__device__ __forceinline__ uint32_t pair_half(uint64_t r, uint64_t n_rows, uint32_t q)
+{
+    const uint32_t nA = 72 + (uint32_t)(mix(~r) % 20), nB = 72 + (uint32_t)(mix(~(r + n_rows)) % 20);
+    const uint32_t sA = kBins / nA, sB = kBins / nB;
+    if (q < 128) return (q & 1u) ? entry(r + n_rows, q >> 1, nB, sB) * 4u : entry(r, q >> 1, nA, sA) * 4u;
+    const uint32_t i = q - 128, restA = nA - 64, restB = nB - 64;
+    if (i < restA) return entry(r, 64 + i, nA, sA) * 4u;
+    if (i < restA + restB) return entry(r + n_rows, 64 + i - restA, nB, sB) * 4u | 1u;
+    return (kBins + i) * 4u;
+}
+
+__global__ __launch_bounds__(256) void fill_rows_pair(uint32_t *__restrict__ table, uint64_t n_rows)
+{
+    const uint64_t n = n_rows * kPairDwords;
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        const uint64_t r = i / kPairDwords;
+        const uint32_t l = (uint32_t)(i % kPairDwords);
+        table[i] = pair_half(r, n_rows, 2 * l) | (pair_half(r, n_rows, 2 * l + 1) << 16);
+    }
+}
+
+// a line-2 dword: bits 15:2 of a half are the counter's byte offset, bit 0 says list B (add 1 << 16), evaluated for every half
+__device__ __forceinline__ void add2_pair_rest(uint32_t *cnt, uint32_t v)
+{
+    char *base = reinterpret_cast<char *>(cnt);
+    __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(base + (v & 0xFFFCu)), (v & 1u) * 0xFFFFu + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(base + ((v >> 16) & 0xFFFCu)), ((v >> 16) & 1u) * 0xFFFFu + 1u, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+struct PairTile {
+    uint32_t v[64];  // dword `lane` of lines 0-1 of slot u
+    uint32_t w[32];  // line 2 of slots 2j (lanes 0-31) and 2j + 1 (lanes 32-63)
+};
+
+// slot `mine` of lane u, as a scalar pointer (readfirstlane: the 64-bit product stays in scalar registers, the lane's dword is the
+// load's vector offset)
+typedef const uint32_t __attribute__((address_space(1))) *pair_gptr;  // global, so that the loads are global_load and count on vmcnt alone
+__device__ __forceinline__ pair_gptr pair_slot(const uint32_t *__restrict__ table, uint32_t mine, int u)
+{
+    const uint64_t a = reinterpret_cast<uint64_t>(table) + (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mine, u) * (kPairDwords * 4);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
+    return reinterpret_cast<pair_gptr>(((uint64_t)hi << 32) | lo);
+}
+
+// COUNT slots (64, or 32 for a read's last tile), group by group: eight loads of lines 0-1 and four of line 2, in this order
+template <bool NT, int COUNT>
+__device__ __forceinline__ void pair_load_n(PairTile &t, const uint32_t *__restrict__ table, uint32_t mine, uint32_t lane)
+{
+#pragma unroll
+    for (int g = 0; g < COUNT / 8; ++g) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const pair_gptr p = pair_slot(table, mine, g * 8 + u) + lane;
+            t.v[g * 8 + u] = NT ? __builtin_nontemporal_load(p) : *p;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const pair_gptr r0 = pair_slot(table, mine, g * 8 + 2 * j), r1 = pair_slot(table, mine, g * 8 + 2 * j + 1);
+            const pair_gptr p = (lane < 32 ? r0 : r1) + 64 + (lane & 31u);
+            t.w[g * 4 + j] = NT ? __builtin_nontemporal_load(p) : *p;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+template <int COUNT>
+__device__ __forceinline__ void pair_add_n(const PairTile &t, uint32_t *cnt, uint32_t *flagged)
+{
+#pragma unroll
+    for (int g = 0; g < COUNT / 8; ++g) {
+        uint32_t fold = 0;  // the overflow test of the kernel: one per group, on lines 0-1 (no slot of this table is flagged)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) fold |= t.v[g * 8 + u];
+        *flagged += (uint32_t)(__ballot((fold & 0x00020002u) != 0u) != 0ULL);  // no branch: the compiler sinks the later groups' loads behind one
+#pragma unroll
+        for (int u = 0; u < 8; ++u) add2_ready(cnt, t.v[g * 8 + u]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) add2_pair_rest(cnt, t.w[g * 4 + j]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+template <int NW>
+__device__ __forceinline__ uint32_t pair_scan_and_clear(uint32_t *cnt, uint32_t wave, uint32_t lane)
+{
+    uint4 *c4 = reinterpret_cast<uint4 *>(cnt);
+    probe_u16x2 a = {0, 0};
+#pragma unroll
+    for (uint32_t i = 0; i < kBins / 4 / 64 / NW; ++i) {
+        const uint32_t at = (i * NW + wave) * 64 + lane;  // < kBins / 4
+        const uint4 q = c4[at];
+        a = __builtin_elementwise_max(a, __builtin_elementwise_max(__builtin_elementwise_max(__builtin_bit_cast(probe_u16x2, q.x), __builtin_bit_cast(probe_u16x2, q.y)),
+                                                                   __builtin_elementwise_max(__builtin_bit_cast(probe_u16x2, q.z), __builtin_bit_cast(probe_u16x2, q.w))));
+        c4[at] = make_uint4(0, 0, 0, 0);
+    }
+    uint32_t m = max((uint32_t)a.x, (uint32_t)a.y);  // the maximum over both strands
+    m = max(m, (uint32_t)__builtin_amdgcn_ds_swizzle((int)m, 0x401F));  // lane ^ 16, ^ 8, ... ^ 1: no index registers kept over the tile loop
+    m = max(m, (uint32_t)__builtin_amdgcn_ds_swizzle((int)m, 0x201F));
+    m = max(m, (uint32_t)__builtin_amdgcn_ds_swizzle((int)m, 0x101F));
+    m = max(m, (uint32_t)__builtin_amdgcn_ds_swizzle((int)m, 0x081F));
+    m = max(m, (uint32_t)__builtin_amdgcn_ds_swizzle((int)m, 0x041F));
+    return max((uint32_t)__builtin_amdgcn_readlane((int)m, 0), (uint32_t)__builtin_amdgcn_readlane((int)m, 32));
+}
+
+// One workgroup of NW waves per read on one counter array, tile t of a read to wave t mod NW.  DB: a wave issues its next tile's gathers
+// before its current tile's adds (two tiles of registers).
+template <int NW, bool DB, bool NT>
+__global__ __launch_bounds__(64 * NW, NW) void pair_probe(  // four workgroups per CU: NW waves per SIMD
+const uint32_t *__restrict__ table, uint32_t lg_rows, uint32_t reads, uint32_t *out)
+{
+    extern __shared__ uint32_t cnt[];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t best = 0, flagged = 0;
+    uint64_t s = mix((uint64_t)blockIdx.x * NW + wave + 1);
+    pair_scan_and_clear<NW>(cnt, wave, lane);
+    if (wave == 0) cnt[kBins + lane] = 0;
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t rd = 0; rd < reads; ++rd) {
+#define PAIR_DRAW() (s += 0x9E3779B97F4A7C15ULL, (uint32_t)(mix(s + lane) >> (64 - lg_rows)))
+        if constexpr (DB) {  // NW == 1: the read's tiles in a fixed order, 64 64 64 64 64 32
+            static_assert(NW == 1 && kPairTiles == 6 && kPairKmers % 64 == 32, "the two-tile order is written out for one wave");
+            PairTile a, b;
+            pair_load_n<NT, 64>(a, table, PAIR_DRAW(), lane);
+#pragma unroll 1
+            for (int i = 0; i < 2; ++i) {
+                pair_load_n<NT, 64>(b, table, PAIR_DRAW(), lane);
+                pair_add_n<64>(a, cnt, &flagged);
+                pair_load_n<NT, 64>(a, table, PAIR_DRAW(), lane);
+                pair_add_n<64>(b, cnt, &flagged);
+            }
+            pair_load_n<NT, 32>(b, table, PAIR_DRAW(), lane);
+            pair_add_n<64>(a, cnt, &flagged);
+            pair_add_n<32>(b, cnt, &flagged);
+        } else {
+#pragma unroll 1
+            for (uint32_t t = wave; t < kPairTiles; t += NW) {  // wave-uniform
+                PairTile a;
+                const uint32_t mine = PAIR_DRAW();
+                if (t * 64u + 64u <= kPairKmers) {
+                    pair_load_n<NT, 64>(a, table, mine, lane);
+                    pair_add_n<64>(a, cnt, &flagged);
+                } else {
+                    pair_load_n<NT, kPairKmers % 64>(a, table, mine, lane);
+                    pair_add_n<kPairKmers % 64>(a, cnt, &flagged);
+                }
+            }
+        }
+#undef PAIR_DRAW
+        __syncthreads();  // a read ends
+        best = max(best, pair_scan_and_clear<NW>(cnt, wave, lane));
+        __syncthreads();
+    }
+    if ((best ^ flagged) == 0x12345678u) out[0] = best;
+}
+
+template <int NW, bool DB, bool NT>
+static int run_pair(const uint32_t *table, uint32_t lg_rows, uint32_t reads, uint32_t *out, double *kmers_per_s)
+{
+    const int blocks = 256 * 4 * 8;  // four workgroups per CU is what 32 KiB of counters allow, eight rounds
+    hipEvent_t a, b;
+    CHECK(hipEventCreate(&a));
+    CHECK(hipEventCreate(&b));
+    float best = 1e30f;
+    for (int rep = 0; rep < 4; ++rep) {
+        CHECK(hipEventRecord(a));
+        hipLaunchKernelGGL((pair_probe<NW, DB, NT>), dim3(blocks), dim3(64 * NW), kPairLds, 0, table, lg_rows, reads, out);
+        CHECK(hipGetLastError());
+        CHECK(hipEventRecord(b));
+        CHECK(hipEventSynchronize(b));
+        float ms = 0;
+        CHECK(hipEventElapsedTime(&ms, a, b));
+        if (rep && ms < best) best = ms;
+    }
+    const double kmers = (double)blocks * reads * kPairKmers;
+    *kmers_per_s = kmers / best / 1e6;  // G k-mers/s
+    printf("pair   %d wave%s %-8s  %-8s : %7.2f G k-mers/s  %7.2f G lines/s  (%.1f ms)\n", NW, NW > 1 ? "s" : " ", DB ? "two-tile" : "one-tile",
+           NT ? "nt" : "temporal", *kmers_per_s, 3.0 * *kmers_per_s, best);
+    fflush(stdout);
+    CHECK(hipEventDestroy(a));
+    CHECK(hipEventDestroy(b));
+    return 0;
+}
+
 template <int R, bool NT, bool LDS, int MODE = 0>
 static int run(const uint32_t *table, uint32_t lg_rows, uint32_t reads, uint32_t *out, double *rows_per_s)
 {
@@ -296,13 +499,56 @@ int main(int argc, char **argv)
     const uint32_t lg_rows = argc > 1 ? (uint32_t)atoi(argv[1]) : 26;
     const uint32_t reads = argc > 2 ? (uint32_t)atoi(argv[2]) : 48;
     const bool addready = argc > 3 && !strcmp(argv[3], "addready");
-    if (lg_rows < 10 || lg_rows > 26 || reads < 1 || reads > 4096 || (argc > 3 && !addready)) {
-        printf("usage: row_list_probe [log2 rows 10..26] [reads per wave 1..4096] [addready]\n");
+    const bool pair = argc > 3 && !strcmp(argv[3], "pair");
+    if (lg_rows < 10 || lg_rows > 26 || reads < 1 || reads > 4096 || (argc > 3 && !addready && !pair)) {
+        printf("usage: row_list_probe [log2 rows 10..26] [reads per wave 1..4096] [addready | pair]\n");
         return 2;
     }
     const uint64_t n_rows = 1ULL << lg_rows;
     const size_t bytes = (size_t)n_rows * kRowDwords * 4;
     uint32_t *table = nullptr, *out = nullptr;
+    if (pair) {  // the pair table's gate: a k-mer's pair slot in at most 0.90 of the time `ready` takes for its two rows, in every round
+        const size_t pair_bytes = (size_t)n_rows * kPairDwords * 4;
+        uint32_t *slots = nullptr;
+        CHECK(hipMalloc(&table, bytes));
+        CHECK(hipMalloc(&slots, pair_bytes));
+        CHECK(hipMalloc(&out, 4));
+        hipLaunchKernelGGL(fill_rows_ready, dim3(256 * 64), dim3(64), 0, 0, table, n_rows);
+        CHECK(hipGetLastError());
+        hipLaunchKernelGGL(fill_rows_pair, dim3(256 * 32), dim3(256), 0, 0, slots, n_rows);
+        CHECK(hipGetLastError());
+        CHECK(hipDeviceSynchronize());
+        const uint32_t pair_reads = reads * 5 / 2;  // 4 workgroups per CU against 10: the same k-mers per launch
+        printf("ready table: 2^%u rows of 256 bytes = %.2f GiB, %u reads of %u rows per wave, 10 waves per CU\n", lg_rows, bytes / 1073741824.0, reads,
+               kRowsPerRead);
+        printf("pair table : 2^%u slots of 384 bytes = %.2f GiB, 2 x 72-91 of 192 entries per slot; %u reads of %u k-mers per workgroup, 4 per CU\n",
+               lg_rows, pair_bytes / 1073741824.0, pair_reads, kPairKmers);
+        const char *name[5] = {"1 wave two-tile", "2 waves one-tile", "4 waves one-tile temporal", "4 waves one-tile", "1 wave one-tile"};
+        double worst[5] = {0, 0, 0, 0, 0};
+        for (int rep = 0; rep < 3; ++rep) {
+            double rdy, p[5];
+            if (run<64, true, true, 3>(table, lg_rows, reads, out, &rdy)) return 1;
+            if (run_pair<1, true, true>(slots, lg_rows, pair_reads, out, &p[0])) return 1;
+            if (run_pair<2, false, true>(slots, lg_rows, pair_reads, out, &p[1])) return 1;
+            if (run_pair<4, false, false>(slots, lg_rows, pair_reads, out, &p[2])) return 1;
+            if (run_pair<4, false, true>(slots, lg_rows, pair_reads, out, &p[3])) return 1;
+            if (run_pair<1, false, true>(slots, lg_rows, pair_reads, out, &p[4])) return 1;
+            printf("round %d, time per k-mer over ready's time for two rows:", rep + 1);
+            for (int i = 0; i < 5; ++i) {
+                const double ratio = (rdy / 2.0) / p[i];  // (1 / p) / (2 / rdy)
+                worst[i] = ratio > worst[i] ? ratio : worst[i];
+                printf("  %s x%.4f", name[i], ratio);
+            }
+            printf("\n");
+        }
+        int pick = 0;
+        for (int i = 1; i < 5; ++i) pick = worst[i] < worst[pick] ? i : pick;
+        printf("best: %s, x%.4f in its slowest round; gate x0.90: %s\n", name[pick], worst[pick], worst[pick] <= 0.90 ? "go on" : "stop");
+        CHECK(hipFree(slots));
+        CHECK(hipFree(table));
+        CHECK(hipFree(out));
+        return 0;
+    }
     CHECK(hipMalloc(&table, bytes));
     CHECK(hipMalloc(&out, 4));
     hipLaunchKernelGGL(fill_rows, dim3(256 * 32), dim3(256), 0, 0, table, n_rows);

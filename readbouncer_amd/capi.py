@@ -114,7 +114,16 @@ class WideListTableInfo(C.Structure):
     _fields_ = _LIST_TABLE_INFO_FIELDS
 
 
-RB_ROW_TABLE_OFF, RB_ROW_TABLE_AUTO, RB_ROW_TABLE_FORCE, RB_ROW_TABLE_LISTS = 0, 1, 2, 3
+class PairTableInfo(C.Structure):
+    """rb_pair_table_info (census_over: sampled pairs that need a tail or more, that need dense rows, whose row(x) has more than 128 bins)"""
+    _fields_ = [("bytes", C.c_uint64), ("rows", C.c_uint64), ("side_bytes", C.c_uint64), ("tail_bytes", C.c_uint64), ("lines", C.c_uint32),
+                ("side_rows", C.c_uint32), ("side_capacity", C.c_uint32), ("tail_rows", C.c_uint32), ("tail_capacity", C.c_uint32),
+                ("refused", C.c_uint32), ("builds", C.c_uint32), ("stride_words", C.c_uint32), ("census_rows", C.c_uint64),
+                ("census_over", C.c_uint64 * 3), ("census_one_line", C.c_uint64), ("build_ms", C.c_double), ("alloc_s", C.c_double)]
+
+
+RB_ROW_TABLE_OFF, RB_ROW_TABLE_AUTO, RB_ROW_TABLE_FORCE, RB_ROW_TABLE_LISTS, RB_ROW_TABLE_PAIRS = 0, 1, 2, 3, 4
+PAIR_CANON_ENTRIES, PAIR_TAIL_MARK, PAIR_TAIL_DWORDS = 256, 0xFFFD, 32  # rb_pair_lists.h
 RB_PASS_LISTS_OFF, RB_PASS_LISTS_CURRENT, RB_PASS_LISTS_BUILD = 0, 1, 2
 (RB_LIST_REFUSED_NONE, RB_LIST_REFUSED_K, RB_LIST_REFUSED_GEOMETRY, RB_LIST_REFUSED_MAX_BYTES, RB_LIST_REFUSED_FREE, RB_LIST_REFUSED_ALLOC,
  RB_LIST_REFUSED_CAPTURE, RB_LIST_REFUSED_DENSITY, RB_LIST_REFUSED_SIDE_FULL) = range(9)
@@ -291,6 +300,12 @@ SIGNATURES = {
     "rb_dibf_list_table_download": (_int, [_vp, _vp, _u64, _vp, _u64]),
     "rb_engine_set_list_min_dense_bytes": (_int, [_vp, _u64]),
     "rb_set_list_side_capacity": (None, [C.c_uint32]),
+    "rb_dibf_pair_table_build": (_int, [_vp, _u64]),
+    "rb_dibf_pair_table_drop": (_int, [_vp]),
+    "rb_dibf_pair_table_info": (_int, [_vp, C.POINTER(PairTableInfo)]),
+    "rb_dibf_pair_table_download": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64]),
+    "rb_engine_set_pair_min_bytes": (_int, [_vp, _u64]),
+    "rb_set_pair_side_capacity": (None, [C.c_uint32, C.c_uint32]),
     "rb_dibf_wide_list_table_build": (_int, [_vp, _u64]),
     "rb_dibf_wide_list_table_drop": (_int, [_vp]),
     "rb_dibf_wide_list_table_info": (_int, [_vp, C.POINTER(WideListTableInfo)]),
@@ -575,6 +590,35 @@ class DeviceIBF:
     def wide_list_table_download(self):
         """-> (np.uint16[rows, 64 x lines]: the canonical slots, np.uint64[side rows in use, stride words]: the dense rows overflow slots name)"""
         return self._list_table("wide_list_table", "download")
+
+    def pair_table_info(self):
+        """-> dict (rb_pair_table_info)"""
+        i = PairTableInfo()
+        _check(lib().rb_dibf_pair_table_info(self.h, C.byref(i)), "rb_dibf_pair_table_info")
+        d = {k: getattr(i, k) for k, _ in PairTableInfo._fields_}
+        d["census_over"] = list(i.census_over)
+        return d
+
+    def pair_table_build(self, max_bytes=0):
+        """build the pair table (per N-free k-mer x the bins of row(x) and of row(rc(x)) in one three-line slot) unless a current one
+        exists -> pair_table_info()"""
+        _check(lib().rb_dibf_pair_table_build(self.h, int(max_bytes)), "rb_dibf_pair_table_build")
+        return self.pair_table_info()
+
+    def pair_table_drop(self):
+        _check(lib().rb_dibf_pair_table_drop(self.h), "rb_dibf_pair_table_drop")
+
+    def pair_table_download(self):
+        """-> (np.uint16[rows, 256]: the canonical slots, np.uint32[tail lines in use, 32]: the tail lines as the device holds them,
+        np.uint64[side rows in use, stride words]: the dense rows, two per dense slot)"""
+        d = self.pair_table_info()
+        slots = np.zeros(d["rows"] * PAIR_CANON_ENTRIES, dtype=np.uint16)
+        tails = np.zeros(d["tail_rows"] * PAIR_TAIL_DWORDS, dtype=np.uint32)
+        side = np.zeros(d["side_rows"] * d["stride_words"], dtype=np.uint64)
+        _check(lib().rb_dibf_pair_table_download(self.h, _ptr(slots) if len(slots) else None, len(slots), _ptr(tails) if len(tails) else None,
+                                                 len(tails), _ptr(side) if len(side) else None, len(side)), "rb_dibf_pair_table_download")
+        return (slots.reshape(d["rows"], PAIR_CANON_ENTRIES) if d["rows"] else slots), tails.reshape(-1, PAIR_TAIL_DWORDS), \
+            side.reshape(d["side_rows"], d["stride_words"])
 
     def placement(self):
         """-> (allocations probed for this table: 0 = not placed by trial, GB/s of the kept one, GB/s of the slowest one)"""
@@ -1064,6 +1108,10 @@ class Engine:
     def set_list_min_dense_bytes(self, n_bytes):
         """size of the dense row table from which RB_ROW_TABLE_AUTO prefers the list table (default 512 MiB; 0: always)"""
         _check(lib().rb_engine_set_list_min_dense_bytes(self.h, int(n_bytes)), "rb_engine_set_list_min_dense_bytes")
+
+    def set_pair_min_bytes(self, n_bytes):
+        """size of the pair table from which RB_ROW_TABLE_AUTO takes it instead of the list table (default 1 GiB; 0: always)"""
+        _check(lib().rb_engine_set_pair_min_bytes(self.h, int(n_bytes)), "rb_engine_set_pair_min_bytes")
 
     def set_prune_trace(self, device_ptr):
         """device memory for one 8-byte record per (filter, read, column slice) of the plain count kernel's waves, or 0 / None: none"""

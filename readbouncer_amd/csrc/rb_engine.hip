@@ -24,6 +24,8 @@
 #include "rb_phase_plan.h"
 #include "rb_lists.h"
 #include "rb_wide_lists.h"
+#include "rb_pair_lists.h"
+#include "rb_pair_lists_launch.h"
 #include "rb_list_tables.h"
 #include "rb_stage.h"
 
@@ -76,6 +78,9 @@ struct rb_dibf {
     // 32 256 bins.  A second object beside the list table, and the same object on the host: one state (rb_list_tables.h) in two kinds
     // (ListTableKind below), owned, guarded (row_mu) and dropped alike.
     rbtables::ListTableState wide;
+    // PAIR TABLE (rb_dibf_pair_table_build; rb_pair_lists.h, rb_pair_lists.hip): the lists of a k-mer and of its reverse complement in one
+    // three-line slot, with tail lines and dense row pairs beside.  A third kind of the same object.
+    rbtables::ListTableState pair;
 };
 
 static void dibf_row_drop_locked(rb_dibf *f)
@@ -88,13 +93,14 @@ static void dibf_row_drop_locked(rb_dibf *f)
     f->row_rows = f->row_bytes = 0;
 }
 
-// either list table of the filter (f->list, f->wide): the memory goes, what the state remembers of builds and refusals stays
+// any list table of the filter (f->list, f->wide, f->pair): the memory goes, what the state remembers of builds and refusals stays
 static void dibf_list_table_drop_locked(rb_dibf *f, rbtables::ListTableState &s)
 {
-    if (s.table || s.side) {
+    if (s.table || s.side || s.tails) {
         (void)hipSetDevice(f->device);
         if (s.table) (void)hipFree(s.table);  // (waits for the kernels that read it)
         if (s.side) (void)hipFree(s.side);
+        if (s.tails) (void)hipFree(s.tails);
     }
     rbtables::clear_dropped(s);
 }
@@ -108,6 +114,7 @@ static void dibf_changed(rb_dibf *f)
     dibf_row_drop_locked(f);
     dibf_list_table_drop_locked(f, f->list);
     dibf_list_table_drop_locked(f, f->wide);
+    dibf_list_table_drop_locked(f, f->pair);
 }
 
 // Tables of 1 GiB and more are PLACED BY TRIAL: the same table allocated at another moment of one process gathers 1.7-2.9 % slower or
@@ -405,6 +412,8 @@ struct rb_engine {
     // ... and from which size of the DENSE row table auto prefers the list table (rb_engine_set_list_min_dense_bytes): a constant of its
     // own, not nt_threshold_bytes -- below it the dense table is served from the Infinity Cache and lines are not what limits it
     uint64_t list_min_dense_bytes = 512ull << 20;
+    // ... and from which size of the PAIR table auto takes it instead of the list table (rb_engine_set_pair_min_bytes)
+    uint64_t pair_min_bytes = 1ull << 30;
     // rb_engine_set_pass_lists: whether locate and hits take a filter's list table (pass_lists_for)
     int pass_lists = RB_PASS_LISTS_OFF;
     // rb_engine_set_prefix_lists: the same for the prefix pass, a setting of its own; and where its prep kernel counts the items the list
@@ -872,6 +881,7 @@ void rb_dibf_free(rb_dibf *f)
     dibf_row_drop_locked(f);  // (nobody else holds a filter that is being freed)
     dibf_list_table_drop_locked(f, f->list);
     dibf_list_table_drop_locked(f, f->wide);
+    dibf_list_table_drop_locked(f, f->pair);
     delete f;
 }
 
@@ -1490,7 +1500,7 @@ int rb_engine_set_prune_parts(rb_engine *e, uint32_t mask)
 
 int rb_engine_set_row_table(rb_engine *e, int mode, uint64_t max_bytes)
 {
-    if (!e || mode < RB_ROW_TABLE_OFF || mode > RB_ROW_TABLE_LISTS) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (auto), 2 (force) or 3 (lists)");
+    if (!e || mode < RB_ROW_TABLE_OFF || mode > RB_ROW_TABLE_PAIRS) return rb::fail(RB_ERR_INVALID_ARG, "mode 0 (off), 1 (auto), 2 (force), 3 (lists) or 4 (pairs)");
     std::lock_guard<std::mutex> lock(e->mu);
     e->row_mode = mode;
     if (max_bytes) e->row_max_bytes = max_bytes;
@@ -1621,10 +1631,23 @@ int rb_dibf_row_table_download(rb_dibf *f, uint64_t *words, uint64_t n_words)
 }
 
 // ---- the list table (rb_lists.h) and the wide list table (rb_wide_lists.h): census, slot size, build, refusals -- once, for a KIND
-static std::atomic<uint32_t> g_list_side_capacity{0}, g_wide_side_capacity{0};
+static std::atomic<uint32_t> g_list_side_capacity{0}, g_wide_side_capacity{0}, g_pair_side_capacity{0}, g_pair_tail_capacity{0};
 
 void rb_set_list_side_capacity(uint32_t rows) { g_list_side_capacity.store(rows); }
 void rb_set_wide_list_side_capacity(uint32_t rows) { g_wide_side_capacity.store(rows); }
+void rb_set_pair_side_capacity(uint32_t rows, uint32_t tails)
+{
+    g_pair_side_capacity.store(rows);
+    g_pair_tail_capacity.store(tails);
+}
+
+int rb_engine_set_pair_min_bytes(rb_engine *e, uint64_t bytes)
+{
+    if (!e) return rb::fail(RB_ERR_INVALID_ARG, "null engine");
+    std::lock_guard<std::mutex> lock(e->mu);
+    e->pair_min_bytes = bytes;
+    return RB_OK;
+}
 
 int rb_engine_set_list_min_dense_bytes(rb_engine *e, uint64_t bytes)
 {
@@ -1650,8 +1673,8 @@ static uint32_t wide_table_geometry_refusal(const rb_dibf *f)
     return RB_LIST_REFUSED_NONE;
 }
 
-// What tells the two tables apart on the host: everything else -- the state, the decision (rb_list_tables.h), drop, build, info, download
-// and the table a call takes -- is written once below and handed one of the two kinds.
+// What tells the tables apart on the host: everything else -- the state, the decision (rb_list_tables.h), drop, build, info, download
+// and the table a call takes -- is written once below and handed one of the kinds.
 struct ListTableKind {
     const char *name;  // in messages
     uint32_t (*geometry_refusal)(const rb_dibf *);
@@ -1661,23 +1684,45 @@ struct ListTableKind {
     uint64_t (*side_capacity)(uint64_t n_rows);  // the default, and what rb_set_*_side_capacity puts in its place
     std::atomic<uint32_t> *side_capacity_set;
     hipError_t (*census)(const IbfDev &f, uint32_t *counters, uint64_t n_rows, uint64_t step, hipStream_t st);
-    hipError_t (*build)(const IbfDev &f, uint32_t *slots, uint64_t *side, uint32_t *counters, uint64_t n_rows, uint32_t lines, uint32_t side_cap, hipStream_t st);
+    hipError_t (*build)(const IbfDev &f, uint32_t *slots, uint64_t *side, uint32_t *tails, uint32_t *counters, uint64_t n_rows, uint32_t lines,
+                        uint32_t side_cap, uint32_t tail_cap, hipStream_t st);
     int (*decode_resident)(const uint32_t *in, uint32_t lines, uint32_t n_bins, uint16_t *slot);
     rbtables::ListTableState rb_dibf::*state;
+    // the pair table alone: tail lines beside the side table (counters[1] of a build counts them), and a canonical slot of more entries
+    // than the resident one has halves (0: lines x 64, as the resident form)
+    uint64_t (*tail_capacity)(uint64_t n_rows);
+    std::atomic<uint32_t> *tail_capacity_set;
+    uint32_t canon_entries;
 };
 
 static const ListTableKind kListKind = {
     "list table", list_table_geometry_refusal, rblist::choose_lines, rblist::slot_bytes, rblist::slot_entries, rblist::side_capacity,
     &g_list_side_capacity, launch_list_census,
-    [](const IbfDev &f, uint32_t *slots, uint64_t *side, uint32_t *counters, uint64_t n_rows, uint32_t lines, uint32_t side_cap, hipStream_t st) {
-        return launch_list_table(f, (uint16_t *)slots, side, counters, n_rows, lines, side_cap, st);
-    },
-    rblist::decode_resident, &rb_dibf::list};
+    [](const IbfDev &f, uint32_t *slots, uint64_t *side, uint32_t *, uint32_t *counters, uint64_t n_rows, uint32_t lines, uint32_t side_cap, uint32_t,
+       hipStream_t st) { return launch_list_table(f, (uint16_t *)slots, side, counters, n_rows, lines, side_cap, st); },
+    rblist::decode_resident, &rb_dibf::list, nullptr, nullptr, 0};
 
 static const ListTableKind kWideKind = {
     "wide list table", wide_table_geometry_refusal, rbwide::choose_lines, rbwide::slot_bytes, rbwide::slot_entries, rbwide::side_capacity,
-    &g_wide_side_capacity, launch_wide_list_census, launch_wide_list_table,
-    rbwide::decode_resident, &rb_dibf::wide};
+    &g_wide_side_capacity, launch_wide_list_census,
+    [](const IbfDev &f, uint32_t *slots, uint64_t *side, uint32_t *, uint32_t *counters, uint64_t n_rows, uint32_t lines, uint32_t side_cap, uint32_t,
+       hipStream_t st) { return launch_wide_list_table(f, slots, side, counters, n_rows, lines, side_cap, st); },
+    rbwide::decode_resident, &rb_dibf::wide, nullptr, nullptr, 0};
+
+// ... and no pair table: the list table's geometry (one column slice of at most 128 words, at most 8192 bins) and three hash functions
+static uint32_t pair_table_geometry_refusal(const rb_dibf *f)
+{
+    const uint32_t r = list_table_geometry_refusal(f);
+    return r ? r : f->geo.n_hash != 3 ? RB_LIST_REFUSED_GEOMETRY : RB_LIST_REFUSED_NONE;
+}
+
+static const ListTableKind kPairKind = {
+    "pair table", pair_table_geometry_refusal, rbpair::choose_lines, [](uint32_t) { return rbpair::slot_bytes(); },
+    [](uint32_t) { return 2u * rbpair::kPairDwords; }, rbpair::side_capacity, &g_pair_side_capacity, launch_pair_census,
+    [](const IbfDev &f, uint32_t *slots, uint64_t *side, uint32_t *tails, uint32_t *counters, uint64_t n_rows, uint32_t, uint32_t side_cap,
+       uint32_t tail_cap, hipStream_t st) { return launch_pair_table(f, slots, tails, side, counters, n_rows, tail_cap, side_cap, st); },
+    [](const uint32_t *in, uint32_t, uint32_t n_bins, uint16_t *slot) { const int r = rbpair::decode_resident(in, n_bins, slot); return r > 0 ? -1 : r; },
+    &rb_dibf::pair, rbpair::tail_capacity, &g_pair_tail_capacity, rbpair::kPairCanonEntries};
 
 static bool list_table_current_locked(const ListTableKind &k, const rb_dibf *f) { return rbtables::current(f->*k.state, f->version.load()); }
 static bool list_refusal_stands_locked(const ListTableKind &k, const rb_dibf *f, uint64_t max_bytes) { return rbtables::refusal_stands(f->*k.state, f->version.load(), max_bytes); }
@@ -1703,10 +1748,12 @@ static int dibf_list_table_build(const ListTableKind &k, rb_dibf *f, uint64_t ma
     uint32_t *d_counters = nullptr;
     uint32_t counters[4] = {0, 0, 0, 0};
     RB_HIP(hipMalloc((void **)&d_counters, sizeof counters));
+    uint32_t *tails = nullptr;
     auto fail_hip = [&](hipError_t e, uint32_t *slots, uint64_t *side) {
         (void)hipFree(d_counters);
         if (slots) (void)hipFree(slots);
         if (side) (void)hipFree(side);
+        if (tails) (void)hipFree(tails);
         return rb::fail(RB_ERR_HIP, std::string(k.name) + ": " + hipGetErrorString(e));
     };
     // the census: how many of up to 2^16 rows, evenly spaced, overflow each slot size
@@ -1717,6 +1764,10 @@ static int dibf_list_table_build(const ListTableKind &k, rb_dibf *f, uint64_t ma
     if (e != hipSuccess) return fail_hip(e, nullptr, nullptr);
     s.census_rows = (n_rows + step - 1) / step;
     for (int i = 0; i < 3; ++i) s.census_over[i] = counters[1 + i];
+    if (k.tail_capacity) {  // (the pair table's census alone counts in counters[0])
+        s.census_extra = counters[0];
+        s.census_version = version;
+    }
     const uint32_t lines = k.choose_lines(s.census_over, s.census_rows);
     if (!lines) {
         (void)hipFree(d_counters);
@@ -1725,10 +1776,12 @@ static int dibf_list_table_build(const ListTableKind &k, rb_dibf *f, uint64_t ma
     }
     const uint32_t cap_set = k.side_capacity_set->load();
     const uint64_t side_cap = cap_set ? cap_set : k.side_capacity(n_rows);
-    const uint64_t bytes = n_rows * k.slot_bytes(lines), side_bytes = side_cap * f->stride * 8;
+    const uint32_t tail_set = k.tail_capacity ? k.tail_capacity_set->load() : 0u;
+    const uint64_t tail_cap = !k.tail_capacity ? 0 : tail_set ? tail_set : k.tail_capacity(n_rows);
+    const uint64_t bytes = n_rows * k.slot_bytes(lines), side_bytes = side_cap * f->stride * 8, tail_bytes = tail_cap * rblist::kLineBytes;
     size_t free_b = 0, total_b = 0;
-    if (max_bytes && bytes + side_bytes > max_bytes) s.refused = RB_LIST_REFUSED_MAX_BYTES;
-    else if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + side_bytes > (uint64_t)free_b / 2) s.refused = RB_LIST_REFUSED_FREE;
+    if (max_bytes && bytes + side_bytes + tail_bytes > max_bytes) s.refused = RB_LIST_REFUSED_MAX_BYTES;
+    else if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + side_bytes + tail_bytes > (uint64_t)free_b / 2) s.refused = RB_LIST_REFUSED_FREE;
     if (s.refused) {
         (void)hipGetLastError();
         (void)hipFree(d_counters);
@@ -1737,23 +1790,26 @@ static int dibf_list_table_build(const ListTableKind &k, rb_dibf *f, uint64_t ma
     const auto t_alloc = std::chrono::steady_clock::now();
     uint32_t *slots = nullptr;
     uint64_t *side = nullptr;
-    if (hipMalloc((void **)&slots, bytes) != hipSuccess || hipMalloc((void **)&side, side_bytes) != hipSuccess) {
+    if (hipMalloc((void **)&slots, bytes) != hipSuccess || hipMalloc((void **)&side, side_bytes) != hipSuccess ||
+        (tail_bytes && hipMalloc((void **)&tails, tail_bytes) != hipSuccess)) {
         (void)hipGetLastError();
         if (slots) (void)hipFree(slots);
+        if (side) (void)hipFree(side);
         (void)hipFree(d_counters);
         s.refused = RB_LIST_REFUSED_ALLOC;
         return RB_OK;
     }
     s.alloc_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_alloc).count();
     e = hipMemset(d_counters, 0, sizeof counters);
-    if (e == hipSuccess) e = k.build(f->dev, slots, side, d_counters, n_rows, lines, (uint32_t)side_cap, nullptr);
+    if (e == hipSuccess) e = k.build(f->dev, slots, side, tails, d_counters, n_rows, lines, (uint32_t)side_cap, (uint32_t)tail_cap, nullptr);
     if (e == hipSuccess) e = hipMemcpy(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail_hip(e, slots, side);
     (void)hipFree(d_counters);
     s.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - s.alloc_s * 1e3;
-    if (counters[0] > side_cap) {  // rows were left unwritten: nothing is ever counted from such a table
+    if (counters[0] > side_cap || (k.tail_capacity && counters[1] > tail_cap)) {  // rows were left unwritten: nothing is ever counted from such a table
         (void)hipFree(slots);
         (void)hipFree(side);
+        if (tails) (void)hipFree(tails);
         s.refused = RB_LIST_REFUSED_SIDE_FULL;
         return RB_OK;
     }
@@ -1765,6 +1821,10 @@ static int dibf_list_table_build(const ListTableKind &k, rb_dibf *f, uint64_t ma
     s.lines = lines;
     s.side_rows = counters[0];
     s.side_cap = (uint32_t)side_cap;
+    s.tails = tails;
+    s.tail_bytes = tail_bytes;
+    s.tail_rows = k.tail_capacity ? counters[1] : 0u;
+    s.tail_cap = (uint32_t)tail_cap;
     s.version = version;
     s.builds += 1;
     return RB_OK;
@@ -1790,10 +1850,18 @@ RB_SAME_FIELD(side_capacity); RB_SAME_FIELD(refused); RB_SAME_FIELD(builds); RB_
 RB_SAME_FIELD(census_over); RB_SAME_FIELD(build_ms); RB_SAME_FIELD(alloc_s);
 #undef RB_SAME_FIELD
 
+static void dibf_list_table_info_locked(const ListTableKind &k, rb_dibf *f, rb_list_table_info *out);
+
 static int dibf_list_table_info(const ListTableKind &k, rb_dibf *f, rb_list_table_info *out)
 {
     if (!f || !out) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> lock(f->row_mu);
+    dibf_list_table_info_locked(k, f, out);
+    return RB_OK;
+}
+
+static void dibf_list_table_info_locked(const ListTableKind &k, rb_dibf *f, rb_list_table_info *out)
+{
     const rbtables::ListTableState &s = f->*k.state;
     std::memset(out, 0, sizeof *out);
     if (list_table_current_locked(k, f)) {
@@ -1811,7 +1879,6 @@ static int dibf_list_table_info(const ListTableKind &k, rb_dibf *f, rb_list_tabl
     for (int i = 0; i < 3; ++i) out->census_over[i] = s.census_over[i];
     out->build_ms = s.build_ms;
     out->alloc_s = s.alloc_s;
-    return RB_OK;
 }
 
 static int dibf_list_table_download(const ListTableKind &k, rb_dibf *f, uint16_t *entries, uint64_t n_entries, uint64_t *side_words, uint64_t n_side_words)
@@ -1821,20 +1888,22 @@ static int dibf_list_table_download(const ListTableKind &k, rb_dibf *f, uint16_t
     const rbtables::ListTableState &s = f->*k.state;
     const std::string name = k.name;
     if (!list_table_current_locked(k, f)) return rb::fail(RB_ERR_INVALID_ARG, "the filter has no current " + name);
-    if (n_entries > s.bytes / 2) return rb::fail(RB_ERR_INVALID_ARG, "more entries than the " + name + " holds");
+    const uint32_t canon = k.canon_entries ? k.canon_entries : k.slot_entries(s.lines);
+    if (n_entries > s.rows * canon) return rb::fail(RB_ERR_INVALID_ARG, "more entries than the " + name + " holds");
     if (n_side_words > (uint64_t)s.side_rows * f->stride) return rb::fail(RB_ERR_INVALID_ARG, "more words than the side table's rows in use hold");
     int st = check_device(f->device);
     if (st != RB_OK) return st;
     if (n_entries) {
         // the device holds the resident form (rb_lists.h, rb_wide_lists.h): the whole slots that cover the prefix are copied -- no more than
         // asked for, rounded up to a slot -- and come back as canonical slots, of which the prefix is handed out
-        const uint32_t lines = s.lines, cap = k.slot_entries(lines);
+        const uint32_t lines = s.lines, cap = canon, dwords = k.slot_entries(lines) / 2;
         const uint64_t n_slots = (n_entries + cap - 1) / cap;
-        std::vector<uint32_t> resident(n_slots * (cap / 2));
+        std::vector<uint32_t> resident(n_slots * dwords);
         RB_HIP(hipMemcpy(resident.data(), s.table, resident.size() * 4, hipMemcpyDeviceToHost));
-        uint16_t slot[std::max(rblist::kMaxLines, rbwide::kWideMaxLines) * rblist::kEntriesPerLine];  // (the largest slot of either kind)
+        uint16_t slot[std::max(rblist::kMaxLines, rbwide::kWideMaxLines) * rblist::kEntriesPerLine];  // (the largest slot of any kind)
+        static_assert(sizeof slot / 2 >= rbpair::kPairCanonEntries, "a canonical pair slot fits");
         for (uint64_t i = 0; i < n_slots; ++i) {
-            if (k.decode_resident(resident.data() + i * (cap / 2), lines, (uint32_t)f->geo.n_bins, slot) == -2)
+            if (k.decode_resident(resident.data() + i * dwords, lines, (uint32_t)f->geo.n_bins, slot) == -2)
                 return rb::fail(RB_ERR_HIP, "the device's " + name + " holds a slot that no builder writes");
             std::memcpy(entries + i * cap, slot, (size_t)std::min<uint64_t>(cap, n_entries - i * cap) * 2);
         }
@@ -1852,6 +1921,48 @@ int rb_dibf_wide_list_table_build(rb_dibf *f, uint64_t max_bytes) { return dibf_
 int rb_dibf_wide_list_table_drop(rb_dibf *f) { return dibf_list_table_drop(kWideKind, f); }
 int rb_dibf_wide_list_table_info(rb_dibf *f, rb_wide_list_table_info *out) { return dibf_list_table_info(kWideKind, f, reinterpret_cast<rb_list_table_info *>(out)); }
 int rb_dibf_wide_list_table_download(rb_dibf *f, uint16_t *entries, uint64_t n, uint64_t *side_words, uint64_t n_side) { return dibf_list_table_download(kWideKind, f, entries, n, side_words, n_side); }
+
+int rb_dibf_pair_table_build(rb_dibf *f, uint64_t max_bytes) { return dibf_list_table_build(kPairKind, f, max_bytes); }
+int rb_dibf_pair_table_drop(rb_dibf *f) { return dibf_list_table_drop(kPairKind, f); }
+int rb_dibf_pair_table_info(rb_dibf *f, rb_pair_table_info *out)
+{
+    if (!f || !out) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
+    rb_list_table_info li;
+    std::lock_guard<std::mutex> lock(f->row_mu);  // one lock for the shared fields and the pair table's own: one table's figures
+    dibf_list_table_info_locked(kPairKind, f, &li);
+    std::memset(out, 0, sizeof *out);
+    out->bytes = li.bytes;
+    out->rows = li.rows;
+    out->side_bytes = li.side_bytes;
+    out->lines = li.lines;
+    out->side_rows = li.side_rows;
+    out->side_capacity = li.side_capacity;
+    out->refused = li.refused;
+    out->builds = li.builds;
+    out->stride_words = li.stride_words;
+    out->census_rows = li.census_rows;
+    for (int i = 0; i < 3; ++i) out->census_over[i] = li.census_over[i];
+    out->build_ms = li.build_ms;
+    out->alloc_s = li.alloc_s;
+    if (list_table_current_locked(kPairKind, f)) {
+        out->tail_bytes = f->pair.tail_bytes;
+        out->tail_rows = f->pair.tail_rows;
+        out->tail_capacity = f->pair.tail_cap;
+    }
+    out->census_one_line = f->pair.census_extra;
+    return RB_OK;
+}
+int rb_dibf_pair_table_download(rb_dibf *f, uint16_t *entries, uint64_t n, uint32_t *tail_dwords, uint64_t n_tail_dwords, uint64_t *side_words, uint64_t n_side)
+{
+    int rc = dibf_list_table_download(kPairKind, f, entries, n, side_words, n_side);
+    if (rc != RB_OK || !n_tail_dwords) return rc;
+    if (!tail_dwords) return rb::fail(RB_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(f->row_mu);
+    if (!list_table_current_locked(kPairKind, f)) return rb::fail(RB_ERR_INVALID_ARG, "the filter has no current pair table");
+    if (n_tail_dwords > (uint64_t)f->pair.tail_rows * rbpair::kPairTailDwords) return rb::fail(RB_ERR_INVALID_ARG, "more dwords than the tail lines in use hold");
+    RB_HIP(hipMemcpy(tail_dwords, f->pair.tails, n_tail_dwords * 4, hipMemcpyDeviceToHost));
+    return RB_OK;
+}
 
 int rb_engine_set_cert_load(rb_engine *e, size_t filter_index, double load)
 {
@@ -2306,7 +2417,7 @@ static int row_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, const uint64_
 // list table has nothing left to repay; no trace asked for.  Size (d) and capture (e) are settled where the table is built.
 static bool list_policy(const rb_engine *e, rb_dibf *f, const CountLaunch &a, size_t n_reads, uint32_t max_len)
 {
-    if (e->row_mode != RB_ROW_TABLE_LISTS && e->row_mode != RB_ROW_TABLE_AUTO) return false;
+    if (e->row_mode != RB_ROW_TABLE_LISTS && e->row_mode != RB_ROW_TABLE_PAIRS && e->row_mode != RB_ROW_TABLE_AUTO) return false;
     if (e->early_decision || e->shard_world != 1) return false;
     CountLaunch as_launch = a;  // (rb_engine_plan plans the geometry without the filter's descriptor)
     as_launch.f.n_hash = (uint32_t)f->geo.n_hash;
@@ -2331,11 +2442,47 @@ static bool list_policy(const rb_engine *e, rb_dibf *f, const CountLaunch &a, si
     return true;
 }
 
-// What a call takes of a filter's list table of either kind: the launch structs of the two forms are filled from it
+// May this launch count from the filter's PAIR table?  Mode pairs: wherever the form serves -- what the list form serves, three hash
+// functions, no trace asked for (the trace records where a strand stopped, and the pair form stops nowhere).  Mode auto, in addition: the
+// list rules (a) and (c) with the pair table's lines and bytes -- a k-mer costs L x h lines on either strand today and 3 for both from a
+// slot -- and a pair table of at least pair_min_bytes.  What the census says (the list table would take two lines, the pair census
+// serves) is settled where the table is built (pair_table_for), and remembered as a refusal for the bits.
+static bool pair_policy(const rb_engine *e, rb_dibf *f, const CountLaunch &a, size_t n_reads, uint32_t max_len)
+{
+    if (e->row_mode != RB_ROW_TABLE_PAIRS && e->row_mode != RB_ROW_TABLE_AUTO) return false;
+    if (e->early_decision || e->shard_world != 1 || e->prune_trace) return false;
+    CountLaunch as_launch = a;  // (rb_engine_plan plans the geometry without the filter's descriptor)
+    as_launch.f.n_hash = (uint32_t)f->geo.n_hash;
+    as_launch.f.k = (uint32_t)f->geo.kmer_size;
+    as_launch.f.n_bins = (uint32_t)f->geo.n_bins;
+    as_launch.f.bin_width = (uint32_t)f->geo.bin_width;
+    as_launch.src.max_len = max_len;
+    if (!pair_form_serves(as_launch) || pair_table_geometry_refusal(f)) return false;
+    if (e->filters.size() > 1 && n_reads <= e->split_threshold) return false;  // a micro-batch that is fused with other filters
+    const uint64_t n_rows = 1ull << (2 * f->geo.kmer_size);
+    if (n_rows * rbpair::slot_bytes() > e->row_max_bytes) return false;
+    if (e->row_mode == RB_ROW_TABLE_AUTO) {
+        if (n_rows * rbpair::slot_bytes() < e->pair_min_bytes) return false;
+        if (row_table_want_bytes(f) <= e->list_min_dense_bytes) return false;
+        std::lock_guard<std::mutex> lock(f->row_mu);
+        if (list_table_current_locked(kPairKind, f)) return true;
+        if (list_table_current_locked(kListKind, f) && f->list.lines != 2) return false;
+        const uint64_t k = f->geo.kmer_size, h = f->geo.n_hash, L = (f->stride * 8 + rblist::kLineBytes - 1) / rblist::kLineBytes;
+        const uint64_t kmers = max_len >= k ? max_len - k + 1 : 0;
+        // in HALF lines, since both strands share one slot of three: a k-mer costs 2 x per_kmer half lines per strand today and 3 from
+        // the slot; the build reads the blocks of x and of rc(x), 2 x L x h lines per slot, and writes 3
+        const uint64_t per_kmer = list_table_current_locked(kListKind, f) ? 2 : row_table_current_locked(f) ? L : L * h;
+        if (!rbtables::repays(n_reads, kmers, 2 * per_kmer, rbpair::kPairLines, n_rows, 4 * L * h + rbpair::kPairLines)) return false;
+    }
+    return true;
+}
+
+// What a call takes of a filter's list table of any kind: the launch structs of the forms are filled from it
 struct ListTableTaken {
     const uint32_t *slots = nullptr;
     const uint64_t *side = nullptr;
-    uint32_t side_rows = 0, lines = 0;
+    const uint32_t *tails = nullptr;
+    uint32_t side_rows = 0, lines = 0, tail_rows = 0;
     uint64_t bytes = 0;
 };
 
@@ -2346,6 +2493,8 @@ static void list_table_take_locked(const rbtables::ListTableState &s, ListTableT
     t->side_rows = s.side_rows;
     t->lines = s.lines;
     t->bytes = s.bytes;
+    t->tails = s.tails;
+    t->tail_rows = s.tail_rows;
 }
 
 // the question alone (rb_engine_plan_pass and its like): the current table or nothing -- no stream, and nothing is built or dropped
@@ -2378,6 +2527,50 @@ static int list_table_for(const ListTableKind &k, rb_engine *e, rb_dibf *f, hipS
     if (rc != RB_OK) return rc;
     list_table_peek(k, f, t);
     return RB_OK;
+}
+
+// The pair table for a launch that pair_policy admits.  Mode pairs: list_table_for.  Mode auto: a current table is taken; without one the
+// census alone is taken first (a kernel over up to 65 536 sampled pairs, nothing is allocated), and the table is built only where the
+// list table's census on that sample would choose two lines -- at most one row in 1024 beyond 128 bins, more than that beyond 64 -- a
+// one-line list table costs two lines per k-mer already, a four-line one means a filter the pair slot cannot hold.  Otherwise the bits
+// are refused the pair table (DENSITY), as where the pair census itself does not serve, and the call goes on to the list table.
+static int pair_table_for(rb_engine *e, rb_dibf *f, hipStream_t st, ListTableTaken *t)
+{
+    if (e->row_mode == RB_ROW_TABLE_AUTO) {
+        *t = ListTableTaken{};
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        const bool capturing = st && hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+        std::lock_guard<std::mutex> lock(f->row_mu);
+        rbtables::ListTableState &s = f->pair;
+        const uint64_t version = f->version.load();
+        if (!capturing && !list_table_current_locked(kPairKind, f) && !list_refusal_stands_locked(kPairKind, f, e->row_max_bytes)) {
+            if (s.census_version != version || !s.census_rows) {
+                int rc = check_device(f->device);
+                if (rc != RB_OK) return rc;
+                const uint64_t n_rows = 1ull << (2 * f->geo.kmer_size), step = std::max<uint64_t>(1, n_rows / rblist::kCensusRows);
+                uint32_t *d_counters = nullptr, counters[4] = {0, 0, 0, 0};
+                RB_HIP(hipMalloc((void **)&d_counters, sizeof counters));
+                hipError_t he = hipMemset(d_counters, 0, sizeof counters);
+                if (he == hipSuccess) he = launch_pair_census(f->dev, d_counters, n_rows, step, nullptr);
+                if (he == hipSuccess) he = hipMemcpy(counters, d_counters, sizeof counters, hipMemcpyDeviceToHost);
+                (void)hipFree(d_counters);
+                if (he != hipSuccess) return rb::fail(RB_ERR_HIP, std::string("pair table: ") + hipGetErrorString(he));
+                s.census_rows = (n_rows + step - 1) / step;
+                for (int i = 0; i < 3; ++i) s.census_over[i] = counters[1 + i];
+                s.census_extra = counters[0];
+                s.census_version = version;
+            }
+            const uint64_t allowed = s.census_rows >> rblist::kOverflowShift;
+            const bool two_lines = s.census_extra > allowed && s.census_over[2] <= allowed;
+            if (!two_lines || !rbpair::choose_lines(s.census_over, s.census_rows)) {
+                s.refused = RB_LIST_REFUSED_DENSITY;
+                s.refused_version = version;
+                s.refused_max_bytes = e->row_max_bytes;
+                return RB_OK;
+            }
+        }
+    }
+    return list_table_for(kPairKind, e, f, st, true, t);
 }
 
 // May this launch count from the filter's WIDE list table (rb_engine_set_wide_lists)?  Host arithmetic on the planned launch, shared by
@@ -3212,6 +3405,27 @@ static int classify_device_impl(rb_engine *e, const rb_batch_desc *desc, double 
                 continue;
             }
         }
+        if (pair_policy(e, e->filters[fi], a, n_reads, max_len)) {  // the pair table before the list table; refused: on to the list rule
+            ListTableTaken t;
+            if ((rc = pair_table_for(e, e->filters[fi], fs, &t)) != RB_OK) return rc;
+            if (t.slots && a.n_slices == 1 && !(!fan_out && nf > 1 && n_reads <= e->split_threshold)) {
+                fold_ok = false;
+                PairCountLaunch p{};
+                p.count = a;
+                p.count.src.max_len = max_len;
+                p.count.nt = t.bytes > e->nt_threshold_bytes;
+                p.count.out = maxcount + fi;
+                p.count.out_read_stride = (uint32_t)nf;
+                p.count.out_slice_stride = 0;
+                p.slots = t.slots;
+                p.tails = t.tails;
+                p.tail_rows = t.tail_rows;
+                p.side = t.side;
+                p.side_rows = t.side_rows;
+                RB_HIP(launch_ibf_count_pair_lists(p, fs));
+                continue;
+            }
+        }
         if (list_policy(e, e->filters[fi], a, n_reads, max_len)) {  // the list table before the dense one; refused: on to the row rule
             ListTableTaken t;
             if ((rc = list_table_for(kListKind, e, e->filters[fi], fs, true, &t)) != RB_OK) return rc;
@@ -3357,6 +3571,18 @@ extern "C" int rb_engine_plan(rb_engine *e, size_t filter_index, size_t n_reads,
         out->row_table_bytes = list_table_current_locked(kWideKind, fm) ? fm->wide.bytes : (1ull << (2 * fm->geo.kmer_size)) * rbwide::slot_bytes(6);
         out->nontemporal = out->row_table_bytes > e->nt_threshold_bytes ? 1u : 0u;
         out->column_slices = 1;
+    }
+    if (!g && !lists_planned && a.n_slices == 1 && pair_policy(e, e->filters[filter_index], a, n_reads, max_len)) {
+        // the pair form, when the filter has its table or the call could build it: not where this version of the bits was refused one
+        rb_dibf *fm = e->filters[filter_index];
+        std::lock_guard<std::mutex> rows_lock(fm->row_mu);
+        const bool current = list_table_current_locked(kPairKind, fm);
+        if (current || !list_refusal_stands_locked(kPairKind, fm, e->row_max_bytes)) {
+            lists_planned = true;
+            form = "ibf_count_pair_lists_kernel";
+            out->row_table_bytes = current ? fm->pair.bytes : (1ull << (2 * fm->geo.kmer_size)) * rbpair::slot_bytes();
+            out->nontemporal = out->row_table_bytes > e->nt_threshold_bytes ? 1u : 0u;
+        }
     }
     if (!g && !lists_planned && list_policy(e, e->filters[filter_index], a, n_reads, max_len)) {
         // the list form, when the filter has its table or the call could build it: not where this version of the bits was refused one

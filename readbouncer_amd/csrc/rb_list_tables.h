@@ -1,7 +1,8 @@
-// rb_list_tables.h -- the HOST side of a filter's list tables, once for both kinds: the LIST TABLE (rb_lists.h: up to 8192 bins, slots of
-// 1, 2 or 4 lines) and the WIDE LIST TABLE (rb_wide_lists.h: 8193 to 32 256 bins, slots of 4, 6 or 8 lines).  The two differ in their slot
+// rb_list_tables.h -- the HOST side of a filter's list tables, once for all kinds: the LIST TABLE (rb_lists.h: up to 8192 bins, slots of
+// 1, 2 or 4 lines), the WIDE LIST TABLE (rb_wide_lists.h: 8193 to 32 256 bins, slots of 4, 6 or 8 lines) and the PAIR TABLE
+// (rb_pair_lists.h: up to 8192 bins, one three-line slot for a k-mer and its reverse complement, and tail lines).  They differ in their slot
 // sizes, their geometry rule and the kernels that build and read them (ListTableKind, rb_engine.hip); what a filter remembers of a table,
-// when a table or a refusal still holds, what a call does with the table and when a batch repays a build are the same for both, and are
+// when a table or a refusal still holds, what a call does with the table and when a batch repays a build are the same for all, and are
 // here.  No HIP in here and nothing that touches the device: tests/cpp/test_list_tables.cpp compiles it alone, plain and with sanitizers,
 // and walks the whole decision -- the branch for a capturing stream among it, which no test on a GPU takes.
 #pragma once
@@ -16,10 +17,12 @@ namespace rbtables {
 struct ListTableState {
     uint32_t *table = nullptr;  // (dwords of the resident form; the list table's kernels take them as 16-bit halves)
     uint64_t *side = nullptr;
-    uint64_t version = 0, rows = 0, bytes = 0, side_bytes = 0;
-    uint32_t lines = 0, side_rows = 0, side_cap = 0;
+    uint32_t *tails = nullptr;  // (the pair table alone: its tail lines)
+    uint64_t version = 0, rows = 0, bytes = 0, side_bytes = 0, tail_bytes = 0;
+    uint32_t lines = 0, side_rows = 0, side_cap = 0, tail_rows = 0, tail_cap = 0;
     // what outlives a drop: the last census, the last build's times, the tables built so far and why the last build did not happen
     uint64_t census_rows = 0, census_over[3] = {0, 0, 0};
+    uint64_t census_extra = 0, census_version = 0;  // (the pair table's census: sampled rows of more than 64 bins, and the bits it looked at)
     double build_ms = 0.0, alloc_s = 0.0;
     uint32_t refused = RB_LIST_REFUSED_NONE;  // RB_LIST_REFUSED_*
     uint64_t refused_version = 0;             // ... the bits it was refused for: an engine does not ask again until they change
@@ -32,8 +35,9 @@ inline void clear_dropped(ListTableState &s)
 {
     s.table = nullptr;
     s.side = nullptr;
-    s.rows = s.bytes = s.side_bytes = 0;
-    s.lines = s.side_rows = s.side_cap = 0;
+    s.tails = nullptr;
+    s.rows = s.bytes = s.side_bytes = s.tail_bytes = 0;
+    s.lines = s.side_rows = s.side_cap = s.tail_rows = s.tail_cap = 0;
 }
 
 // a table of the bits as they are (`version`: the filter's)
